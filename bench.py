@@ -17,6 +17,10 @@ one RCCL all-gather of fixed-size padded buffers.  Rank 0 prints ONE JSON line.
 
 ``python bench.py --gpus N`` without a torch.distributed environment starts the N ranks itself
 (a child ``torch.distributed.run``, before this process touches a GPU).
+
+A plain run sets up, warms up, times K steps of the replayed pipeline and prints the line (``--dump-outputs DIR``:
+plus the results of the last timed step as .npy files).  ``--full`` adds what needs more than that: the conv roofline
+from event-stamped steps, the CPU baseline, and the accuracy and trained-heads legs against the CPU oracle.
 """
 from __future__ import annotations
 
@@ -37,6 +41,11 @@ PEAK_FP32_MFMA_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md, "Pe
 PEAK_BF16_MFMA_TFLOPS = 2500.0     # the same table, "Peak BF16/FP16 MFMA" (dense): 16x the f32-input MFMA
 X3_TERMS = 6                       # bf16 MFMA products conv_pw_x3_kernel issues per f32 product (csrc/conv_pw_x3.h)
 H2_TERMS = 3                       # f16 MFMA products conv_pw_h2_kernel issues per f32 product (csrc/conv_pw_h2.h)
+# options of the legs a plain run leaves out (argparse dests)
+FULL_ONLY = ('no_cpu_baseline', 'cpu_episodes', 'accuracy_episodes', 'train_heads_steps', 'trained_eval_episodes',
+             'isolated_steps', 'launch_records')
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MASK_SAMPLES = 8192           # pixels of every RLE mask written by --dump-outputs (fixed seeded positions)
 
 
 def mfma_terms(kernel: str):
@@ -83,6 +92,14 @@ def parse_args():
     ap.add_argument('--steps', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--workload', default='cfg3')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: the conv roofline of event-stamped steps (an eagerly launched '
+                         'isolated timed step, an overlapped warm-up step), the CPU baseline, the accuracy and trained-heads '
+                         'legs against the CPU oracle, and the multi-rank check of the gathered results.  Without it a run '
+                         'sets up, warms up, times --steps replayed steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the result dicts of the last one as DIR/<name>.npy (float32 / '
+                         'float64): the same arguments give the same inputs, so two builds compare output for output')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-episodes', type=int, default=5, help='timed episodes of the CPU baseline (after 2 warm-up episodes)')
     ap.add_argument('--accuracy-episodes', type=int, default=0,
@@ -135,6 +152,11 @@ def parse_args():
     ap.add_argument('--cache-supports', action='store_true',
                     help='not the headline: encode each support set once (SURVEY 8f row 3) and time query passes only')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    full_only = ['--' + d.replace('_', '-') for d in FULL_ONLY if getattr(args, d) != ap.get_default(d)]
+    if full_only and not args.full:
+        ap.error(f'{", ".join(full_only)}: only with --full')
     if args.graphs is None:
         args.graphs = True
     if args.streams is None:
@@ -262,6 +284,38 @@ def cpu_model() -> str:
     except OSError:
         pass
     return 'unknown'
+
+
+def dump_outputs(results: list, out_dir: str) -> None:
+    """--dump-outputs: the result dicts of one step, as ``FGN.pack_results`` hands them to its caller, written as
+    ``out_dir/ep<i>_<key>.npy``.  Float arrays keep their dtype, integer arrays become float64 (exact).  A list of COCO
+    RLE masks becomes ``<key>_area`` (pixels per mask) and ``<key>_sample`` (every mask at the same DUMP_MASK_SAMPLES
+    seeded pixel positions, 0 / 1): a dense float32 800x1333 mask per detection would take 4 MB."""
+    import numpy as np
+    from fgn_amd import rle
+    arrays = {}
+    for i, res in enumerate(results):
+        for key, val in res.items():
+            if key.endswith('_rle'):
+                masks = [rle.decode(r) for r in val]
+                sample = np.zeros((0, DUMP_MASK_SAMPLES), np.float32)
+                if masks:
+                    h, w = masks[0].shape
+                    pos = np.sort(np.random.default_rng(0).choice(h * w, DUMP_MASK_SAMPLES, replace=False))
+                    sample = np.stack([m[pos // w, pos % w] for m in masks]).astype(np.float32)
+                base = f'ep{i}_{key[:-len("_rle")]}'
+                arrays[base + '_area'] = np.array([m.sum() for m in masks], np.float64)
+                arrays[base + '_sample'] = sample
+            elif val is not None:
+                a = np.asarray(val)
+                if a.dtype.kind in 'biuf':
+                    arrays[f'ep{i}_{key}'] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget')
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def main():
@@ -524,15 +578,19 @@ def main():
     #    launch_classes`.  Rounds 1-4 instrumented step 0 - the first work after the barrier's device synchronisation, on
     #    an idle chip: its launches read 5 % longer than the same launches anywhere else;
     #  * one warm-up step is event-stamped while episodes overlap (`roofline.overlapped`, informational).
-    if args.isolated_steps == 'none':
+    # All of it is --full only: a plain run's warm-up and timed steps are the replayed pipeline and nothing else.
+    if not args.full or args.isolated_steps == 'none':
         alone_steps = []
     elif args.isolated_steps == 'last':
         alone_steps = [args.steps - 1]
     else:
         alone_steps = sorted({int(t) for t in args.isolated_steps.split(',') if t.strip() != '' and 0 <= int(t) < args.steps})
-    overlapped_in_warmup = args.warmup >= 3
-    prof_steps = [] if overlapped_in_warmup else ([args.steps // 2] if args.steps >= 4 and (args.steps // 2) not in alone_steps else [])
-    prof = ops.ConvProfile().reserve(2 * len(prime) + 16)            # overlapped step
+    overlapped_in_warmup = args.full and args.warmup >= 3
+    prof_steps = [] if (overlapped_in_warmup or not args.full) else \
+        ([args.steps // 2] if args.steps >= 4 and (args.steps // 2) not in alone_steps else [])
+    prof = ops.ConvProfile()                                         # overlapped step
+    if args.full:
+        prof.reserve(2 * len(prime) + 16)
     prof_alone = {i: ops.ConvProfile().reserve(2 * len(prime) + 16) for i in alone_steps}      # isolated steps -> roofline
     for pr in [prof] + list(prof_alone.values()):
         for ev in pr.pool:
@@ -594,132 +652,199 @@ def main():
             rank_info = gathered_info
         except Exception as e:       # diagnostics must never cost the bench line
             rank_info = [dict(rank=rank, **placement), {'gather_error': f'{type(e).__name__}: {e}'}]
-    n_prof_steps = 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_results, args.dump_outputs)
+    roofline = None
+    if args.full:
+        n_prof_steps = 1
 
-    # ---- roofline of the dominant kernel, from the HIP events recorded live ----------------------------------
-    def per_kernel(records):
-        out = {}
-        for rec in records:
-            ms = rec['e0'].elapsed_time(rec['e1'])
-            n = rec['n_img'] if rec['n_img_dev'] is None else min(rec['n_img'], int(rec['n_img_dev'].item()))
-            k = out.setdefault(rec['kernel'], dict(ms=0.0, launches=0, issued=0.0, direct=0.0))
-            k['ms'] += ms
-            k['launches'] += 1
-            k['issued'] += rec['flop_issued'] * n
-            k['direct'] += rec['flop_direct'] * n
-        return out
-    def launch_classes(records, kernel):
-        """The launches of one kernel split by what bounds them on paper: algorithmic bytes of a launch = (A + B + C
-        (+ residual)) x 4 B, arithmetic intensity = issued FLOP / those bytes, against the machine balance 157.3 TF/s /
-        8 TB/s = 19.7 FLOP/B.  A 1x1 convolution with K = 64 writes 4 bytes per 128 FLOP of its row: no MFMA rate
-        can make it faster than its output stream."""
-        out = {'mfma_bound': dict(launches=0, ms=0.0, flop=0.0, bytes=0.0), 'hbm_bound': dict(launches=0, ms=0.0, flop=0.0, bytes=0.0)}
-        # f32-equivalent MFMA ceiling of the kernel: the f32 pipe, or the bf16 pipe at six products per f32 product
-        peak_eq = mfma_terms(kernel)[1] / mfma_terms(kernel)[0]
-        for rec in records:
-            if rec['kernel'] != kernel or 'gemm' not in rec:
-                continue
-            n = rec['n_img'] if rec['n_img_dev'] is None else min(rec['n_img'], int(rec['n_img_dev'].item()))
-            g, rows, N, K = rec['gemm']
-            M = rows * n if rec['kind'] == 'conv' else rows
-            byts = 4.0 * g * (M * K + N * K + M * N * (2 if rec.get('residual') else 1))
-            flop = rec['flop_issued'] * n
-            c = out['mfma_bound' if flop / max(byts, 1.0) >= peak_eq / 8.0 else 'hbm_bound']
-            c['launches'] += 1
-            c['ms'] += rec['e0'].elapsed_time(rec['e1'])
-            c['flop'] += flop
-            c['bytes'] += byts
-        res = {}
-        for k, c in out.items():
-            if c['launches']:
-                res[k] = {'launches': c['launches'], 'ms': round(c['ms'], 3), 'tflops': round(c['flop'] / c['ms'] / 1e9, 1),
-                          'frac_of_mfma_peak': round(c['flop'] / c['ms'] / 1e9 / peak_eq, 4),
-                          'algorithmic_tb_per_s': round(c['bytes'] / c['ms'] / 1e9, 2),
-                          'frac_of_hbm_peak': round(c['bytes'] / c['ms'] / 1e9 / 8.0, 4)}
-        return res
-    by_kernel_overlapped = per_kernel(prof)
-    # the isolated steps: the dominant kernel is the one with the largest summed duration; `roofline` reports the MEDIAN
-    # isolated step (by the dominant kernel's time), the others as min / max
-    iso = {i: per_kernel(pr) for i, pr in prof_alone.items() if len(pr)}
-    dom_votes = [max(bk, key=lambda n: bk[n]['ms']) for bk in iso.values()]
-    dom_name = max(set(dom_votes), key=dom_votes.count) if dom_votes else \
-        (max(by_kernel_overlapped, key=lambda n: by_kernel_overlapped[n]['ms']) if by_kernel_overlapped else 'none')
-    iso_order = sorted(iso, key=lambda i: iso[i].get(dom_name, {'ms': 0.0})['ms'])
-    med_step = iso_order[len(iso_order) // 2] if iso_order else None
-    by_kernel = iso[med_step] if med_step is not None else by_kernel_overlapped
-    records_med = prof_alone[med_step] if med_step is not None else prof
-    tot = dict(ms=sum(k['ms'] for k in by_kernel.values()), launches=sum(k['launches'] for k in by_kernel.values()),
-               issued=sum(k['issued'] for k in by_kernel.values()), direct=sum(k['direct'] for k in by_kernel.values()))
-    dom = by_kernel.get(dom_name, dict(ms=0.0, launches=0, issued=0.0, direct=0.0))
-    tf = lambda flop, ms: flop / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-    # conv_pw_x3_kernel issues X3_TERMS bf16 MFMA products per f32 product of its GEMM: its roofline is the bf16 pipe,
-    # `achieved` the bf16 MFMA FLOPs it issued per second; the f32 products per second are reported beside it
-    dom_terms, dom_peak = mfma_terms(dom_name)
-    dom_x3 = dom_terms > 1               # a kernel on the 16-bit matrix pipe (conv_pw_x3_kernel / conv_pw_h2_kernel)
-    achieved = tf(dom['issued'], dom['ms']) * dom_terms
-    iso_table = [dict(step=i, kernel_ms=round(iso[i][dom_name]['ms'], 4), launches=iso[i][dom_name]['launches'],
-                      avg_launch_us=round(iso[i][dom_name]['ms'] * 1e3 / max(iso[i][dom_name]['launches'], 1), 2),
-                      frac=round(tf(iso[i][dom_name]['issued'], iso[i][dom_name]['ms']) * dom_terms / dom_peak, 4),
-                      all_conv_ms=round(sum(k['ms'] for k in iso[i].values()), 3))
-                 for i in sorted(iso) if dom_name in iso[i]]
-
-    # ---- the dominant kernel over the WHOLE timed window: the launch records inside the captured graphs --------------
-    window = None
-    # launch records are handed out in launch order to every launch of the two persistent GEMM kernels (f32 and x3)
-    takes_record = lambda rec: rec['kernel'] == 'conv_pw_persist_kernel' or mfma_terms(rec['kernel'])[0] > 1
-    rec_sites = [rec for rec in records_med if takes_record(rec)]
-    keep = [i for i, rec in enumerate(rec_sites) if rec['kernel'] == dom_name]
-    sites = [rec_sites[i] for i in keep]
-    if model.use_graphs and sites and (dom_name == 'conv_pw_persist_kernel' or dom_x3):
-        per_site = [dict(executions=0, total_us=0.0, min_us=None, max_us=None) for _ in sites]
-        # (a graph whose captured launch sequence does not have the isolated step's launch sites cannot be matched)
-        ok = bool(graphs) and all(ge.stamps is not None and ge.stamp_count == len(rec_sites) for ge in graphs)
-        for ge in graphs if ok else []:
-            all_recs = ops.read_stamps(ge.stamps, ge.stamp_count)
-            for a, b in zip(per_site, [all_recs[i] for i in keep]):
-                a['executions'] += b['executions']
-                a['total_us'] += b['total_us']
-                if b['executions']:
-                    a['min_us'] = b['min_us'] if a['min_us'] is None else min(a['min_us'], b['min_us'])
-                    a['max_us'] = b['max_us'] if a['max_us'] is None else max(a['max_us'], b['max_us'])
-        n_exec = sum(a['executions'] for a in per_site)
-        if ok and n_exec:
-            flop_of = []
-            for rec in sites:
+        # ---- roofline of the dominant kernel, from the HIP events recorded live ----------------------------------
+        def per_kernel(records):
+            out = {}
+            for rec in records:
+                ms = rec['e0'].elapsed_time(rec['e1'])
                 n = rec['n_img'] if rec['n_img_dev'] is None else min(rec['n_img'], int(rec['n_img_dev'].item()))
-                flop_of.append(rec['flop_issued'] * n)
-            w_us = sum(a['total_us'] for a in per_site)
-            w_flop = sum(f * a['executions'] for f, a in zip(flop_of, per_site))
-            ratios = sorted(a['total_us'] / a['executions'] / (1e3 * r['e0'].elapsed_time(r['e1']))
-                            for a, r in zip(per_site, sites) if a['executions'] and r['e0'].elapsed_time(r['e1']) > 0)
-            window = {'what': 'EVERY launch of the kernel in the timed region (all steps, both caller streams, inside the '
-                              'replayed hipGraphs): span first workgroup start -> last workgroup end on the 100 MHz '
-                              'in-kernel clock, folded into a launch record by the kernel itself (fgn_profile_stamps): the '
-                              'launches as they run in the untraced pipeline, beside the other caller stream',
-                      'launches': n_exec, 'launch_sites_per_step': len(sites),
-                      'executions_per_site': sorted({a['executions'] for a in per_site}),
-                      'avg_launch_us': round(w_us / n_exec, 2),
-                      'achieved': round(w_flop / w_us / 1e6 * dom_terms, 2),
-                      'frac': round(w_flop / w_us / 1e6 * dom_terms / dom_peak, 4),
-                      'site_us_over_isolated_event_us': ({'p10': round(ratios[len(ratios) // 10], 3), 'p50': round(ratios[len(ratios) // 2], 3),
-                                                          'p90': round(ratios[(len(ratios) * 9) // 10], 3)} if ratios else None),
-                      'largest_site': (lambda k: {'avg_us': round(per_site[k]['total_us'] / per_site[k]['executions'], 1),
-                                                  'min_us': per_site[k]['min_us'], 'max_us': per_site[k]['max_us'],
-                                                  'isolated_event_us': round(1e3 * sites[k]['e0'].elapsed_time(sites[k]['e1']), 1)})(
-                          max(range(len(sites)), key=lambda k: flop_of[k]))}
+                k = out.setdefault(rec['kernel'], dict(ms=0.0, launches=0, issued=0.0, direct=0.0))
+                k['ms'] += ms
+                k['launches'] += 1
+                k['issued'] += rec['flop_issued'] * n
+                k['direct'] += rec['flop_direct'] * n
+            return out
+        def launch_classes(records, kernel):
+            """The launches of one kernel split by what bounds them on paper: algorithmic bytes of a launch = (A + B + C
+            (+ residual)) x 4 B, arithmetic intensity = issued FLOP / those bytes, against the machine balance 157.3 TF/s /
+            8 TB/s = 19.7 FLOP/B.  A 1x1 convolution with K = 64 writes 4 bytes per 128 FLOP of its row: no MFMA rate
+            can make it faster than its output stream."""
+            out = {'mfma_bound': dict(launches=0, ms=0.0, flop=0.0, bytes=0.0), 'hbm_bound': dict(launches=0, ms=0.0, flop=0.0, bytes=0.0)}
+            # f32-equivalent MFMA ceiling of the kernel: the f32 pipe, or the bf16 pipe at six products per f32 product
+            peak_eq = mfma_terms(kernel)[1] / mfma_terms(kernel)[0]
+            for rec in records:
+                if rec['kernel'] != kernel or 'gemm' not in rec:
+                    continue
+                n = rec['n_img'] if rec['n_img_dev'] is None else min(rec['n_img'], int(rec['n_img_dev'].item()))
+                g, rows, N, K = rec['gemm']
+                M = rows * n if rec['kind'] == 'conv' else rows
+                byts = 4.0 * g * (M * K + N * K + M * N * (2 if rec.get('residual') else 1))
+                flop = rec['flop_issued'] * n
+                c = out['mfma_bound' if flop / max(byts, 1.0) >= peak_eq / 8.0 else 'hbm_bound']
+                c['launches'] += 1
+                c['ms'] += rec['e0'].elapsed_time(rec['e1'])
+                c['flop'] += flop
+                c['bytes'] += byts
+            res = {}
+            for k, c in out.items():
+                if c['launches']:
+                    res[k] = {'launches': c['launches'], 'ms': round(c['ms'], 3), 'tflops': round(c['flop'] / c['ms'] / 1e9, 1),
+                              'frac_of_mfma_peak': round(c['flop'] / c['ms'] / 1e9 / peak_eq, 4),
+                              'algorithmic_tb_per_s': round(c['bytes'] / c['ms'] / 1e9, 2),
+                              'frac_of_hbm_peak': round(c['bytes'] / c['ms'] / 1e9 / 8.0, 4)}
+            return res
+        by_kernel_overlapped = per_kernel(prof)
+        # the isolated steps: the dominant kernel is the one with the largest summed duration; `roofline` reports the MEDIAN
+        # isolated step (by the dominant kernel's time), the others as min / max
+        iso = {i: per_kernel(pr) for i, pr in prof_alone.items() if len(pr)}
+        dom_votes = [max(bk, key=lambda n: bk[n]['ms']) for bk in iso.values()]
+        dom_name = max(set(dom_votes), key=dom_votes.count) if dom_votes else \
+            (max(by_kernel_overlapped, key=lambda n: by_kernel_overlapped[n]['ms']) if by_kernel_overlapped else 'none')
+        iso_order = sorted(iso, key=lambda i: iso[i].get(dom_name, {'ms': 0.0})['ms'])
+        med_step = iso_order[len(iso_order) // 2] if iso_order else None
+        by_kernel = iso[med_step] if med_step is not None else by_kernel_overlapped
+        records_med = prof_alone[med_step] if med_step is not None else prof
+        tot = dict(ms=sum(k['ms'] for k in by_kernel.values()), launches=sum(k['launches'] for k in by_kernel.values()),
+                   issued=sum(k['issued'] for k in by_kernel.values()), direct=sum(k['direct'] for k in by_kernel.values()))
+        dom = by_kernel.get(dom_name, dict(ms=0.0, launches=0, issued=0.0, direct=0.0))
+        tf = lambda flop, ms: flop / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        # conv_pw_x3_kernel issues X3_TERMS bf16 MFMA products per f32 product of its GEMM: its roofline is the bf16 pipe,
+        # `achieved` the bf16 MFMA FLOPs it issued per second; the f32 products per second are reported beside it
+        dom_terms, dom_peak = mfma_terms(dom_name)
+        dom_x3 = dom_terms > 1               # a kernel on the 16-bit matrix pipe (conv_pw_x3_kernel / conv_pw_h2_kernel)
+        achieved = tf(dom['issued'], dom['ms']) * dom_terms
+        iso_table = [dict(step=i, kernel_ms=round(iso[i][dom_name]['ms'], 4), launches=iso[i][dom_name]['launches'],
+                          avg_launch_us=round(iso[i][dom_name]['ms'] * 1e3 / max(iso[i][dom_name]['launches'], 1), 2),
+                          frac=round(tf(iso[i][dom_name]['issued'], iso[i][dom_name]['ms']) * dom_terms / dom_peak, 4),
+                          all_conv_ms=round(sum(k['ms'] for k in iso[i].values()), 3))
+                     for i in sorted(iso) if dom_name in iso[i]]
 
-    # HBM traffic of the dominant kernel: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this same command
-    # (tools/profile_round.sh), corrected per MI355X_MICROARCH.md; PMC collection serialises kernels, so it is
-    # read from the committed profile, not collected inside the timed run
-    traffic = None
-    pdir = os.path.join(ROOT, 'profiles')
-    tfiles = sorted(f for f in os.listdir(pdir) if f.endswith('conv_traffic.json')) if os.path.isdir(pdir) else []
-    if tfiles and args.workload == 'cfg3' and args.batch == 1:
-        with open(os.path.join(pdir, tfiles[-1])) as fh:
-            tj = json.load(fh)
-        per = tj.get('per_kernel', {})
-        hit = [v for name, v in per.items() if name.replace(' ', '') == dom_name.replace(' ', '')]
-        traffic = hit[0]['hbm_bytes_per_launch'] if hit else None
+        # ---- the dominant kernel over the WHOLE timed window: the launch records inside the captured graphs --------------
+        window = None
+        # launch records are handed out in launch order to every launch of the two persistent GEMM kernels (f32 and x3)
+        takes_record = lambda rec: rec['kernel'] == 'conv_pw_persist_kernel' or mfma_terms(rec['kernel'])[0] > 1
+        rec_sites = [rec for rec in records_med if takes_record(rec)]
+        keep = [i for i, rec in enumerate(rec_sites) if rec['kernel'] == dom_name]
+        sites = [rec_sites[i] for i in keep]
+        if model.use_graphs and sites and (dom_name == 'conv_pw_persist_kernel' or dom_x3):
+            per_site = [dict(executions=0, total_us=0.0, min_us=None, max_us=None) for _ in sites]
+            # (a graph whose captured launch sequence does not have the isolated step's launch sites cannot be matched)
+            ok = bool(graphs) and all(ge.stamps is not None and ge.stamp_count == len(rec_sites) for ge in graphs)
+            for ge in graphs if ok else []:
+                all_recs = ops.read_stamps(ge.stamps, ge.stamp_count)
+                for a, b in zip(per_site, [all_recs[i] for i in keep]):
+                    a['executions'] += b['executions']
+                    a['total_us'] += b['total_us']
+                    if b['executions']:
+                        a['min_us'] = b['min_us'] if a['min_us'] is None else min(a['min_us'], b['min_us'])
+                        a['max_us'] = b['max_us'] if a['max_us'] is None else max(a['max_us'], b['max_us'])
+            n_exec = sum(a['executions'] for a in per_site)
+            if ok and n_exec:
+                flop_of = []
+                for rec in sites:
+                    n = rec['n_img'] if rec['n_img_dev'] is None else min(rec['n_img'], int(rec['n_img_dev'].item()))
+                    flop_of.append(rec['flop_issued'] * n)
+                w_us = sum(a['total_us'] for a in per_site)
+                w_flop = sum(f * a['executions'] for f, a in zip(flop_of, per_site))
+                ratios = sorted(a['total_us'] / a['executions'] / (1e3 * r['e0'].elapsed_time(r['e1']))
+                                for a, r in zip(per_site, sites) if a['executions'] and r['e0'].elapsed_time(r['e1']) > 0)
+                window = {'what': 'EVERY launch of the kernel in the timed region (all steps, both caller streams, inside the '
+                                  'replayed hipGraphs): span first workgroup start -> last workgroup end on the 100 MHz '
+                                  'in-kernel clock, folded into a launch record by the kernel itself (fgn_profile_stamps): the '
+                                  'launches as they run in the untraced pipeline, beside the other caller stream',
+                          'launches': n_exec, 'launch_sites_per_step': len(sites),
+                          'executions_per_site': sorted({a['executions'] for a in per_site}),
+                          'avg_launch_us': round(w_us / n_exec, 2),
+                          'achieved': round(w_flop / w_us / 1e6 * dom_terms, 2),
+                          'frac': round(w_flop / w_us / 1e6 * dom_terms / dom_peak, 4),
+                          'site_us_over_isolated_event_us': ({'p10': round(ratios[len(ratios) // 10], 3), 'p50': round(ratios[len(ratios) // 2], 3),
+                                                              'p90': round(ratios[(len(ratios) * 9) // 10], 3)} if ratios else None),
+                          'largest_site': (lambda k: {'avg_us': round(per_site[k]['total_us'] / per_site[k]['executions'], 1),
+                                                      'min_us': per_site[k]['min_us'], 'max_us': per_site[k]['max_us'],
+                                                      'isolated_event_us': round(1e3 * sites[k]['e0'].elapsed_time(sites[k]['e1']), 1)})(
+                              max(range(len(sites)), key=lambda k: flop_of[k]))}
+
+        # HBM traffic of the dominant kernel: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over this same command
+        # (tools/profile_round.sh), corrected per MI355X_MICROARCH.md; PMC collection serialises kernels, so it is
+        # read from the committed profile, not collected inside the timed run
+        traffic = None
+        pdir = os.path.join(ROOT, 'profiles')
+        tfiles = sorted(f for f in os.listdir(pdir) if f.endswith('conv_traffic.json')) if os.path.isdir(pdir) else []
+        if tfiles and args.workload == 'cfg3' and args.batch == 1:
+            with open(os.path.join(pdir, tfiles[-1])) as fh:
+                tj = json.load(fh)
+            per = tj.get('per_kernel', {})
+            hit = [v for name, v in per.items() if name.replace(' ', '') == dom_name.replace(' ', '')]
+            traffic = hit[0]['hbm_bytes_per_launch'] if hit else None
+        # frac = MFMA FLOPs the dominant kernel actually ISSUED / its summed HIP-event launch durations / peak.
+        # Reproducible from profiles/rNN_kernel_stats.csv: flop_per_step * steps / TotalDurationNs of `kernel`.
+        roofline = {'bound': 'mfma', 'kernel': dom_name,
+                    'achieved': round(achieved, 2), 'peak': dom_peak, 'unit': 'TFLOP/s',
+                    'frac': round(achieved / dom_peak, 4),
+                    'traffic': traffic,
+                    'mfma': ('v_mfma_f32_16x16x32_f16: %d f16 products per f32 product of the GEMM (two-way splits of the '
+                             'power-of-two scaled f32 operands, f32 accumulation); achieved / peak are f16 MFMA FLOP/s' % H2_TERMS)
+                            if dom_name.startswith('conv_pw_h2_kernel') else
+                            ('v_mfma_f32_16x16x32_bf16: %d bf16 products per f32 product of the GEMM (exact 3-way splits of '
+                             'both f32 operands, f32 accumulation); achieved / peak are bf16 MFMA FLOP/s' % X3_TERMS) if dom_x3
+                            else 'v_mfma_f32_16x16x4_f32 (f32 operands)',
+                    # the GEMM's own (f32) products per second, and against the f32-input MFMA peak this kernel no
+                    # longer runs on - above 1.0 means faster than any f32-MFMA kernel could be
+                    'f32_equivalent_tflops': round(achieved / dom_terms, 2),
+                    'f32_equivalent_over_f32_mfma_peak': round(achieved / dom_terms / PEAK_FP32_MFMA_TFLOPS, 4),
+                    'flop_per_step': round(dom['issued'] / n_prof_steps),
+                    'launches_per_step': dom['launches'] / n_prof_steps,
+                    'avg_launch_us': round(dom['ms'] * 1e3 / max(dom['launches'], 1), 2),
+                    'kernel_ms_per_step': round(dom['ms'] / n_prof_steps, 3),
+                    'share_of_conv_time': round(dom['ms'] / tot['ms'], 3) if tot['ms'] else None,
+                    # `frac` is the average over ALL launches of the kernel; split by the bound a launch has on
+                    # paper (arithmetic intensity against 157.3 TF/s / 8 TB/s): the MFMA-bound ones against the
+                    # MFMA peak, the output-bound 1x1 convolutions of layer1 / layer2 against the HBM peak
+                    'launch_classes': launch_classes(records_med, dom_name),
+                    'profiled_steps': n_prof_steps,
+                    'timing': 'start/stop HIP events stamped by each launch of the kernel itself (hipExtLaunchKernelGGL) on '
+                              'its own stream, in the isolated timed step(s) below: queued behind the episodes in flight '
+                              'on the GPU (no idle chip in front of them), no other episode beside them (their own side '
+                              'stream only).  With several isolated steps this is the MEDIAN one',
+                    'isolated_steps': iso_table,
+                    'frac_min_max_over_isolated_steps': ([min(r_['frac'] for r_ in iso_table), max(r_['frac'] for r_ in iso_table)]
+                                                         if iso_table else None),
+                    'timed_window': window,
+                    # the same kernel in a mid-run step, while two episodes overlap on the two caller streams (the
+                    # way the other steps run): launches share the CUs with another episode's kernels
+                    'overlapped': (lambda k: None if not k or not k['ms'] else {
+                        'avg_launch_us': round(k['ms'] * 1e3 / max(k['launches'], 1), 2),
+                        'achieved': round(tf(k['issued'], k['ms']), 2),
+                        'frac': round(tf(k['issued'], k['ms']) * dom_terms / dom_peak, 4),
+                        'all_conv_ms_per_step': round(sum(v['ms'] for v in by_kernel_overlapped.values()), 3),
+                        'measured_in': 'a warm-up step with steps queued before and behind it' if overlapped_in_warmup else 'a mid-run timed step',
+                        'what': 'per-launch durations while another episode runs on the second caller stream: '
+                                'not a kernel-quality figure'})(by_kernel_overlapped.get(dom_name)),
+                    # every MFMA FLOP issued in a step over the wall time of a step (all kernels, all gaps)
+                    'whole_step': {'issued_gflop': round(tot['issued'] / 1e9, 1),
+                                   'tflops': round(tot['issued'] / (dt / args.steps) / 1e12, 2),
+                                   'frac': round(tot['issued'] / (dt / args.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)},
+                    'all_conv_launches': {
+                        'what': 'every convolution-family kernel of a step (implicit-GEMM kernels, Winograd transforms, '
+                                'split-K reduces)',
+                        'ms_per_step': round(tot['ms'] / n_prof_steps, 3),
+                        'launches_per_step': tot['launches'] / n_prof_steps,
+                        'issued_gflop_per_step': round(tot['issued'] / n_prof_steps / 1e9, 1),
+                        'issued_tflops': round(tf(tot['issued'], tot['ms']), 2),
+                        'issued_frac': round(tf(tot['issued'], tot['ms']) / PEAK_FP32_MFMA_TFLOPS, 4),
+                        'direct_form_gflop_per_step': round(tot['direct'] / n_prof_steps / 1e9, 1),
+                        'direct_form_tflops_not_a_utilisation_figure': round(tf(tot['direct'], tot['ms']), 2)},
+                    'by_kernel': [dict(kernel=n, ms_per_step=round(k['ms'] / n_prof_steps, 3),
+                                       launches_per_step=k['launches'] / n_prof_steps,
+                                       issued_gflop_per_step=round(k['issued'] / n_prof_steps / 1e9, 1),
+                                       issued_tflops=round(tf(k['issued'], k['ms']), 1))
+                                  for n, k in sorted(by_kernel.items(), key=lambda kv: -kv[1]['ms'])]}
 
     if rank == 0:
         R = cfg['test_cfg']['rpn']['max_per_img']
@@ -789,71 +914,10 @@ def main():
                        'reference_formulation_gflop_per_episode': round(gflop, 1),
                        'reference_formulation_tflops_not_a_utilisation_figure':
                            round(gflop * world * args.steps * args.batch / dt / 1e3, 2)},
-            # frac = MFMA FLOPs the dominant kernel actually ISSUED / its summed HIP-event launch durations / peak.
-            # Reproducible from profiles/rNN_kernel_stats.csv: flop_per_step * steps / TotalDurationNs of `kernel`.
-            'roofline': {'bound': 'mfma', 'kernel': dom_name,
-                         'achieved': round(achieved, 2), 'peak': dom_peak, 'unit': 'TFLOP/s',
-                         'frac': round(achieved / dom_peak, 4),
-                         'traffic': traffic,
-                         'mfma': ('v_mfma_f32_16x16x32_f16: %d f16 products per f32 product of the GEMM (two-way splits of the '
-                                  'power-of-two scaled f32 operands, f32 accumulation); achieved / peak are f16 MFMA FLOP/s' % H2_TERMS)
-                                 if dom_name.startswith('conv_pw_h2_kernel') else
-                                 ('v_mfma_f32_16x16x32_bf16: %d bf16 products per f32 product of the GEMM (exact 3-way splits of '
-                                  'both f32 operands, f32 accumulation); achieved / peak are bf16 MFMA FLOP/s' % X3_TERMS) if dom_x3
-                                 else 'v_mfma_f32_16x16x4_f32 (f32 operands)',
-                         # the GEMM's own (f32) products per second, and against the f32-input MFMA peak this kernel no
-                         # longer runs on - above 1.0 means faster than any f32-MFMA kernel could be
-                         'f32_equivalent_tflops': round(achieved / dom_terms, 2),
-                         'f32_equivalent_over_f32_mfma_peak': round(achieved / dom_terms / PEAK_FP32_MFMA_TFLOPS, 4),
-                         'flop_per_step': round(dom['issued'] / n_prof_steps),
-                         'launches_per_step': dom['launches'] / n_prof_steps,
-                         'avg_launch_us': round(dom['ms'] * 1e3 / max(dom['launches'], 1), 2),
-                         'kernel_ms_per_step': round(dom['ms'] / n_prof_steps, 3),
-                         'share_of_conv_time': round(dom['ms'] / tot['ms'], 3) if tot['ms'] else None,
-                         # `frac` is the average over ALL launches of the kernel; split by the bound a launch has on
-                         # paper (arithmetic intensity against 157.3 TF/s / 8 TB/s): the MFMA-bound ones against the
-                         # MFMA peak, the output-bound 1x1 convolutions of layer1 / layer2 against the HBM peak
-                         'launch_classes': launch_classes(records_med, dom_name),
-                         'profiled_steps': n_prof_steps,
-                         'timing': 'start/stop HIP events stamped by each launch of the kernel itself (hipExtLaunchKernelGGL) on '
-                                   'its own stream, in the isolated timed step(s) below: queued behind the episodes in flight '
-                                   'on the GPU (no idle chip in front of them), no other episode beside them (their own side '
-                                   'stream only).  With several isolated steps this is the MEDIAN one',
-                         'isolated_steps': iso_table,
-                         'frac_min_max_over_isolated_steps': ([min(r_['frac'] for r_ in iso_table), max(r_['frac'] for r_ in iso_table)]
-                                                              if iso_table else None),
-                         'timed_window': window,
-                         # the same kernel in a mid-run step, while two episodes overlap on the two caller streams (the
-                         # way the other steps run): launches share the CUs with another episode's kernels
-                         'overlapped': (lambda k: None if not k or not k['ms'] else {
-                             'avg_launch_us': round(k['ms'] * 1e3 / max(k['launches'], 1), 2),
-                             'achieved': round(tf(k['issued'], k['ms']), 2),
-                             'frac': round(tf(k['issued'], k['ms']) * dom_terms / dom_peak, 4),
-                             'all_conv_ms_per_step': round(sum(v['ms'] for v in by_kernel_overlapped.values()), 3),
-                             'measured_in': 'a warm-up step with steps queued before and behind it' if overlapped_in_warmup else 'a mid-run timed step',
-                             'what': 'per-launch durations while another episode runs on the second caller stream: '
-                                     'not a kernel-quality figure'})(by_kernel_overlapped.get(dom_name)),
-                         # every MFMA FLOP issued in a step over the wall time of a step (all kernels, all gaps)
-                         'whole_step': {'issued_gflop': round(tot['issued'] / 1e9, 1),
-                                        'tflops': round(tot['issued'] / (dt / args.steps) / 1e12, 2),
-                                        'frac': round(tot['issued'] / (dt / args.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)},
-                         'all_conv_launches': {
-                             'what': 'every convolution-family kernel of a step (implicit-GEMM kernels, Winograd transforms, '
-                                     'split-K reduces)',
-                             'ms_per_step': round(tot['ms'] / n_prof_steps, 3),
-                             'launches_per_step': tot['launches'] / n_prof_steps,
-                             'issued_gflop_per_step': round(tot['issued'] / n_prof_steps / 1e9, 1),
-                             'issued_tflops': round(tf(tot['issued'], tot['ms']), 2),
-                             'issued_frac': round(tf(tot['issued'], tot['ms']) / PEAK_FP32_MFMA_TFLOPS, 4),
-                             'direct_form_gflop_per_step': round(tot['direct'] / n_prof_steps / 1e9, 1),
-                             'direct_form_tflops_not_a_utilisation_figure': round(tf(tot['direct'], tot['ms']), 2)},
-                         'by_kernel': [dict(kernel=n, ms_per_step=round(k['ms'] / n_prof_steps, 3),
-                                            launches_per_step=k['launches'] / n_prof_steps,
-                                            issued_gflop_per_step=round(k['issued'] / n_prof_steps / 1e9, 1),
-                                            issued_tflops=round(tf(k['issued'], k['ms']), 1))
-                                       for n, k in sorted(by_kernel.items(), key=lambda kv: -kv[1]['ms'])]},
         }
-        if world > 1 and 'g' in gathered_last:
+        if roofline is not None:
+            out['roofline'] = roofline
+        if args.full and world > 1 and 'g' in gathered_last:
             # rank 0 holds every rank's detections of the last step incl. the mask probabilities: materialise the
             # complete result dicts of all `world` episodes from the gathered records (off the timed path) and
             # check rank 0's own episode against the dict its normal path produced
@@ -868,7 +932,7 @@ def main():
                     bool((mine['dt_scores'] == last_results[0]['dt_scores']).all()))
             out['gather'] = {'episodes_materialised_on_rank0': len(full), 'bytes_per_episode': int(g_recs[0, 0].numel() * 4 + 4),
                              'rank0_episode_identical_to_local_result': same}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out.update(cpu_and_accuracy(args, cfg, sd, shape, model))
         print(json.dumps(out), flush=True)
     if world > 1:

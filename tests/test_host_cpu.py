@@ -534,7 +534,7 @@ def test_backbone_only_pretrained_checkpoint_loads_into_backbone_only(tmp_path):
     assert any('mask_thr_binary' in str(x.message) for x in w)
 
 
-def test_rank_placement_from_a_kfd_topology(tmp_path):
+def test_rank_placement_from_a_kfd_topology(tmp_path, monkeypatch):
     """bench.pin_rank: ranks are pinned to the cores local to their GPU (sysfs ``local_cpulist`` of the GPU's DRM render
     node, found through the KFD topology), split evenly among the ranks whose GPUs share that list; a node without
     locality information falls back to an even split of the allowed cores.  Fake sysfs tree: 2 CPU nodes + 4 GPUs."""
@@ -543,6 +543,8 @@ def test_rank_placement_from_a_kfd_topology(tmp_path):
     allowed = sorted(os.sched_getaffinity(0))
     if len(allowed) < 4:
         pytest.skip('needs 4 cores')
+    for var in ('HIP_VISIBLE_DEVICES', 'ROCR_VISIBLE_DEVICES'):     # the fake box's 4 GPUs, not the caller's device filter
+        monkeypatch.delenv(var, raising=False)
     half = len(allowed) // 2
     lists = [allowed[:half], allowed[half:]]
     fmt = lambda cpus: ','.join(str(c) for c in cpus)
@@ -560,6 +562,9 @@ def test_rank_placement_from_a_kfd_topology(tmp_path):
             (dev / 'numa_node').write_text(f'{(n - 2) // 2}\n')
     gpus = bench.gpu_local_cpus(str(tmp_path))
     assert [g['numa'] for g in gpus] == [0, 0, 1, 1] and gpus[0]['cpus'] == lists[0] and gpus[3]['cpus'] == lists[1]
+    with monkeypatch.context() as m:                     # a launcher's device filter keeps the listed GPUs, in its order
+        m.setenv('HIP_VISIBLE_DEVICES', '3,0')
+        assert [g['kfd_node'] for g in bench.gpu_local_cpus(str(tmp_path))] == [5, 2]
     got = [bench.pin_rank(r, 4, sysfs=str(tmp_path), apply=False) for r in range(4)]
     assert all(g['policy'] == 'gpu-local' and g['sharers'] == 2 for g in got)
     sets = [set(g['cpu_list']) for g in got]

@@ -45,7 +45,14 @@ def test_bbox_head_targets_and_loss_match_the_reference():
              pos_gt_labels=t('pos_gt_labels'))
     tg = T.bbox_targets_single(s, 3, (0., 0., 0., 0.), (0.1, 0.1, 0.2, 0.2), -1)
     for a, k in zip(tg, ('labels', 'label_weights', 'bbox_targets', 'bbox_weights')):
-        assert np.array_equal(a.numpy(), z[k]), k
+        if k == 'bbox_targets':
+            # dx, dy are IEEE add / mul / div: bit-exact on any host.  dw, dh are torch.log of a float32 ratio, which x86
+            # torch takes from MKL's vector math, and MKL picks its code path per CPU: its AVX2 path gives 1 ulp more or
+            # less than the AVX-512 path the golden was recorded on in 1-2 of these 32 rows.  Those two columns: 1 ulp
+            assert np.array_equal(a.numpy()[:, :2], z[k][:, :2]), k
+            np.testing.assert_array_max_ulp(a.numpy()[:, 2:], z[k][:, 2:], maxulp=1)
+        else:
+            assert np.array_equal(a.numpy(), z[k]), k
     L = T.bbox_loss(t('cls_score'), t('bbox_pred'), *tg, 3)
     assert float(L['loss_cls']) == pytest.approx(float(z['loss_cls']), rel=1e-6)
     assert float(L['loss_bbox']) == pytest.approx(float(z['loss_bbox']), rel=1e-6)

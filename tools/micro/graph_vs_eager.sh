@@ -4,7 +4,7 @@
 set -uo pipefail
 B=${1:-4}; OUT=${2:-gpurun_out/gve}; mkdir -p "$OUT"; ROOT=$(pwd)
 for m in graphs no-graphs; do
-  ( cd /tmp && export TMPDIR=/tmp && rm -rf "$ROOT/$OUT/$m" && rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/$m" --output-format csv -- python3 "$ROOT/bench.py" --workload cfg4 --batch "$B" --steps 12 --warmup 3 --no-cpu-baseline --$m --streams 1 --inflight 1 > "$ROOT/$OUT/$m.log" 2>&1 )
+  ( cd /tmp && export TMPDIR=/tmp && rm -rf "$ROOT/$OUT/$m" && rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/$m" --output-format csv -- python3 "$ROOT/bench.py" --workload cfg4 --batch "$B" --steps 12 --warmup 3 --full --no-cpu-baseline --$m --streams 1 --inflight 1 > "$ROOT/$OUT/$m.log" 2>&1 )
   cp "$OUT/$m"/*/*kernel_stats.csv "$OUT/${m}_kernel_stats.csv" 2>/dev/null
   grep '^{' "$OUT/$m.log" | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$m', round(d['value'],1), 'img/s', round(d['ms_per_step'],2), 'ms/step')"
   rm -rf "$OUT/$m"

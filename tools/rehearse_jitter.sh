@@ -11,7 +11,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/jitter_$R; mkdir -p "$OUT"; cd "$GRAFT_REPO_ROOT
 last_json() { grep '^{' "$1" | tail -1; }
 run() {  # name, env...
   name=$1; shift
-  env FGN_BENCH_BACKEND=gloo "$@" timeout -k 10 400 python bench.py --gpus 5 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/$name.out" 2> "$OUT/$name.err" || { echo "$name failed"; tail -5 "$OUT/$name.err"; return 1; }
+  env FGN_BENCH_BACKEND=gloo "$@" timeout -k 10 400 python bench.py --gpus 5 --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/$name.out" 2> "$OUT/$name.err" || { echo "$name failed"; tail -5 "$OUT/$name.err"; return 1; }
   last_json "$OUT/$name.out" > "$OUT/$name.json"
   python - "$OUT/$name.json" "$name" <<'PY'
 import json, sys

@@ -16,7 +16,7 @@ ROOT=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 OUT=$ROOT/gpurun_out/trace_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --memory-copy-trace -d "$OUT/kt" --output-format csv -- python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline "$@" > "$OUT/bench.log" 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace -d "$OUT/kt" --output-format csv -- python3 "$ROOT/bench.py" --steps 10 --warmup 2 --full --no-cpu-baseline "$@" > "$OUT/bench.log" 2>&1
 python3 "$ROOT/tools/timeline.py" "$OUT/kt" > "$ROOT/gpurun_out/timeline_$TAG.txt"
 rm -rf "$OUT/kt"
 tail -1 "$OUT/bench.log" | cut -c1-200
