@@ -18,7 +18,9 @@
 //    32 RB x 32 fragment holds a non-zero element sets S so that the fragment's largest |x| lands in [2^13, 2^14); every
 //    later K-tile is looked at once (max |x| of the raw fragment against 65504 / S: `v_max3_f32` with |.| modifiers, 0.25 vector instruction per element),
 //    and one that would leave the f16 range - an element 4x .. 8x above what S was chosen for - picks a new S from its
-//    own maximum and multiplies the accumulators by the ratio (a power of two: exact).  S comes out of the accumulators
+//    own maximum and multiplies the accumulators by the ratio (a power of two: exact); the maxima are those of the
+//    FINITE elements (a row holding Inf / NaN comes out non-finite and leaves the other rows' scale alone: they keep the
+//    bits they have with that element replaced by zero).  S comes out of the accumulators
 //    when they go to the C tile.  An element within 2^15 of the maximum S was chosen for keeps both planes at full
 //    precision; a smaller one loses low bits of its l plane (f16 subnormals): an absolute error below 2^-38 of that
 //    maximum per element.  The splits are scale-invariant otherwise: row tiles / stage counts differ only through such
@@ -342,19 +344,25 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
                 for (int q = 0; q < 2; ++q)
                     bq[j][q] = *reinterpret_cast<const f16x8_t*>(S + b16_rd + j * (16 * 64) + q * (BN * 64));
             __builtin_amdgcn_sched_barrier(0);       // every read of the K-tile in flight before the first split
-            // a new scale from the maximum of this K-tile's fragment (wave-uniform); the accumulators follow it
+            // a new scale from the maximum of this K-tile's fragment (wave-uniform); the accumulators follow it.  Only finite
+            // elements count: a row holding Inf / NaN comes out non-finite whatever the scale, and must not take the scale of
+            // the wave's other rows with it (Inf would leave them at the old scale - or at 1 - however large or small they are)
             auto adapt = [&]() {
+                auto fin = [](const float v) { const float a = fabsf(v); return a < __builtin_inff() ? a : 0.f; };   // NaN: 0
                 float m = 0.f;
 #pragma unroll
                 for (int i = 0; i < 2 * RB; ++i) {
-                    m = fmaxf(m, fmaxf(fmaxf(fabsf(alo[i].x), fabsf(alo[i].y)), fmaxf(fabsf(alo[i].z), fabsf(alo[i].w))));
-                    m = fmaxf(m, fmaxf(fmaxf(fabsf(ahi[i].x), fabsf(ahi[i].y)), fmaxf(fabsf(ahi[i].z), fabsf(ahi[i].w))));
+                    m = fmaxf(m, fmaxf(fmaxf(fin(alo[i].x), fin(alo[i].y)), fmaxf(fin(alo[i].z), fin(alo[i].w))));
+                    m = fmaxf(m, fmaxf(fmaxf(fin(ahi[i].x), fin(ahi[i].y)), fmaxf(fin(ahi[i].z), fin(ahi[i].w))));
                 }
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
                 const unsigned mb = __builtin_amdgcn_readfirstlane(__float_as_uint(m));
                 const int e = (int)((mb >> 23) & 0xffu);
-                if (e < 27 || e == 255) return;             // all zero (or tiny / non-finite): keep the scale
+                if (e < 27) return;                         // all zero (or tiny, or nothing finite): keep the scale
+                // the finite elements fit the scale the wave has (only a non-finite one sent it here): keep it.  (A finite
+                // fragment comes here only with an element above a_lim: this never returns for one, its bits are unchanged.)
+                if (have_s && __uint_as_float(mb) <= a_lim) return;
                 const float ns = __uint_as_float((unsigned)(267 - e) << 23);         // 2^(13 - (e - 127))
                 const float ratio = ns * a_inv;                                      // new / old, a power of two
                 if (have_s) {

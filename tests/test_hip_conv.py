@@ -28,6 +28,19 @@ def _nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
 
+def _route(fn):
+    """Run ``fn`` under a ConvProfile -> (its result, the arithmetic its MFMA launches ran on: 'h2' / 'x3' / 'f32' each) -
+    the routing rules leave launches too small for the GEMM kernels' tiles to the f32 kernels whatever GEMM_MATH says."""
+    from fgn_amd import ops
+    prev, ops.PROFILE = ops.PROFILE, ops.ConvProfile()
+    try:
+        out = fn()
+        maths = [r.get('math', 'f32') for r in ops.PROFILE if r['kind'] in ('conv', 'wg_gemm')]
+    finally:
+        ops.PROFILE = prev
+    return out, maths
+
+
 CASES = [
     # n, cin, h, w, cout, k, stride, pad, bn, bias, residual, relu
     (2, 64, 17, 23, 64, 1, 1, 0, True, False, False, True),
@@ -190,7 +203,8 @@ def test_persistent_pointwise_kernel_matches_fp64_and_the_one_tile_kernel(rows, 
     rc = None if r is None else r.cuda().view(1, rows, 1, cout)
     L = lib.load()
     assert L.fgn_conv2d_kernel_id(1, rows, 1, cin, cout, layer.cout_pad, 1, 1, 1, 0, 1, 0, int(res), 0) % 10 == 4
-    y = ops.conv2d(xc, layer, residual=rc)
+    y, route = _route(lambda: ops.conv2d(xc, layer, residual=rc))
+    assert route == ['f32' if cout == 260 else math], route         # (Cout 260: too much column padding for either)
     sc = bn['weight'].double() / torch.sqrt(bn['running_var'].double() + 1e-5)
     ref = (x.double() @ wt.reshape(cout, cin).double().T) * sc + (bn['bias'].double() - bn['running_mean'].double() * sc)
     if r is not None:
@@ -234,7 +248,8 @@ def test_two_tensor_launch_equals_one_launch_per_tensor(cin, cout, k, stride, ma
     if cin == 4:
         xq[..., 3] = 0
         xs[..., 3] = 0
-    yq, ys = ops.conv2d_pair(xq, xs, layer)
+    (yq, ys), route = _route(lambda: ops.conv2d_pair(xq, xs, layer))
+    assert route == ['h2' if h2 else 'f32'], route
     L = lib.load()
     sc = bn['weight'].double() / torch.sqrt(bn['running_var'].double() + 1e-5)
     for x, y in ((xq, yq), (xs, ys)):
@@ -304,7 +319,11 @@ def test_dual_operand_pointwise_conv_is_conv3_plus_shortcut(rows, cin1, cin2, co
         layer = ops.pack_conv_dual(w3, bn3, wd, bnd, relu=True).to('cuda')
         assert (layer.w3 is not None) == ops._x3_ok(cin1 + cin2, cout)
     yc, xc = y.cuda().view(1, rows, 1, cin1), x.cuda().view(1, rows, 1, cin2)
-    got = ops.conv1x1_dual(yc, xc, layer)
+    got, route = _route(lambda: ops.conv1x1_dual(yc, xc, layer))
+    # only the layer1.0 shape reaches the GEMM kernels' tiles: Cout 132 pads its 128-column tiles too much, 777 rows are
+    # too few - those two run on the f32 kernel under every math (the strided production launches on h2:
+    # tests/test_hip_launches.py::test_strided_dual_launch_on_h2_at_production_size)
+    assert route == [math if rows == 103664 else 'f32'], route
     assert tuple(got.shape) == (1, rows, 1, cout)
     assert (got.view(rows, cout).cpu().double() - ref).abs().max().item() <= 2e-5 * ref.abs().max().item()
     with ops.gemm_math('f32'):
@@ -319,7 +338,8 @@ def test_dual_operand_pointwise_conv_is_conv3_plus_shortcut(rows, cin1, cin2, co
 def test_dual_operand_conv_with_a_strided_shortcut(math):
     """The 1x1 / stride 2 shortcut of layer2.0 / layer3.0 inside conv3's K loop: output row m reads row x2_rows[m] of the
     stage's input (``ops.strided_rows`` over the query map and the support maps lying one behind the other) - against the
-    two-launch form (strided shortcut conv, then conv3 with the residual in its epilogue) and fp64."""
+    two-launch form (strided shortcut conv, then conv3 with the residual in its epilogue) and fp64.  At 262 rows the
+    launch is below the GEMM kernels' tile rule: it runs on the f32 kernel whatever the math (asserted)."""
     from fgn_amd import ops
     g = torch.Generator().manual_seed(5)
     cin1, cin2, cout = 64, 96, 128
@@ -336,7 +356,9 @@ def test_dual_operand_conv_with_a_strided_shortcut(math):
     with ops.gemm_math(math):
         layer = ops.pack_conv_dual(w3, bn3, wd, bnd, relu=True).to('cuda')
     yc = y.cuda().view(1, rows, 1, cin1)
-    got = ops.conv1x1_dual(yc, buf.view(1, -1, 1, cin2), layer, x2_rows=rows_tab)
+    got, route = _route(lambda: ops.conv1x1_dual(yc, buf.view(1, -1, 1, cin2), layer, x2_rows=rows_tab))
+    assert route == ['f32'], route       # 262 rows: the f32 kernel under either math (h2 / x3 at production size:
+    #                                      tests/test_hip_launches.py::test_strided_dual_launch_on_h2_at_production_size)
     with ops.gemm_math('f32'):
         down = ops.pack_conv(wd, bn=bnd, stride=2).to('cuda')
         idt = torch.cat([ops.conv2d(q.cuda(), down).reshape(-1, cout), ops.conv2d(s_.cuda(), down).reshape(-1, cout)])

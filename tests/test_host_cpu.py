@@ -1014,28 +1014,39 @@ def test_h2_per_wave_scale_search_is_exact_in_the_scales():
     above 65504 / S picks a new S from its own maximum and the accumulator is multiplied by the power-of-two ratio; all-zero
     K-tiles pass as they are; S comes out at the end).  On fragments whose K-tiles differ by orders of magnitude in both
     directions the result stays within f32 accuracy of fp64, no plane ever leaves the f16 range, and the number of scale
-    changes is what the rule predicts."""
+    changes is what the rule predicts.  Only finite elements choose a scale: a row holding +-Inf or NaN comes out
+    non-finite, and every other row of the wave keeps the bits it has with that element replaced by zero - also where the
+    non-finite element sits in the K-tile that must raise the scale.  (The rule before it, the maximum over all elements
+    with Inf meaning "keep the scale", leaves the other rows at the scale of 1 or of earlier K-tiles: they overflow.)"""
     import numpy as np
     rng = np.random.default_rng(3)
 
-    def run(x, w):                                   # x [rows, K] f32 (one wave's rows), w [K, n] f16-exact weights (scaled)
+    def run(x, w, finite_only=True):                 # x [rows, K] f32 (one wave's rows), w [K, n] f16-exact weights (scaled)
         acc = np.zeros((x.shape[0], w.shape[1]), np.float32)
         s, inv, lim, have, changes = np.float32(1), np.float32(1), np.float32(0), False, 0
         wh = w.astype(np.float16).astype(np.float32)
         wl = (w - wh).astype(np.float16).astype(np.float32)
         for k0 in range(0, x.shape[1], 32):
             f = x[:, k0:k0 + 32]
-            big = np.abs(f).max()
-            if not (big <= lim):
-                e = int(np.floor(np.log2(big)))
-                ns = np.float32(2.0 ** (13 - e))
-                if have:
-                    acc *= ns * inv                  # a power of two: exact
-                    changes += 1
-                s, inv, lim, have = ns, np.float32(2.0 ** (e - 13)), np.float32(65504.0 * 2.0 ** (e - 13)), True
+            a = np.abs(f)
+            if not (np.nanmax(a) <= lim) or np.isnan(a).any():       # the per-K-tile look (NaN: the kernel may or may not stop)
+                if finite_only:
+                    big = a[np.isfinite(a)].max(initial=0.0)         # adapt(): finite elements only
+                    keep = big < 2.0 ** -100 or (have and big <= lim)
+                else:
+                    big = np.nanmax(a)                                # the rule before: Inf keeps the scale
+                    keep = big < 2.0 ** -100 or not np.isfinite(big)
+                if not keep:
+                    e = int(np.floor(np.log2(big)))
+                    ns = np.float32(2.0 ** (13 - e))
+                    if have:
+                        acc *= ns * inv              # a power of two: exact
+                        changes += 1
+                    s, inv, lim, have = ns, np.float32(2.0 ** (e - 13)), np.float32(65504.0 * 2.0 ** (e - 13)), True
             fs = f * s
             h = fs.astype(np.float16)
-            assert np.isfinite(h).all()              # never leaves the f16 range
+            if finite_only:
+                assert np.isfinite(h[np.isfinite(f)]).all()          # never leaves the f16 range
             hf = h.astype(np.float32)
             lo = (fs - hf).astype(np.float16).astype(np.float32)
             kw_h, kw_l = wh[k0:k0 + 32], wl[k0:k0 + 32]
@@ -1055,3 +1066,24 @@ def test_h2_per_wave_scale_search_is_exact_in_the_scales():
         scale = np.abs(ref).max()
         assert changes == expect, (mags, changes)
         assert np.abs(got - ref).max() <= max(3e-7 * scale, 2.0 * np.abs(f32 - ref).max()), mags
+    # a non-finite element in one row: that row only.  Rows at 1e5 and 1e-4 (S != 1), the element in the first K-tile, or in
+    # K-tile 3 that also raises the other rows 1e3-fold (the wave must pick a new scale exactly there)
+    x = np.maximum(rng.standard_normal((32, K)), 0).astype(np.float32)
+    x[:16] *= np.float32(1e5)
+    x[16:] *= np.float32(1e-4)
+    x[:, 96:128] *= np.float32(1e3)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for bad in (np.inf, -np.inf, np.nan):
+            for r, k in ((5, 3), (20, 100)):
+                xb, x0 = x.copy(), x.copy()
+                xb[r, k], x0[r, k] = bad, 0.0
+                got, _ = run(xb, w)
+                zero, _ = run(x0, w)
+                others = np.arange(32) != r
+                assert not np.isfinite(got[r]).any(), (bad, r, k)
+                assert np.array_equal(got[others], zero[others]), (bad, r, k)
+                ref = x0[others].astype(np.float64) @ w.astype(np.float64)
+                assert np.abs(got[others] - ref).max() <= 3e-7 * np.abs(ref).max(), (bad, r, k)
+                if bad == np.inf:
+                    old, _ = run(xb, w, finite_only=False)
+                    assert not np.isfinite(old[others]).all(), (r, k)      # what the finite-only rule fixes
