@@ -420,14 +420,14 @@ extern "C" int fgn_relation_gn_head_backward_f32(const float* Q, const float* S,
                                                  float* dQ, float* dZ, float* pooled, float* dgamma_part,
                                                  float* dbeta_part, int n_rois, int n_ways, int C, int gn_groups,
                                                  int roi_size, float eps, hipStream_t stream) {
-    if (!Q || !S || !rois || !gn_weight || !gn_bias || !fc_weight || !d_out6 || !dQ || !dZ || !pooled || !dgamma_part ||
-        !dbeta_part)
-        return FGN_ERR_ARG;
-    if (roi_size != 7 || gn_groups <= 0 || C % 32 != 0 || C % gn_groups != 0 || n_ways < 1 || n_ways > RELB_MAX_N)
+    // (the per-RoI operands of an empty RoI set are null pointers: nothing is read or written then)
+    if (!S || !gn_weight || !gn_bias || !fc_weight) return FGN_ERR_ARG;
+    if (n_rois > 0 && (!Q || !rois || !d_out6 || !dQ || !dZ || !pooled || !dgamma_part || !dbeta_part)) return FGN_ERR_ARG;
+    if (roi_size != 7 || gn_groups <= 0 || C <= 0 || C % 32 != 0 || C % gn_groups != 0 || n_ways < 1 || n_ways > RELB_MAX_N)
         return FGN_ERR_SHAPE;
     const int gw = C / gn_groups;
     if (gw != 8 && gw != 16 && gw != 32) return FGN_ERR_SHAPE;
-    if (n_rois == 0) return FGN_OK;
+    if (n_rois <= 0) return FGN_OK;
     hipLaunchKernelGGL(relation_head_backward_kernel, dim3(n_rois), dim3(64 * RELB_WAVES), 0, stream, Q, S, rois,
                        gn_weight, gn_bias, fc_weight, d_out6, dQ, dZ, pooled, dgamma_part, dbeta_part, n_rois, n_ways, C,
                        gw, eps);
@@ -467,6 +467,7 @@ __global__ __launch_bounds__(256) void mask_logits_backward_kernel(const float* 
 extern "C" int fgn_mask_logits_backward_f32(const float* up, const float* dlogit, const float* w, float* d_up,
                                             float* dw_part, int n_det, int roi_size, int C, hipStream_t stream) {
     if (n_det > 0 && (!up || !dlogit || !w || !d_up || !dw_part)) return FGN_ERR_ARG;
+    if (roi_size <= 0 || C <= 0) return FGN_ERR_SHAPE;
     if (n_det <= 0) return FGN_OK;
     hipLaunchKernelGGL(mask_logits_backward_kernel, dim3(n_det), dim3(256), 0, stream, up, dlogit, w, d_up, dw_part,
                        roi_size, C);

@@ -1663,7 +1663,7 @@ def mask_logits_backward(up: torch.Tensor, dlogit: torch.Tensor, w: torch.Tensor
     _chk(dlogit, 'dlogit')
     _chk(w, 'w')
     d, c = up.shape[0], w.numel()
-    if up[0].numel() != roi_size * roi_size * 4 * c or tuple(dlogit.shape) != (d, 2 * roi_size, 2 * roi_size):
+    if up.numel() != d * roi_size * roi_size * 4 * c or tuple(dlogit.shape) != (d, 2 * roi_size, 2 * roi_size):
         raise _lib.FgnHipError('mask_logits_backward: operand shapes inconsistent')
     d_up = torch.empty_like(up)
     part = torch.empty((d, c), device=up.device, dtype=torch.float32)

@@ -619,14 +619,13 @@ def backward(model, W: dict, tape: dict) -> dict:
     return grads
 
 
-def _backward_roi_stage(model, W: dict, tape: dict, grads: dict) -> None:
-    cfg = model.cfg
-    N, K = model.n_ways, model.k_shots
-    P = model._P
-    rh = cfg['roi_head']
+def _backward_mask_head(model, W: dict, tape: dict, grads: dict):
+    """The mask head (fgn_roi_head.py:360-417) backwards: its weight gradients go into ``grads``; -> (the gradient that
+    reaches ``feats`` [n_rois,7,7,C], the gradient of the masked-pooled class vectors ``cat_mean_mp`` [B*N,C]), or
+    (None, None) when the step sampled no positive RoI."""
+    N = model.n_ways
+    rh = model.cfg['roi_head']
     dev = tape['roi']['rois'].device
-
-    # ---- mask head (fgn_roi_head.py:360-417) ------------------------------------------------------------
     tr_, tm = tape['roi'], tape['mask']
     feats = tr_['feats']
     d_feats = None
@@ -666,6 +665,19 @@ def _backward_roi_stage(model, W: dict, tape: dict, grads: dict) -> None:
         for r_ in np.unique(tm['rows_h']):
             sel = _dev_idx(np.flatnonzero(tm['rows_h'] == r_), dev, model)
             ops.colsum(d_vmask[sel].contiguous(), out=d_cat_mean_mp[int(r_)])
+    return d_feats, d_cat_mean_mp
+
+
+def _backward_roi_stage(model, W: dict, tape: dict, grads: dict) -> None:
+    cfg = model.cfg
+    N, K = model.n_ways, model.k_shots
+    P = model._P
+    rh = cfg['roi_head']
+    dev = tape['roi']['rois'].device
+    tr_ = tape['roi']
+    feats = tr_['feats']
+    C = feats.shape[-1]
+    d_feats, d_cat_mean_mp = _backward_mask_head(model, W, tape, grads)
 
     # ---- box head losses -> relation head (fgn_roi_head.py:58-118, 253-279, 302-326) ---------------------
     n = tr_['n_rois']

@@ -417,7 +417,7 @@ int fgn_relation_gn_head_backward_f32(const float* Q, const float* S, const floa
                                       int n_ways, int C, int gn_groups, int roi_size, float eps, void* stream);
 
 /* Backward of fgn_mask_logits_f32 (ReLU(deconv) -> conv_logits): up [D,P*P,4,C], dlogit [D,2P,2P] ->
- * d_up (through the ReLU) and dw_part [D,C] (column-summed by the caller) */
+ * d_up (through the ReLU) and dw_part [D,C] (column-summed by the caller); roi_size > 0 and C > 0 */
 int fgn_mask_logits_backward_f32(const float* up, const float* dlogit, const float* w, float* d_up, float* dw_part,
                                  int n_det, int roi_size, int C, void* stream);
 
