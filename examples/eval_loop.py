@@ -5,6 +5,7 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
 
     python examples/eval_loop.py --episodes 8 --batch 2 --height 320 --width 480
     python examples/eval_loop.py --dataset OMNIISEG --episodes 16 --n-ways 3 --k-shots 1     (cfg2-shaped)
+    python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --uint8      (decoded pixels in, normalised on the GPU)
 """
 import argparse
 import os
@@ -31,14 +32,21 @@ def main():
     ap.add_argument('--width', type=int, default=1333)
     ap.add_argument('--dataset', default='SYNTH', choices=['SYNTH', 'MNISTISEG', 'OMNIISEG'])
     ap.add_argument('--checkpoint', default=None, help='mmcv checkpoint of a trained reference FGN')
+    ap.add_argument('--uint8', action='store_true',
+                    help='character datasets: the loader yields uint8 pixels, the detector normalises them on the GPU')
     args = ap.parse_args()
+    if args.uint8 and args.dataset == 'SYNTH':
+        ap.error('--uint8 needs --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
 
     if args.dataset == 'SYNTH':
         ds = SyntheticFewShotISEG(args.n_ways, args.k_shots, args.episodes, args.height, args.width, batch=args.batch)
     else:       # cluttered characters: 128^2 (MNISTISEG, cfg1) / 256^2 (OMNIISEG, cfg2) queries, 128^2 supports
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
-                                       img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch)
+                                       img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,
+                                       raw_uint8=args.uint8)
     model = FGN(args.n_ways, args.k_shots)
+    if args.uint8:
+        model.set_input_norm(**ds.input_norm)
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'))
     loader = DataLoader(ds, batch_size=ds.batch, num_workers=2, collate_fn=collate)

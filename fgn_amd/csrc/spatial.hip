@@ -32,6 +32,58 @@ extern "C" int fgn_nchw3_to_nhwc4_f32(const float* x, float* y, int n_img, int H
 }
 
 // ----------------------------------------------------------------------------------
+// uint8 channels-last [n,H,W,3] -> NHWC4 [n,H,W,4] fp32, normalised: the same tensor nchw3_to_nhwc4_kernel makes of the
+// host-normalised NCHW image (ToTensor + Normalize of the reference's data loader, mnistiseg_ds.py:69-70, moved behind
+// the upload).  y = {lut[0][r], lut[1][g], lut[2][b], +0}: the per-channel table holds the host's own
+// ((v / scale - mean) / std) for the 256 byte values, so the result does not depend on how the device rounds a division.
+// The batch is one flat pixel array; a lane takes 4 consecutive pixels: one 12-byte load (dword-aligned: three dwords)
+// and four 16-byte stores, 3 B read and 16 B written per pixel.  Pixels [4 * groups, total) - the last total % 4, or all
+// of them when x is not dword-aligned (groups = 0: a sliced view) - go one per lane.
+// The table sits in LDS (3 KB per workgroup); the lookups are ds_read_b32 at data-dependent addresses, so lanes of a
+// half-wave do meet on a bank.  Accepted: an image's bytes repeat (background) and identical addresses broadcast, and
+// the kernel waits on HBM stores, 64 B per lane and group, not on the LDS.
+// ----------------------------------------------------------------------------------
+constexpr int U8_BLOCK = 256;
+constexpr int U8_GRID_CAP = 256 * 8;      // workgroups; more 4-pixel groups than U8_GRID_CAP * U8_BLOCK take further passes
+__global__ __launch_bounds__(U8_BLOCK) void u8hwc3_to_nhwc4_kernel(const uint8_t* __restrict__ x,
+                                                                   const float* __restrict__ lut,
+                                                                   float4* __restrict__ y, long long groups,
+                                                                   long long total) {
+    __shared__ float t[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += U8_BLOCK) t[i] = lut[i];
+    __syncthreads();
+    const long long first = blockIdx.x * (long long)U8_BLOCK + threadIdx.x, step = (long long)gridDim.x * U8_BLOCK;
+    const uint3* x12 = reinterpret_cast<const uint3*>(x);
+    for (long long g = first; g < groups; g += step) {
+        const uint3 w = x12[g];           // bytes r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+        float4* o = y + 4 * g;
+        o[0] = make_float4(t[w.x & 255u], t[256 + ((w.x >> 8) & 255u)], t[512 + ((w.x >> 16) & 255u)], 0.f);
+        o[1] = make_float4(t[w.x >> 24], t[256 + (w.y & 255u)], t[512 + ((w.y >> 8) & 255u)], 0.f);
+        o[2] = make_float4(t[(w.y >> 16) & 255u], t[256 + (w.y >> 24)], t[512 + (w.z & 255u)], 0.f);
+        o[3] = make_float4(t[(w.z >> 8) & 255u], t[256 + ((w.z >> 16) & 255u)], t[512 + (w.z >> 24)], 0.f);
+    }
+    for (long long p = 4 * groups + first; p < total; p += step) {
+        const uint8_t* s = x + 3 * p;
+        y[p] = make_float4(t[s[0]], t[256 + s[1]], t[512 + s[2]], 0.f);
+    }
+}
+
+extern "C" int fgn_u8hwc3_to_nhwc4_f32(const unsigned char* x, const float* lut, float* y, int n_img, int H, int W,
+                                       hipStream_t stream) {
+    if (!x || !lut || !y) return FGN_ERR_ARG;
+    if (n_img < 0 || H < 0 || W < 0) return FGN_ERR_SHAPE;
+    const long long total = (long long)n_img * H * W;
+    if (total == 0) return FGN_OK;
+    const long long groups = (reinterpret_cast<uintptr_t>(x) & 3u) ? 0 : total / 4;
+    const long long items = std::max(groups, total - 4 * groups);
+    const int grid = (int)std::min<long long>((items + U8_BLOCK - 1) / U8_BLOCK, U8_GRID_CAP);
+    hipLaunchKernelGGL(u8hwc3_to_nhwc4_kernel, dim3(grid), dim3(U8_BLOCK), 0, stream, x, lut,
+                       reinterpret_cast<float4*>(y), groups, total);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------
 // 3x3 / stride 2 / pad 1 max-pool, NHWC (mmdet ResNet stem; floor mode, -inf padding)
 // ----------------------------------------------------------------------------------
 __global__ void maxpool3x3s2_kernel(const float4* __restrict__ x, float4* __restrict__ y, int H, int W,

@@ -479,6 +479,8 @@ class FGN(torch.nn.Module):
         self.use_packed_transfers = True
         self.stamp_capacity = 0                   # > 0: captured graphs carry launch records of the dominant kernel (ops.read_stamps)
         self._graphs: dict = {}
+        self.input_lut: Optional[np.ndarray] = None   # [3,256] fp32 normalisation table of uint8 images (set_input_norm)
+        self._input_lut_dev = None                # (device, its copy there)
         self._streams: dict = {}                  # (role, caller stream) -> HIP stream: 'side', 'copy', 'upload'
         self._pinned: dict = {}                   # (batch, max_det, byte cap) -> list of pinned host slots
 
@@ -774,12 +776,65 @@ class FGN(torch.nn.Module):
         P['logit_w'].copy_(sd['roi_head.mask_head.conv_logits.weight'].reshape(-1))
         P['logit_b'].copy_(sd['roi_head.mask_head.conv_logits.bias'].reshape(-1)[:1])
 
+    # --- input images ---------------------------------------------------------------------
+    def set_input_norm(self, mean=None, std=None, scale: float = 255.0, lut=None) -> None:
+        """Accept decoded images: with a table set, every ``torch.uint8`` image tensor is taken as channels-last pixels
+        (``qry_img`` [B,H,W,3], ``spp_imgs`` [B,N*K,S,S,3] or [N*K,S,S,3]) and normalised on the device,
+        ``(v / scale - mean[c]) / std[c]`` through a per-channel table of the 256 byte values built here in the data
+        loader's float32 arithmetic (``ops.input_lut``) - the same bytes as the host-normalised float NCHW image, without
+        the host arithmetic and with a quarter of the upload.  Float tensors keep going the NCHW way, per tensor.
+        ``lut``: a ready [3,256] table instead of mean / std.  No arguments: back to float input only (a uint8 tensor is
+        then cast as it is, as before)."""
+        if lut is not None:
+            if mean is not None or std is not None:
+                raise ValueError('set_input_norm: give mean and std, or lut')
+            table = np.ascontiguousarray(np.asarray(lut, np.float32))
+            if table.shape != (3, 256):
+                raise ValueError(f'set_input_norm: lut must be [3,256], got {list(table.shape)}')
+        elif mean is not None:
+            if std is None:
+                raise ValueError('set_input_norm: mean needs std')
+            table = ops.input_lut(mean, std, scale)
+        elif std is not None:
+            raise ValueError('set_input_norm: std needs mean')
+        else:
+            table = None
+        self.input_lut = table
+        self._input_lut_dev = None
+        self._graphs = {}               # the table's device address is an argument of the captured launches
+
+    def _lut_on(self, dev) -> torch.Tensor:
+        if self._input_lut_dev is None or self._input_lut_dev[0] != dev:
+            self._input_lut_dev = (dev, torch.from_numpy(self.input_lut).to(dev))
+        return self._input_lut_dev[1]
+
+    def _image_dims(self, img: torch.Tensor, what: str, lead=(1,)) -> tuple:
+        """(leading dimensions, H, W) of an image tensor as given: channels-last pixels when it is uint8 and a table is
+        set (``set_input_norm``), NCHW otherwise.  ``lead``: the numbers of leading dimensions allowed."""
+        if self.input_lut is not None and img.dtype == torch.uint8:
+            if img.dim() - 3 not in lead or img.shape[-1] != 3:
+                raise ValueError(f'{what}: with set_input_norm in effect a uint8 image tensor is channels-last pixels '
+                                 f'[..,H,W,3] behind {" or ".join(str(n) for n in lead)} leading dimension(s), got '
+                                 f'{list(img.shape)}')
+            return tuple(img.shape[:-3]), int(img.shape[-3]), int(img.shape[-2])
+        return tuple(img.shape[:-3]), int(img.shape[-2]), int(img.shape[-1])
+
+    def _stem_input(self, img: torch.Tensor) -> torch.Tensor:
+        """Image batch as given (host or device) -> the NHWC4 fp32 input of the stem on the current device: uint8 pixels
+        [n,H,W,3] through the normalisation table, anything else cast to fp32 NCHW [n,3,H,W] and re-laid."""
+        dev = torch.device('cuda', torch.cuda.current_device())
+        if self.input_lut is not None and img.dtype == torch.uint8:
+            self._image_dims(img, 'image')
+            return ops.u8hwc3_to_nhwc4(img.to(dev, non_blocking=True).contiguous(), self._lut_on(dev))
+        return ops.nchw3_to_nhwc4(img.to(dev, torch.float32, non_blocking=True).contiguous())
+
     # --- stages ---------------------------------------------------------------------------
-    def extract_feat(self, img_nchw: torch.Tensor) -> torch.Tensor:
-        """ResNet-50 stages 1-3 (fgn.py:67-77): NCHW fp32 in, NHWC [B,h,w,1024] out."""
+    def extract_feat(self, img: torch.Tensor) -> torch.Tensor:
+        """ResNet-50 stages 1-3 (fgn.py:67-77): NCHW fp32 (or uint8 pixels, ``set_input_norm``) in, NHWC [B,h,w,1024]
+        out."""
         P = self._P
         bb = self.cfg['backbone']
-        x = ops.nchw3_to_nhwc4(img_nchw.contiguous())
+        x = self._stem_input(img)
         for conv, gn in P['stem']:
             x = ops.conv2d(x, conv)
             if gn is not None:
@@ -790,11 +845,11 @@ class FGN(torch.nn.Module):
                 x = blk(x)
         return x
 
-    def extract_feat_pair(self, qry_nchw: torch.Tensor, spp_nchw: torch.Tensor, phase_counter=None):
+    def extract_feat_pair(self, qry: torch.Tensor, spp: torch.Tensor, phase_counter=None):
         """Both backbone passes of an episode (fgn.py:212-215) through SHARED launches wherever a layer does not look at
         the spatial structure (``use_merged_backbone``; frozen-BN bottleneck backbones only)."""
         P = self._P
-        outs = [ops.nchw3_to_nhwc4(img.contiguous()) for img in (qry_nchw, spp_nchw)]
+        outs = [self._stem_input(img) for img in (qry, spp)]
         for conv, _ in P['stem']:
             y = [torch.empty((o.shape[0], (o.shape[1] + 2 * conv.pad - conv.kh) // conv.stride + 1,
                               (o.shape[2] + 2 * conv.pad - conv.kw) // conv.stride + 1, conv.cout), device=o.device,
@@ -881,7 +936,8 @@ class FGN(torch.nn.Module):
         """modify_input for the supports (fgn.py:79-108: H2D, YXYX -> XYXY on private copies), their
         backbone pass and the AG-RPN class vectors."""
         N, K = self.n_ways, self.k_shots
-        spp = spp_imgs.to(dev, torch.float32, non_blocking=True).reshape(B * N * K, *spp_imgs.shape[-3:])
+        self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
+        spp = spp_imgs.to(dev, non_blocking=True).reshape(B * N * K, *spp_imgs.shape[-3:])    # (dtype: _stem_input)
         b = spp_bboxes.to(dev, torch.float32, non_blocking=True).reshape(B * N * K, 4)
         spp_xyxy = torch.stack((b[:, 1], b[:, 0], b[:, 3], b[:, 2]), 1)      # no host-built index tensor: graph-capturable
         m = spp_isegmaps.to(dev, non_blocking=True).reshape(B * N * K, *spp_isegmaps.shape[-2:])
@@ -1049,8 +1105,10 @@ class FGN(torch.nn.Module):
             raise ops._lib.FgnHipError('FGN.simple_test needs a GPU: the HIP path has no CPU fallback')
         dev = torch.device('cuda', torch.cuda.current_device())
         main = torch.cuda.current_stream()
+        self._image_dims(qry_img, 'qry_img')              # (a wrong uint8 layout is refused before anything is queued)
         ins = {'qry_img': qry_img}
         if support_code is None:
+            self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
             ins.update(spp_imgs=spp_imgs, spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps)
         graphed = self.use_graphs and self.debug_trace is None and ops.PROFILE is None
         if phase_counter is None:
@@ -1130,12 +1188,12 @@ class FGN(torch.nn.Module):
         P, cfg = self._P, self.cfg
         N, K = self.n_ways, self.k_shots
         tr = self.debug_trace
-        B, _, H, W = qry_img.shape
+        (B,), H, W = self._image_dims(qry_img, 'qry_img')
         rh, rp, tc = cfg['roi_head'], cfg['rpn_head'], cfg['test_cfg']
         PS = rh['roi_out_size']
         inv_stride = 1.0 / rh['featmap_stride']
 
-        qry = qry_img.to(dev, torch.float32, non_blocking=True)
+        qry = qry_img.to(dev, non_blocking=True)              # (dtype and layout: _stem_input)
 
         # Two HIP streams: the support branch (9 small crops: low-occupancy launches) runs beside
         # the query branch, and its RoI/shared-head/reduction tail runs beside the single-workgroup

@@ -213,15 +213,18 @@ class ClutteredCharsFewShotISEG(Dataset):
     instance each with the reference's crop geometry (``support_from_instance``: offset ratio from fill ratio 0.8,
     square reflect-padded crop, resize of the longer side, centre pad), per-episode category ids 0..N-1, images normalised with the
     dataset mean/std (datasets/mnistiseg/ParamsMNISTISEG.json:1-5, datasets/omniiseg/ParamsOMNIISEG.json:1-5).
-    Character datasets are batched without aspect-ratio grouping (base_fst.py:611-624)."""
+    Character datasets are batched without aspect-ratio grouping (base_fst.py:611-624).
+    ``raw_uint8``: the images stay decoded pixels - ``qry_img`` uint8 [H,W,3], ``spp_imgs`` uint8 [N*K,S,S,3] - for a
+    detector that normalises on the device (``FGN.set_input_norm(**ds.input_norm)``); nothing else of the sample changes."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
                                std=(0.16037128865718842, 0.15775758028030396, 0.15985246002674103), n_cats=26)}
 
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
-                 spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234):
+                 spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False):
         par = self.PARAMS[dataset]
+        self.raw_uint8 = bool(raw_uint8)
         self.n_ways, self.k_shots, self.batch, self.shuffle = n_ways, k_shots, batch, shuffle
         self.img_size, self.spp_img_size, self.spp_fill_ratio = img_size, spp_img_size, spp_fill_ratio
         self.sampling_origin_ds, self.sampling_origin_ds_subset = dataset, 'val'
@@ -248,7 +251,14 @@ class ClutteredCharsFewShotISEG(Dataset):
             random.Random((2 ** e) % 1000).shuffle(order)
         self.order = np.array(order, dtype=np.int32)
 
+    @property
+    def input_norm(self) -> dict:
+        """The normalisation ``_norm`` applies, as the arguments of ``FGN.set_input_norm``."""
+        return dict(mean=self.mean.copy(), std=self.std.copy())
+
     def _norm(self, img_u8):
+        if self.raw_uint8:
+            return torch.from_numpy(img_u8.copy())         # (a private copy, like the float form)
         return torch.from_numpy(((img_u8.astype(np.float32) / 255.0 - self.mean) / self.std).transpose(2, 0, 1).copy())
 
     def __getitem__(self, idx):

@@ -1000,6 +1000,39 @@ def nchw3_to_nhwc4(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def input_lut(mean, std, scale: float = 255.0) -> np.ndarray:
+    """The normalisation table of ``u8hwc3_to_nhwc4``: lut[c][v] = (float32(v) / scale - mean[c]) / std[c] in float32
+    numpy arithmetic, exactly what the data loader computes per pixel (``ClutteredCharsFewShotISEG._norm``; bit-equal to
+    torch's ``float().div(255).sub(mean).div(std)``).  [3,256] float32."""
+    mean, std = np.asarray(mean, np.float32).reshape(3), np.asarray(std, np.float32).reshape(3)
+    v = np.arange(256, dtype=np.uint8)[:, None]
+    return np.ascontiguousarray(((v.astype(np.float32) / scale - mean) / std).T)
+
+
+# pixels one pass of u8hwc3_to_nhwc4_kernel's grid-stride loop covers: U8_GRID_CAP workgroups x 256 lanes x 4 pixels
+# (csrc/spatial.hip)
+U8_PIXELS_PER_PASS = 256 * 8 * 256 * 4
+
+
+def u8hwc3_to_nhwc4(x_u8: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
+    """uint8 channels-last [n,H,W,3] -> NHWC4 fp32 [n,H,W,4], normalised through ``lut`` ([3,256] fp32 on the device,
+    from ``input_lut``): the bytes ``nchw3_to_nhwc4`` gives for the host-normalised image.  ``x_u8`` may start at any
+    byte (a sliced view)."""
+    _chk(x_u8, 'x_u8', torch.uint8)
+    _chk(lut, 'lut')
+    if x_u8.dim() != 4 or x_u8.shape[3] != 3:
+        raise _lib.FgnHipError('u8hwc3_to_nhwc4: expects [n,H,W,3]')
+    if tuple(lut.shape) != (3, 256) or lut.device != x_u8.device:
+        raise _lib.FgnHipError('u8hwc3_to_nhwc4: lut must be [3,256] on the device of x_u8')
+    n, h, w, _ = x_u8.shape
+    y = torch.empty((n, h, w, 4), device=x_u8.device, dtype=torch.float32)
+    if y.numel() == 0:                  # (an empty tensor has no address to hand over)
+        return y
+    _lib.check(_lib.load().fgn_u8hwc3_to_nhwc4_f32(_ptr(x_u8), _ptr(lut), _ptr(y), n, h, w, _stream()),
+               'fgn_u8hwc3_to_nhwc4_f32')
+    return y
+
+
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x, 'x')
     n, h, w, c = x.shape

@@ -276,7 +276,8 @@ def forward_train(model, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bbo
     main = torch.cuda.current_stream()
 
     # ---- modify_input (fgn.py:79-108): H2D, YXYX -> XYXY on private copies
-    qry = qry_img.to(dev, torch.float32, non_blocking=True)
+    model._image_dims(qry_img, 'qry_img')
+    qry = qry_img.to(dev, non_blocking=True)                               # (dtype and layout: FGN._stem_input)
     gt_h = [torch.as_tensor(b).detach().cpu().float().reshape(-1, 4)[:, [1, 0, 3, 2]].contiguous().numpy()
             for b in qry_bboxes]                                            # host copies drive the bookkeeping
     cat_h = [torch.as_tensor(c).detach().cpu().long().reshape(-1).numpy() for c in qry_cat_ids]

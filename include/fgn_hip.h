@@ -210,6 +210,13 @@ int fgn_winograd_pack_weights_f32(const float* w, const double* G, float* U, int
 /* NCHW [n,3,H,W] -> NHWC4 [n,H,W,4] (input side of fgn.py:212,215) */
 int fgn_nchw3_to_nhwc4_f32(const float* x, float* y, int n_img, int H, int W, void* stream);
 
+/* uint8 channels-last [n,H,W,3] -> the same NHWC4 [n,H,W,4] fp32 stem input, normalised on the way: y[..,c] =
+ * lut[c][x[..,c]] for c < 3, y[..,3] = +0.0f.  lut: [3][256] fp32 in device memory, built by the host in the data
+ * loader's own arithmetic ((v / scale - mean[c]) / std[c], fgn_amd.ops.input_lut), so y is bit-identical to
+ * fgn_nchw3_to_nhwc4_f32 of the host-normalised image by construction - no device division is involved.  x needs no
+ * alignment (a pointer that is not dword-aligned takes a pixel-per-lane path).  An empty tensor is FGN_OK. */
+int fgn_u8hwc3_to_nhwc4_f32(const unsigned char* x, const float* lut, float* y, int n_img, int H, int W, void* stream);
+
 /* 3x3/2 pad 1 max-pool of the ResNet stem */
 int fgn_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n_img, int H, int W, int C, void* stream);
 
