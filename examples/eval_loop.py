@@ -6,6 +6,7 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
     python examples/eval_loop.py --episodes 8 --batch 2 --height 320 --width 480
     python examples/eval_loop.py --dataset OMNIISEG --episodes 16 --n-ways 3 --k-shots 1     (cfg2-shaped)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --uint8      (decoded pixels in, normalised on the GPU)
+    python examples/eval_loop.py --episodes 8 --match-on-device     (mask overlaps counted on the GPU: the evaluator decodes no RLE)
 """
 import argparse
 import os
@@ -34,6 +35,9 @@ def main():
     ap.add_argument('--checkpoint', default=None, help='mmcv checkpoint of a trained reference FGN')
     ap.add_argument('--uint8', action='store_true',
                     help='character datasets: the loader yields uint8 pixels, the detector normalises them on the GPU')
+    ap.add_argument('--match-on-device', action='store_true',
+                    help='count the overlaps of detections and ground truth on the GPU (FGN.match_on_device): the results '
+                         'carry dt_gt_inter / dt_area / gt_area and the evaluator decodes no RLE')
     args = ap.parse_args()
     if args.uint8 and args.dataset == 'SYNTH':
         ap.error('--uint8 needs --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
@@ -47,6 +51,7 @@ def main():
     model = FGN(args.n_ways, args.k_shots)
     if args.uint8:
         model.set_input_norm(**ds.input_norm)
+    model.match_on_device = args.match_on_device
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'))
     loader = DataLoader(ds, batch_size=ds.batch, num_workers=2, collate_fn=collate)
@@ -60,8 +65,11 @@ def main():
         t0 = time.perf_counter()
         write_chunked(results(), out)
         dt = time.perf_counter() - t0
+        t0 = time.perf_counter()
         metrics = ds.evaluate(results_pkl_dir_fp=out, model_dir=work_dir)
-    print(f'{len(ds)} episodes in {dt:.2f} s ({len(ds) / dt:.1f} img/s incl. data loading and H2D)')
+        de = time.perf_counter() - t0
+    print(f'{len(ds)} episodes in {dt:.2f} s ({len(ds) / dt:.1f} img/s incl. data loading and H2D), '
+          f'evaluation {de:.2f} s ({de / len(ds) * 1e3:.1f} ms per image)')
     print(metrics)
 
 

@@ -564,3 +564,145 @@ extern "C" int fgn_dense_mask_rle(const uint8_t* masks, void* scratch, size_t sc
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }
+
+// ----------------------------------------------------------------------------------------------
+// Matching on the device: exact pixel counts |d & g|, |d|, |g| of every (detection, ground truth) pair.
+// The evaluator (fgn_amd/fsiseg_eval.py) needs nothing else from the masks, and both operands are on the device while
+// the episode is in flight: the ground-truth masks (uploaded for the RLE above) and the mask probabilities + boxes the
+// RLE kernel pastes from.  Two kernels:
+//   mask_bits_kernel     [G][H][W] bytes -> bit planes, one 64-bit word per 64 consecutive x of a row (a wave-wide
+//                        ballot; bits of x >= W are zero), laid out [H][ceil(W/64)][G]: the words of all masks for
+//                        one (row, x-word) are contiguous, which is what the consumer loads; + the areas |g|
+//   mask_overlap_kernel  per (detection, block of rows): the pasted bits of a 64-pixel row segment are one ballot
+//                        (lane = pixel; make_paste_box / paste_axis / paste_value of this file, so the bits are those of
+//                        mask_paste_kernel and mask_rle_kernel), then lane = ground-truth index ANDs its own word with it
+//                        and counts.  Integer atomics: the result does not depend on the order of the additions.
+// Neither the D x H x W nor the bit form of the detections' masks is ever written.
+// ----------------------------------------------------------------------------------------------
+constexpr int BITS_THREADS = 256;
+constexpr int BITS_ROWS = 8;        // image rows per workgroup of mask_bits_kernel
+constexpr int OVL_THREADS = 256;
+constexpr int OVL_WAVES = OVL_THREADS / 64;
+constexpr int OVL_ROWS = 32;        // image rows per workgroup of mask_overlap_kernel
+
+// a[0..na) = 0 and b[0..nb) = 0 (b may be null with nb = 0)
+__global__ __launch_bounds__(256) void zero_i32_kernel(int32_t* __restrict__ a, long long na, int32_t* __restrict__ b,
+                                                       long long nb) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < na + nb;
+         i += (long long)gridDim.x * blockDim.x) {
+        if (i < na) a[i] = 0;
+        else b[i - na] = 0;
+    }
+}
+
+// grid: row block * G + g.  area[] is zero on entry.
+__global__ __launch_bounds__(BITS_THREADS) void mask_bits_kernel(const uint8_t* __restrict__ masks,
+                                                                 unsigned long long* __restrict__ bits,
+                                                                 int32_t* __restrict__ area, int G, int H, int W, int NW) {
+    __shared__ int wave_cnt[BITS_THREADS / 64];
+    const int g = blockIdx.x % G, rb = blockIdx.x / G;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int y0 = rb * BITS_ROWS, rows = min(BITS_ROWS, H - y0);
+    const uint8_t* src = masks + (size_t)g * H * W;
+    int cnt = 0;
+    for (int i = wv; i < rows * NW; i += BITS_THREADS / 64) {     // (wave-uniform trip count)
+        const int r = i / NW, xw = i - r * NW;
+        const int y = y0 + r, x = xw * 64 + lane;
+        const bool v = x < W && src[(size_t)y * W + x] != 0;
+        const unsigned long long word = __ballot(v);
+        if (lane == 0) bits[((size_t)y * NW + xw) * G + g] = word;
+        cnt += __popcll(word);
+    }
+    if (lane == 0) wave_cnt[wv] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int s = 0;
+        for (int w = 0; w < BITS_THREADS / 64; ++w) s += wave_cnt[w];
+        if (s) atomicAdd(area + g, s);
+    }
+}
+
+extern "C" int fgn_mask_bits_u64(const uint8_t* masks, uint64_t* bits, int32_t* area, int n_masks, int img_h, int img_w,
+                                 hipStream_t stream) {
+    if (n_masks == 0) return FGN_OK;
+    if (!masks || !bits || !area) return FGN_ERR_ARG;
+    if (n_masks < 0 || img_h < 1 || img_w < 1 || (long long)img_h * img_w >= (1ll << 31)) return FGN_ERR_SHAPE;
+    const long long blocks = (long long)cdiv(img_h, BITS_ROWS) * n_masks;
+    if (blocks >= (1ll << 31)) return FGN_ERR_SHAPE;
+    hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(n_masks, 256)), dim3(256), 0, stream, area, (long long)n_masks,
+                       (int32_t*)nullptr, 0ll);
+    FGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mask_bits_kernel, dim3((unsigned)blocks), dim3(BITS_THREADS), 0, stream, masks,
+                       reinterpret_cast<unsigned long long*>(bits), area, n_masks, img_h, img_w, cdiv(img_w, 64));
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// grid: (detection, block of OVL_ROWS rows).  inter / det_area are zero on entry.
+__global__ __launch_bounds__(OVL_THREADS) void mask_overlap_kernel(
+    const float* __restrict__ prob, const float* __restrict__ boxes, int box_stride,
+    const unsigned long long* __restrict__ gt_bits, int32_t* __restrict__ inter, int32_t* __restrict__ det_area,
+    const int32_t* __restrict__ n_dev, int n_det, int G, int H, int W, int NW, int MS, float thr, int skip_empty) {
+    __shared__ float m[32 * 32];
+    __shared__ int red[OVL_WAVES][64];
+    __shared__ int red_area[OVL_WAVES];
+    const int d = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int D = n_det;
+    if (n_dev) D = min(D, *n_dev);
+    if (d >= D) return;
+    const PasteBox pb = make_paste_box(boxes + (size_t)d * box_stride, H, W, MS, skip_empty, thr);
+    const int y_lo = max(pb.y0i, (int)blockIdx.y * OVL_ROWS), y_hi = min(pb.y1i, ((int)blockIdx.y + 1) * OVL_ROWS);
+    if (y_lo >= y_hi || pb.x0i >= pb.x1i) return;          // rows outside the pasted region (workgroup-uniform)
+    for (int i = t; i < MS * MS; i += OVL_THREADS) m[i] = prob[(size_t)d * MS * MS + i];
+    __syncthreads();
+    const int w_lo = pb.x0i >> 6, w_hi = (pb.x1i - 1) >> 6;  // x-words of the region, inclusive; 0 <= x0i < x1i <= W
+    for (int g0 = 0; g0 < G; g0 += 64) {                     // passes of 64 ground-truth masks (lane = mask)
+        const int g = g0 + lane;
+        int acc = 0, area = 0;
+        for (int xw = w_lo; xw <= w_hi; ++xw) {
+            const int x = xw * 64 + lane;                    // lane = pixel of the segment
+            const bool in_x = x >= pb.x0i && x < pb.x1i;
+            const AxisLerp ax = paste_axis(x, pb.bx0, pb.bx1, MS);
+            for (int y = y_lo + wv; y < y_hi; y += OVL_WAVES) {
+                const AxisLerp ay = paste_axis(y, pb.by0, pb.by1, MS);
+                const bool v = in_x && paste_value(m, MS, ax, ay) >= thr;
+                const unsigned long long det = __ballot(v);
+                if (det) {                                   // (wave-uniform)
+                    area += __popcll(det);
+                    if (g < G) acc += __popcll(det & gt_bits[((size_t)y * NW + xw) * G + g]);
+                }
+            }
+        }
+        red[wv][lane] = acc;
+        if (lane == 0) red_area[wv] = area;
+        __syncthreads();
+        if (wv == 0) {
+            int s = 0, a = 0;
+#pragma unroll
+            for (int w = 0; w < OVL_WAVES; ++w) { s += red[w][lane]; a += red_area[w]; }
+            if (g < G && s) atomicAdd(inter + (size_t)d * G + g, s);
+            if (g0 == 0 && lane == 0 && a) atomicAdd(det_area + d, a);   // |d| once, not once per pass
+        }
+        __syncthreads();
+    }
+}
+
+extern "C" int fgn_mask_overlap_i32(const float* prob, const float* boxes, int box_stride, const uint64_t* gt_bits,
+                                    int32_t* inter, int32_t* det_area, const int32_t* n_dev, int n_det, int n_gt,
+                                    int img_h, int img_w, int mask_size, float thr, int skip_empty, hipStream_t stream) {
+    if (n_det == 0 || n_gt == 0) return FGN_OK;
+    if (!prob || !boxes || !gt_bits || !inter || !det_area) return FGN_ERR_ARG;
+    if (n_det < 0 || n_gt < 0 || box_stride < 4) return FGN_ERR_ARG;
+    if (mask_size > 32 || mask_size < 1 || img_h < 1 || img_w < 1 || (long long)img_h * img_w >= (1ll << 31) ||
+        cdiv(img_h, OVL_ROWS) > 65535)
+        return FGN_ERR_SHAPE;
+    const long long n_out = (long long)n_det * n_gt;
+    hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)std::min<long long>((n_out + n_det + 255) / 256, 1024)), dim3(256),
+                       0, stream, inter, n_out, det_area, (long long)n_det);
+    FGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mask_overlap_kernel, dim3(n_det, cdiv(img_h, OVL_ROWS)), dim3(OVL_THREADS), 0, stream, prob, boxes,
+                       box_stride, reinterpret_cast<const unsigned long long*>(gt_bits), inter, det_area, n_dev, n_det,
+                       n_gt, img_h, img_w, cdiv(img_w, 64), mask_size, thr, skip_empty);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}

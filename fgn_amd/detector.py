@@ -456,6 +456,10 @@ class FGN(torch.nn.Module):
         self.debug_trace: Optional[dict] = None   # set to {} to capture intermediates (tests)
         self.use_side_stream = True               # support branch on a second HIP stream
         self.use_graphs = False                   # replay a captured hipGraph per input geometry
+        # exact overlap counts |d & g|, |d|, |g| of every detection with every ground-truth mask of its image, counted
+        # on the device while the episode is in flight (result keys dt_gt_inter / dt_area / gt_area: the evaluator then
+        # decodes no RLE); needs ``qry_isegmaps``.  False: nothing is launched, allocated or added
+        self.match_on_device = False
         self._use_winograd = ops.WINOGRAD_M       # Winograd form of the 3x3 / stride 1 convs: 4 = F(4x4,3x3), 2 = F(2x2,3x3), 0 = direct
         self.use_roi_commute = True               # shared_head conv1 on the feature map, RoIAlign after (set before first use)
         # query + support maps through SHARED backbone launches (1x1 / stride 1 convolutions and the grouped Winograd GEMM
@@ -1050,14 +1054,18 @@ class FGN(torch.nn.Module):
         self.transfer_mode = int(mode)
         return self._stream_for('upload', torch.cuda.current_stream())
 
-    def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None):
+    def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None,
+                bits_out: Optional[list] = None):
         """``modify_input`` (fgn.py:79-108): host -> device copies of one batch, on an upload stream so that they
         overlap the previous batch's kernels (a pinned source makes them asynchronous); the compute streams wait
         on one event.  Tensors already on the device pass through.  The ground-truth masks (copied to the GPU by
         the reference too, fgn.py:95) are run-length encoded right there (``qry_isegmaps_rle``, fgn.py:298): two
         small kernels on the upload stream instead of ~4 ms of host work per 800x1333 episode.  ``into``: device
         tensors to copy INTO (the static input buffers of a captured graph, when the upload stream is the caller
-        stream itself and so ordered behind the previous replay that reads them) instead of fresh allocations."""
+        stream itself and so ordered behind the previous replay that reads them) instead of fresh allocations.
+        ``bits_out`` (``match_on_device``): a list that receives, per image, the bit planes of its ground-truth masks
+        (``ops.mask_bits`` on the device copy made for the RLE, right behind it on the upload stream; None for an image
+        without ground truth)."""
         gts = None
         if gt_masks is not None:
             gts = [g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
@@ -1081,7 +1089,10 @@ class FGN(torch.nn.Module):
                 for g in gts:
                     g = g.to(dev, non_blocking=True)
                     g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
-                    gt_out.append(ops.dense_mask_rle(g.contiguous(), packed=True))
+                    g = g.contiguous()
+                    gt_out.append(ops.dense_mask_rle(g, packed=True))
+                    if bits_out is not None:
+                        bits_out.append(ops.mask_bits(g) if g.shape[0] else None)
             ready = up.record_event()
         for k, t in out.items():
             if t is not None and not (into is not None and t is into.get(k)):
@@ -1119,7 +1130,8 @@ class FGN(torch.nn.Module):
         if graphed and self.use_packed_transfers and self._stream_for('upload', main) is main:
             ge0 = self._graphs.get(self._graph_key(ins, img_shape, support_code, phase_counter, main, dev))
             into = ge0.static if ge0 is not None else None
-        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into)
+        gt_bits = [] if (self.match_on_device and qry_isegmaps is not None) else None
+        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits)
         if uploaded is not None:
             main.wait_event(uploaded)
         if graphed:
@@ -1130,6 +1142,17 @@ class FGN(torch.nn.Module):
         if gt_rle is not None:
             for d, g in zip(outs, gt_rle):
                 d['gt_rle'] = g
+        if gt_bits:
+            # eager, on the caller's stream behind the network - also when the episode was a graph replay: the number of
+            # ground-truth masks differs from image to image and is no part of the captured geometry (as for their RLE)
+            thr = self.cfg['test_cfg']['rcnn']['mask_thr_binary']
+            for d, gb in zip(outs, gt_bits):
+                if gb is None:
+                    continue
+                for t in gb[:2]:
+                    t.record_stream(main)                 # allocated on the upload stream
+                d['overlap'] = ops.mask_overlap(d['mask_prob'], d['det_bboxes'], gb, *d['img_hw'], thr, d['n_dets'],
+                                                skip_empty=self._skip_empty(), packed=True)[3]
         self._start_download(outs, main, uploaded if gt_rle is not None else None)
         if graphed:
             ge.last_download = outs[0]['host_ready']
@@ -1376,7 +1399,7 @@ class FGN(torch.nn.Module):
 
     MAX_SLOTS = 64
 
-    def _pinned_slot(self, batch: int, max_det: int, n_gt: int, mask_size: int = 14) -> dict:
+    def _pinned_slot(self, batch: int, max_det: int, n_gt: int, mask_size: int = 14, n_ov: int = 0) -> dict:
         """A free pinned host slot for one batch's results (pinned allocation is slow, so slots are kept per
         (batch, max_det, mask size) and reused): the host mirror of a ``_ResultRecord`` plus a byte buffer for the
         packed ground-truth RLE.  A slot is busy from ``detect_device`` until ``pack_results`` has read it; when every
@@ -1397,6 +1420,12 @@ class FGN(torch.nn.Module):
             # pipelined run - with caps of 2 x the first count seen, slots kept growing for dozens of steps
             cap = max(64, 2 * n_gt)
             slot.update(gt_cap=cap, gt_buf=torch.empty(cap * (ops.RLE_BYTE_CAP + 8), dtype=torch.uint8, pin_memory=True))
+        if n_ov > slot.get('ov_cap', 0):
+            # overlap counts (``match_on_device``), grown like gt_buf: n_ov ground-truth masks take at most
+            # n_ov * (max_det + 1) + batch * max_det int32 ([inter | det_area | gt_area] per image)
+            cap = max(64, 2 * n_ov)
+            slot.update(ov_cap=cap, ov_buf=torch.empty(cap * (max_det + 1) + batch * max_det, dtype=torch.int32,
+                                                       pin_memory=True))
         slot['busy'] = True
         return slot
 
@@ -1414,7 +1443,8 @@ class FGN(torch.nn.Module):
         max_det = outs[0]['det_bboxes'].shape[0]
         n_gt = sum(d['gt_rle'][1].shape[0] for d in outs if 'gt_rle' in d)
         rec = outs[0].get('record')
-        slot = self._pinned_slot(len(outs), max_det, n_gt, outs[0]['mask_prob'].shape[-1])
+        n_ov = sum(d['gt_rle'][1].shape[0] for d in outs if 'overlap' in d)
+        slot = self._pinned_slot(len(outs), max_det, n_gt, outs[0]['mask_prob'].shape[-1], n_ov)
         cp.wait_stream(main)
         if also_wait is not None:
             cp.wait_event(also_wait)           # the ground-truth RLE kernels run on the upload stream
@@ -1448,6 +1478,14 @@ class FGN(torch.nn.Module):
                                 t.record_stream(cp)
                     d['gt_slice'] = (g0, n)
                     g0 += n
+            o0 = 0
+            for d in outs:
+                if 'overlap' in d:
+                    n = d['overlap'].numel()
+                    slot['ov_buf'][o0:o0 + n].copy_(d['overlap'], non_blocking=True)
+                    d['overlap'].record_stream(cp)
+                    d['ov_slice'] = (o0, n)
+                    o0 += n
             ev = cp.record_event()
         for d in outs:
             d['host'] = slot
@@ -1503,6 +1541,14 @@ class FGN(torch.nn.Module):
             elif gt is not None:
                 gt = gt.cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)
                 one['qry_isegmaps_rle'] = rle.encode_many(gt)
+            if 'ov_slice' in di:                   # overlap counts from the device: [inter [D,G] | det_area [D] | gt_area [G]]
+                o0, nov = di['ov_slice']
+                md = host['det'].shape[1]
+                ng = (nov - md) // (md + 1)
+                hb = host['ov_buf'][o0:o0 + nov].numpy()
+                one['dt_gt_inter'] = hb[:md * ng].reshape(md, ng)[:n].copy()
+                one['dt_area'] = hb[md * ng:md * ng + md][:n].copy()
+                one['gt_area'] = hb[md * ng + md:].copy()
             results.append(one)
         host['busy'] = False
         return results

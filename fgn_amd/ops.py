@@ -1474,6 +1474,57 @@ def dense_mask_rle(masks: torch.Tensor, packed: bool = False):
     return (out, lens, ovf, buf) if packed else (out, lens, ovf)
 
 
+def mask_bits(masks: torch.Tensor):
+    """Bit planes of dense binary masks [G,H,W] (bool / uint8, non-zero = set), the ground-truth operand of
+    ``mask_overlap``: returns (bits int64 [H, ceil(W/64), G] - bit b of word xw of a row = pixel 64 xw + b - ,
+    area [G] int32, (H, W))."""
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    _chk(masks, 'masks', torch.uint8)
+    if masks.dim() != 3:
+        raise _lib.FgnHipError('mask_bits: masks must be [G,H,W]')
+    g, h, w = masks.shape
+    bits = torch.empty((h, (w + 63) // 64, g), device=masks.device, dtype=torch.int64)
+    area = torch.empty((g,), device=masks.device, dtype=torch.int32)
+    _lib.check(_lib.load().fgn_mask_bits_u64(_ptr(masks), _ptr(bits), _ptr(area), g, h, w, _stream()),
+               'fgn_mask_bits_u64')
+    return bits, area, (h, w)
+
+
+def mask_overlap(prob: torch.Tensor, boxes: torch.Tensor, gt_masks, img_h: int, img_w: int, thr: float,
+                 n_dev: Optional[torch.Tensor] = None, skip_empty: bool = True, packed: bool = False):
+    """Exact overlap counts of the pasted, thresholded detection masks (``prob`` [D,M,M], ``boxes`` [D,>=4], ``thr``,
+    ``n_dev``, ``skip_empty`` as for ``mask_rle`` / ``mask_paste``: the same bits, never written) with the ground-truth
+    masks ``gt_masks`` ([G,H,W] bool / uint8, or what ``mask_bits`` returned for them).  Returns (inter [D,G] int32 =
+    |d & g|, det_area [D] int32 = |d|, gt_area [G] int32 = |g|), the three being views of ONE int32 allocation laid out
+    [inter | det_area | gt_area]; ``packed``: that allocation is returned as a fourth value (one device-to-host copy
+    moves them all).  Rows at or beyond the device count are zero.  With G == 0 nothing is launched and det_area is
+    zero."""
+    _chk(prob, 'prob')
+    _chk(boxes, 'boxes')
+    d, m, _ = prob.shape
+    if boxes.shape[0] != d or boxes.shape[1] < 4:
+        raise _lib.FgnHipError('mask_overlap: boxes shape mismatch')
+    if n_dev is not None:
+        _chk(n_dev, 'n_dev', torch.int32)
+    bits, gt_area, hw = gt_masks if isinstance(gt_masks, tuple) else mask_bits(gt_masks)
+    if tuple(hw) != (img_h, img_w):
+        raise _lib.FgnHipError(f'mask_overlap: ground-truth masks are {tuple(hw)}, image is {(img_h, img_w)}')
+    g = gt_area.numel()
+    buf = torch.empty(d * g + d + g, device=prob.device, dtype=torch.int32)
+    inter, det_area, ga = buf[:d * g].view(d, g), buf[d * g:d * g + d], buf[d * g + d:]
+    if g:
+        ga.copy_(gt_area)
+    if d == 0 or g == 0:
+        det_area.zero_()
+        return (inter, det_area, ga, buf) if packed else (inter, det_area, ga)
+    rc = _lib.load().fgn_mask_overlap_i32(_ptr(prob), _ptr(boxes), boxes.shape[1], _ptr(bits), _ptr(inter),
+                                          _ptr(det_area), _ptr(n_dev), d, g, img_h, img_w, m, float(thr),
+                                          int(bool(skip_empty)), _stream())
+    _lib.check(rc, 'fgn_mask_overlap_i32')
+    return (inter, det_area, ga, buf) if packed else (inter, det_area, ga)
+
+
 # --------------------------------------------------------------------------------------
 # forward_train pieces (csrc/train.hip)
 # --------------------------------------------------------------------------------------

@@ -347,6 +347,23 @@ int fgn_dense_mask_rle(const uint8_t* masks, void* scratch, size_t scratch_bytes
                        int32_t* out_len, int32_t* overflow, int n_masks, int img_h, int img_w, int trans_cap,
                        int byte_cap, void* stream);
 
+/* Matching on the device: the exact pixel counts the evaluator needs from the masks, so that no RLE is decoded on the
+ * host.  Step 1, bit planes of the ground-truth masks: masks [n][H][W] bytes (non-zero = set) -> bits, one 64-bit word
+ * per 64 consecutive x of a row (bit b of word xw = pixel x = 64 xw + b; bits of x >= W are zero), laid out
+ * [H][ceil(W/64)][n] (the words of all masks for one row segment are contiguous); area [n] = pixel count of each mask.
+ * H*W < 2^31 (counts are int32).  n_masks == 0 launches nothing. */
+int fgn_mask_bits_u64(const uint8_t* masks, uint64_t* bits, int32_t* area, int n_masks, int img_h, int img_w,
+                      void* stream);
+
+/* Step 2: inter [D][n_gt] = pixels set in both the pasted, thresholded mask of detection d and ground-truth mask g;
+ * det_area [D] = pixels of the pasted mask.  prob / boxes / n_dev / thr / skip_empty as for fgn_mask_rle: the pasted bits
+ * are those of fgn_mask_paste_u8, and the masks are never written.  gt_bits: from fgn_mask_bits_u64 for the same image
+ * size.  Both outputs are fully written: rows at or beyond the device count are zero.  mask_size <= 32, H*W < 2^31.
+ * n_det == 0 or n_gt == 0 launches nothing and leaves the outputs as they are. */
+int fgn_mask_overlap_i32(const float* prob, const float* boxes, int box_stride, const uint64_t* gt_bits, int32_t* inter,
+                         int32_t* det_area, const int32_t* n_dev, int n_det, int n_gt, int img_h, int img_w,
+                         int mask_size, float thr, int skip_empty, void* stream);
+
 /* ---- forward_train (fgn.py:125-185) ----------------------------------------------------- */
 
 /* The proposal stage at training sizes (train_cfg.rpn_proposal, fgn_r50_c4_densecl.py:153-157: nms_pre 12000,
