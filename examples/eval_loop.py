@@ -6,6 +6,7 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
     python examples/eval_loop.py --episodes 8 --batch 2 --height 320 --width 480
     python examples/eval_loop.py --dataset OMNIISEG --episodes 16 --n-ways 3 --k-shots 1     (cfg2-shaped)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --uint8      (decoded pixels in, normalised on the GPU)
+    python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --source-size 200     (200^2 sources, resized to 128^2 on the GPU)
     python examples/eval_loop.py --episodes 8 --match-on-device     (mask overlaps counted on the GPU: the evaluator decodes no RLE)
 """
 import argparse
@@ -35,25 +36,30 @@ def main():
     ap.add_argument('--checkpoint', default=None, help='mmcv checkpoint of a trained reference FGN')
     ap.add_argument('--uint8', action='store_true',
                     help='character datasets: the loader yields uint8 pixels, the detector normalises them on the GPU')
+    ap.add_argument('--source-size', type=int, default=None, metavar='S',
+                    help='character datasets: queries are generated at S x S and stay at that size in the loader; the '
+                         'detector resizes image and masks to the network size on the GPU (qry_resize_to; implies --uint8)')
     ap.add_argument('--match-on-device', action='store_true',
                     help='count the overlaps of detections and ground truth on the GPU (FGN.match_on_device): the results '
                          'carry dt_gt_inter / dt_area / gt_area and the evaluator decodes no RLE')
     args = ap.parse_args()
+    args.uint8 = args.uint8 or args.source_size is not None
     if args.uint8 and args.dataset == 'SYNTH':
-        ap.error('--uint8 needs --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
+        ap.error('--uint8 / --source-size need --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
 
     if args.dataset == 'SYNTH':
         ds = SyntheticFewShotISEG(args.n_ways, args.k_shots, args.episodes, args.height, args.width, batch=args.batch)
     else:       # cluttered characters: 128^2 (MNISTISEG, cfg1) / 256^2 (OMNIISEG, cfg2) queries, 128^2 supports
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,
-                                       raw_uint8=args.uint8)
+                                       raw_uint8=args.uint8, source_size=args.source_size)
     model = FGN(args.n_ways, args.k_shots)
     if args.uint8:
         model.set_input_norm(**ds.input_norm)
     model.match_on_device = args.match_on_device
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'))
+    # (source-size queries of one size stack like any other; a real loader hands qry_img over as a list when they differ)
     loader = DataLoader(ds, batch_size=ds.batch, num_workers=2, collate_fn=collate)
 
     def results():

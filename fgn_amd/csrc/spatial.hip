@@ -84,6 +84,162 @@ extern "C" int fgn_u8hwc3_to_nhwc4_f32(const unsigned char* x, const float* lut,
 }
 
 // ----------------------------------------------------------------------------------
+// Query resize behind the upload (BaseFewShotISEG.get_query, base_fst.py:876-887: cv2.resize of the decoded image and
+// of every ground-truth mask to the network size).  The arithmetic is the integer rule of fgn_amd/fewshot_ds.py
+// (resize_taps / resize_image_u8 / resize_masks) - a restatement of cv2's bilinear design (half-pixel
+// centres, clamped edges, 11-bit weights, round half up), not cv2's bytes - and both kernels agree with those host
+// functions bit for bit: everything is int32, every dimension is at most RESIZE_MAX_DIM.
+//   tap of destination sample j on an axis of n_src -> n_dst samples:
+//     num = (2j+1) * n_src - n_dst, den = 2 * n_dst, i0 = floor(num / den), rem = num - i0 * den,
+//     w1 = (rem * 4096 + den) / (2 * den), w1 = 0 where i0 < 0, i1 = min(i0 + 1, n_src - 1), i0 clamped, w0 = 2048 - w1
+// num > -den, so the floor division is one unsigned division of num + den; w1 costs a second one (divisor 2 * den).
+// The unit of work is one wave on 64 consecutive lane items of ONE output row: image, row and the row's y taps are
+// wave-uniform (scalar registers, one scalar division pair per unit), the x taps are per lane.
+// ----------------------------------------------------------------------------------
+constexpr int RESIZE_MAX_DIM = 16384;
+constexpr int RESIZE_BLOCK = 256;
+constexpr int RESIZE_GRID_CAP = 256 * 8;      // workgroups; waves loop over further units
+constexpr int RESIZE_HALF = 1 << 21;          // half of the weight sum 2048 * 2048
+
+struct ResizeTap { int i0, i1, w0, w1; };
+__device__ __forceinline__ ResizeTap resize_tap(int j, int n_src, int n_dst) {
+    const unsigned den = 2u * (unsigned)n_dst;
+    const unsigned nump = (2u * (unsigned)j + 1u) * (unsigned)n_src + (unsigned)n_dst;     // num + den, in [1, 2^30)
+    const unsigned q = nump / den;                                                         // i0 + 1
+    const unsigned rem = nump - q * den;
+    ResizeTap t;
+    t.w1 = q == 0u ? 0 : (int)((rem * 4096u + den) / (2u * den));
+    t.w0 = 2048 - t.w1;
+    t.i1 = min((int)q, n_src - 1);
+    t.i0 = min(max((int)q - 1, 0), n_src - 1);
+    return t;
+}
+
+// Source images [h_b, w_b, 3] uint8 at src + b * stride (any byte alignment), sizes from the DEVICE array src_hw[b] =
+// {h_b, w_b} (no launch argument depends on a source size: one captured launch serves every source size) ->
+// y [n,H,W,4] fp32 = {lut[0][r], lut[1][g], lut[2][b], +0}: u8hwc3_to_nhwc4_kernel of the resized image.  A lane makes
+// one output pixel: 4 taps x 3 bytes from two source rows (neighbouring lanes share cache lines; the source is a few MB
+// and stays in L2), three table lookups in LDS, one 16-byte store - 1 KB per wave, coalesced; like the kernel above it
+// waits on those stores.  Every index is clamped into [0,h) x [0,w); an image whose size is outside 1..RESIZE_MAX_DIM
+// or does not fit its slot is written as zeros and none of its bytes are read.
+__global__ __launch_bounds__(RESIZE_BLOCK) void resize_u8hwc3_to_nhwc4_kernel(const uint8_t* __restrict__ src,
+                                                                              long long stride,
+                                                                              const int* __restrict__ src_hw,
+                                                                              const float* __restrict__ lut,
+                                                                              float4* __restrict__ y, int H, int W,
+                                                                              int chunks, int units) {
+    __shared__ float t[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += RESIZE_BLOCK) t[i] = lut[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int WAVES = RESIZE_BLOCK / 64;
+    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
+        const int r = u / chunks;                           // image * H + row
+        const int chunk = u - r * chunks;
+        const int b = r / H, oy = r - b * H;
+        const int h = src_hw[2 * b], w = src_hw[2 * b + 1];
+        const int ox = chunk * 64 + lane;
+        if (ox >= W) continue;
+        float4* o = y + (size_t)r * W + ox;
+        const bool ok = h >= 1 && h <= RESIZE_MAX_DIM && w >= 1 && w <= RESIZE_MAX_DIM && (long long)h * w * 3 <= stride;
+        if (!ok) {
+            *o = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const ResizeTap ty = resize_tap(oy, h, H), tx = resize_tap(ox, w, W);
+        const uint8_t* img = src + (long long)b * stride;
+        const uint8_t* r0 = img + (size_t)ty.i0 * w * 3;
+        const uint8_t* r1 = img + (size_t)ty.i1 * w * 3;
+        const int a = tx.i0 * 3, c = tx.i1 * 3;
+        const int w00 = ty.w0 * tx.w0, w01 = ty.w0 * tx.w1, w10 = ty.w1 * tx.w0, w11 = ty.w1 * tx.w1;
+        int v[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            v[k] = ((int)r0[a + k] * w00 + (int)r0[c + k] * w01 + (int)r1[a + k] * w10 + (int)r1[c + k] * w11 +
+                    RESIZE_HALF) >> 22;
+        *o = make_float4(t[v[0]], t[256 + v[1]], t[512 + v[2]], 0.f);
+    }
+}
+
+extern "C" int fgn_resize_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stride_bytes, const int* src_hw,
+                                              const float* lut, float* y, int n_img, int H, int W,
+                                              hipStream_t stream) {
+    if (!src || !src_hw || !lut || !y) return FGN_ERR_ARG;
+    if (n_img < 0 || H < 0 || W < 0 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM || src_stride_bytes < 0)
+        return FGN_ERR_SHAPE;
+    if ((long long)n_img * H * W == 0) return FGN_OK;
+    const int chunks = cdiv(W, 64);
+    const long long units = (long long)n_img * H * chunks;
+    if (units > INT32_MAX - 4 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;       // (unit indices are int32, stride included)
+    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP);
+    hipLaunchKernelGGL(resize_u8hwc3_to_nhwc4_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes,
+                       src_hw, lut, reinterpret_cast<float4*>(y), H, W, chunks, (int)units);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// Masks [G,h,w] (bool or bytes: nonzero = set) -> [G,H,W] 0/1 bytes by the same taps on 0/1 values, set where
+// acc >= 2^21 (half counts as set): cv2.resize(m.astype(uint8)).astype(bool) of base_fst.py:885.  A lane makes the
+// four pixels of one ALIGNED dword of the output row (the first group of a row starts up to 3 bytes before the row, so
+// that dst + 4 * k is dword-aligned whatever W and the row are) and stores it whole; a group that the row's ends cut
+// goes bytewise.  Dimensions are launch arguments: the ground-truth work of an episode is eager (G differs per image).
+__global__ __launch_bounds__(RESIZE_BLOCK) void resize_mask_u8_kernel(const uint8_t* __restrict__ src,
+                                                                      uint8_t* __restrict__ dst, int h, int w, int H,
+                                                                      int W, int chunks, int units) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int WAVES = RESIZE_BLOCK / 64;
+    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
+        const int r = u / chunks;                           // mask * H + row
+        const int chunk = u - r * chunks;
+        const int g = r / H, oy = r - g * H;
+        uint8_t* row = dst + (size_t)r * W;
+        const int lead = (int)(reinterpret_cast<uintptr_t>(row) & 3u);      // bytes of the row's first dword before it
+        const int x_lo = (chunk * 64 + lane) * 4 - lead;
+        if (x_lo >= W) continue;
+        const ResizeTap ty = resize_tap(oy, h, H);
+        const uint8_t* r0 = src + ((size_t)g * h + ty.i0) * w;
+        const uint8_t* r1 = src + ((size_t)g * h + ty.i1) * w;
+        unsigned word = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ox = x_lo + k;
+            if (ox < 0 || ox >= W) continue;
+            const ResizeTap tx = resize_tap(ox, w, W);
+            const int acc = (r0[tx.i0] ? ty.w0 * tx.w0 : 0) + (r0[tx.i1] ? ty.w0 * tx.w1 : 0) +
+                            (r1[tx.i0] ? ty.w1 * tx.w0 : 0) + (r1[tx.i1] ? ty.w1 * tx.w1 : 0);
+            word |= (acc >= RESIZE_HALF ? 1u : 0u) << (8 * k);
+        }
+        if (x_lo >= 0 && x_lo + 4 <= W) {
+            *reinterpret_cast<unsigned*>(row + x_lo) = word;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x_lo + k >= 0 && x_lo + k < W) row[x_lo + k] = (uint8_t)((word >> (8 * k)) & 1u);
+        }
+    }
+}
+
+extern "C" int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, int G, int h, int w, int H, int W,
+                                  hipStream_t stream) {
+    if (!src || !dst) return FGN_ERR_ARG;
+    if (G < 0 || h < 0 || w < 0 || H < 0 || W < 0 || h > RESIZE_MAX_DIM || w > RESIZE_MAX_DIM || H > RESIZE_MAX_DIM ||
+        W > RESIZE_MAX_DIM)
+        return FGN_ERR_SHAPE;
+    if ((long long)G * H * W == 0) return FGN_OK;
+    if (h == 0 || w == 0) return FGN_ERR_SHAPE;               // (pixels to make and none to make them of)
+    const int chunks = cdiv(W + 3, 256);
+    const long long units = (long long)G * H * chunks;
+    if (units > INT32_MAX - 16 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;      // (unit indices are int32, stride included)
+    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP * 4);
+    hipLaunchKernelGGL(resize_mask_u8_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, dst, h, w, H, W, chunks,
+                       (int)units);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------
 // 3x3 / stride 2 / pad 1 max-pool, NHWC (mmdet ResNet stem; floor mode, -inf padding)
 // ----------------------------------------------------------------------------------
 __global__ void maxpool3x3s2_kernel(const float4* __restrict__ x, float4* __restrict__ y, int H, int W,

@@ -22,7 +22,7 @@ from __future__ import annotations
 import copy
 import os
 from collections import OrderedDict
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional, Union
 
 import numpy as np
 import torch
@@ -363,8 +363,12 @@ class _GraphedEpisode:
     ``pack_results`` may read."""
     CODE_KEYS = ('vec', 'S', 'cat_mean_mp')
 
-    def __init__(self, model, ins: dict, img_shape, support_code, dev, phase_counter=None):
+    def __init__(self, model, ins: dict, img_shape, support_code, dev, phase_counter=None, source=None):
         self.static = {k: torch.empty(v.shape, dtype=v.dtype, device=dev) for k, v in ins.items()}
+        resize_to = None
+        if source is not None:      # source-size queries: the slot has the configured size, whatever this batch needs
+            self.static['qry_src'] = torch.empty((source['B'], source['capacity']), dtype=torch.uint8, device=dev)
+            resize_to = source['hw']
         self.img_shape = torch.as_tensor(img_shape).cpu().clone()
         self.code = None
         if support_code is not None:
@@ -373,8 +377,10 @@ class _GraphedEpisode:
                 self.code[k] = support_code[k].clone()
         self.last_download = None
         for k, v in ins.items():
-            self.static[k].copy_(v, non_blocking=True)
-        args = lambda: (self.static['qry_img'], self.static.get('spp_imgs'), self.static.get('spp_bboxes'),
+            self._copy_in(k, v)
+        qry = lambda: self.static['qry_img'] if resize_to is None else \
+            _SrcQuery(self.static['qry_src'], self.static['qry_src_hw'], *resize_to)
+        args = lambda: (qry(), self.static.get('spp_imgs'), self.static.get('spp_bboxes'),
                         self.static.get('spp_isegmaps'), self.img_shape, self.code)
         # eager pass first: packs the weights, sets kernel attributes, sizes the allocator pools
         # (the eager run that precedes the capture sends no phase mark: every ``detect_device`` call bumps the caller's
@@ -399,10 +405,16 @@ class _GraphedEpisode:
             if self.stamps is not None:
                 self.stamp_count = ops.arm_stamps(None)
 
+    def _copy_in(self, k: str, v: torch.Tensor) -> None:
+        if k == 'qry_src':          # [B, what the batch needs] into the front of the slot rows; the rest is never read
+            self.static[k][:, :v.shape[1]].copy_(v, non_blocking=True)
+        else:
+            self.static[k].copy_(v, non_blocking=True)
+
     def run(self, model, ins: dict, support_code, main) -> list:
         for k, v in ins.items():
             if v is not self.static[k]:                # (already uploaded straight into the static buffer: detect_device)
-                self.static[k].copy_(v, non_blocking=True)
+                self._copy_in(k, v)
         if support_code is not None:
             for k in self.CODE_KEYS:
                 if support_code[k].data_ptr() != self.code[k].data_ptr():
@@ -413,6 +425,24 @@ class _GraphedEpisode:
         # (the static outputs are views of the batch's result record: its one download carries everything pack_results
         # reads, the mask probabilities and boxes of the rare RLE-overflow fallback included)
         return [dict(d) for d in self.outs]          # detect_device queues the download and sets ``last_download``
+
+
+class _SrcQuery(NamedTuple):
+    """Query images at their source size on the way to the stem (``qry_resize_to``): ``src`` uint8 [B, capacity], image b
+    = [h_b, w_b, 3] pixels at the start of row b; ``hw`` int32 [B,2] = (h_b, w_b); (H, W) the network size.  Stands where
+    the ``qry_img`` tensor stands between ``detect_device`` / ``forward_train`` and ``_stem_input``; on that way only
+    ``shape[0]``, ``to(device)`` and ``FGN._image_dims`` are asked of a query, and those it answers."""
+    src: torch.Tensor
+    hw: torch.Tensor
+    H: int
+    W: int
+
+    @property
+    def shape(self) -> tuple:
+        return (self.src.shape[0], self.H, self.W, 3)
+
+    def to(self, dev, *a, **kw) -> '_SrcQuery':
+        return _SrcQuery(self.src.to(dev, non_blocking=True), self.hw.to(dev, non_blocking=True), self.H, self.W)
 
 
 class FGN(torch.nn.Module):
@@ -483,6 +513,9 @@ class FGN(torch.nn.Module):
         self.use_packed_transfers = True
         self.stamp_capacity = 0                   # > 0: captured graphs carry launch records of the dominant kernel (ops.read_stamps)
         self._graphs: dict = {}
+        # bytes per image of the static source slot of a captured graph (``qry_resize_to`` under ``use_graphs``): the
+        # graph key holds this size, not the source sizes, so every source that fits replays one graph
+        self.query_source_capacity = 3 * 2_000_000
         self.input_lut: Optional[np.ndarray] = None   # [3,256] fp32 normalisation table of uint8 images (set_input_norm)
         self._input_lut_dev = None                # (device, its copy there)
         self._streams: dict = {}                  # (role, caller stream) -> HIP stream: 'side', 'copy', 'upload'
@@ -812,9 +845,12 @@ class FGN(torch.nn.Module):
             self._input_lut_dev = (dev, torch.from_numpy(self.input_lut).to(dev))
         return self._input_lut_dev[1]
 
-    def _image_dims(self, img: torch.Tensor, what: str, lead=(1,)) -> tuple:
+    def _image_dims(self, img: Union[torch.Tensor, '_SrcQuery'], what: str, lead=(1,)) -> tuple:
         """(leading dimensions, H, W) of an image tensor as given: channels-last pixels when it is uint8 and a table is
-        set (``set_input_norm``), NCHW otherwise.  ``lead``: the numbers of leading dimensions allowed."""
+        set (``set_input_norm``), NCHW otherwise; source-size pixels (``_SrcQuery``) count with the size they are resized
+        to.  ``lead``: the numbers of leading dimensions allowed."""
+        if isinstance(img, _SrcQuery):
+            return (int(img.src.shape[0]),), img.H, img.W
         if self.input_lut is not None and img.dtype == torch.uint8:
             if img.dim() - 3 not in lead or img.shape[-1] != 3:
                 raise ValueError(f'{what}: with set_input_norm in effect a uint8 image tensor is channels-last pixels '
@@ -823,17 +859,94 @@ class FGN(torch.nn.Module):
             return tuple(img.shape[:-3]), int(img.shape[-3]), int(img.shape[-2])
         return tuple(img.shape[:-3]), int(img.shape[-2]), int(img.shape[-1])
 
-    def _stem_input(self, img: torch.Tensor) -> torch.Tensor:
+    def _stem_input(self, img: Union[torch.Tensor, '_SrcQuery']) -> torch.Tensor:
         """Image batch as given (host or device) -> the NHWC4 fp32 input of the stem on the current device: uint8 pixels
-        [n,H,W,3] through the normalisation table, anything else cast to fp32 NCHW [n,3,H,W] and re-laid."""
+        [n,H,W,3] through the normalisation table, source-size pixels (``_SrcQuery``) resized and normalised in one
+        kernel, anything else cast to fp32 NCHW [n,3,H,W] and re-laid."""
         dev = torch.device('cuda', torch.cuda.current_device())
+        if isinstance(img, _SrcQuery):
+            img = img.to(dev)
+            return ops.resize_u8_to_nhwc4(img.src.contiguous(), img.hw.contiguous(), self._lut_on(dev), img.H, img.W)
         if self.input_lut is not None and img.dtype == torch.uint8:
             self._image_dims(img, 'image')
             return ops.u8hwc3_to_nhwc4(img.to(dev, non_blocking=True).contiguous(), self._lut_on(dev))
         return ops.nchw3_to_nhwc4(img.to(dev, torch.float32, non_blocking=True).contiguous())
 
+    def _source_query(self, qry_img, qry_resize_to, img_shape, qry_isegmaps=None, graphed: bool = False) -> dict:
+        """The contract of ``qry_resize_to`` (host only, nothing is queued): ``qry_img`` is a uint8 tensor [B,h,w,3] or
+        a list of B uint8 tensors [h_i,w_i,3], a table is set, (H, W) comes as a pair or as a [B,2] tensor of equal
+        rows, ``img_shape`` (default (H, W, 3) per image) agrees with it, the masks are at their image's source size and
+        every image fits the slot.  -> B, (H, W), the images as flat byte tensors, their sizes, the slot size in bytes
+        per image and ``img_shape``."""
+        rt = np.asarray(qry_resize_to.cpu() if isinstance(qry_resize_to, torch.Tensor) else qry_resize_to)
+        ok = rt.dtype.kind in 'iuf' and (rt.shape == (2,) or (rt.ndim == 2 and rt.shape[1] == 2 and rt.shape[0] >= 1))
+        if ok:
+            rt = rt.reshape(-1, 2)
+            ok = bool(np.all(rt == np.floor(rt)) and np.all(rt == rt[:1]))
+        if not ok:
+            raise ValueError(f'qry_resize_to must be (H, W) or a [B,2] tensor of equal rows, got {qry_resize_to!r}')
+        H, W = int(rt[0, 0]), int(rt[0, 1])
+        if not (1 <= H <= ops.RESIZE_MAX_DIM and 1 <= W <= ops.RESIZE_MAX_DIM):
+            raise ValueError(f'qry_resize_to: sizes must be within 1..{ops.RESIZE_MAX_DIM}, got {(H, W)}')
+        if self.input_lut is None:
+            raise ValueError('qry_resize_to needs the normalisation table: call set_input_norm first')
+        imgs = list(qry_img) if isinstance(qry_img, (list, tuple)) else qry_img
+        if isinstance(imgs, torch.Tensor):
+            if imgs.dim() != 4:
+                raise ValueError(f'qry_img: with qry_resize_to, a uint8 tensor [B,h,w,3] or a list of [h,w,3] tensors, '
+                                 f'got {list(imgs.shape)}')
+            imgs = list(imgs.unbind(0))
+        for im in imgs:
+            if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
+                what = f'{im.dtype} {list(im.shape)}' if isinstance(im, torch.Tensor) else type(im).__name__
+                raise ValueError(f'qry_img: with qry_resize_to every image is channels-last uint8 pixels [h,w,3], got {what}')
+            if not (1 <= im.shape[0] <= ops.RESIZE_MAX_DIM and 1 <= im.shape[1] <= ops.RESIZE_MAX_DIM):
+                raise ValueError(f'qry_img: source sizes must be within 1..{ops.RESIZE_MAX_DIM}, got {list(im.shape)}')
+        B = len(imgs)
+        if len(rt) not in (1, B):
+            raise ValueError(f'qry_resize_to has {len(rt)} rows for {B} images')
+        if img_shape is None:
+            img_shape = np.tile(np.array([H, W, 3], np.int32), (B, 1))
+        elif len(img_shape) != B or any(int(sh[0]) != H or int(sh[1]) != W for sh in img_shape):
+            raise ValueError(f'img_shape {[tuple(int(v) for v in sh) for sh in img_shape]} disagrees with '
+                             f'qry_resize_to {(H, W)}')
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+        if qry_isegmaps is not None:
+            if len(qry_isegmaps) != B:
+                raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {B} images')
+            for g, hw in zip(qry_isegmaps, sizes):
+                if len(g.shape) != 3 or (int(g.shape[1]), int(g.shape[2])) != hw:
+                    raise ValueError(f'qry_isegmaps: with qry_resize_to the masks are at source size {hw}, got '
+                                     f'{list(g.shape)}')
+        need = max((3 * h * w for h, w in sizes), default=0)
+        capacity = need
+        if graphed:
+            capacity = int(self.query_source_capacity)
+            if need > capacity:
+                raise ValueError(f'a query image of {need} bytes exceeds FGN.query_source_capacity = {capacity}: raise '
+                                 f'the attribute (the static source slot of the captured graph)')
+        return dict(B=B, hw=(H, W), flats=[im.contiguous().reshape(-1) for im in imgs], sizes=sizes, need=need,
+                    capacity=capacity, img_shape=img_shape)
+
+    @staticmethod
+    def _scaled_boxes(qry_bboxes, sizes, hw):
+        """The boxes of source-size queries at the network size, exactly as ``fewshot_ds.resize_query`` scales them
+        (base_fst.py:877-878; the caller's arrays are never written; untouched at equal size)."""
+        if qry_bboxes is None:
+            return None
+        from .fewshot_ds import scale_boxes_yxyx
+        out = []
+        for b, (h, w) in zip(qry_bboxes, sizes):
+            if (h, w) == tuple(hw) or b is None:
+                out.append(b)
+            elif isinstance(b, torch.Tensor):
+                out.append(torch.from_numpy(scale_boxes_yxyx(b.detach().cpu().numpy(), h, w, *hw)))
+            else:
+                out.append(scale_boxes_yxyx(np.asarray(b), h, w, *hw))
+        return out
+
     # --- stages ---------------------------------------------------------------------------
-    def extract_feat(self, img: torch.Tensor) -> torch.Tensor:
+    def extract_feat(self, img: Union[torch.Tensor, '_SrcQuery']) -> torch.Tensor:
         """ResNet-50 stages 1-3 (fgn.py:67-77): NCHW fp32 (or uint8 pixels, ``set_input_norm``) in, NHWC [B,h,w,1024]
         out."""
         P = self._P
@@ -849,7 +962,7 @@ class FGN(torch.nn.Module):
                 x = blk(x)
         return x
 
-    def extract_feat_pair(self, qry: torch.Tensor, spp: torch.Tensor, phase_counter=None):
+    def extract_feat_pair(self, qry: Union[torch.Tensor, '_SrcQuery'], spp: torch.Tensor, phase_counter=None):
         """Both backbone passes of an episode (fgn.py:212-215) through SHARED launches wherever a layer does not look at
         the spatial structure (``use_merged_backbone``; frozen-BN bottleneck backbones only)."""
         P = self._P
@@ -912,11 +1025,22 @@ class FGN(torch.nn.Module):
 
     @torch.no_grad()
     def forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
-                      spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, **kwargs) -> Dict:
+                      spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
+                      **kwargs) -> Dict:
         """The loss dict of one training step (fgn.py:125-185) as forward values - see ``fgn_amd.train``.  Keys and
         container types are the reference's: ``loss_rpn_cls`` / ``loss_rpn_bbox`` (lists of one tensor),
-        ``loss_cls``, ``ACC-Unbalanced``, ``ACC-Balanced``, ``loss_bbox``, ``loss_mask``."""
+        ``loss_cls``, ``ACC-Unbalanced``, ``ACC-Balanced``, ``loss_bbox``, ``loss_mask``.  ``qry_resize_to``: source-size
+        query images, masks and boxes, as for ``simple_test``."""
         from . import train
+        if qry_resize_to is not None:
+            rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
+            if not torch.cuda.is_available():
+                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
+            dev = torch.device('cuda', torch.cuda.current_device())
+            qry_img = self._upload_source(rs, dev)
+            qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
+            qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) for g in qry_isegmaps]
+            img_shape = rs['img_shape']
         return train.forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps,
                                    qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals, spp_imgs=spp_imgs,
                                    spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps, img_shape=img_shape, **kwargs)
@@ -925,15 +1049,27 @@ class FGN(torch.nn.Module):
     def simple_test(self, qry_img, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None, qry_bboxes_ignore=None,
                     spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, qry_child_idx=None, img_shape=None,
                     rescale=False, cats_ids_to_sample_real=None, spp_insts_ids=None, idx=None,
-                    support_code=None, **kwargs) -> List[Dict]:
+                    support_code=None, qry_resize_to=None, **kwargs) -> List[Dict]:
         """Test without augmentation (fgn.py:187-303).  ``support_code`` (optional, from
-        ``encode_supports``) replaces the three ``spp_*`` inputs."""
-        dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
-                                  qry_isegmaps=qry_isegmaps)
-        return self.pack_results(dets, qry_img.shape[0], qry_bboxes=qry_bboxes, qry_cat_ids=qry_cat_ids,
+        ``encode_supports``) replaces the three ``spp_*`` inputs.  ``qry_resize_to`` = (H, W) (or a [B,2] tensor of
+        equal rows): ``qry_img`` holds decoded images at their SOURCE size - a uint8 tensor [B,h,w,3] or a list of B
+        uint8 tensors [h_i,w_i,3] - and ``qry_isegmaps`` / ``qry_bboxes`` are at source size too; image and masks are
+        resized to the network size on the device (``fewshot_ds.resize_query`` bit for bit, base_fst.py:876-887), the
+        boxes on the host; needs ``set_input_norm``."""
+        if qry_resize_to is None:
+            dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
+                                      qry_isegmaps=qry_isegmaps)
+            batch = qry_img.shape[0]
+        else:
+            rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps, self._graphed())
+            dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
+                                      qry_isegmaps=qry_isegmaps, qry_resize_to=rs)
+            batch, img_shape = rs['B'], rs['img_shape']
+            qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
+        return self.pack_results(dets, batch, qry_bboxes=qry_bboxes, qry_cat_ids=qry_cat_ids,
                                  qry_isegmaps=qry_isegmaps, img_shape=img_shape, qry_child_idx=qry_child_idx,
                                  cats_ids_to_sample_real=cats_ids_to_sample_real, spp_insts_ids=spp_insts_ids,
-                                 idx=idx)
+                                 idx=idx, qry_resize_to=None if qry_resize_to is None else rs['hw'])
 
     # --- support branch (fgn.py:212-215 backbone pass; fgn_ag_rpn_head.py:38-41; fgn_roi_head.py:419-449) ---
     def _support_front(self, spp_imgs, spp_bboxes, spp_isegmaps, B, dev, stream, defer_backbone: bool = False) -> dict:
@@ -1054,8 +1190,38 @@ class FGN(torch.nn.Module):
         self.transfer_mode = int(mode)
         return self._stream_for('upload', torch.cuda.current_stream())
 
+    def _upload_source(self, rs: dict, dev, into: Optional[dict] = None) -> '_SrcQuery':
+        """The source pixels of ``_source_query`` on the device, on the current stream: h_i * w_i * 3 bytes per image
+        into row i of ``into['qry_src']`` (the [B, capacity] static slot of a captured graph) when that is given, else of
+        a fresh buffer as wide as the largest image of the batch - what lies behind an image in its row is never read -
+        and the sizes as int32 [B,2]."""
+        dst = None if into is None else into.get('qry_src')
+        if dst is None or tuple(dst.shape) != (rs['B'], rs['capacity']):
+            dst = torch.empty((rs['B'], rs['need']), dtype=torch.uint8, device=dev)
+        for i, flat in enumerate(rs['flats']):
+            dst[i, :flat.numel()].copy_(flat, non_blocking=True)
+        hw = torch.tensor(rs['sizes'], dtype=torch.int32).reshape(-1, 2)
+        dhw = None if into is None else into.get('qry_src_hw')
+        if dhw is not None and tuple(dhw.shape) == tuple(hw.shape):
+            dhw.copy_(hw, non_blocking=True)
+        else:
+            dhw = hw.to(dev, non_blocking=True)
+        return _SrcQuery(dst, dhw, *rs['hw'])
+
+    @staticmethod
+    def _resized_masks(g, hw, dev) -> torch.Tensor:
+        """Ground-truth masks of one image on the device as bool / uint8 [n,H,W]; at another size than ``hw`` (not None)
+        they are resized there (``ops.resize_masks``)."""
+        g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
+        g = g.to(dev, non_blocking=True)
+        g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
+        g = g.contiguous()
+        if hw is not None and tuple(g.shape[1:]) != tuple(hw):
+            g = ops.resize_masks(g, *hw)
+        return g
+
     def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None,
-                bits_out: Optional[list] = None):
+                bits_out: Optional[list] = None, source: Optional[dict] = None):
         """``modify_input`` (fgn.py:79-108): host -> device copies of one batch, on an upload stream so that they
         overlap the previous batch's kernels (a pinned source makes them asynchronous); the compute streams wait
         on one event.  Tensors already on the device pass through.  The ground-truth masks (copied to the GPU by
@@ -1065,12 +1231,14 @@ class FGN(torch.nn.Module):
         stream itself and so ordered behind the previous replay that reads them) instead of fresh allocations.
         ``bits_out`` (``match_on_device``): a list that receives, per image, the bit planes of its ground-truth masks
         (``ops.mask_bits`` on the device copy made for the RLE, right behind it on the upload stream; None for an image
-        without ground truth)."""
+        without ground truth).  ``source`` (``_source_query``): the query comes at source size - its pixels go up as
+        ``qry_src`` / ``qry_src_hw`` (``_upload_source``) and the masks are resized right behind their upload."""
         gts = None
         if gt_masks is not None:
             gts = [g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
-        on_host = [t for t in list(tensors.values()) + (gts or []) if t is not None and not t.is_cuda]
-        if not on_host and gts is None:
+        on_host = [t for t in list(tensors.values()) + (gts or []) + (source['flats'] if source else [])
+                   if t is not None and not t.is_cuda]
+        if not on_host and gts is None and source is None:
             return tensors, None, None
         up = self._stream_for('upload', main)
         if not on_host:
@@ -1084,12 +1252,13 @@ class FGN(torch.nn.Module):
                     out[k] = into[k]
                 else:
                     out[k] = None if t is None else t.to(dev, non_blocking=True)
+            if source is not None:
+                sq = self._upload_source(source, dev, into)
+                out['qry_src'], out['qry_src_hw'] = sq.src, sq.hw
             if gts is not None:
                 gt_out = []
                 for g in gts:
-                    g = g.to(dev, non_blocking=True)
-                    g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
-                    g = g.contiguous()
+                    g = self._resized_masks(g, source['hw'] if source else None, dev)
                     gt_out.append(ops.dense_mask_rle(g, packed=True))
                     if bits_out is not None:
                         bits_out.append(ops.mask_bits(g) if g.shape[0] else None)
@@ -1101,7 +1270,7 @@ class FGN(torch.nn.Module):
 
     @torch.no_grad()
     def detect_device(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
-                      qry_isegmaps=None, phase_counter=None) -> list:
+                      qry_isegmaps=None, phase_counter=None, qry_resize_to=None) -> list:
         """Everything up to the host wait: queues the host->device copies, the whole path and the device->host
         copies of the results.  Returns, per image, a dict of device tensors (det_bboxes [D,5], det_labels [D],
         n_dets [1], mask_prob, RLE bytes) plus the pinned host slot ``pack_results`` reads.
@@ -1111,33 +1280,45 @@ class FGN(torch.nn.Module):
         (same kernels, same results; ~0.2 ms of host time instead of ~2 ms).  ``phase_counter``: the one-element int32
         device counter THIS call's episode bumps at ``phase_point`` (see ``_phase_mark``); passed per call, so two
         caller threads never see each other's counter (the attribute of the same name is the fallback for callers that
-        set it on the model)."""
+        set it on the model).  ``qry_resize_to``: the query comes at source size (see ``simple_test``); its pixels
+        travel as ``qry_src`` (uint8 [B, slot]) and ``qry_src_hw`` (int32 [B,2]) in place of ``qry_img``, and a captured
+        graph is keyed by the slot size and (H, W), not by the source sizes.  (``simple_test`` hands over the checked
+        form, the dict of ``_source_query``, instead of checking twice.)"""
+        graphed = self._graphed()
+        source = None
+        if qry_resize_to is not None:                     # (every contract error is raised here, before anything is queued)
+            source = qry_resize_to if isinstance(qry_resize_to, dict) else \
+                self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps, graphed)
+            img_shape = source['img_shape']
         if not torch.cuda.is_available():
             raise ops._lib.FgnHipError('FGN.simple_test needs a GPU: the HIP path has no CPU fallback')
         dev = torch.device('cuda', torch.cuda.current_device())
         main = torch.cuda.current_stream()
-        self._image_dims(qry_img, 'qry_img')              # (a wrong uint8 layout is refused before anything is queued)
-        ins = {'qry_img': qry_img}
+        if source is None:
+            self._image_dims(qry_img, 'qry_img')          # (a wrong uint8 layout is refused before anything is queued)
+            ins = {'qry_img': qry_img}
+        else:
+            ins = {}
         if support_code is None:
             self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
             ins.update(spp_imgs=spp_imgs, spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps)
-        graphed = self.use_graphs and self.debug_trace is None and ops.PROFILE is None
         if phase_counter is None:
             phase_counter = self.phase_counter
         # graph replay with the transfers on the caller stream: host tensors go straight into the graph's static input
         # buffers (the caller stream orders the copy behind the previous replay that reads them) - no device-to-device hop
         into = None
         if graphed and self.use_packed_transfers and self._stream_for('upload', main) is main:
-            ge0 = self._graphs.get(self._graph_key(ins, img_shape, support_code, phase_counter, main, dev))
+            ge0 = self._graphs.get(self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source))
             into = ge0.static if ge0 is not None else None
         gt_bits = [] if (self.match_on_device and qry_isegmaps is not None) else None
-        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits)
+        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits, source=source)
         if uploaded is not None:
             main.wait_event(uploaded)
         if graphed:
-            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter)
+            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter, source)
         else:
-            outs = self._detect_eager(ins['qry_img'], ins.get('spp_imgs'), ins.get('spp_bboxes'),
+            qry = ins['qry_img'] if source is None else _SrcQuery(ins['qry_src'], ins['qry_src_hw'], *source['hw'])
+            outs = self._detect_eager(qry, ins.get('spp_imgs'), ins.get('spp_bboxes'),
                                       ins.get('spp_isegmaps'), img_shape, support_code, phase_counter=phase_counter)
         if gt_rle is not None:
             for d, g in zip(outs, gt_rle):
@@ -1158,7 +1339,10 @@ class FGN(torch.nn.Module):
             ge.last_download = outs[0]['host_ready']
         return outs
 
-    def _graph_key(self, ins: dict, img_shape, support_code, phase_counter, main, dev) -> tuple:
+    def _graphed(self) -> bool:
+        return bool(self.use_graphs and self.debug_trace is None and ops.PROFILE is None)
+
+    def _graph_key(self, ins: dict, img_shape, support_code, phase_counter, main, dev, source=None) -> tuple:
         hw = tuple((int(s[0]), int(s[1])) for s in img_shape)
         # everything the captured launch sequence depends on besides the weights (those drop ``_graphs`` when they
         # change): the paste semantic is an argument of the captured RLE kernel, the transfer arrangement decides which
@@ -1167,16 +1351,20 @@ class FGN(torch.nn.Module):
         mark = None if (phase_counter is None or not self.phase_point) else (phase_counter.data_ptr(), self.phase_point)
         return (main.cuda_stream, dev.index, hw, support_code is not None, bool(self.use_merged_backbone),
                 bool(self.use_merged_support_head), self.paste_semantics, int(self.transfer_mode), mark,
-                bool(self.use_side_stream), bool(self.use_packed_transfers)) + \
-            tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items() if v is not None)
+                bool(self.use_side_stream), bool(self.use_packed_transfers),
+                # source-size queries: the slot and the size they are resized to - NOT the source sizes, which the kernel
+                # reads from ``qry_src_hw`` (the slot tensors are in ``ins`` only once they are uploaded: keyed here)
+                None if source is None else (source['B'], source['capacity'], source['hw'])) + \
+            tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items()
+                  if v is not None and k not in ('qry_src', 'qry_src_hw'))
 
-    def _detect_graphed(self, ins: dict, img_shape, support_code, phase_counter=None):
+    def _detect_graphed(self, ins: dict, img_shape, support_code, phase_counter=None, source=None):
         main = torch.cuda.current_stream()
         dev = torch.device('cuda', torch.cuda.current_device())
-        key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev)
+        key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source)
         ge = self._graphs.get(key)
         if ge is None:
-            ge = self._graphs[key] = _GraphedEpisode(self, ins, img_shape, support_code, dev, phase_counter)
+            ge = self._graphs[key] = _GraphedEpisode(self, ins, img_shape, support_code, dev, phase_counter, source)
         return ge, ge.run(self, ins, support_code, main)
 
     def _detect_eager(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
@@ -1493,9 +1681,17 @@ class FGN(torch.nn.Module):
 
     def pack_results(self, dets: list, batch: int, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None,
                      img_shape=None, qry_child_idx=None, cats_ids_to_sample_real=None, spp_insts_ids=None,
-                     idx=None) -> List[Dict]:
+                     idx=None, qry_resize_to=None) -> List[Dict]:
         """Device->host copy and result dicts (fgn.py:240-303).  Passthrough boxes stay YXYX
-        (SERVER semantics); caller tensors are never mutated."""
+        (SERVER semantics); caller tensors are never mutated.  ``qry_resize_to`` = (H, W):
+        ``qry_isegmaps`` are at source size (they are read only where a device RLE overflowed or none was made, and
+        resized on the host then)."""
+        def host_mask(m):
+            m = np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m)
+            if qry_resize_to is not None and tuple(m.shape[-2:]) != tuple(qry_resize_to):
+                from .fewshot_ds import resize_masks
+                m = resize_masks(m.reshape((-1,) + m.shape[-2:]), *qry_resize_to).reshape(m.shape[:-2] + tuple(qry_resize_to))
+            return m
         passthrough = {'idx': idx, 'qry_bboxes': qry_bboxes, 'qry_img_shape': img_shape,
                        'qry_cat_ids': qry_cat_ids, 'qry_child_idx': qry_child_idx,
                        'cats_ids_to_sample_real': cats_ids_to_sample_real, 'spp_insts_ids': spp_insts_ids}
@@ -1536,11 +1732,10 @@ class FGN(torch.nn.Module):
                 gstr = hb[ng * 8:].view(ng, ops.RLE_BYTE_CAP).numpy()
                 one['qry_isegmaps_rle'] = [
                     {'size': [ih, iw], 'counts': gstr[j, :glen[j]].tobytes()} if not govf[j] else
-                    rle.encode(np.asarray(gt[j].cpu() if isinstance(gt[j], torch.Tensor) else gt[j]))
+                    rle.encode(host_mask(gt[j]))
                     for j in range(ng)]
             elif gt is not None:
-                gt = gt.cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)
-                one['qry_isegmaps_rle'] = rle.encode_many(gt)
+                one['qry_isegmaps_rle'] = rle.encode_many(host_mask(gt))
             if 'ov_slice' in di:                   # overlap counts from the device: [inter [D,G] | det_area [D] | gt_area [G]]
                 o0, nov = di['ov_slice']
                 md = host['det'].shape[1]

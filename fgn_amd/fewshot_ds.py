@@ -159,6 +159,92 @@ def support_from_instance(img: np.ndarray, bbox_yxyx, isegmap: np.ndarray, spp_i
     return out, (box_r + np.array([top, left, top, left], np.float32)).astype(np.float32), m
 
 
+# ---- query resize (BaseFewShotISEG.get_query, base_fst.py:876-887) -------------------------------------------------
+# cv2.resize (bilinear) is third party and its uint8 path differs between versions, so the rule is this project's own
+# restatement of its design - half-pixel centres, clamped edges, 11-bit weights, round half up - in INTEGERS, so that
+# the kernels of csrc/spatial.hip (resize_u8hwc3_to_nhwc4_kernel, resize_mask_u8_kernel) agree with these functions bit
+# for bit.  No pin is held by the reference; a float bilinear differs by at most 1 grey level.
+RESIZE_MAX_DIM = 16384        # every intermediate of the rule fits int32 up to here; larger dimensions are refused
+RESIZE_W_BITS = 11            # weights 0..2048 per axis; acc <= 255 * 2^22
+
+
+def _check_resize_dims(*dims) -> None:
+    for d in dims:
+        if not 1 <= int(d) <= RESIZE_MAX_DIM:
+            raise ValueError(f'resize: every dimension must be in 1..{RESIZE_MAX_DIM}, got {int(d)}')
+
+
+def resize_taps(n_src: int, n_dst: int):
+    """Taps of one axis: destination sample j blends source samples i0[j], i1[j] with weights w0[j] + w1[j] = 2048.
+    num = (2j+1) * n_src - n_dst over den = 2 * n_dst is the source coordinate of j's centre; i0 its floor, w1 the
+    fraction rounded half up to 11 bits; left of the first centre the weight is all on sample 0, right of the last
+    both taps are the last sample.  -> (i0, i1, w0, w1) int32 [n_dst]."""
+    _check_resize_dims(n_src, n_dst)
+    n_src, n_dst = int(n_src), int(n_dst)
+    j = np.arange(n_dst, dtype=np.int32)
+    den = np.int32(2 * n_dst)
+    num = (2 * j + 1) * np.int32(n_src) - np.int32(n_dst)
+    i0 = num // den                                     # (floor division)
+    rem = num - i0 * den
+    w1 = (rem * np.int32(1 << (RESIZE_W_BITS + 1)) + den) // (2 * den)
+    w1 = np.where(i0 < 0, 0, w1).astype(np.int32)
+    i1 = np.minimum(i0 + 1, n_src - 1).astype(np.int32)
+    i0 = np.clip(i0, 0, n_src - 1).astype(np.int32)
+    return i0, i1, (np.int32(1 << RESIZE_W_BITS) - w1).astype(np.int32), w1
+
+
+def _resize_acc(planes: np.ndarray, H: int, W: int) -> np.ndarray:
+    """planes uint8 [..,h,w] -> the int32 accumulators [..,H,W] of the rule (weights sum to 2^22)."""
+    h, w = planes.shape[-2:]
+    y0, y1, wy0, wy1 = resize_taps(h, H)
+    x0, x1, wx0, wx1 = resize_taps(w, W)
+    p = planes.astype(np.int32)
+    top, bot = p[..., y0, :], p[..., y1, :]
+    wy0, wy1 = wy0[:, None], wy1[:, None]
+    return (top[..., x0] * (wy0 * wx0) + top[..., x1] * (wy0 * wx1)
+            + bot[..., x0] * (wy1 * wx0) + bot[..., x1] * (wy1 * wx1))
+
+
+def resize_image_u8(img: np.ndarray, H: int, W: int) -> np.ndarray:
+    """uint8 [h,w,3] -> uint8 [H,W,3]: per channel (acc + 2^21) >> 22."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3:
+        raise ValueError(f'resize_image_u8: expects a uint8 [h,w,c] image, got {img.dtype} {list(img.shape)}')
+    acc = _resize_acc(np.moveaxis(img, 2, 0), H, W)
+    half = np.int32(1 << (2 * RESIZE_W_BITS - 1))
+    return np.ascontiguousarray(np.moveaxis((acc + half) >> (2 * RESIZE_W_BITS), 0, 2).astype(np.uint8))
+
+
+def resize_masks(m: np.ndarray, H: int, W: int) -> np.ndarray:
+    """bool (or 0 / nonzero) [G,h,w] -> bool [G,H,W]: resized as 0/1 bytes by the same rule, set where acc >= 2^21
+    (a half counts as set) - what ``cv2.resize(m.astype(uint8)).astype(bool)`` means."""
+    m = np.asarray(m)
+    if m.ndim != 3:
+        raise ValueError(f'resize_masks: expects [G,h,w], got {list(m.shape)}')
+    _check_resize_dims(H, W)
+    if m.shape[0] == 0:
+        return np.zeros((0, int(H), int(W)), bool)
+    return _resize_acc((m != 0).astype(np.uint8), H, W) >= (1 << (2 * RESIZE_W_BITS - 1))
+
+
+def scale_boxes_yxyx(bboxes_yxyx: np.ndarray, h: int, w: int, H: int, W: int) -> np.ndarray:
+    """base_fst.py:877-878 on a copy: rows 0, 2 times H / h and rows 1, 3 times W / w (Python floats), in the boxes'
+    own dtype."""
+    out = np.array(bboxes_yxyx, copy=True)
+    out[:, [0, 2]] = out[:, [0, 2]] * (H / h)
+    out[:, [1, 3]] = out[:, [1, 3]] * (W / w)
+    return out
+
+
+def resize_query(img: np.ndarray, bboxes_yxyx: np.ndarray, isegmaps: np.ndarray, H: int, W: int):
+    """What ``get_query`` does between the decoded image and the sample (base_fst.py:876-887): image and masks to
+    (H, W), boxes scaled.  At equal size everything passes through untouched (the same objects)."""
+    h, w = img.shape[:2]
+    if int(H) == h and int(W) == w:
+        return img, bboxes_yxyx, isegmaps
+    return resize_image_u8(img, H, W), scale_boxes_yxyx(bboxes_yxyx, h, w, H, W), resize_masks(isegmaps, H, W)
+
+
 class SyntheticFewShotISEG(Dataset):
     def __init__(self, n_ways=3, k_shots=3, length=64, height=800, width=1333, spp_img_size=256, batch=4,
                  seed=1234, suffix='SYNTH_val_novel'):
@@ -215,16 +301,25 @@ class ClutteredCharsFewShotISEG(Dataset):
     dataset mean/std (datasets/mnistiseg/ParamsMNISTISEG.json:1-5, datasets/omniiseg/ParamsOMNIISEG.json:1-5).
     Character datasets are batched without aspect-ratio grouping (base_fst.py:611-624).
     ``raw_uint8``: the images stay decoded pixels - ``qry_img`` uint8 [H,W,3], ``spp_imgs`` uint8 [N*K,S,S,3] - for a
-    detector that normalises on the device (``FGN.set_input_norm(**ds.input_norm)``); nothing else of the sample changes."""
+    detector that normalises on the device (``FGN.set_input_norm(**ds.input_norm)``); nothing else of the sample changes.
+    ``source_size`` = S (needs ``raw_uint8``): the images are generated at S x S instead of the network size and the
+    query is NOT resized by the loader (``get_query``'s cv2.resize, base_fst.py:876-887) - ``qry_img`` [S,S,3],
+    ``qry_isegmaps`` and ``qry_bboxes`` stay at source size and the sample carries ``qry_resize_to`` = (img_size,
+    img_size) for a detector that resizes on the device (``FGN.simple_test(qry_resize_to=...)``); ``img_shape`` is the
+    network size.  Without it the samples are what they always were."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
                                std=(0.16037128865718842, 0.15775758028030396, 0.15985246002674103), n_cats=26)}
 
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
-                 spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False):
+                 spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None):
         par = self.PARAMS[dataset]
         self.raw_uint8 = bool(raw_uint8)
+        self.source_size = None if source_size is None else int(source_size)
+        if self.source_size is not None and not self.raw_uint8:
+            raise ValueError('source_size needs raw_uint8=True: source-size queries are resized by the detector, which '
+                             'takes decoded pixels')
         self.n_ways, self.k_shots, self.batch, self.shuffle = n_ways, k_shots, batch, shuffle
         self.img_size, self.spp_img_size, self.spp_fill_ratio = img_size, spp_img_size, spp_fill_ratio
         self.sampling_origin_ds, self.sampling_origin_ds_subset = dataset, 'val'
@@ -233,7 +328,8 @@ class ClutteredCharsFewShotISEG(Dataset):
         self.std = np.asarray(par['std'], np.float32)
         self.seed = seed
         cats = np.arange(par['n_cats'])
-        self.images = [cc.make_image(seed + j, img_size, cats) for j in range(n_imgs)]
+        self.images = [cc.make_image(seed + j, img_size if self.source_size is None else self.source_size, cats)
+                       for j in range(n_imgs)]
         # instance table: (image, object) per class, instance id = position in this table
         self.inst = [(j, o) for j, im in enumerate(self.images) for o in range(len(im['cat_ids']))]
         self.inst_cat = np.array([self.images[j]['cat_ids'][o] for j, o in self.inst])
@@ -289,7 +385,7 @@ class ClutteredCharsFewShotISEG(Dataset):
                 crop, nb, m = support_from_instance(src['img'], src['bboxes'][o], src['isegmaps'][o],
                                                     self.spp_img_size, self.spp_fill_ratio)
                 spp_imgs.append(self._norm(crop)); spp_boxes.append(nb); spp_masks.append(m); spp_ids.append(p)
-        return {
+        sample = {
             'idx': int(idx),
             'qry_child_idx': child,
             'qry_img': self._norm(im['img']),
@@ -305,6 +401,9 @@ class ClutteredCharsFewShotISEG(Dataset):
             'spp_insts_ids': np.asarray(spp_ids, np.int64),
             'img_shape': np.array([self.img_size, self.img_size, 3], dtype=np.int32),
         }
+        if self.source_size is not None:
+            sample['qry_resize_to'] = np.array([self.img_size, self.img_size], dtype=np.int32)
+        return sample
 
     evaluate = SyntheticFewShotISEG.evaluate
 

@@ -38,6 +38,8 @@ SIGNATURES = {
     'fgn_winograd4_output2_f32': (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_nchw3_to_nhwc4_f32': (_i, [_p, _p, _i, _i, _i, _p]),
     'fgn_u8hwc3_to_nhwc4_f32': (_i, [_p, _p, _p, _i, _i, _i, _p]),
+    'fgn_resize_u8hwc3_to_nhwc4_f32': (_i, [_p, C.c_longlong, _p, _p, _p, _i, _i, _i, _p]),
+    'fgn_resize_mask_u8': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'fgn_maxpool3x3s2_nhwc_f32': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgn_group_norm_workspace_bytes': (C.c_size_t, [_i] * 4),
     'fgn_group_norm_nhwc_f32': (_i, [_p] * 6 + [C.c_size_t, _i, _i, _i, _i, _f, _i, _p]),
@@ -109,7 +111,7 @@ SIGNATURES = {
     'fgn_adagrad_multi_f32': (_i, [_p, _p, _p, _p, _p, _i, _f, _f, _p]),
 }
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 _lib = None
 
 

@@ -1033,6 +1033,58 @@ def u8hwc3_to_nhwc4(x_u8: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
     return y
 
 
+RESIZE_MAX_DIM = 16384       # csrc/spatial.hip; fewshot_ds.RESIZE_MAX_DIM: int32 arithmetic of the resize rule
+
+
+def resize_u8_to_nhwc4(src: torch.Tensor, src_hw: torch.Tensor, lut: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Source-size images -> the NHWC4 fp32 stem input at (H, W): ``u8hwc3_to_nhwc4`` of
+    ``fewshot_ds.resize_image_u8`` of every image, bit for bit.  ``src`` uint8 [n, capacity]: image b is
+    [h_b, w_b, 3] pixels at the start of row b; ``src_hw`` int32 [n,2] ON THE DEVICE holds (h_b, w_b) and is read by
+    the kernel (the launch is the same for every source size).  An image whose size is outside 1..16384 or exceeds the
+    capacity comes out as zeros."""
+    _chk(src, 'src', torch.uint8)
+    _chk(src_hw, 'src_hw', torch.int32)
+    _chk(lut, 'lut')
+    if src.dim() != 2 or tuple(src_hw.shape) != (src.shape[0], 2) or src_hw.device != src.device:
+        raise _lib.FgnHipError('resize_u8_to_nhwc4: expects src [n,capacity] and src_hw [n,2] on one device')
+    if tuple(lut.shape) != (3, 256) or lut.device != src.device:
+        raise _lib.FgnHipError('resize_u8_to_nhwc4: lut must be [3,256] on the device of src')
+    H, W = int(H), int(W)
+    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM):
+        raise _lib.FgnHipError(f'resize_u8_to_nhwc4: output size must be within 0..{RESIZE_MAX_DIM}, got {(H, W)}')
+    n = src.shape[0]
+    y = torch.empty((n, H, W, 4), device=src.device, dtype=torch.float32)
+    if y.numel() == 0:                  # (an empty tensor has no address to hand over)
+        return y
+    if src.shape[1] == 0:
+        src = src.new_zeros((n, 1))     # (capacity 0: every image is refused by the kernel; it needs an address only)
+    _lib.check(_lib.load().fgn_resize_u8hwc3_to_nhwc4_f32(_ptr(src), int(src.shape[1]), _ptr(src_hw), _ptr(lut),
+                                                           _ptr(y), n, H, W, _stream()),
+               'fgn_resize_u8hwc3_to_nhwc4_f32')
+    return y
+
+
+def resize_masks(masks: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Dense binary masks [G,h,w] (bool / uint8, non-zero = set) -> uint8 0/1 [G,H,W]: ``fewshot_ds.resize_masks`` bit
+    for bit (the ground-truth side of the query resize)."""
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    _chk(masks, 'masks', torch.uint8)
+    if masks.dim() != 3:
+        raise _lib.FgnHipError('resize_masks: masks must be [G,h,w]')
+    g, h, w = masks.shape
+    H, W = int(H), int(W)
+    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM and h <= RESIZE_MAX_DIM and w <= RESIZE_MAX_DIM):
+        raise _lib.FgnHipError(f'resize_masks: every dimension must be at most {RESIZE_MAX_DIM}')
+    out = torch.empty((g, H, W), device=masks.device, dtype=torch.uint8)
+    if out.numel() == 0:
+        return out
+    if h == 0 or w == 0:
+        raise _lib.FgnHipError('resize_masks: empty source masks')
+    _lib.check(_lib.load().fgn_resize_mask_u8(_ptr(masks), _ptr(out), g, h, w, H, W, _stream()), 'fgn_resize_mask_u8')
+    return out
+
+
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x, 'x')
     n, h, w, c = x.shape

@@ -217,6 +217,22 @@ int fgn_nchw3_to_nhwc4_f32(const float* x, float* y, int n_img, int H, int W, vo
  * alignment (a pointer that is not dword-aligned takes a pixel-per-lane path).  An empty tensor is FGN_OK. */
 int fgn_u8hwc3_to_nhwc4_f32(const unsigned char* x, const float* lut, float* y, int n_img, int H, int W, void* stream);
 
+/* Query resize behind the upload (BaseFewShotISEG.get_query, base_fst.py:876-887).  Both entries compute the integer
+ * bilinear rule of fgn_amd.fewshot_ds (resize_taps: half-pixel centres, clamped edges, 11-bit weights, round half up; a
+ * restatement of cv2.resize's design that no reference golden pins) and agree with resize_image_u8 / resize_masks bit for
+ * bit.  Every dimension is at most 16384 (int32 arithmetic); larger or negative ones are FGN_ERR_SHAPE, a null pointer
+ * FGN_ERR_ARG, an empty output FGN_OK with no launch.
+ *
+ * fgn_resize_u8hwc3_to_nhwc4_f32: image b is [h_b][w_b][3] bytes at src + b * src_stride_bytes (no alignment needed),
+ * {h_b, w_b} = src_hw[b] is read ON THE DEVICE (int32 [n_img][2]) - the launch does not depend on the source sizes, so
+ * one captured launch serves all of them.  y [n_img][H][W][4] fp32 = fgn_u8hwc3_to_nhwc4_f32 of the resized images.
+ * An image with h_b or w_b outside 1..16384 or h_b * w_b * 3 > src_stride_bytes is written as +0.0f and not read. */
+int fgn_resize_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stride_bytes, const int* src_hw,
+                                   const float* lut, float* y, int n_img, int H, int W, void* stream);
+/* fgn_resize_mask_u8: src [G][h][w] bytes (nonzero = set; bool storage) -> dst [G][H][W] 0 / 1 bytes, set where the
+ * weighted sum of the four taps reaches half (cv2.resize(m.astype(uint8)).astype(bool)). */
+int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, int G, int h, int w, int H, int W, void* stream);
+
 /* 3x3/2 pad 1 max-pool of the ResNet stem */
 int fgn_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n_img, int H, int W, int C, void* stream);
 
