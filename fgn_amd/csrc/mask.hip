@@ -45,9 +45,10 @@ __global__ __launch_bounds__(256) void mask_logits_kernel(const float* __restric
 
 extern "C" int fgn_mask_logits_f32(const float* x, const float* w, float bias, const float* bias_dev, float* logits, float* prob,
                                    const int32_t* n_dev, int n_det, int roi_size, int C, hipStream_t stream) {
-    if (!x || !w || !logits || !prob) return FGN_ERR_ARG;
-    if (C % 4) return FGN_ERR_SHAPE;
-    if (n_det == 0) return FGN_OK;
+    // (the per-detection operands of an empty detection set are null pointers: nothing is read or written then)
+    if (!w || (n_det > 0 && (!x || !logits || !prob))) return FGN_ERR_ARG;
+    if (C <= 0 || C % 4 || roi_size <= 0) return FGN_ERR_SHAPE;
+    if (n_det <= 0) return FGN_OK;
     const int waves = n_det * roi_size * roi_size * 4;
     hipLaunchKernelGGL(mask_logits_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, stream, x, w, bias, bias_dev, logits, prob,
                        n_dev, n_det, roi_size, C);

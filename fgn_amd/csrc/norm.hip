@@ -2,8 +2,8 @@
 // (fgn_r50_c4_scratch.py:16-23: deep_stem, avg_down, norm_cfg GN(32)).  GroupNorm statistics
 // depend on the whole image, so unlike eval-mode BatchNorm it cannot be folded into the conv
 // epilogue: three HBM-bound passes per layer (partial sums, finalise, apply), NHWC fp32, every
-// lane moves 16 B.  Sums are fp32 per lane over <= a few hundred values, fp64 across lanes /
-// chunks (deterministic: fixed chunking, no atomics).
+// lane moves 16 B.  The statistics are fp64 sums of shifted values (gn_partial_kernel), deterministic: fixed
+// chunking, no atomics.
 #include "common.h"
 
 constexpr int GN_THREADS = 256;
@@ -11,11 +11,15 @@ constexpr int GN_MAX_CHUNKS = 128;
 
 static inline int gn_chunks(int HW) { return std::max(1, std::min(GN_MAX_CHUNKS, cdiv(HW, 32))); }
 
-// partial[(n*chunks + chunk)*G + g] = (sum, sum of squares) of the chunk's pixels x the group's channels
+// partial[(n*chunks + chunk)*G + g] = (sum, sum of squares) of d = x - K over the chunk's pixels x the group's channels,
+// K = the group's first value of the image (pixel 0, channel g * cpg).  The differences, their squares and every sum
+// are fp64: d is exact, so E[d^2] - E[d]^2 loses (K - mean)^2 / var <= count units of 2^-53 whatever mean / std is
+// (K is one of the group's own values), where fp32 squares of the raw values lost (mean / std)^2 units of 2^-24:
+// rstd was 12 % off at mean / std = 3000.  A constant group has d = 0 and variance exactly 0.
 __global__ __launch_bounds__(GN_THREADS) void gn_partial_kernel(const float4* __restrict__ x,
                                                                 double2* __restrict__ partial, int HW, int C,
                                                                 int G, int chunks) {
-    __shared__ float2 red[GN_THREADS * 4];
+    __shared__ double2 red[GN_THREADS * 4];
     const int qc = C >> 2;                       // float4 columns per pixel
     const int stripes = GN_THREADS / qc;          // pixel stripes of this block (>= 1: C <= 1024)
     const int t = threadIdx.x;
@@ -23,36 +27,43 @@ __global__ __launch_bounds__(GN_THREADS) void gn_partial_kernel(const float4* __
     const int n = blockIdx.y, chunk = blockIdx.x;
     const int per = (HW + chunks - 1) / chunks;
     const int p0 = chunk * per, p1 = min(HW, p0 + per);
-    float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+    const int cpg = C / G;
+    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
     if (st < stripes) {
+        const float* x0 = reinterpret_cast<const float*>(x) + (size_t)n * HW * C;
+        double k[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) k[j] = (double)x0[(cq * 4 + j) / cpg * cpg];
         const float4* base = x + (size_t)n * HW * qc + cq;
         for (int p = p0 + st; p < p1; p += stripes) {
             const float4 v = base[(size_t)p * qc];
-            s[0] += v.x; q[0] += v.x * v.x;
-            s[1] += v.y; q[1] += v.y * v.y;
-            s[2] += v.z; q[2] += v.z * v.z;
-            s[3] += v.w; q[3] += v.w * v.w;
+            const double d0 = (double)v.x - k[0], d1 = (double)v.y - k[1], d2 = (double)v.z - k[2],
+                         d3 = (double)v.w - k[3];
+            s[0] += d0; q[0] += d0 * d0;
+            s[1] += d1; q[1] += d1 * d1;
+            s[2] += d2; q[2] += d2 * d2;
+            s[3] += d3; q[3] += d3 * d3;
         }
     }
 #pragma unroll
-    for (int j = 0; j < 4; ++j) red[t * 4 + j] = make_float2(s[j], q[j]);   // [stripe][channel]
+    for (int j = 0; j < 4; ++j) red[t * 4 + j] = make_double2(s[j], q[j]);   // [stripe][channel]
     __syncthreads();
-    const int cpg = C / G;
     for (int g = t; g < G; g += GN_THREADS) {
         double a = 0.0, b = 0.0;
         for (int sidx = 0; sidx < stripes; ++sidx)
             for (int c = g * cpg; c < (g + 1) * cpg; ++c) {
-                const float2 v = red[(sidx * qc + (c >> 2)) * 4 + (c & 3)];
-                a += (double)v.x;
-                b += (double)v.y;
+                const double2 v = red[(sidx * qc + (c >> 2)) * 4 + (c & 3)];
+                a += v.x;
+                b += v.y;
             }
         partial[((size_t)n * chunks + chunk) * G + g] = make_double2(a, b);
     }
 }
 
-// stats[n*G + g] = (mean, rstd)
-__global__ void gn_finalize_kernel(const double2* __restrict__ partial, float2* __restrict__ stats, int G,
-                                   int chunks, double count, float eps) {
+// stats[n*G + g] = (mean, rstd);  mean = K + E[d], var = E[d^2] - E[d]^2 (K, d: gn_partial_kernel)
+__global__ void gn_finalize_kernel(const float* __restrict__ x, const double2* __restrict__ partial,
+                                   float2* __restrict__ stats, int HW, int C, int G, int chunks, double count,
+                                   float eps) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     const int n = blockIdx.y;
     if (g >= G) return;
@@ -62,9 +73,10 @@ __global__ void gn_finalize_kernel(const double2* __restrict__ partial, float2* 
         a += v.x;
         b += v.y;
     }
-    const double mean = a / count;
-    const double var = fmax(b / count - mean * mean, 0.0);
-    stats[(size_t)n * G + g] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
+    const double k = (double)x[(size_t)n * HW * C + (size_t)g * (C / G)];
+    const double md = a / count;
+    const double var = fmax(b / count - md * md, 0.0);
+    stats[(size_t)n * G + g] = make_float2((float)(k + md), (float)(1.0 / sqrt(var + (double)eps)));
 }
 
 // y = x * (rstd*gamma) + (beta - mean*rstd*gamma)  [+ residual]  [ReLU]
@@ -117,8 +129,8 @@ extern "C" int fgn_group_norm_nhwc_f32(const float* x, float* y, const float* ga
     hipLaunchKernelGGL(gn_partial_kernel, dim3(chunks, n_img), dim3(GN_THREADS), 0, stream,
                        reinterpret_cast<const float4*>(x), partial, HW, C, groups, chunks);
     FGN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(groups, 64), n_img), dim3(64), 0, stream, partial, stats,
-                       groups, chunks, (double)HW * (C / groups), eps);
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(groups, 64), n_img), dim3(64), 0, stream, x, partial, stats,
+                       HW, C, groups, chunks, (double)HW * (C / groups), eps);
     FGN_LAUNCH_CHECK();
     const long long total = (long long)n_img * HW * (C / 4);
     const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 16);

@@ -219,13 +219,14 @@ extern "C" int fgn_relation_gn_head_f32(const float* Q, const float* S, const fl
                                         float* cls_out, float* reg_out, const int32_t* n_rois_dev, int n_rois,
                                         int n_ways, int C, int gn_groups, int roi_size, float eps,
                                         float* rel_out_debug, float* scratch, hipStream_t stream) {
-    if (!Q || !S || !rois || !gn_weight || !gn_bias || !fc_weight || !fc_bias || !cls_out || !reg_out || !scratch)
-        return FGN_ERR_ARG;
+    // (the per-RoI operands of an empty RoI set are null pointers: nothing is read or written then)
+    if (!S || !gn_weight || !gn_bias || !fc_weight || !fc_bias) return FGN_ERR_ARG;
+    if (n_rois > 0 && (!Q || !rois || !cls_out || !reg_out || !scratch)) return FGN_ERR_ARG;
     if (roi_size != 7 || gn_groups <= 0 || C % 32 != 0 || C % gn_groups != 0 || n_ways < 1 || n_ways > REL_MAX_N)
         return FGN_ERR_SHAPE;
     const int gw = C / gn_groups;              // channels per GroupNorm group
     if (gw != 8 && gw != 16 && gw != 32) return FGN_ERR_SHAPE;
-    if (n_rois == 0) return FGN_OK;
+    if (n_rois <= 0) return FGN_OK;
     const int chunks = cdiv(C / 32, REL_WAVES);
 #define REL_LAUNCH(NW)                                                                                                  \
     case NW:                                                                                                            \

@@ -375,8 +375,15 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
         const float start = (is_y ? y1 + (float)ph * bin_h : x1 + (float)pw * bin_w), step = is_y ? bin_h : bin_w;
         float* w = is_y ? wy_sh : wx_sh;
         // (an empty sampling grid - a box of no extent - has no pixels: the bin is 0, as in the per-sample form)
-        const int first = g > 0 ? axis_sample(start + 0.5f * step / (float)g, size).lo : 0;
-        const int last = g > 0 ? axis_sample(start + ((float)(g - 1) + 0.5f) * step / (float)g, size).hi : -1;
+        // (the samples run upwards from the first, or downwards where an aligned box has a negative extent and the grid
+        // is fixed: the span lies between the two end samples either way)
+        int first = 0, last = -1;
+        if (g > 0) {
+            const AxisSample s0 = axis_sample(start + 0.5f * step / (float)g, size);
+            const AxisSample s1 = axis_sample(start + ((float)(g - 1) + 0.5f) * step / (float)g, size);
+            first = min(s0.lo, s1.lo);
+            last = max(s0.hi, s1.hi);
+        }
         const int n = last - first + 1;
         span_sh[is_y ? 0 : 2] = first;
         span_sh[is_y ? 1 : 3] = n;
@@ -668,10 +675,10 @@ __global__ void scale_channels_kernel(const float4* __restrict__ x, const float4
 
 extern "C" int fgn_scale_channels_f32(const float* x, const float* v, float* out, int n_out, int div, int P, int C,
                                       hipStream_t stream) {
-    if (!x || !v || !out) return FGN_ERR_ARG;
-    if (C % 4 || div < 1) return FGN_ERR_SHAPE;
+    if (C % 4 || div < 1 || n_out < 0 || P < 0) return FGN_ERR_SHAPE;
     const long long pc4 = (long long)P * C / 4, total = pc4 * n_out;
-    if (total == 0) return FGN_OK;
+    if (total == 0) return FGN_OK;          // (the operands of an empty tensor are null pointers)
+    if (!x || !v || !out) return FGN_ERR_ARG;
     const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 16);
     hipLaunchKernelGGL(scale_channels_kernel, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4*>(x),
                        reinterpret_cast<const float4*>(v), reinterpret_cast<float4*>(out), div, pc4, C / 4, total);

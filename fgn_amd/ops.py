@@ -1230,7 +1230,7 @@ def scale_channels(x: torch.Tensor, v: torch.Tensor, div: int) -> torch.Tensor:
     if x.shape[0] * div != n_out or x.shape[-1] != c:
         raise _lib.FgnHipError('scale_channels: operand shapes inconsistent')
     out = torch.empty((n_out,) + tuple(x.shape[1:]), device=x.device, dtype=torch.float32)
-    p = x[0].numel() // c
+    p = math.prod(x.shape[1:-1])
     _lib.check(_lib.load().fgn_scale_channels_f32(_ptr(x), _ptr(v), _ptr(out), n_out, div, p, c, _stream()),
                'fgn_scale_channels_f32')
     return out
@@ -1427,7 +1427,7 @@ def mask_logits(x: torch.Tensor, w: torch.Tensor, bias, roi_size: int,
     _chk(w, 'w')
     d = x.shape[0]
     c = w.numel()
-    if x[0].numel() != roi_size * roi_size * 4 * c:
+    if x.numel() != d * roi_size * roi_size * 4 * c:
         raise _lib.FgnHipError('mask_logits: x shape inconsistent with weight')
     logits = zeros((d, 2 * roi_size, 2 * roi_size), x.device)
     if prob_out is not None:        # caller-owned, ZERO on entry (rows beyond the device count are not written)

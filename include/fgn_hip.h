@@ -239,7 +239,8 @@ int fgn_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n_img, int H, int W,
 /* GroupNorm over NHWC (+ residual) (+ ReLU): the norm layers of the from-scratch backbone variant
  * (fgn_r50_c4_scratch.py:16-23, norm_cfg GN(32); torch.nn.GroupNorm inside mmdet ResNet at
  * fgn.py:71-73).  y = (x - mean_g) * rstd_g * gamma[c] + beta[c] per (image, group);
- * ws from fgn_group_norm_workspace_bytes.  x == y (in place) is allowed. */
+ * ws from fgn_group_norm_workspace_bytes.  x == y (in place) is allowed.  Mean and variance are fp64 sums of the
+ * values shifted by the group's first one (fixed order, no atomics): accurate whatever mean / std is. */
 size_t fgn_group_norm_workspace_bytes(int n_img, int HW, int C, int groups);
 int fgn_group_norm_nhwc_f32(const float* x, float* y, const float* gamma, const float* beta,
                             const float* residual, void* ws, size_t ws_bytes, int n_img, int HW, int C,
