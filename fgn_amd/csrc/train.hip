@@ -256,7 +256,10 @@ extern "C" int fgn_softmax_ce_sum_f32(const float* logits, const int64_t* labels
 // BatchNorm2d in training mode on NHWC rows x [P, C] (P = samples x pixels).
 //   stats    per-channel sum and sum of squares in fp64 over row chunks (HBM-bound: one read of x), partials
 //            [chunks][C][2] reduced in chunk order -> mean, biased variance; running estimates updated with
-//            momentum (unbiased variance, torch.nn.BatchNorm2d)
+//            momentum (unbiased variance, torch.nn.BatchNorm2d).  The sums are those of d = x - K, K = the channel's
+//            value in row 0 (mean = K + E[d], var = E[d^2] - E[d]^2): K is one of the channel's own values, so
+//            (K - mean)^2 <= P var and the cancellation costs at most P units of 2^-53 whatever mean / std is (raw
+//            moments lose (mean / std)^2 of them); a constant channel has variance exactly 0 and mean exactly K
 //   apply    y = (x - mean) * rsqrt(var + eps) * gamma + beta (+ residual) (ReLU): one read, one write
 // ---------------------------------------------------------------------------------------------------------
 constexpr int BN_CHUNKS = 64;
@@ -271,12 +274,15 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float4* __restric
     const int r0 = blockIdx.y * rows_per, r1 = min(P, r0 + rows_per);
     double s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
     if (c4 < C4) {
+        const float4 k4 = x[c4];                                  // row 0: the shift of this channel quad
+        const double k[4] = {(double)k4.x, (double)k4.y, (double)k4.z, (double)k4.w};
         for (int r = r0 + ph; r < r1; r += 4) {
             const float4 v = x[(size_t)r * C4 + c4];
-            s[0] += v.x; q[0] += (double)v.x * v.x;
-            s[1] += v.y; q[1] += (double)v.y * v.y;
-            s[2] += v.z; q[2] += (double)v.z * v.z;
-            s[3] += v.w; q[3] += (double)v.w * v.w;
+            const double d0 = (double)v.x - k[0], d1 = (double)v.y - k[1], d2 = (double)v.z - k[2], d3 = (double)v.w - k[3];
+            s[0] += d0; q[0] += d0 * d0;
+            s[1] += d1; q[1] += d1 * d1;
+            s[2] += d2; q[2] += d2 * d2;
+            s[3] += d3; q[3] += d3 * d3;
         }
     }
 #pragma unroll
@@ -289,7 +295,8 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const float4* __restric
     }
 }
 
-__global__ void bn_finalize_kernel(const double* __restrict__ partial, int P, int C, float* __restrict__ mean,
+__global__ void bn_finalize_kernel(const double* __restrict__ partial, const float* __restrict__ x, int P, int C,
+                                   float* __restrict__ mean,
                                    float* __restrict__ var, float* __restrict__ running_mean,
                                    float* __restrict__ running_var, float momentum) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -301,8 +308,9 @@ __global__ void bn_finalize_kernel(const double* __restrict__ partial, int P, in
         s += o[j];
         q += o[4 + j];
     }
-    const double m = s / P;
-    double v = q / P - m * m;
+    const double md = s / P;                                      // of the shifted values: mean = x[0][c] + md
+    const double m = (double)x[c] + md;
+    double v = q / P - md * md;
     if (v < 0.0) v = 0.0;
     mean[c] = (float)m;
     var[c] = (float)v;
@@ -346,8 +354,8 @@ extern "C" int fgn_bn_train_f32(const float* x, int P, int C, const float* gamma
     double* partial = reinterpret_cast<double*>(scratch);
     hipLaunchKernelGGL(bn_partial_kernel, dim3(cdiv(C4, 64), BN_CHUNKS), dim3(256), 0, stream,
                        reinterpret_cast<const float4*>(x), P, C4, partial);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, stream, partial, P, C, mean, var,
-                       running_mean, running_var, momentum);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, stream, partial, x, P, C, mean,
+                       var, running_mean, running_var, momentum);
     const long long total4 = (long long)P * C4;
     const int grid = (int)((total4 + 255) / 256 < 4096 ? (total4 + 255) / 256 : 4096);
     hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, stream, reinterpret_cast<const float4*>(x),
