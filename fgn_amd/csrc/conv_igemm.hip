@@ -33,52 +33,55 @@
 #include "common.h"
 #include <cstdlib>
 
+// Every member has a default: a default-constructed ConvParams describes an inert point-wise GEMM (no operands, no rows,
+// 1x1 / stride 1 geometry, one K split), so an entry point states only what its launch differs in and no field reaches a
+// kernel unset.
 struct ConvParams {
-    const float* x;
-    const float* w;
-    float* y;
-    const float* scale;
-    const float* shift;
-    const float* residual;
-    const float* in_scale;
-    const int32_t* n_img_dev;
-    int n_img, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad;
-    int a_img_div;
-    int relu;
-    int K;          // padded reduction length (multiple of 32)
-    int n_tiles_n;  // Cout tiles
+    const float* x = nullptr;
+    const float* w = nullptr;
+    float* y = nullptr;
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+    const float* residual = nullptr;
+    const float* in_scale = nullptr;
+    const int32_t* n_img_dev = nullptr;
+    int n_img = 0, H = 1, W = 1, Cin = 0, Ho = 1, Wo = 1, Cout = 0, KH = 1, KW = 1, stride = 1, pad = 0;
+    int a_img_div = 1;
+    int relu = 0;
+    int K = 0;          // padded reduction length (multiple of 32)
+    int n_tiles_n = 0;  // Cout tiles
     // banded tile raster (LDS-DMA kernel): when the weight matrix of a launch (Cout x K) does not fit an XCD's L2
     // next to the activations, the plain order (all Cout tiles of one row tile, then the next row tile) re-streams
     // it from the Infinity Cache for every row tile (measured: 1.53 GB fetched by the AG-RPN Winograd GEMM against
     // 0.28 GB of operands).  Tiles are therefore walked band by band: `band_nt` Cout tiles (<= ~2 MB of weights)
     // x all `band_mt` row tiles of the group (grouped GEMM) or launch, then the next band.  0 = plain order.
-    int band_nt, band_mt;
+    int band_nt = 0, band_mt = 0;
     // split-K: blockIdx.y owns K-tiles [y*kt_per_split, (y+1)*kt_per_split) and writes its raw
     // partial tile to slab y of `ws` ([splits][n_img*Ho*Wo][Cout]); splitk_epilogue_kernel sums
     // the slabs in a fixed order (deterministic) and applies the epilogue.
-    float* ws;
-    int splits, kt_per_split;
+    float* ws = nullptr;
+    int splits = 1, kt_per_split = 0;
 #ifdef FGN_EXPERIMENTS      // tools/micro/conv_pw_experiments.inc (not part of libfgn_hip.so)
-    int32_t* tickets;        // Stream-K: one zero-initialised word per remaining tile
-    int32_t* sched;          // tile scheduler of conv_pw_persist2_kernel: zero-initialised counters
-    int sk_U, sk_dp;         // Stream-K launch: tiles [0, sk_dp) whole, the rest in ranges of sk_U K-tiles
+    int32_t* tickets = nullptr;   // Stream-K: one zero-initialised word per remaining tile
+    int32_t* sched = nullptr;     // tile scheduler of conv_pw_persist2_kernel: zero-initialised counters
+    int sk_U = 0, sk_dp = 0;      // Stream-K launch: tiles [0, sk_dp) whole, the rest in ranges of sk_U K-tiles
 #endif
-    unsigned x_bytes, w_bytes;   // extents for the buffer descriptors of the LDS-DMA kernel
+    unsigned x_bytes = 0, w_bytes = 0;   // extents for the buffer descriptors of the LDS-DMA kernel
     // grouped GEMM (Winograd; 64x64 kernel, point-wise mode): rows [g*grp_rows, (g+1)*grp_rows) use the weight
     // matrix at w + g*grp_w_stride floats; within a group only the first `valid` rows are computed, valid =
     // grp_valid, or min(grp_items, *grp_count_dev) * grp_rows_per_item when the item count lives on the
     // device.  grp_rows == 0: plain convolution.
-    int grp_rows, grp_valid, grp_items, grp_rows_per_item, grp_w_stride;
-    const int32_t* grp_count_dev;
+    int grp_rows = 0, grp_valid = 0, grp_items = 0, grp_rows_per_item = 0, grp_w_stride = 0;
+    const int32_t* grp_count_dev = nullptr;
     // launch record (conv_pw_persist_kernel; fgn_profile_stamps): FGN_STAMP_WORDS x uint64 in device memory or nullptr
-    unsigned long long* stamp;
+    unsigned long long* stamp = nullptr;
     // second A operand of conv_pw_persist_kernel (fgn_conv1x1_dual_nhwc_f32): the K-tiles from kt1 on are read from x2
     // (rows of cin2 floats) instead of x (rows of Cin floats) - two 1x1 convolutions on the same pixels summed in one
     // K loop (a bottleneck's conv3 and the 1x1 / stride 1 shortcut of its stage's first block).  nullptr: one operand.
-    const float* x2;
-    unsigned x2_bytes;
-    int kt1, cin2;
-    const int32_t* x2_rows;      // optional: row m of the output reads row x2_rows[m] of x2 (a strided shortcut); nullptr: row m
+    const float* x2 = nullptr;
+    unsigned x2_bytes = 0;
+    int kt1 = 0, cin2 = 0;
+    const int32_t* x2_rows = nullptr;   // optional: row m of the output reads row x2_rows[m] of x2 (a strided shortcut); nullptr: row m
     // conv_pw_x3_kernel (conv_pw_x3.h): the weights as three bf16 planes, [group][K-tile][plane][npad3][32], or nullptr
     const void* w3 = nullptr;
     unsigned w3_bytes = 0;
@@ -1147,12 +1150,12 @@ static int plan_splits(long long M, int Cout, int KT, int tile_hint, bool pw = f
     return s < 2 ? 1 : s;
 }
 
-// banded raster when the launch's weights exceed the L2 budget (see ConvParams::band_nt)
-static void set_band(ConvParams& p, int BM, int BN, int m_tiles) {
+// banded raster when the launch's weights exceed the L2 budget (see ConvParams::band_nt); per_nt = bytes of weights (or
+// of their plane image) that one Cout tile reads: f32 BN * (K / splits) * 4, x3 X3_BN * K * 6, h2 BN * K * 4
+static void set_band(ConvParams& p, int BM, int m_tiles, long long per_nt) {
     constexpr long long budget = 2048 * 1024;       // bytes of weights per band: half an XCD's L2
-    const long long per_nt = (long long)BN * (p.K / p.splits) * 4;
     p.band_nt = 0; p.band_mt = 0;
-    if (budget > 0 && per_nt * p.n_tiles_n > budget) {
+    if (per_nt * p.n_tiles_n > budget) {
         int nb = (int)std::max<long long>(1, budget / per_nt);
         while (nb > 1 && p.n_tiles_n % nb) --nb;
         const int mt = p.grp_rows ? p.grp_rows / BM : m_tiles;
@@ -1172,7 +1175,7 @@ static int launch_cfg(const ConvParams& p0, int M_max, bool cin4, hipStream_t st
     p.n_tiles_n = cdiv(p.Cout, BN);
     const int m_tiles = cdiv(M_max, BM);
     const dim3 grid(m_tiles * p.n_tiles_n, p.splits);
-    set_band(p, BM, BN, m_tiles);
+    set_band(p, BM, m_tiles, (long long)BN * (p.K / p.splits) * 4);
     const size_t lds = 2 * (BM + BN) * LDS_STRIDE * sizeof(float);
     static unsigned long long lds_ok[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
     hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WM, WN, true, MW>), &lds_ok[0]);
@@ -1301,14 +1304,9 @@ extern "C" int fgn_conv2d_nhwc_f32(const float* x, const float* w_packed, float*
     if (a_img_div < 1 || stride < 1 || cout_pad % 128 != 0 || cout_pad < Cout) return FGN_ERR_SHAPE;
     ConvParams p;
     p.x = x; p.w = w_packed; p.y = y; p.scale = scale; p.shift = shift; p.residual = residual;
-    p.in_scale = in_scale; p.n_img_dev = n_img_dev; p.stamp = nullptr; p.x2 = nullptr; p.x2_bytes = 0; p.kt1 = 0; p.cin2 = 0; p.x2_rows = nullptr;
-#ifdef FGN_EXPERIMENTS
-    p.tickets = nullptr; p.sched = nullptr; p.sk_U = 0; p.sk_dp = 0;
-#endif
+    p.in_scale = in_scale; p.n_img_dev = n_img_dev;
     p.n_img = n_img; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW;
     p.stride = stride; p.pad = pad; p.a_img_div = a_img_div; p.relu = relu;
-    p.grp_rows = 0; p.grp_valid = 0; p.grp_items = 0; p.grp_rows_per_item = 0; p.grp_w_stride = 0;
-    p.grp_count_dev = nullptr;
     p.Ho = (H + 2 * pad - KH) / stride + 1;
     p.Wo = (W + 2 * pad - KW) / stride + 1;
     if (p.Ho <= 0 || p.Wo <= 0) return FGN_ERR_SHAPE;
@@ -1325,7 +1323,7 @@ extern "C" int fgn_conv2d_nhwc_f32(const float* x, const float* w_packed, float*
     if (M * (long long)Cout >= (1ll << 31) * 4) return FGN_ERR_SHAPE;
 
     int tile;
-    p.ws = nullptr; p.splits = 1; p.kt_per_split = p.K / BK;
+    p.kt_per_split = p.K / BK;
     {
         // descriptor extents (< 4 GiB checked below); tile_hint >= 100 forces the register-staged kernel
         const long long xb = (long long)((n_img + a_img_div - 1) / a_img_div) * H * W * Cin * 4;
@@ -1382,15 +1380,9 @@ extern "C" int fgn_conv2d_pair_nhwc_f32(const float* x0, float* y0, int n_img0, 
     const int ns[2] = {n_img0, n_img1}, Hs[2] = {H0, H1}, Ws[2] = {W0, W1};
     for (int i = 0; i < 2; ++i) {
         ConvParams& p = ps[i];
-        p.x = xs[i]; p.w = w_packed; p.y = ys[i]; p.scale = scale; p.shift = shift; p.residual = nullptr;
-        p.in_scale = nullptr; p.n_img_dev = nullptr; p.stamp = nullptr; p.x2 = nullptr; p.x2_bytes = 0; p.kt1 = 0; p.cin2 = 0; p.x2_rows = nullptr;
-#ifdef FGN_EXPERIMENTS
-        p.tickets = nullptr; p.sched = nullptr; p.sk_U = 0; p.sk_dp = 0;
-#endif
+        p.x = xs[i]; p.w = w_packed; p.y = ys[i]; p.scale = scale; p.shift = shift;
         p.n_img = ns[i]; p.H = Hs[i]; p.W = Ws[i]; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW;
-        p.stride = stride; p.pad = pad; p.a_img_div = 1; p.relu = relu;
-        p.grp_rows = 0; p.grp_valid = 0; p.grp_items = 0; p.grp_rows_per_item = 0; p.grp_w_stride = 0;
-        p.grp_count_dev = nullptr;
+        p.stride = stride; p.pad = pad; p.relu = relu;
         p.Ho = (p.H + 2 * pad - KH) / stride + 1;
         p.Wo = (p.W + 2 * pad - KW) / stride + 1;
         if (p.Ho <= 0 || p.Wo <= 0) return FGN_ERR_SHAPE;
@@ -1401,10 +1393,10 @@ extern "C" int fgn_conv2d_pair_nhwc_f32(const float* x0, float* y0, int n_img0, 
         const long long xb = (long long)p.n_img * p.H * p.W * Cin * 4, wb = (long long)cout_pad * p.K * 4;
         if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll) return FGN_ERR_SHAPE;
         p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
-        p.ws = nullptr; p.splits = 1; p.kt_per_split = p.K / BK;
+        p.kt_per_split = p.K / BK;
         p.n_tiles_n = cdiv(Cout, 64);
         const int m_tiles = cdiv((int)M, 64);
-        set_band(p, 64, 64, m_tiles);
+        set_band(p, 64, m_tiles, 64ll * p.K * 4);
         tiles[i] = (m_tiles * p.n_tiles_n + 7) / 8 * 8;       // workgroups past the last tile leave at once
     }
     constexpr int NST = CONV_DMA_STAGES;
@@ -1419,50 +1411,6 @@ extern "C" int fgn_conv2d_pair_nhwc_f32(const float* x0, float* y0, int n_img0, 
         FGN_LAUNCH_TIMED((conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 2>), grid, dim3(256), dlds, stream, ps[0], ps[1], tiles[0]);
     else
         FGN_LAUNCH_TIMED((conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 0>), grid, dim3(256), dlds, stream, ps[0], ps[1], tiles[0]);
-    FGN_LAUNCH_CHECK();
-    return FGN_OK;
-}
-
-// y = (x * W1^T + x2 * W2^T) + shift (ReLU) on the same rows: two 1x1 / stride 1 convolutions summed in ONE K loop of
-// conv_pw_persist_kernel - a bottleneck's conv3 (+BN) and the 1x1 / stride 1 shortcut (+BN) of the first block of a stage
-// whose stride is 1 (mmdet ResNet layer1.0: out = relu(bn3(conv3(y)) + bn_d(conv_d(x)))), with the two BatchNorm scales
-// folded into the packed weights [cout_pad][Cin1 + Cin2] and the two shifts added.  Saves the shortcut's launch and the
-// write + re-read of its [rows, Cout] output (106 MB at cfg3).  x [rows, Cin1], y [rows, Cout]; x2 [x2_total_rows, Cin2]:
-// output row m reads row x2_rows[m] of it (int32 on the device: the 1x1 / STRIDE 2 shortcut of layer2.0 / layer3.0 reads
-// every second pixel of every second row of the stage's input), or row m when x2_rows is NULL (then x2_total_rows = rows).
-extern "C" int fgn_conv1x1_dual_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
-                                         const float* w_packed, float* y, const float* shift, int rows, int Cin1, int Cin2,
-                                         int Cout, int cout_pad, int relu, hipStream_t stream) {
-    if (!x || !x2 || !w_packed || !y) return FGN_ERR_ARG;
-    if (rows <= 0) return FGN_OK;
-    if (Cin1 % BK || Cin2 % BK || Cin1 <= 0 || Cin2 <= 0 || (Cout & 3) || cout_pad % 128 || cout_pad < Cout) return FGN_ERR_SHAPE;
-    if ((!x2_rows && x2_total_rows != rows) || x2_total_rows < 1) return FGN_ERR_ARG;
-    const long long K = (long long)Cin1 + Cin2;
-    const long long xb = (long long)rows * Cin1 * 4, x2b = (long long)x2_total_rows * Cin2 * 4, wb = (long long)cout_pad * K * 4;
-    if (xb >= 0x7fffff00ll || x2b >= 0x7fffff00ll || wb >= 0x7fffff00ll || (long long)rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
-    ConvParams p;
-    p.x = x; p.w = w_packed; p.y = y; p.scale = nullptr; p.shift = shift; p.residual = nullptr; p.in_scale = nullptr;
-    p.n_img_dev = nullptr; p.stamp = nullptr;
-#ifdef FGN_EXPERIMENTS
-    p.tickets = nullptr; p.sched = nullptr; p.sk_U = 0; p.sk_dp = 0;
-#endif
-    p.x2 = x2; p.x2_bytes = (unsigned)x2b; p.kt1 = Cin1 / BK; p.cin2 = Cin2; p.x2_rows = x2_rows;
-    p.n_img = rows; p.H = 1; p.W = 1; p.Cin = Cin1; p.Ho = 1; p.Wo = 1; p.Cout = Cout; p.KH = 1; p.KW = 1;
-    p.stride = 1; p.pad = 0; p.a_img_div = 1; p.relu = relu; p.K = (int)K;
-    p.ws = nullptr; p.splits = 1; p.kt_per_split = (int)K / BK;
-    p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
-    p.grp_rows = 0; p.grp_valid = 0; p.grp_items = 0; p.grp_rows_per_item = 0; p.grp_w_stride = 0; p.grp_count_dev = nullptr;
-    p.n_tiles_n = cdiv(Cout, 64);
-    const int m_tiles = cdiv(rows, 64);
-    set_band(p, 64, 64, m_tiles);
-    const int tiles = m_tiles * p.n_tiles_n;
-    static unsigned long long pk_ok = 0ull;
-    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_persist_kernel), &pk_ok);
-    if (attr != hipSuccess) return (int)attr;
-    const size_t plds = (size_t)2 * (64 + 64) * BK * sizeof(float);
-    const int grid = std::min(persist_blocks(), (tiles + 7) / 8 * 8);
-    p.stamp = fgn_next_stamp_record();
-    FGN_LAUNCH_TIMED(conv_pw_persist_kernel, dim3(grid), dim3(256), plds, stream, p, tiles);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }
@@ -1498,16 +1446,7 @@ template <int WMW, int RB, int NT, int NST, bool SH16>
 static int launch_x3_cfg(ConvParams& p, int M_max, hipStream_t stream) {
     constexpr int BM = 32 * RB * WMW;
     const int m_tiles = cdiv(M_max, BM);
-    {   // banded raster: <= 2 MB of weight image per band (see ConvParams::band_nt)
-        const long long per_nt = (long long)X3_BN * p.K * 6;
-        p.band_nt = 0; p.band_mt = 0;
-        if (per_nt * p.n_tiles_n > 2048 * 1024) {
-            int nb = (int)std::max<long long>(1, 2048 * 1024 / per_nt);
-            while (nb > 1 && p.n_tiles_n % nb) --nb;
-            const int mt = p.grp_rows ? p.grp_rows / BM : m_tiles;
-            if (nb < p.n_tiles_n && mt > 0 && m_tiles % mt == 0) { p.band_nt = nb; p.band_mt = mt; }
-        }
-    }
+    set_band(p, BM, m_tiles, (long long)X3_BN * p.K * 6);
     const int tiles = m_tiles * p.n_tiles_n;
     static unsigned long long ok = 0ull;
     hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_x3_kernel<WMW, RB, NT, NST, SH16>), &ok);
@@ -1565,115 +1504,6 @@ extern "C" int fgn_x3_phases(unsigned long long* host16) {
 }
 #endif
 
-// y[rows, Cout] = relu?(x[rows, K] * W^T + shift + residual) with W given as its bf16-plane image (ops.pack_x3);
-// grouped: rows = n_groups * grp_rows, group g uses image g and computes its first grp_valid rows.  The direct entry
-// of conv_pw_x3_kernel (tests, tools); the convolution entry points take the image as an optional argument.
-extern "C" int fgn_gemm_x3_f32(const float* x, const void* w3, float* y, const float* shift, const float* residual,
-                               int rows, int K, int Cout, int npad, int relu, int grp_rows, int grp_valid, int n_groups,
-                               int bm, int nterms, hipStream_t stream) {
-    if (!x || !w3 || !y) return FGN_ERR_ARG;
-    if (rows <= 0) return FGN_OK;
-    if (K % BK || K <= 0 || (Cout & 3) || npad % X3_BN || npad < Cout || n_groups < 1) return FGN_ERR_SHAPE;
-    if (n_groups > 1 && (grp_rows <= 0 || (long long)n_groups * grp_rows != rows || grp_valid > grp_rows)) return FGN_ERR_SHAPE;
-    const long long xb = (long long)rows * K * 4, wb = (long long)fgn_x3_image_bytes(K, npad, n_groups);
-    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || (long long)rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
-    ConvParams p;
-    p.x = x; p.w = nullptr; p.y = y; p.scale = nullptr; p.shift = shift; p.residual = residual; p.in_scale = nullptr;
-    p.n_img_dev = nullptr; p.stamp = nullptr; p.x2 = nullptr; p.x2_bytes = 0; p.kt1 = 0; p.cin2 = 0; p.x2_rows = nullptr;
-#ifdef FGN_EXPERIMENTS
-    p.tickets = nullptr; p.sched = nullptr; p.sk_U = 0; p.sk_dp = 0;
-#endif
-    p.n_img = rows; p.H = 1; p.W = 1; p.Cin = K; p.Ho = 1; p.Wo = 1; p.Cout = Cout; p.KH = 1; p.KW = 1;
-    p.stride = 1; p.pad = 0; p.a_img_div = 1; p.relu = relu; p.K = K;
-    p.ws = nullptr; p.splits = 1; p.kt_per_split = K / BK;
-    p.x_bytes = (unsigned)xb; p.w_bytes = 0;
-    p.grp_rows = n_groups > 1 ? grp_rows : 0; p.grp_valid = grp_valid; p.grp_items = 0; p.grp_rows_per_item = 0;
-    p.grp_w_stride = 0; p.grp_count_dev = nullptr;
-    p.band_nt = 0; p.band_mt = 0; p.n_tiles_n = 0;
-    p.w3 = w3; p.w3_bytes = (unsigned)wb; p.npad3 = npad;
-#ifdef X3_PHASES
-    if (!g_x3_ph && (hipMalloc(&g_x3_ph, 128) != hipSuccess || hipMemset(g_x3_ph, 0, 128) != hipSuccess)) return FGN_ERR_ARG;
-    p.ws = reinterpret_cast<float*>(g_x3_ph);
-#endif
-    return launch_x3(p, rows, bm, nterms, stream);
-}
-
-// The three GEMM-shaped entry points of the detector on conv_pw_x3_kernel.  Arguments as their f32-MFMA counterparts
-// (fgn_conv2d_nhwc_f32 for a 1x1 / stride 1 / unpadded convolution, fgn_conv1x1_dual_nhwc_f32, fgn_winograd_gemm_f32),
-// with the weights given as the bf16-plane image of ops.pack_x3 ([groups][K / 32][3][cout_pad][32] bf16) instead of
-// [cout_pad][K] floats.  Results: the same f32 values to within the rounding of an f32 accumulation (conv_pw_x3.h).
-static void x3_base_params(ConvParams& p) {
-    p.w = nullptr; p.scale = nullptr; p.shift = nullptr; p.residual = nullptr; p.in_scale = nullptr; p.n_img_dev = nullptr;
-    p.stamp = nullptr; p.x2 = nullptr; p.x2_bytes = 0; p.kt1 = 0; p.cin2 = 0; p.x2_rows = nullptr;
-#ifdef FGN_EXPERIMENTS
-    p.tickets = nullptr; p.sched = nullptr; p.sk_U = 0; p.sk_dp = 0;
-#endif
-    p.H = 1; p.W = 1; p.Ho = 1; p.Wo = 1; p.KH = 1; p.KW = 1; p.stride = 1; p.pad = 0; p.a_img_div = 1; p.relu = 0;
-    p.ws = nullptr; p.splits = 1; p.w_bytes = 0;
-    p.grp_rows = 0; p.grp_valid = 0; p.grp_items = 0; p.grp_rows_per_item = 0; p.grp_w_stride = 0; p.grp_count_dev = nullptr;
-    p.band_nt = 0; p.band_mt = 0; p.n_tiles_n = 0;
-}
-
-extern "C" int fgn_conv1x1_x3_nhwc_f32(const float* x, const void* w_x3, float* y, const float* scale, const float* shift,
-                                       const float* residual, const int32_t* n_img_dev, int n_img, int H, int W, int Cin,
-                                       int Cout, int cout_pad, int relu, hipStream_t stream) {
-    if (!x || !w_x3 || !y) return FGN_ERR_ARG;
-    if (n_img <= 0) return FGN_OK;
-    if (Cin % BK || Cin < 2 * BK || (Cout & 3) || cout_pad % X3_BN || cout_pad < Cout || H <= 0 || W <= 0) return FGN_ERR_SHAPE;
-    const long long M = (long long)n_img * H * W;
-    const long long xb = M * Cin * 4, wb = (long long)fgn_x3_image_bytes(Cin, cout_pad, 1);
-    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || M * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
-    ConvParams p;
-    x3_base_params(p);
-    p.x = x; p.y = y; p.scale = scale; p.shift = shift; p.residual = residual; p.n_img_dev = n_img_dev;
-    p.n_img = n_img; p.H = H; p.W = W; p.Ho = H; p.Wo = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu; p.K = Cin;
-    p.kt_per_split = Cin / BK; p.x_bytes = (unsigned)xb;
-    p.w3 = w_x3; p.w3_bytes = (unsigned)wb; p.npad3 = cout_pad;
-    return launch_x3(p, (int)M, 0, 6, stream);
-}
-
-extern "C" int fgn_conv1x1_dual_x3_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
-                                            const void* w_x3, float* y, const float* shift, int rows, int Cin1, int Cin2,
-                                            int Cout, int cout_pad, int relu, hipStream_t stream) {
-    if (!x || !x2 || !w_x3 || !y) return FGN_ERR_ARG;
-    if (rows <= 0) return FGN_OK;
-    if (Cin1 % BK || Cin2 % BK || Cin1 <= 0 || Cin2 <= 0 || (Cout & 3) || cout_pad % X3_BN || cout_pad < Cout) return FGN_ERR_SHAPE;
-    if ((!x2_rows && x2_total_rows != rows) || x2_total_rows < 1) return FGN_ERR_ARG;
-    const int K = Cin1 + Cin2;
-    const long long xb = (long long)rows * Cin1 * 4, x2b = (long long)x2_total_rows * Cin2 * 4;
-    const long long wb = (long long)fgn_x3_image_bytes(K, cout_pad, 1);
-    if (xb >= 0x7fffff00ll || x2b >= 0x7fffff00ll || wb >= 0x7fffff00ll || (long long)rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
-    ConvParams p;
-    x3_base_params(p);
-    p.x = x; p.y = y; p.shift = shift;
-    p.x2 = x2; p.x2_bytes = (unsigned)x2b; p.kt1 = Cin1 / BK; p.cin2 = Cin2; p.x2_rows = x2_rows;
-    p.n_img = rows; p.Cin = Cin1; p.Cout = Cout; p.relu = relu; p.K = K;
-    p.kt_per_split = K / BK; p.x_bytes = (unsigned)xb;
-    p.w3 = w_x3; p.w3_bytes = (unsigned)wb; p.npad3 = cout_pad;
-    return launch_x3(p, rows, 0, 6, stream);
-}
-
-extern "C" int fgn_winograd_gemm_x3_f32(const float* V, const void* U_x3, float* Mo, const int32_t* n_img_dev, int n_img,
-                                        int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups,
-                                        hipStream_t stream) {
-    if (!V || !U_x3 || !Mo) return FGN_ERR_ARG;
-    if (n_img <= 0) return FGN_OK;
-    if (Cin % BK != 0 || Cin < 2 * BK || Cout % 4 != 0 || cout_pad % X3_BN != 0 || cout_pad < Cout || t_pad % 64 != 0 ||
-        (n_groups != 16 && n_groups != 36) || (long long)n_img * tiles_per_img > t_pad)
-        return FGN_ERR_SHAPE;
-    const long long rows = (long long)n_groups * t_pad;
-    const long long xb = rows * Cin * 4, wb = (long long)fgn_x3_image_bytes(Cin, cout_pad, n_groups);
-    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
-    ConvParams p;
-    x3_base_params(p);
-    p.x = V; p.y = Mo;
-    p.n_img = (int)rows; p.Cin = Cin; p.Cout = Cout; p.K = Cin; p.kt_per_split = Cin / BK; p.x_bytes = (unsigned)xb;
-    p.grp_rows = t_pad; p.grp_valid = n_img * tiles_per_img; p.grp_items = n_img;
-    p.grp_rows_per_item = tiles_per_img; p.grp_count_dev = n_img_dev;
-    p.w3 = U_x3; p.w3_bytes = (unsigned)wb; p.npad3 = cout_pad;
-    return launch_x3(p, (int)rows, 0, 6, stream);
-}
-
 // ------------------------------------------------------------------------------------------------
 // conv_pw_h2_kernel launches (conv_pw_h2.h): the same GEMMs with three f16 MFMA products per f32 product.  p carries the
 // two-plane f16 image of the column-scaled weights (ops.pack_h2: image, then the inverse column scales).
@@ -1702,16 +1532,7 @@ static int launch_h2_cfg(ConvParams& p, const H2Im2col& q2, int M_max, hipStream
     constexpr int BM = 32 * RB * WMW, BN = 64 * WNW;
     const int m_tiles = cdiv(M_max, BM);
     p.n_tiles_n = cdiv(p.Cout, BN);
-    {   // banded raster: <= 2 MB of weight image per band (see ConvParams::band_nt)
-        const long long per_nt = (long long)BN * p.K * 4;
-        p.band_nt = 0; p.band_mt = 0;
-        if (per_nt * p.n_tiles_n > 2048 * 1024) {
-            int nb = (int)std::max<long long>(1, 2048 * 1024 / per_nt);
-            while (nb > 1 && p.n_tiles_n % nb) --nb;
-            const int mt = p.grp_rows ? p.grp_rows / BM : m_tiles;
-            if (nb < p.n_tiles_n && mt > 0 && m_tiles % mt == 0) { p.band_nt = nb; p.band_mt = mt; }
-        }
-    }
+    set_band(p, BM, m_tiles, (long long)BN * p.K * 4);
     const int tiles = m_tiles * p.n_tiles_n;
     static unsigned long long ok = 0ull;
     hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL>), &ok);
@@ -1781,7 +1602,6 @@ extern "C" int fgn_conv2d_pair_h2_nhwc_f32(const float* x0, int n_img0, int H0, 
     const long long wb = (long long)fgn_h2_image_bytes(K, cout_pad, 1);
     if (span >= 0x7fffff00ll || wb >= 0x7fffff00ll || (M0 + M1) * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
     ConvParams p;
-    x3_base_params(p);
     p.x = reinterpret_cast<const float*>(lo); p.x_bytes = (unsigned)span; p.y = y0; p.scale = scale; p.shift = shift;
     p.n_img = n_img0; p.H = H0; p.W = W0; p.Ho = Ho0; p.Wo = Wo0; p.Cin = Cin; p.Cout = Cout; p.relu = relu;
     p.KH = KH; p.KW = KW; p.stride = stride; p.pad = pad; p.K = K; p.kt_per_split = K / BK;
@@ -1794,86 +1614,170 @@ extern "C" int fgn_conv2d_pair_h2_nhwc_f32(const float* x0, int n_img0, int H0, 
     return launch_h2(p, (int)(M0 + M1), 1, 0, stream, &q);
 }
 
-// y[rows, Cout] = relu?(x[rows, K] * W^T + shift + residual) with W given as its two-plane f16 image (ops.pack_h2);
-// grouped as fgn_gemm_x3_f32.  The direct entry of conv_pw_h2_kernel (tests, tools).
-extern "C" int fgn_gemm_h2_f32(const float* x, const void* w_h2, float* y, const float* shift, const float* residual,
-                               int rows, int K, int Cout, int npad, int relu, int grp_rows, int grp_valid, int n_groups,
-                               int bm, hipStream_t stream) {
-    if (!x || !w_h2 || !y) return FGN_ERR_ARG;
-    if (rows <= 0) return FGN_OK;
-    if (K % BK || K <= 0 || (Cout & 3) || npad % H2_BN || npad < Cout || n_groups < 1) return FGN_ERR_SHAPE;
-    if (n_groups > 1 && (grp_rows <= 0 || (long long)n_groups * grp_rows != rows || grp_valid > grp_rows)) return FGN_ERR_SHAPE;
-    const long long xb = (long long)rows * K * 4, wb = (long long)fgn_h2_image_bytes(K, npad, n_groups);
-    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || (long long)rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
-    ConvParams p;
-    x3_base_params(p);
-    p.x = x; p.y = y; p.shift = shift; p.residual = residual;
-    p.n_img = rows; p.Cin = K; p.Cout = Cout; p.relu = relu; p.K = K; p.kt_per_split = K / BK; p.x_bytes = (unsigned)xb;
-    p.grp_rows = n_groups > 1 ? grp_rows : 0; p.grp_valid = grp_valid;
-    p.w3 = w_h2; p.npad3 = npad;
-    return launch_h2(p, rows, n_groups, bm, stream);
+// ------------------------------------------------------------------------------------------------
+// The GEMM-shaped entry points (1x1 / stride 1 convolutions, the fused conv3 + shortcut, the Winograd GEMMs, the direct
+// grouped GEMMs) in their arithmetics: f32 MFMA, conv_pw_x3_kernel, conv_pw_h2_kernel - the same f32 values to within the
+// rounding of an f32 accumulation.  ONE function per shape family validates the arguments and describes the launch in a
+// ConvParams, given what differs between arithmetics (GemmMath); an entry point hands that description to its launcher.
+// ------------------------------------------------------------------------------------------------
+struct GemmMath {
+    int bn;               // cout_pad is a multiple of this many columns
+    bool deep;            // the K loop needs two K-tiles: Cin >= 2 * BK
+    size_t (*image_bytes)(int K, int npad, int n_groups);   // the weights are a plane image of this size (ops.pack_x3 /
+};                                                          // ops.pack_h2) in p.w3; nullptr: floats [groups][cout_pad][K] in p.w
+static const GemmMath MATH_F32 = {128, false, nullptr}, MATH_X3 = {X3_BN, true, fgn_x3_image_bytes},
+                      MATH_H2 = {H2_BN, true, fgn_h2_image_bytes};      // (launch_h2 splits its image into planes and scales)
+constexpr int FGN_DESCRIBED = 1;      // a family function filled p: launch it (FGN_OK: nothing to do; < 0: rejected)
+
+static long long gemm_weight_bytes(const GemmMath& m, long long K, int npad, int n_groups) {
+    return m.image_bytes ? (long long)m.image_bytes((int)K, npad, n_groups) : (long long)n_groups * npad * K * 4;
 }
 
-// The three GEMM-shaped entry points of the detector on conv_pw_h2_kernel: arguments as fgn_winograd_gemm_x3_f32 /
-// fgn_conv1x1_x3_nhwc_f32 / fgn_conv1x1_dual_x3_nhwc_f32, the weights as their two-plane f16 image (ops.pack_h2)
-extern "C" int fgn_winograd_gemm_h2_f32(const float* V, const void* U_h2, float* Mo, const int32_t* n_img_dev, int n_img,
-                                        int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups,
-                                        hipStream_t stream) {
-    if (!V || !U_h2 || !Mo) return FGN_ERR_ARG;
+static void gemm_set_weights(ConvParams& p, const GemmMath& m, const void* w, long long wb, int npad) {
+    if (m.image_bytes) { p.w3 = w; p.w3_bytes = (unsigned)wb; p.npad3 = npad; }
+    else { p.w = static_cast<const float*>(w); p.w_bytes = (unsigned)wb; }
+}
+
+// A 1x1 / stride 1 / unpadded convolution with folded scale / shift / residual / ReLU: arguments as fgn_conv2d_nhwc_f32,
+// the weights as a plane image.  (The f32 form of this family is fgn_conv2d_nhwc_f32 itself.)
+static int describe_conv1x1(ConvParams& p, const GemmMath& m, const float* x, const void* w, float* y, const float* scale,
+                            const float* shift, const float* residual, const int32_t* n_img_dev, int n_img, int H, int W,
+                            int Cin, int Cout, int cout_pad, int relu) {
+    if (!x || !w || !y) return FGN_ERR_ARG;
     if (n_img <= 0) return FGN_OK;
-    if (Cin % BK != 0 || Cin < 2 * BK || Cout % 4 != 0 || cout_pad % H2_BN != 0 || cout_pad < Cout || t_pad % 64 != 0 ||
-        (n_groups != 16 && n_groups != 36) || (long long)n_img * tiles_per_img > t_pad)
-        return FGN_ERR_SHAPE;
-    const long long rows = (long long)n_groups * t_pad;
-    const long long xb = rows * Cin * 4, wb = (long long)fgn_h2_image_bytes(Cin, cout_pad, n_groups);
-    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
+    if (Cin % BK || (m.deep && Cin < 2 * BK) || (Cout & 3) || cout_pad % m.bn || cout_pad < Cout || H <= 0 || W <= 0) return FGN_ERR_SHAPE;
+    const long long M = (long long)n_img * H * W;
+    const long long xb = M * Cin * 4, wb = gemm_weight_bytes(m, Cin, cout_pad, 1);
+    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || M * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
+    p.x = x; p.y = y; p.scale = scale; p.shift = shift; p.residual = residual; p.n_img_dev = n_img_dev;
+    p.n_img = n_img; p.H = H; p.W = W; p.Ho = H; p.Wo = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu; p.K = Cin;
+    p.kt_per_split = Cin / BK; p.x_bytes = (unsigned)xb;
+    gemm_set_weights(p, m, w, wb, cout_pad);
+    return FGN_DESCRIBED;
+}
+
+extern "C" int fgn_conv1x1_x3_nhwc_f32(const float* x, const void* w_x3, float* y, const float* scale, const float* shift,
+                                       const float* residual, const int32_t* n_img_dev, int n_img, int H, int W, int Cin,
+                                       int Cout, int cout_pad, int relu, hipStream_t stream) {
     ConvParams p;
-    x3_base_params(p);
-    p.x = V; p.y = Mo;
-    p.n_img = (int)rows; p.Cin = Cin; p.Cout = Cout; p.K = Cin; p.kt_per_split = Cin / BK; p.x_bytes = (unsigned)xb;
-    p.grp_rows = t_pad; p.grp_valid = n_img * tiles_per_img; p.grp_items = n_img;
-    p.grp_rows_per_item = tiles_per_img; p.grp_count_dev = n_img_dev;
-    p.w3 = U_h2; p.npad3 = cout_pad;
-    return launch_h2(p, (int)rows, n_groups, 0, stream);
+    const int rc = describe_conv1x1(p, MATH_X3, x, w_x3, y, scale, shift, residual, n_img_dev, n_img, H, W, Cin, Cout, cout_pad, relu);
+    if (rc != FGN_DESCRIBED) return rc;
+    return launch_x3(p, n_img * H * W, 0, 6, stream);
 }
 
 extern "C" int fgn_conv1x1_h2_nhwc_f32(const float* x, const void* w_h2, float* y, const float* scale, const float* shift,
                                        const float* residual, const int32_t* n_img_dev, int n_img, int H, int W, int Cin,
                                        int Cout, int cout_pad, int relu, hipStream_t stream) {
-    if (!x || !w_h2 || !y) return FGN_ERR_ARG;
-    if (n_img <= 0) return FGN_OK;
-    if (Cin % BK || Cin < 2 * BK || (Cout & 3) || cout_pad % H2_BN || cout_pad < Cout || H <= 0 || W <= 0) return FGN_ERR_SHAPE;
-    const long long M = (long long)n_img * H * W;
-    const long long xb = M * Cin * 4, wb = (long long)fgn_h2_image_bytes(Cin, cout_pad, 1);
-    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || M * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
     ConvParams p;
-    x3_base_params(p);
-    p.x = x; p.y = y; p.scale = scale; p.shift = shift; p.residual = residual; p.n_img_dev = n_img_dev;
-    p.n_img = n_img; p.H = H; p.W = W; p.Ho = H; p.Wo = W; p.Cin = Cin; p.Cout = Cout; p.relu = relu; p.K = Cin;
-    p.kt_per_split = Cin / BK; p.x_bytes = (unsigned)xb;
-    p.w3 = w_h2; p.npad3 = cout_pad;
-    return launch_h2(p, (int)M, 1, 0, stream);
+    const int rc = describe_conv1x1(p, MATH_H2, x, w_h2, y, scale, shift, residual, n_img_dev, n_img, H, W, Cin, Cout, cout_pad, relu);
+    if (rc != FGN_DESCRIBED) return rc;
+    return launch_h2(p, n_img * H * W, 1, 0, stream);
+}
+
+// y = (x * W1^T + x2 * W2^T) + shift (ReLU) on the same rows: two 1x1 / stride 1 convolutions summed in ONE K loop of
+// conv_pw_persist_kernel - a bottleneck's conv3 (+BN) and the 1x1 / stride 1 shortcut (+BN) of the first block of a stage
+// whose stride is 1 (mmdet ResNet layer1.0: out = relu(bn3(conv3(y)) + bn_d(conv_d(x)))), with the two BatchNorm scales
+// folded into the packed weights [cout_pad][Cin1 + Cin2] and the two shifts added.  Saves the shortcut's launch and the
+// write + re-read of its [rows, Cout] output (106 MB at cfg3).  x [rows, Cin1], y [rows, Cout]; x2 [x2_total_rows, Cin2]:
+// output row m reads row x2_rows[m] of it (int32 on the device: the 1x1 / STRIDE 2 shortcut of layer2.0 / layer3.0 reads
+// every second pixel of every second row of the stage's input), or row m when x2_rows is NULL (then x2_total_rows = rows).
+static int describe_dual(ConvParams& p, const GemmMath& m, const float* x, const float* x2, const int32_t* x2_rows,
+                         int x2_total_rows, const void* w, float* y, const float* shift, int rows, int Cin1, int Cin2,
+                         int Cout, int cout_pad, int relu) {
+    if (!x || !x2 || !w || !y) return FGN_ERR_ARG;
+    if (rows <= 0) return FGN_OK;
+    if (Cin1 % BK || Cin2 % BK || Cin1 <= 0 || Cin2 <= 0 || (Cout & 3) || cout_pad % m.bn || cout_pad < Cout) return FGN_ERR_SHAPE;
+    if ((!x2_rows && x2_total_rows != rows) || x2_total_rows < 1) return FGN_ERR_ARG;
+    const long long K = (long long)Cin1 + Cin2;
+    const long long xb = (long long)rows * Cin1 * 4, x2b = (long long)x2_total_rows * Cin2 * 4;
+    const long long wb = gemm_weight_bytes(m, K, cout_pad, 1);
+    if (xb >= 0x7fffff00ll || x2b >= 0x7fffff00ll || wb >= 0x7fffff00ll || (long long)rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
+    p.x = x; p.y = y; p.shift = shift;
+    p.x2 = x2; p.x2_bytes = (unsigned)x2b; p.kt1 = Cin1 / BK; p.cin2 = Cin2; p.x2_rows = x2_rows;
+    p.n_img = rows; p.Cin = Cin1; p.Cout = Cout; p.relu = relu; p.K = (int)K;
+    p.kt_per_split = (int)K / BK; p.x_bytes = (unsigned)xb;
+    gemm_set_weights(p, m, w, wb, cout_pad);
+    return FGN_DESCRIBED;
+}
+
+extern "C" int fgn_conv1x1_dual_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
+                                         const float* w_packed, float* y, const float* shift, int rows, int Cin1, int Cin2,
+                                         int Cout, int cout_pad, int relu, hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_dual(p, MATH_F32, x, x2, x2_rows, x2_total_rows, w_packed, y, shift, rows, Cin1, Cin2, Cout, cout_pad, relu);
+    if (rc != FGN_DESCRIBED) return rc;
+    p.n_tiles_n = cdiv(Cout, 64);
+    const int m_tiles = cdiv(rows, 64);
+    set_band(p, 64, m_tiles, 64ll * p.K * 4);
+    const int tiles = m_tiles * p.n_tiles_n;
+    static unsigned long long pk_ok = 0ull;
+    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_persist_kernel), &pk_ok);
+    if (attr != hipSuccess) return (int)attr;
+    const size_t plds = (size_t)2 * (64 + 64) * BK * sizeof(float);
+    const int grid = std::min(persist_blocks(), (tiles + 7) / 8 * 8);
+    p.stamp = fgn_next_stamp_record();
+    FGN_LAUNCH_TIMED(conv_pw_persist_kernel, dim3(grid), dim3(256), plds, stream, p, tiles);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+extern "C" int fgn_conv1x1_dual_x3_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
+                                            const void* w_x3, float* y, const float* shift, int rows, int Cin1, int Cin2,
+                                            int Cout, int cout_pad, int relu, hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_dual(p, MATH_X3, x, x2, x2_rows, x2_total_rows, w_x3, y, shift, rows, Cin1, Cin2, Cout, cout_pad, relu);
+    if (rc != FGN_DESCRIBED) return rc;
+    return launch_x3(p, rows, 0, 6, stream);
 }
 
 extern "C" int fgn_conv1x1_dual_h2_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
                                             const void* w_h2, float* y, const float* shift, int rows, int Cin1, int Cin2,
                                             int Cout, int cout_pad, int relu, hipStream_t stream) {
-    if (!x || !x2 || !w_h2 || !y) return FGN_ERR_ARG;
-    if (rows <= 0) return FGN_OK;
-    if (Cin1 % BK || Cin2 % BK || Cin1 <= 0 || Cin2 <= 0 || (Cout & 3) || cout_pad % H2_BN || cout_pad < Cout) return FGN_ERR_SHAPE;
-    if ((!x2_rows && x2_total_rows != rows) || x2_total_rows < 1) return FGN_ERR_ARG;
-    const int K = Cin1 + Cin2;
-    const long long xb = (long long)rows * Cin1 * 4, x2b = (long long)x2_total_rows * Cin2 * 4;
-    const long long wb = (long long)fgn_h2_image_bytes(K, cout_pad, 1);
-    if (xb >= 0x7fffff00ll || x2b >= 0x7fffff00ll || wb >= 0x7fffff00ll || (long long)rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
     ConvParams p;
-    x3_base_params(p);
-    p.x = x; p.y = y; p.shift = shift;
-    p.x2 = x2; p.x2_bytes = (unsigned)x2b; p.kt1 = Cin1 / BK; p.cin2 = Cin2; p.x2_rows = x2_rows;
-    p.n_img = rows; p.Cin = Cin1; p.Cout = Cout; p.relu = relu; p.K = K;
-    p.kt_per_split = K / BK; p.x_bytes = (unsigned)xb;
-    p.w3 = w_h2; p.npad3 = cout_pad;
+    const int rc = describe_dual(p, MATH_H2, x, x2, x2_rows, x2_total_rows, w_h2, y, shift, rows, Cin1, Cin2, Cout, cout_pad, relu);
+    if (rc != FGN_DESCRIBED) return rc;
     return launch_h2(p, rows, 1, 0, stream);
+}
+
+// y[rows, Cout] = relu?(x[rows, K] * W^T + shift + residual) with W given as its plane image (ops.pack_x3 / ops.pack_h2);
+// grouped: rows = n_groups * grp_rows, group g uses image g and computes its first grp_valid rows.  The direct entries
+// of conv_pw_x3_kernel / conv_pw_h2_kernel (tests, tools); the convolution entry points take the image as an argument.
+static int describe_gemm(ConvParams& p, const GemmMath& m, const float* x, const void* w, float* y, const float* shift,
+                         const float* residual, int rows, int K, int Cout, int npad, int relu, int grp_rows, int grp_valid,
+                         int n_groups) {
+    if (!x || !w || !y) return FGN_ERR_ARG;
+    if (rows <= 0) return FGN_OK;
+    if (K % BK || K <= 0 || (Cout & 3) || npad % m.bn || npad < Cout || n_groups < 1) return FGN_ERR_SHAPE;
+    if (n_groups > 1 && (grp_rows <= 0 || (long long)n_groups * grp_rows != rows || grp_valid > grp_rows)) return FGN_ERR_SHAPE;
+    const long long xb = (long long)rows * K * 4, wb = gemm_weight_bytes(m, K, npad, n_groups);
+    if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || (long long)rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
+    p.x = x; p.y = y; p.shift = shift; p.residual = residual;
+    p.n_img = rows; p.Cin = K; p.Cout = Cout; p.relu = relu; p.K = K; p.kt_per_split = K / BK; p.x_bytes = (unsigned)xb;
+    p.grp_rows = n_groups > 1 ? grp_rows : 0; p.grp_valid = grp_valid;
+    gemm_set_weights(p, m, w, wb, npad);
+    return FGN_DESCRIBED;
+}
+
+extern "C" int fgn_gemm_x3_f32(const float* x, const void* w3, float* y, const float* shift, const float* residual,
+                               int rows, int K, int Cout, int npad, int relu, int grp_rows, int grp_valid, int n_groups,
+                               int bm, int nterms, hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_gemm(p, MATH_X3, x, w3, y, shift, residual, rows, K, Cout, npad, relu, grp_rows, grp_valid, n_groups);
+    if (rc != FGN_DESCRIBED) return rc;
+#ifdef X3_PHASES
+    if (!g_x3_ph && (hipMalloc(&g_x3_ph, 128) != hipSuccess || hipMemset(g_x3_ph, 0, 128) != hipSuccess)) return FGN_ERR_ARG;
+    p.ws = reinterpret_cast<float*>(g_x3_ph);
+#endif
+    return launch_x3(p, rows, bm, nterms, stream);
+}
+
+extern "C" int fgn_gemm_h2_f32(const float* x, const void* w_h2, float* y, const float* shift, const float* residual,
+                               int rows, int K, int Cout, int npad, int relu, int grp_rows, int grp_valid, int n_groups,
+                               int bm, hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_gemm(p, MATH_H2, x, w_h2, y, shift, residual, rows, K, Cout, npad, relu, grp_rows, grp_valid, n_groups);
+    if (rc != FGN_DESCRIBED) return rc;
+    return launch_h2(p, rows, n_groups, bm, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1886,35 +1790,56 @@ extern "C" int fgn_conv1x1_dual_h2_nhwc_f32(const float* x, const float* x2, con
 // ------------------------------------------------------------------------------------------------
 extern "C" int fgn_winograd_t_pad(int tiles_total) { return (tiles_total + 127) / 128 * 128; }   // whole 64- and 128-row tiles per group
 
-extern "C" int fgn_winograd_gemm_f32(const float* V, const float* U, float* Mo, const int32_t* n_img_dev, int n_img,
-                                     int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups,
-                                     hipStream_t stream) {
+// p.n_img = the stacked rows n_groups * t_pad
+static int describe_winograd_gemm(ConvParams& p, const GemmMath& m, const float* V, const void* U, float* Mo,
+                                  const int32_t* n_img_dev, int n_img, int tiles_per_img, int t_pad, int Cin, int Cout,
+                                  int cout_pad, int n_groups) {
     if (!V || !U || !Mo) return FGN_ERR_ARG;
     if (n_img <= 0) return FGN_OK;
-    if (Cin % BK != 0 || Cout % 4 != 0 || cout_pad % 128 != 0 || cout_pad < Cout || t_pad % 64 != 0 ||
+    if (Cin % BK != 0 || (m.deep && Cin < 2 * BK) || Cout % 4 != 0 || cout_pad % m.bn != 0 || cout_pad < Cout || t_pad % 64 != 0 ||
         (n_groups != 16 && n_groups != 36) || (long long)n_img * tiles_per_img > t_pad)
         return FGN_ERR_SHAPE;
     const long long rows = (long long)n_groups * t_pad;
-    const long long xb = rows * Cin * 4, wb = (long long)n_groups * cout_pad * Cin * 4;
+    const long long xb = rows * Cin * 4, wb = gemm_weight_bytes(m, Cin, cout_pad, n_groups);
     if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll || rows * Cout >= (1ll << 31)) return FGN_ERR_SHAPE;
-    ConvParams p;
-    p.x = V; p.w = U; p.y = Mo; p.scale = nullptr; p.shift = nullptr; p.residual = nullptr; p.in_scale = nullptr;
-    p.n_img_dev = nullptr; p.stamp = nullptr; p.x2 = nullptr; p.x2_bytes = 0; p.kt1 = 0; p.cin2 = 0; p.x2_rows = nullptr;
-#ifdef FGN_EXPERIMENTS
-    p.tickets = nullptr; p.sched = nullptr; p.sk_U = 0; p.sk_dp = 0;
-#endif
-    p.n_img = (int)rows; p.H = 1; p.W = 1; p.Cin = Cin; p.Ho = 1; p.Wo = 1; p.Cout = Cout; p.KH = 1; p.KW = 1;
-    p.stride = 1; p.pad = 0; p.a_img_div = 1; p.relu = 0; p.K = Cin;
-    p.ws = nullptr; p.splits = 1; p.kt_per_split = Cin / BK;
-    p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
+    p.x = V; p.y = Mo;
+    p.n_img = (int)rows; p.Cin = Cin; p.Cout = Cout; p.K = Cin; p.kt_per_split = Cin / BK; p.x_bytes = (unsigned)xb;
     p.grp_rows = t_pad; p.grp_valid = n_img * tiles_per_img; p.grp_items = n_img;
-    p.grp_rows_per_item = tiles_per_img; p.grp_w_stride = cout_pad * Cin; p.grp_count_dev = n_img_dev;
-    p.n_tiles_n = 0;
+    p.grp_rows_per_item = tiles_per_img; p.grp_count_dev = n_img_dev;
+    gemm_set_weights(p, m, U, wb, cout_pad);
+    if (!m.image_bytes) p.grp_w_stride = cout_pad * Cin;        // the image kernels find a group in w3 from K and npad3
+    return FGN_DESCRIBED;
+}
+
+extern "C" int fgn_winograd_gemm_f32(const float* V, const float* U, float* Mo, const int32_t* n_img_dev, int n_img,
+                                     int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups,
+                                     hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_winograd_gemm(p, MATH_F32, V, U, Mo, n_img_dev, n_img, tiles_per_img, t_pad, Cin, Cout, cout_pad, n_groups);
+    if (rc != FGN_DESCRIBED) return rc;
 #ifdef FGN_EXPERIMENTS
     {
-        int rc = FGN_OK;
-        if (fgn_exp_pointwise(p, rows, 4, true, t_pad, stream, &rc)) return rc;
+        int rc2 = FGN_OK;
+        if (fgn_exp_pointwise(p, p.n_img, 4, true, t_pad, stream, &rc2)) return rc2;
     }
 #endif
-    return launch_cfg<64, 64, 32, 32, 4>(p, (int)rows, false, stream);
+    return launch_cfg<64, 64, 32, 32, 4>(p, p.n_img, false, stream);
+}
+
+extern "C" int fgn_winograd_gemm_x3_f32(const float* V, const void* U_x3, float* Mo, const int32_t* n_img_dev, int n_img,
+                                        int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups,
+                                        hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_winograd_gemm(p, MATH_X3, V, U_x3, Mo, n_img_dev, n_img, tiles_per_img, t_pad, Cin, Cout, cout_pad, n_groups);
+    if (rc != FGN_DESCRIBED) return rc;
+    return launch_x3(p, p.n_img, 0, 6, stream);
+}
+
+extern "C" int fgn_winograd_gemm_h2_f32(const float* V, const void* U_h2, float* Mo, const int32_t* n_img_dev, int n_img,
+                                        int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups,
+                                        hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_winograd_gemm(p, MATH_H2, V, U_h2, Mo, n_img_dev, n_img, tiles_per_img, t_pad, Cin, Cout, cout_pad, n_groups);
+    if (rc != FGN_DESCRIBED) return rc;
+    return launch_h2(p, p.n_img, n_groups, 0, stream);
 }

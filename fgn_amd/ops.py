@@ -87,6 +87,25 @@ def kernel_name(kid: int) -> str:
     return f'conv_igemm_dma_kernel<{bm}, {bn}, {wm}, {wn}, 2, {mw}, {mode}>'
 
 
+# route (arithmetic) of a GEMM-shaped launch -> its entry point: fgn_conv1x1_[dual_]<infix>nhwc_f32, fgn_winograd_gemm_<infix>f32
+_ROUTE_INFIX = {'h2': 'h2_', 'x3': 'x3_', 'f32': ''}
+
+
+def _gemm_route(L, w3, wh, rows: int, cout: int, k: int, grp_rows: int = 0, grp_valid: int = 0) -> str:
+    """Route of a GEMM-shaped launch of a layer with the weight images ``w3`` (pack_x3) / ``wh`` (pack_h2) or None: that of
+    the image it carries (h2 first) if that kernel's tile rule takes the shape, else 'f32'.  Preconditions: the caller's."""
+    if wh is not None:
+        return 'h2' if L.fgn_h2_row_tile(rows, cout, k, grp_rows, grp_valid) > 0 else 'f32'
+    if w3 is not None:
+        return 'x3' if L.fgn_x3_row_tile(rows, cout, k, grp_rows, grp_valid) > 0 else 'f32'
+    return 'f32'
+
+
+def _gemm_kernel(route: str, f32_kernel: Optional[str], *gemm) -> str:
+    """Kernel name of a GEMM record by route (``gemm``: rows, cout, k[, grp_rows, grp_valid]; ``f32_kernel``: on 'f32')."""
+    return f32_kernel if route == 'f32' else (h2_kernel if route == 'h2' else x3_kernel)(*gemm)
+
+
 class ZeroArena:
     """One zero-filled allocation per episode from which the small zero-initialised outputs of the selection
     / head kernels are carved (counters, logits of RoIs beyond the device count, ...): one fill kernel
@@ -383,18 +402,19 @@ def conv2d(x: torch.Tensor, layer: ConvLayer, residual: Optional[torch.Tensor] =
                              flop_direct=flop, flop_issued=flop, n_img=n_img, n_img_dev=None, gemm=(1, ho * wo, layer.cout, k),
                              residual=False, shape=(n_img, H, W, cin, layer.cout, layer.kh, layer.stride)))
         return out
-    if pw and (layer.w3 is not None or layer.wh is not None) and in_scale is None and a_img_div == 1 and tile_hint == 0 and \
-            x.numel() * 4 < 0x7fffff00 and out.numel() < (1 << 31) and \
-            (L.fgn_h2_row_tile if layer.wh is not None else L.fgn_x3_row_tile)(n_img * ho * wo, layer.cout, cin, 0, 0) > 0:
-        h2 = layer.wh is not None
-        f = L.fgn_conv1x1_h2_nhwc_f32 if h2 else L.fgn_conv1x1_x3_nhwc_f32
-        rc = f(_ptr(x), (layer.wh if h2 else layer.w3).data_ptr(), _ptr(out), _ptr(layer.scale), _ptr(layer.shift),
-               _ptr(residual), _ptr(n_img_dev), n_img, H, W, cin, layer.cout, layer.cout_pad, int(layer.relu), _stream())
-        _lib.check(rc, 'fgn_conv1x1_h2_nhwc_f32' if h2 else 'fgn_conv1x1_x3_nhwc_f32')
+    route = 'f32'
+    if pw and in_scale is None and a_img_div == 1 and tile_hint == 0 and x.numel() * 4 < 0x7fffff00 and out.numel() < (1 << 31):
+        route = _gemm_route(L, layer.w3, layer.wh, n_img * ho * wo, layer.cout, cin)
+    if route != 'f32':
+        name = 'fgn_conv1x1_%snhwc_f32' % _ROUTE_INFIX[route]
+        rc = getattr(L, name)(_ptr(x), (layer.wh if route == 'h2' else layer.w3).data_ptr(), _ptr(out), _ptr(layer.scale),
+                              _ptr(layer.shift), _ptr(residual), _ptr(n_img_dev), n_img, H, W, cin, layer.cout, layer.cout_pad,
+                              int(layer.relu), _stream())
+        _lib.check(rc, name)
         if prof is not None:
             flop = 2.0 * ho * wo * layer.cout * cin
-            prof.append(dict(kind='conv', kernel=(h2_kernel if h2 else x3_kernel)(n_img * ho * wo, layer.cout, cin),
-                             math='h2' if h2 else 'x3', e0=e0, e1=e1, flop_direct=flop, flop_issued=flop,
+            prof.append(dict(kind='conv', kernel=_gemm_kernel(route, None, n_img * ho * wo, layer.cout, cin),
+                             math=route, e0=e0, e1=e1, flop_direct=flop, flop_issued=flop,
                              n_img=n_img, n_img_dev=n_img_dev, gemm=(1, ho * wo, layer.cout, cin),
                              residual=residual is not None, shape=(n_img, H, W, cin, layer.cout, 1, 1)))
         return out
@@ -614,22 +634,19 @@ def conv1x1_dual(x1: torch.Tensor, x2: torch.Tensor, layer: DualConvLayer, out: 
     L = _lib.load()
     if prof is not None:
         e0, e1 = prof.arm()
-    use_x3 = (layer.w3 is not None or layer.wh is not None) and max(x1.numel(), x2.numel()) * 4 < 0x7fffff00 and \
-        (L.fgn_h2_row_tile if layer.wh is not None else L.fgn_x3_row_tile)(rows, layer.cout, layer.cin1 + layer.cin2, 0, 0) > 0
-    use_h2 = use_x3 and layer.wh is not None
-    if use_x3:
-        f = L.fgn_conv1x1_dual_h2_nhwc_f32 if use_h2 else L.fgn_conv1x1_dual_x3_nhwc_f32
-        rc = f(_ptr(x1), _ptr(x2), _ptr(x2_rows), x2_total, (layer.wh if use_h2 else layer.w3).data_ptr(), _ptr(out),
-               _ptr(layer.shift), rows, layer.cin1, layer.cin2, layer.cout, layer.cout_pad, int(layer.relu), _stream())
-    else:
-        rc = L.fgn_conv1x1_dual_nhwc_f32(_ptr(x1), _ptr(x2), _ptr(x2_rows), x2_total, _ptr(layer.w), _ptr(out), _ptr(layer.shift),
-                                         rows, layer.cin1, layer.cin2, layer.cout, layer.cout_pad, int(layer.relu), _stream())
+    k = layer.cin1 + layer.cin2
+    route = 'f32'
+    if max(x1.numel(), x2.numel()) * 4 < 0x7fffff00:
+        route = _gemm_route(L, layer.w3, layer.wh, rows, layer.cout, k)
+    w = {'h2': layer.wh, 'x3': layer.w3, 'f32': layer.w}[route]
+    rc = getattr(L, 'fgn_conv1x1_dual_%snhwc_f32' % _ROUTE_INFIX[route])(
+        _ptr(x1), _ptr(x2), _ptr(x2_rows), x2_total, w.data_ptr(), _ptr(out), _ptr(layer.shift), rows, layer.cin1, layer.cin2,
+        layer.cout, layer.cout_pad, int(layer.relu), _stream())
     _lib.check(rc, 'fgn_conv1x1_dual_nhwc_f32')
     if prof is not None:
-        k = layer.cin1 + layer.cin2
         flop = 2.0 * rows * layer.cout * k
-        prof.append(dict(kind='conv', kernel=h2_kernel(rows, layer.cout, k) if use_h2 else x3_kernel(rows, layer.cout, k) if use_x3 else 'conv_pw_persist_kernel',
-                         math='h2' if use_h2 else 'x3' if use_x3 else 'f32', e0=e0, e1=e1, flop_direct=flop, flop_issued=flop,
+        prof.append(dict(kind='conv', kernel=_gemm_kernel(route, 'conv_pw_persist_kernel', rows, layer.cout, k),
+                         math=route, e0=e0, e1=e1, flop_direct=flop, flop_issued=flop,
                          n_img=1, n_img_dev=None, gemm=(1, rows, layer.cout, k), residual=False,
                          shape=(1, rows, 1, k, layer.cout, 1, 1)))
     return out
@@ -830,6 +847,36 @@ def winograd_pays(n_img: int, H: int, W: int, cin: int, cout: int, m: Optional[i
     return cin >= (_WG_MIN_CIN if m == 4 else 128) and n_img * H * W >= 1024 and winograd_fits(n_img, H, W, cin, cout, m)
 
 
+def _winograd_gemm(L, layer: WinogradLayer, V, Mo, n_img_dev, n_img: int, tiles: int, t_pad: int, st) -> str:
+    """The grouped GEMM Mo = V U^T of a Winograd convolution (n_img x tiles valid rows per group).  -> its route."""
+    route = _gemm_route(L, layer.u3, layer.uh, layer.groups * t_pad, layer.cout, layer.cin, t_pad, n_img * tiles)
+    name = 'fgn_winograd_gemm_%sf32' % _ROUTE_INFIX[route]
+    u = {'h2': layer.uh, 'x3': layer.u3, 'f32': layer.u}[route]
+    _lib.check(getattr(L, name)(_ptr(V), u.data_ptr(), _ptr(Mo), _ptr(n_img_dev), n_img, tiles, t_pad, layer.cin, layer.cout,
+                                layer.cout_pad, layer.groups, st), name)
+    return route
+
+
+def _winograd_records(prof, ev, L, layer: WinogradLayer, route: str, t_pad: int, valid: int, tiles: int, pixels: int,
+                      **common) -> None:
+    """The three PROFILE records of a Winograd convolution (ev: the event pairs of input transform, GEMM, output transform).
+    ``valid`` tiles are computed per group; a record's FLOPs are per image of ``tiles`` tiles and ``pixels`` pixels."""
+    G, cin, cout = layer.groups, layer.cin, layer.cout
+    kin, kout = 'wg_input_kernel', 'wg_output_kernel'
+    if layer.m == 4:     # the template instances of the F(4x4) transforms (csrc/winograd.hip): <vector width, eager>
+        vi, vo = L.fgn_winograd4_variant(valid, cin, 0), L.fgn_winograd4_variant(valid, cout, 1)
+        kin = 'wg4_input_kernel<%d, %s>' % (vi // 10, 'true' if vi % 10 else 'false')
+        kout = 'wg4_output_kernel<%d>' % (vo // 10)
+    prof.append(dict(kind='wg_in', kernel=kin, e0=ev[0][0], e1=ev[0][1], flop_direct=0.0, flop_issued=0.0, **common))
+    # direct-convolution FLOPs of the layer (what the reference's formulation executes) are booked on the GEMM record; the
+    # MFMA work issued is (m+2)^2 products per m x m output tile instead of 9 m^2.  The GEMM: point-wise over [G * t_pad] rows
+    gid = L.fgn_conv2d_kernel_id(G * t_pad, 1, 1, cin, cout, layer.cout_pad, 1, 1, 1, 0, 1, 0, 0, 4)   # 64x64 tile
+    prof.append(dict(kind='wg_gemm', kernel=_gemm_kernel(route, kernel_name(gid), G * t_pad, cout, cin, t_pad, valid),
+                     math=route, e0=ev[1][0], e1=ev[1][1], flop_direct=2.0 * pixels * cout * 9 * cin,
+                     flop_issued=2.0 * G * tiles * cout * cin, gemm=(G, tiles, cout, cin), **common))
+    prof.append(dict(kind='wg_out', kernel=kout, e0=ev[2][0], e1=ev[2][1], flop_direct=0.0, flop_issued=0.0, **common))
+
+
 def conv3x3_winograd(x: torch.Tensor, layer: WinogradLayer, in_scale: Optional[torch.Tensor] = None,
                      a_img_div: int = 1, n_img_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x [n_in,H,W,Cin] -> relu?(conv3x3(x[i // a_img_div] * in_scale[i]) + shift) [n_in*a_img_div,H,W,Cout]."""
@@ -858,48 +905,18 @@ def conv3x3_winograd(x: torch.Tensor, layer: WinogradLayer, in_scale: Optional[t
     ev = [] if prof is not None else None
     if ev is not None:
         ev.append(prof.arm())
-    use_x3 = (layer.u3 is not None or layer.uh is not None) and \
-        (L.fgn_h2_row_tile if layer.uh is not None else L.fgn_x3_row_tile)(G * t_pad, layer.cout, cin, t_pad, n_img * tiles) > 0
-    use_h2 = use_x3 and layer.uh is not None
-    use_x3 = use_x3 and not use_h2
     _lib.check(f_in(_ptr(x), _ptr(in_scale), _ptr(V), _ptr(n_img_dev), n_img, a_img_div, H, W, cin, t_pad, st),
                'fgn_winograd_input_f32')
     if ev is not None:
         ev.append(prof.arm())
-    if use_h2:
-        _lib.check(L.fgn_winograd_gemm_h2_f32(_ptr(V), layer.uh.data_ptr(), _ptr(Mo), _ptr(n_img_dev), n_img, tiles, t_pad, cin,
-                                              layer.cout, layer.cout_pad, G, st), 'fgn_winograd_gemm_h2_f32')
-    elif use_x3:
-        _lib.check(L.fgn_winograd_gemm_x3_f32(_ptr(V), layer.u3.data_ptr(), _ptr(Mo), _ptr(n_img_dev), n_img, tiles, t_pad, cin,
-                                              layer.cout, layer.cout_pad, G, st), 'fgn_winograd_gemm_x3_f32')
-    else:
-        _lib.check(L.fgn_winograd_gemm_f32(_ptr(V), _ptr(layer.u), _ptr(Mo), _ptr(n_img_dev), n_img, tiles, t_pad, cin,
-                                           layer.cout, layer.cout_pad, G, st), 'fgn_winograd_gemm_f32')
+    route = _winograd_gemm(L, layer, V, Mo, n_img_dev, n_img, tiles, t_pad, st)
     if ev is not None:
         ev.append(prof.arm())
     _lib.check(f_out(_ptr(Mo), _ptr(y), _ptr(layer.shift), _ptr(n_img_dev), n_img, H, W, layer.cout, t_pad,
                      int(layer.relu), st), 'fgn_winograd_output_f32')
     if ev is not None:
-        # direct-convolution FLOPs of the layer (what the reference's formulation executes) are booked on the GEMM
-        # record; the MFMA work actually issued is (m+2)^2 products per m x m output tile instead of 9 m^2
-        shape = (n_img, H, W, cin, layer.cout, 3, 1)
-        common = dict(n_img=n_img, n_img_dev=n_img_dev, shape=shape)
-        kin, kout = 'wg_input_kernel', 'wg_output_kernel'
-        if layer.m == 4:     # the template instances of the F(4x4) transforms (csrc/winograd.hip): <vector width, eager>
-            vi, vo = L.fgn_winograd4_variant(n_img * tiles, cin, 0), L.fgn_winograd4_variant(n_img * tiles, layer.cout, 1)
-            kin = 'wg4_input_kernel<%d, %s>' % (vi // 10, 'true' if vi % 10 else 'false')
-            kout = 'wg4_output_kernel<%d>' % (vo // 10)
-        prof.append(dict(kind='wg_in', kernel=kin, e0=ev[0][0], e1=ev[0][1], flop_direct=0.0, flop_issued=0.0,
-                         **common))
-        # the grouped GEMM is a point-wise launch over [groups * t_pad] rows
-        gid = L.fgn_conv2d_kernel_id(G * t_pad, 1, 1, cin, layer.cout, layer.cout_pad, 1, 1, 1, 0, 1, 0, 0, 4)   # 64x64 tile
-        prof.append(dict(kind='wg_gemm', kernel=h2_kernel(G * t_pad, layer.cout, cin, t_pad, n_img * tiles) if use_h2 else
-                         x3_kernel(G * t_pad, layer.cout, cin, t_pad, n_img * tiles) if use_x3 else kernel_name(gid),
-                         math='h2' if use_h2 else 'x3' if use_x3 else 'f32', e0=ev[1][0], e1=ev[1][1],
-                         flop_direct=2.0 * H * W * layer.cout * 9 * cin,
-                         flop_issued=2.0 * G * tiles * layer.cout * cin, gemm=(G, tiles, layer.cout, cin), **common))
-        prof.append(dict(kind='wg_out', kernel=kout, e0=ev[2][0], e1=ev[2][1], flop_direct=0.0,
-                         flop_issued=0.0, **common))
+        _winograd_records(prof, ev, L, layer, route, t_pad, n_img * tiles, tiles, H * W, n_img=n_img, n_img_dev=n_img_dev,
+                          shape=(n_img, H, W, cin, layer.cout, 3, 1))
     return y
 
 
@@ -932,10 +949,6 @@ def conv3x3_winograd_multi(xs, layer: WinogradLayer, outs) -> None:
     ev = []
     if prof is not None:
         ev.append(prof.arm())
-    use_x3 = (layer.u3 is not None or layer.uh is not None) and \
-        (L.fgn_h2_row_tile if layer.uh is not None else L.fgn_x3_row_tile)(G * t_pad, cout, cin, t_pad, total) > 0
-    use_h2 = use_x3 and layer.uh is not None
-    use_x3 = use_x3 and not use_h2
     if pair:
         (n0, h0, w0, _), (n1, h1, w1, _) = xs[0].shape, xs[1].shape
         _lib.check(L.fgn_winograd4_input2_f32(_ptr(xs[0]), n0, h0, w0, _ptr(xs[1]), n1, h1, w1, _ptr(V), cin, t_pad, st),
@@ -949,15 +962,7 @@ def conv3x3_winograd_multi(xs, layer: WinogradLayer, outs) -> None:
             off += n_t
     if prof is not None:
         ev.append(prof.arm())
-    if use_h2:
-        _lib.check(L.fgn_winograd_gemm_h2_f32(_ptr(V), layer.uh.data_ptr(), _ptr(Mo), None, 1, total, t_pad, cin, cout,
-                                              layer.cout_pad, G, st), 'fgn_winograd_gemm_h2_f32')
-    elif use_x3:
-        _lib.check(L.fgn_winograd_gemm_x3_f32(_ptr(V), layer.u3.data_ptr(), _ptr(Mo), None, 1, total, t_pad, cin, cout,
-                                              layer.cout_pad, G, st), 'fgn_winograd_gemm_x3_f32')
-    else:
-        _lib.check(L.fgn_winograd_gemm_f32(_ptr(V), _ptr(layer.u), _ptr(Mo), None, 1, total, t_pad, cin, cout, layer.cout_pad,
-                                           G, st), 'fgn_winograd_gemm_f32')
+    route = _winograd_gemm(L, layer, V, Mo, None, 1, total, t_pad, st)
     if prof is not None:
         ev.append(prof.arm())
     if pair:
@@ -972,18 +977,8 @@ def conv3x3_winograd_multi(xs, layer: WinogradLayer, outs) -> None:
             off += n_t
     if prof is not None:
         pixels = sum(x.shape[0] * x.shape[1] * x.shape[2] for x in xs)
-        common = dict(n_img=1, n_img_dev=None, shape=(len(xs), pixels, 1, cin, cout, 3, 1))
-        vi, vo = L.fgn_winograd4_variant(total, cin, 0), L.fgn_winograd4_variant(total, cout, 1)
-        prof.append(dict(kind='wg_in', kernel='wg4_input_kernel<%d, %s>' % (vi // 10, 'true' if vi % 10 else 'false'),
-                         e0=ev[0][0], e1=ev[0][1], flop_direct=0.0, flop_issued=0.0, **common))
-        gid = L.fgn_conv2d_kernel_id(G * t_pad, 1, 1, cin, cout, layer.cout_pad, 1, 1, 1, 0, 1, 0, 0, 4)
-        prof.append(dict(kind='wg_gemm', kernel=h2_kernel(G * t_pad, cout, cin, t_pad, total) if use_h2 else
-                         x3_kernel(G * t_pad, cout, cin, t_pad, total) if use_x3 else kernel_name(gid),
-                         math='h2' if use_h2 else 'x3' if use_x3 else 'f32', e0=ev[1][0], e1=ev[1][1],
-                         flop_direct=2.0 * pixels * cout * 9 * cin, flop_issued=2.0 * G * total * cout * cin,
-                         gemm=(G, total, cout, cin), **common))
-        prof.append(dict(kind='wg_out', kernel='wg4_output_kernel<%d>' % (vo // 10), e0=ev[2][0], e1=ev[2][1],
-                         flop_direct=0.0, flop_issued=0.0, **common))
+        _winograd_records(prof, ev, L, layer, route, t_pad, total, total, pixels, n_img=1, n_img_dev=None,
+                          shape=(len(xs), pixels, 1, cin, cout, 3, 1))
 
 
 # --------------------------------------------------------------------------------------
