@@ -1150,6 +1150,100 @@ static int plan_splits(long long M, int Cout, int KT, int tile_hint, bool pw = f
     return s < 2 ? 1 : s;
 }
 
+// tile choice (measured on MI355X, tools/conv_bench.py): 64x64 everywhere, except when the 128x128 grid is one nearly
+// full round of 2 workgroups per CU (the 1024 -> 512 conv on 300 RoIs: 460 tiles), where half the L2 traffic per
+// MAC is worth ~8 %.  1 = 128x128, 2 = 64x128, 3 = 128x64, 4 = 64x64 (tile_hint forces one; tests).
+static int pick_tile(long long M, int Cout, bool has_residual, int tile_hint) {
+    int tile = tile_hint < 0 ? -tile_hint : tile_hint;
+    if (tile >= 100) tile -= 100;
+    if (tile == 0) {
+        const long long b128 = ((M + 127) / 128) * cdiv(Cout, 128);
+        tile = (b128 >= 420 && b128 <= 512 && !has_residual && (Cout % 4) == 0) ? 1 : 4;
+    }
+    return tile;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The plan of a direct launch (fgn_conv2d_nhwc_f32): THE place where its kernel, tile, K split and loader are decided.
+// The launch copies it into ConvParams, fgn_conv2d_kernel_id reports tile * 10 + mode of it and
+// fgn_conv2d_workspace_bytes its ws_bytes, so the three cannot disagree.
+// ------------------------------------------------------------------------------------------------
+struct ConvPlan {
+    int rc = FGN_ERR_SHAPE;              // FGN_OK, or the code the launch is refused with (the rest is then unset)
+    int Ho = 0, Wo = 0, K = 0;           // output size; padded reduction length
+    long long M = 0;                     // output pixels
+    unsigned x_bytes = 0, w_bytes = 0;   // buffer descriptor extents of the LDS-DMA kernels; 0: register-staged loader
+    int tile = 4;                        // 1 = 128x128, 2 = 64x128, 3 = 128x64, 4 = 64x64 (pick_tile)
+    int mode = 0;                        // the kernel, as documented above fgn_conv2d_kernel_id
+    int splits = 1, kt_per_split = 0;    // split-K (plan_splits, given the workspace for it)
+    size_t ws_bytes = 0;                 // the workspace the split uses
+};
+
+// Geometry and extents of ONE tensor of a direct convolution (the plan's first half; fgn_conv2d_pair_nhwc_f32 asks per
+// tensor): refuses what no kernel of the family can address and leaves the extents 0 where an operand does not fit the
+// 2 GiB of a buffer descriptor.
+static ConvPlan conv_geometry(int n_img, int H, int W, int Cin, int Cout, int cout_pad, int KH, int KW, int stride, int pad,
+                              int a_img_div) {
+    ConvPlan g;
+    const bool cin4 = Cin == 4;
+    if (n_img <= 0 || (!cin4 && Cin % BK != 0) || a_img_div < 1 || stride < 1 || cout_pad % 128 != 0 || cout_pad < Cout) return g;
+    g.Ho = (H + 2 * pad - KH) / stride + 1;
+    g.Wo = (W + 2 * pad - KW) / stride + 1;
+    if (g.Ho <= 0 || g.Wo <= 0) return g;
+    if (KH * KW > 64) return g;                   // tap validity is a 64-bit mask
+    if (cin4 && KW > 8) return g;                 // stem layout: one K-tile per filter row, [KH][8 pixels][4]
+    g.K = cin4 ? KH * BK : cdiv(KH * KW * Cin, BK) * BK;
+    // offsets are 32-bit element indices
+    if ((long long)(n_img / a_img_div + 1) * H * W * Cin >= (1ll << 31)) return g;
+    g.M = (long long)n_img * g.Ho * g.Wo;
+    if (g.M * (long long)Cout >= (1ll << 31) * 4) return g;
+    const long long xb = (long long)((n_img + a_img_div - 1) / a_img_div) * H * W * Cin * 4;
+    const long long wb = (long long)cout_pad * g.K * 4;
+    if (xb < 0x7fffff00ll && wb < 0x7fffff00ll) { g.x_bytes = (unsigned)xb; g.w_bytes = (unsigned)wb; }
+    g.rc = FGN_OK;
+    return g;
+}
+
+// Kernel of a point-wise (1x1 / stride 1 / unpadded, one input image per output image) launch on the LDS-DMA path, as
+// ConvPlan::mode: with more 64x64 output tiles than resident workgroups, persistent workgroups walk them
+// (conv_pw_persist_kernel: no split-K, rows written 16 bytes at a time); else one tile per workgroup.
+static int pointwise_mode(int tile, long long M, int Cout, int splits) {
+    return tile == 4 && splits == 1 && (Cout & 3) == 0 && ((M + 63) / 64) * cdiv(Cout, 64) > persist_blocks() ? 4 : 1;
+}
+
+// ws_avail: bytes of split-K workspace the launch was handed (SIZE_MAX: what fgn_conv2d_workspace_bytes says)
+static ConvPlan plan_conv(int n_img, int H, int W, int Cin, int Cout, int cout_pad, int KH, int KW, int stride, int pad,
+                          int a_img_div, bool in_scale, bool has_residual, int tile_hint, size_t ws_avail) {
+    ConvPlan pl = conv_geometry(n_img, H, W, Cin, Cout, cout_pad, KH, KW, stride, pad, a_img_div);
+    if (pl.rc != FGN_OK) return pl;
+    const bool cin4 = Cin == 4;
+    pl.rc = FGN_ERR_SHAPE;
+    if (cin4 && in_scale) return pl;
+    if (tile_hint >= 100) {                       // tile_hint >= 100 forces the register-staged kernel
+        if (!cin4) pl.x_bytes = pl.w_bytes = 0u;
+        tile_hint -= 100;
+    }
+    pl.tile = pick_tile(pl.M, Cout, has_residual, tile_hint);
+    if (pl.tile < 1 || pl.tile > 4) { pl.rc = FGN_ERR_ARG; return pl; }
+    if (cin4 && pl.x_bytes == 0) return pl;       // the stem runs on the LDS-DMA kernel only (input < 2 GiB)
+    const bool dma = pl.x_bytes != 0 && !in_scale;
+    const bool pw = KH == 1 && KW == 1 && stride == 1 && pad == 0 && a_img_div == 1;
+    const int KT = pl.K / BK;
+    pl.kt_per_split = KT;
+    if (pl.tile == 4) {
+        const int sp = plan_splits(pl.M, Cout, KT, tile_hint, pw && !in_scale);
+        const size_t need = (size_t)sp * pl.M * Cout * sizeof(float);
+        if (sp > 1 && ws_avail >= need) {
+            pl.kt_per_split = cdiv(KT, sp);
+            pl.splits = cdiv(KT, pl.kt_per_split);
+            pl.ws_bytes = need;
+        }
+    }
+    pl.mode = !dma ? 3 : cin4 ? 2 : pw ? pointwise_mode(pl.tile, pl.M, Cout, pl.splits) : 0;
+    pl.rc = FGN_OK;
+    return pl;
+}
+
 // banded raster when the launch's weights exceed the L2 budget (see ConvParams::band_nt); per_nt = bytes of weights (or
 // of their plane image) that one Cout tile reads: f32 BN * (K / splits) * 4, x3 X3_BN * K * 6, h2 BN * K * 4
 static void set_band(ConvParams& p, int BM, int m_tiles, long long per_nt) {
@@ -1169,59 +1263,56 @@ static void set_band(ConvParams& p, int BM, int m_tiles, long long per_nt) {
 #undef FGN_EXP_PART
 #endif
 
+// One launch of KERNEL through FGN_LAUNCH_TIMED, its dynamic LDS allowed first (once per kernel and device)
+template <auto KERNEL, typename... Args>
+static int launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
+    static unsigned long long lds_ok = 0ull;
+    const hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(KERNEL), &lds_ok);
+    if (attr != hipSuccess) return (int)attr;
+    FGN_LAUNCH_TIMED(KERNEL, grid, block, lds, stream, args...);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// conv_pw_persist_kernel on a described point-wise launch of `tiles` 64x64 output tiles (n_tiles_n and the band set):
+// whole rounds of 8 workgroups (XCDs), at most persist_blocks()
+static int launch_persist(ConvParams& p, int tiles, hipStream_t stream) {
+#ifdef FGN_EXPERIMENTS
+    { int rc = FGN_OK; if (fgn_exp_launch_persist_ws(p, tiles, stream, &rc)) return rc; }
+#endif
+    const size_t plds = (size_t)2 * (64 + 64) * BK * sizeof(float);
+    const int grid = std::min(persist_blocks(), (tiles + 7) / 8 * 8);
+    p.stamp = fgn_next_stamp_record();
+    return launch_kernel<conv_pw_persist_kernel>(dim3(grid), dim3(256), plds, stream, p, tiles);
+}
+
+// Launches the kernel `mode` names (ConvPlan::mode) on a described launch; mode 4 exists for the 64x64 tile only.
 template <int BM, int BN, int WM, int WN, int MW>
-static int launch_cfg(const ConvParams& p0, int M_max, bool cin4, hipStream_t stream) {
+static int launch_cfg(const ConvParams& p0, int M_max, int mode, hipStream_t stream) {
     ConvParams p = p0;
     p.n_tiles_n = cdiv(p.Cout, BN);
     const int m_tiles = cdiv(M_max, BM);
     const dim3 grid(m_tiles * p.n_tiles_n, p.splits);
     set_band(p, BM, m_tiles, (long long)BN * (p.K / p.splits) * 4);
-    const size_t lds = 2 * (BM + BN) * LDS_STRIDE * sizeof(float);
-    static unsigned long long lds_ok[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
-    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WM, WN, true, MW>), &lds_ok[0]);
-    if (attr == hipSuccess)
-        attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_kernel<BM, BN, WM, WN, false, MW>), &lds_ok[1]);
-    if (attr != hipSuccess) return (int)attr;
-    if (!p.in_scale && p.x_bytes != 0) {
-        constexpr int NST = (BM + BN >= 256) ? 2 : CONV_DMA_STAGES;   // 128x128 keeps 2 blocks/CU
-        const size_t dlds = std::max((size_t)NST * (BM + BN) * BK, (size_t)BM * (BN + 4)) * sizeof(float);
-        attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 0>), &lds_ok[2]);
-        if (attr == hipSuccess)
-            attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 1>), &lds_ok[3]);
-        if (attr == hipSuccess)
-            attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 2>), &lds_ok[4]);
-        if (attr != hipSuccess) return (int)attr;
-        const bool pw = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.a_img_div == 1;
-        if (cin4)
-            FGN_LAUNCH_TIMED((conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 2>), grid, dim3(256), dlds, stream, p);
 #ifdef FGN_EXPERIMENTS
-        else if (pw && BM == 64 && BN == 64 && p.splits == 1 && (p.Cout & 3) == 0 && p.sk_U > 0 && p.ws && p.tickets) {
-            const int rc = fgn_exp_launch_streamk(p, (int)grid.x, stream);
-            if (rc != FGN_OK) return rc;
-        }
+    if ((mode == 1 || mode == 4) && p.sk_U > 0 && p.ws && p.tickets) return fgn_exp_launch_streamk(p, (int)grid.x, stream);
 #endif
-        else if (pw && BM == 64 && BN == 64 && p.splits == 1 && (p.Cout & 3) == 0 && (int)grid.x > persist_blocks()) {
-            // more output tiles than resident workgroups: persistent workgroups walk them (conv_pw_persist_kernel)
-            static unsigned long long pk_ok = 0ull;
-            attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_persist_kernel), &pk_ok);
-            if (attr != hipSuccess) return (int)attr;
-            const size_t plds = (size_t)2 * (64 + 64) * BK * sizeof(float);
-#ifdef FGN_EXPERIMENTS
-            { int rc = FGN_OK; if (fgn_exp_launch_persist_ws(p, (int)grid.x, stream, &rc)) return rc; }
-#endif
-            p.stamp = fgn_next_stamp_record();
-            FGN_LAUNCH_TIMED(conv_pw_persist_kernel, dim3(persist_blocks()), dim3(256), plds, stream, p, (int)grid.x);
-        } else if (pw)
-            FGN_LAUNCH_TIMED((conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 1>), grid, dim3(256), dlds, stream, p);
-        else
-            FGN_LAUNCH_TIMED((conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 0>), grid, dim3(256), dlds, stream, p);
-    } else if (cin4)
-        return FGN_ERR_SHAPE;      // the stem runs on the LDS-DMA kernel only (input < 2 GiB)
-    else if (p.in_scale)
-        FGN_LAUNCH_TIMED((conv_igemm_kernel<BM, BN, WM, WN, true, MW>), grid, dim3(256), lds, stream, p);
-    else
-        FGN_LAUNCH_TIMED((conv_igemm_kernel<BM, BN, WM, WN, false, MW>), grid, dim3(256), lds, stream, p);
-    FGN_LAUNCH_CHECK();
+    constexpr int NST = (BM + BN >= 256) ? 2 : CONV_DMA_STAGES;   // 128x128 keeps 2 blocks/CU
+    const size_t dlds = std::max((size_t)NST * (BM + BN) * BK, (size_t)BM * (BN + 4)) * sizeof(float);   // LDS-DMA kernel
+    const size_t lds = 2 * (BM + BN) * LDS_STRIDE * sizeof(float);                                       // register-staged
+    const dim3 wg(256);
+    int rc = FGN_ERR_ARG;
+    switch (mode) {     // (instances are emitted in the order they are named: register-staged first, as the code object has them)
+        case 3:         // one mode, two instances: the fused input scale is a template argument
+            rc = p.in_scale ? launch_kernel<conv_igemm_kernel<BM, BN, WM, WN, true, MW>>(grid, wg, lds, stream, p)
+                            : launch_kernel<conv_igemm_kernel<BM, BN, WM, WN, false, MW>>(grid, wg, lds, stream, p);
+            break;
+        case 0: rc = launch_kernel<conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 0>>(grid, wg, dlds, stream, p); break;
+        case 1: rc = launch_kernel<conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 1>>(grid, wg, dlds, stream, p); break;
+        case 2: rc = launch_kernel<conv_igemm_dma_kernel<BM, BN, WM, WN, NST, MW, 2>>(grid, wg, dlds, stream, p); break;
+        case 4: if (BM == 64 && BN == 64) rc = launch_persist(p, (int)grid.x, stream); break;
+    }
+    if (rc != FGN_OK) return rc;
     if (p.splits > 1) {
         const size_t total4 = (size_t)M_max * p.Cout / 4;
         const int eg = (int)std::min<size_t>((total4 + 255) / 256, 2048);
@@ -1231,63 +1322,31 @@ static int launch_cfg(const ConvParams& p0, int M_max, bool cin4, hipStream_t st
     return FGN_OK;
 }
 
-
-// tile choice (measured on MI355X, tools/conv_bench.py): 64x64 everywhere, except when the 128x128 grid is one nearly
-// full round of 2 workgroups per CU (the 1024 -> 512 conv on 300 RoIs: 460 tiles), where half the L2 traffic per
-// MAC is worth ~8 %.  1 = 128x128, 2 = 64x128, 3 = 128x64, 4 = 64x64 (tile_hint forces one; tests).
-static int pick_tile(long long M, int Cout, bool has_residual, int tile_hint) {
-    int tile = tile_hint < 0 ? -tile_hint : tile_hint;
-    if (tile >= 100) tile -= 100;
-    if (tile == 0) {
-        const long long b128 = ((M + 127) / 128) * cdiv(Cout, 128);
-        tile = (b128 >= 420 && b128 <= 512 && !has_residual && (Cout % 4) == 0) ? 1 : 4;
-    }
-    return tile;
-}
-
 // Which kernel the dispatcher launches for a layer: tile * 10 + mode, mode 0 = LDS-DMA generic, 1 = LDS-DMA
 // point-wise, 2 = LDS-DMA stem, 3 = register-staged (fused input scale, or operands beyond the 2 GiB buffer
 // descriptors), 4 = conv_pw_persist_kernel (point-wise, more output tiles than resident workgroups).  Lets a profiler
 // attribute a launch to the kernel name rocprofv3 reports, e.g. 41 = conv_igemm_dma_kernel<64, 64, 32, 32, 2, 4, 1>.
+// The plan of the launch that is handed the workspace fgn_conv2d_workspace_bytes asks for; what that launch refuses on
+// shape or hint is refused here with the same code.
 extern "C" int fgn_conv2d_kernel_id(int n_img, int H, int W, int Cin, int Cout, int cout_pad, int KH, int KW, int stride,
                                     int pad, int a_img_div, int has_in_scale, int has_residual, int tile_hint) {
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    if (Ho <= 0 || Wo <= 0 || n_img <= 0 || a_img_div < 1) return FGN_ERR_SHAPE;
-    const bool cin4 = Cin == 4;
-    const long long M = (long long)n_img * Ho * Wo;
-    const int K = cin4 ? KH * BK : cdiv(KH * KW * Cin, BK) * BK;
-    const long long xb = (long long)((n_img + a_img_div - 1) / a_img_div) * H * W * Cin * 4;
-    const long long wb = (long long)cout_pad * K * 4;
-    const bool use_dma = (tile_hint < 100 || cin4) && xb < 0x7fffff00ll && wb < 0x7fffff00ll;
-    const int tile = pick_tile(M, Cout, has_residual != 0, tile_hint);
-    int mode = 3;
-    if (use_dma && !has_in_scale)
-        mode = cin4 ? 2 : (KH == 1 && KW == 1 && stride == 1 && pad == 0 && a_img_div == 1) ? 1 : 0;
+    const ConvPlan pl = plan_conv(n_img, H, W, Cin, Cout, cout_pad, KH, KW, stride, pad, a_img_div, has_in_scale != 0,
+                                  has_residual != 0, tile_hint, SIZE_MAX);
+    if (pl.rc != FGN_OK) return pl.rc;
 #ifdef FGN_EXPERIMENTS
     {   // conv_pw_persist2_kernel: tile code * 10 + 5; Stream-K launches: tile * 10 + 6
-        const int id = fgn_exp_kernel_id(mode, tile, M, Cout, K, tile_hint, has_residual);
+        const int id = fgn_exp_kernel_id(pl, Cout, tile_hint, has_residual);
         if (id) return id;
     }
 #endif
-    // point-wise launches with more 64x64 output tiles than resident workgroups run on conv_pw_persist_kernel
-    if (mode == 1 && tile == 4 && (Cout & 3) == 0 &&
-        ((M + 63) / 64) * cdiv(Cout, 64) > persist_blocks() && plan_splits(M, Cout, K / BK, tile_hint, true) == 1)
-        mode = 4;
-    return tile * 10 + mode;
+    return pl.tile * 10 + pl.mode;
 }
 
+// The split depends on neither the weights' padding, a shared input image nor a residual (which only moves a launch
+// between two tiles that are never split): the plan of the plain launch of this geometry.  0 for what the launch refuses.
 extern "C" size_t fgn_conv2d_workspace_bytes(int n_img, int H, int W, int Cin, int Cout, int KH, int KW,
                                              int stride, int pad, int tile_hint) {
-    const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-    if (Ho <= 0 || Wo <= 0 || n_img <= 0) return 0;
-    if (tile_hint >= 100) tile_hint -= 100;
-    const long long M = (long long)n_img * Ho * Wo;
-    const int KT = cdiv(KH * KW * Cin, BK);
-    if (tile_hint > 0 && tile_hint != 4) return 0;
-    const bool pw = KH == 1 && KW == 1 && stride == 1 && pad == 0;
-    const int s = plan_splits(M, Cout, KT, tile_hint, pw);
-    if (s > 1) return (size_t)s * M * Cout * sizeof(float);
-    return 0;
+    return plan_conv(n_img, H, W, Cin, Cout, cdiv(Cout, 128) * 128, KH, KW, stride, pad, 1, false, false, tile_hint, SIZE_MAX).ws_bytes;
 }
 
 extern "C" int fgn_conv2d_nhwc_f32(const float* x, const float* w_packed, float* y, const float* scale,
@@ -1298,64 +1357,28 @@ extern "C" int fgn_conv2d_nhwc_f32(const float* x, const float* w_packed, float*
                                    hipStream_t stream) {
     if (!x || !w_packed || !y) return FGN_ERR_ARG;
     if (n_img <= 0) return FGN_OK;
-    const bool cin4 = (Cin == 4);
-    if (!cin4 && (Cin % BK) != 0) return FGN_ERR_SHAPE;
-    if (cin4 && in_scale) return FGN_ERR_SHAPE;
-    if (a_img_div < 1 || stride < 1 || cout_pad % 128 != 0 || cout_pad < Cout) return FGN_ERR_SHAPE;
+    const ConvPlan pl = plan_conv(n_img, H, W, Cin, Cout, cout_pad, KH, KW, stride, pad, a_img_div, in_scale != nullptr,
+                                  residual != nullptr, tile_hint, splitk_ws ? splitk_ws_bytes : 0);
+    if (pl.rc != FGN_OK) return pl.rc;
     ConvParams p;
     p.x = x; p.w = w_packed; p.y = y; p.scale = scale; p.shift = shift; p.residual = residual;
     p.in_scale = in_scale; p.n_img_dev = n_img_dev;
     p.n_img = n_img; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW;
     p.stride = stride; p.pad = pad; p.a_img_div = a_img_div; p.relu = relu;
-    p.Ho = (H + 2 * pad - KH) / stride + 1;
-    p.Wo = (W + 2 * pad - KW) / stride + 1;
-    if (p.Ho <= 0 || p.Wo <= 0) return FGN_ERR_SHAPE;
-    if (KH * KW > 64) return FGN_ERR_SHAPE;                   // tap validity is a 64-bit mask
-    const int k_raw = KH * KW * Cin;
-    p.K = cdiv(k_raw, BK) * BK;
-    if (cin4) {                                   // stem layout: one K-tile per filter row, [KH][8 pixels][4]
-        if (KW > 8 || in_scale) return FGN_ERR_SHAPE;
-        p.K = KH * BK;
-    }
-    // offsets are 32-bit element indices
-    if ((long long)(n_img / a_img_div + 1) * H * W * Cin >= (1ll << 31)) return FGN_ERR_SHAPE;
-    const long long M = (long long)n_img * p.Ho * p.Wo;
-    if (M * (long long)Cout >= (1ll << 31) * 4) return FGN_ERR_SHAPE;
-
-    int tile;
-    p.kt_per_split = p.K / BK;
-    {
-        // descriptor extents (< 4 GiB checked below); tile_hint >= 100 forces the register-staged kernel
-        const long long xb = (long long)((n_img + a_img_div - 1) / a_img_div) * H * W * Cin * 4;
-        const long long wb = (long long)cout_pad * p.K * 4;
-        const bool use_dma = (tile_hint < 100 || cin4) && xb < 0x7fffff00ll && wb < 0x7fffff00ll;
-        p.x_bytes = use_dma ? (unsigned)xb : 0u;
-        p.w_bytes = use_dma ? (unsigned)wb : 0u;
-        if (tile_hint >= 100) tile_hint -= 100;
-    }
-    tile = pick_tile(M, Cout, residual != nullptr, tile_hint);
-    if (tile == 4 && splitk_ws) {
-        const int KT = p.K / BK;
-        const int sp = plan_splits(M, Cout, KT, tile_hint, KH == 1 && KW == 1 && stride == 1 && pad == 0 && a_img_div == 1 && !in_scale);
-        if (sp > 1 && splitk_ws_bytes >= (size_t)sp * M * Cout * sizeof(float)) {
-            p.ws = splitk_ws;
-            p.kt_per_split = cdiv(KT, sp);
-            p.splits = cdiv(KT, p.kt_per_split);
-        }
-    }
+    p.Ho = pl.Ho; p.Wo = pl.Wo; p.K = pl.K; p.x_bytes = pl.x_bytes; p.w_bytes = pl.w_bytes;
+    p.splits = pl.splits; p.kt_per_split = pl.kt_per_split;
+    if (pl.splits > 1) p.ws = splitk_ws;
 #ifdef FGN_EXPERIMENTS
-    if (p.splits == 1 && !in_scale && p.x_bytes != 0 && !cin4 && KH == 1 && KW == 1 && stride == 1 && pad == 0 &&
-        a_img_div == 1 && (Cout & 3) == 0 && tile_hint == 0) {
+    if ((pl.mode == 1 || pl.mode == 4) && pl.splits == 1 && (Cout & 3) == 0 && tile_hint == 0) {
         int rc = FGN_OK;
-        if (fgn_exp_pointwise(p, M, tile, false, 0, stream, &rc)) return rc;
+        if (fgn_exp_pointwise(p, pl.M, pl.tile, false, 0, stream, &rc)) return rc;
     }
 #endif
-    switch (tile) {
-        case 1: return launch_cfg<128, 128, 64, 64, 2>(p, (int)M, cin4, stream);
-        case 2: return launch_cfg<64, 128, 32, 64, 3>(p, (int)M, cin4, stream);
-        case 3: return launch_cfg<128, 64, 64, 32, 3>(p, (int)M, cin4, stream);
-        case 4: return launch_cfg<64, 64, 32, 32, 4>(p, (int)M, cin4, stream);
-        default: return FGN_ERR_ARG;
+    switch (pl.tile) {
+        case 1: return launch_cfg<128, 128, 64, 64, 2>(p, (int)pl.M, pl.mode, stream);
+        case 2: return launch_cfg<64, 128, 32, 64, 3>(p, (int)pl.M, pl.mode, stream);
+        case 3: return launch_cfg<128, 64, 64, 32, 3>(p, (int)pl.M, pl.mode, stream);
+        default: return launch_cfg<64, 64, 32, 32, 4>(p, (int)pl.M, pl.mode, stream);
     }
 }
 
@@ -1368,51 +1391,31 @@ extern "C" int fgn_conv2d_pair_nhwc_f32(const float* x0, float* y0, int n_img0, 
                                         const float* shift, int Cin, int Cout, int cout_pad, int KH, int KW, int stride,
                                         int pad, int relu, hipStream_t stream) {
     if (!x0 || !y0 || !x1 || !y1 || !w_packed) return FGN_ERR_ARG;
-    if (n_img0 <= 0 || n_img1 <= 0) return FGN_ERR_SHAPE;
-    const bool cin4 = (Cin == 4);
-    if (!cin4 && (Cin % BK) != 0) return FGN_ERR_SHAPE;
-    if (stride < 1 || cout_pad % 128 != 0 || cout_pad < Cout || (Cout & 3) != 0 || KH * KW > 64 || (cin4 && KW > 8))
-        return FGN_ERR_SHAPE;
+    if ((Cout & 3) != 0) return FGN_ERR_SHAPE;
     ConvParams ps[2];
     int tiles[2];
     const float* xs[2] = {x0, x1};
     float* ys[2] = {y0, y1};
     const int ns[2] = {n_img0, n_img1}, Hs[2] = {H0, H1}, Ws[2] = {W0, W1};
     for (int i = 0; i < 2; ++i) {
+        const ConvPlan g = conv_geometry(ns[i], Hs[i], Ws[i], Cin, Cout, cout_pad, KH, KW, stride, pad, 1);
+        if (g.rc != FGN_OK || g.x_bytes == 0) return FGN_ERR_SHAPE;      // LDS-DMA kernel only: operands within 2 GiB
         ConvParams& p = ps[i];
         p.x = xs[i]; p.w = w_packed; p.y = ys[i]; p.scale = scale; p.shift = shift;
         p.n_img = ns[i]; p.H = Hs[i]; p.W = Ws[i]; p.Cin = Cin; p.Cout = Cout; p.KH = KH; p.KW = KW;
         p.stride = stride; p.pad = pad; p.relu = relu;
-        p.Ho = (p.H + 2 * pad - KH) / stride + 1;
-        p.Wo = (p.W + 2 * pad - KW) / stride + 1;
-        if (p.Ho <= 0 || p.Wo <= 0) return FGN_ERR_SHAPE;
-        p.K = cin4 ? KH * BK : cdiv(KH * KW * Cin, BK) * BK;
-        if ((long long)(p.n_img + 1) * p.H * p.W * Cin >= (1ll << 31)) return FGN_ERR_SHAPE;
-        const long long M = (long long)p.n_img * p.Ho * p.Wo;
-        if (M * (long long)Cout >= (1ll << 31) * 4) return FGN_ERR_SHAPE;
-        const long long xb = (long long)p.n_img * p.H * p.W * Cin * 4, wb = (long long)cout_pad * p.K * 4;
-        if (xb >= 0x7fffff00ll || wb >= 0x7fffff00ll) return FGN_ERR_SHAPE;
-        p.x_bytes = (unsigned)xb; p.w_bytes = (unsigned)wb;
+        p.Ho = g.Ho; p.Wo = g.Wo; p.K = g.K; p.x_bytes = g.x_bytes; p.w_bytes = g.w_bytes;
         p.kt_per_split = p.K / BK;
         p.n_tiles_n = cdiv(Cout, 64);
-        const int m_tiles = cdiv((int)M, 64);
+        const int m_tiles = cdiv((int)g.M, 64);
         set_band(p, 64, m_tiles, 64ll * p.K * 4);
         tiles[i] = (m_tiles * p.n_tiles_n + 7) / 8 * 8;       // workgroups past the last tile leave at once
     }
     constexpr int NST = CONV_DMA_STAGES;
     const size_t dlds = std::max((size_t)NST * (64 + 64) * BK, (size_t)64 * (64 + 4)) * sizeof(float);
-    static unsigned long long lds_ok[2] = {0ull, 0ull};
-    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 0>), &lds_ok[0]);
-    if (attr == hipSuccess)
-        attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 2>), &lds_ok[1]);
-    if (attr != hipSuccess) return (int)attr;
-    const dim3 grid(tiles[0] + tiles[1]);
-    if (cin4)
-        FGN_LAUNCH_TIMED((conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 2>), grid, dim3(256), dlds, stream, ps[0], ps[1], tiles[0]);
-    else
-        FGN_LAUNCH_TIMED((conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 0>), grid, dim3(256), dlds, stream, ps[0], ps[1], tiles[0]);
-    FGN_LAUNCH_CHECK();
-    return FGN_OK;
+    const dim3 grid(tiles[0] + tiles[1]), wg(256);
+    return Cin != 4 ? launch_kernel<conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 0>>(grid, wg, dlds, stream, ps[0], ps[1], tiles[0])
+                    : launch_kernel<conv_igemm_dma_pair_kernel<64, 64, 32, 32, NST, 4, 2>>(grid, wg, dlds, stream, ps[0], ps[1], tiles[0]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1709,16 +1712,7 @@ extern "C" int fgn_conv1x1_dual_nhwc_f32(const float* x, const float* x2, const 
     p.n_tiles_n = cdiv(Cout, 64);
     const int m_tiles = cdiv(rows, 64);
     set_band(p, 64, m_tiles, 64ll * p.K * 4);
-    const int tiles = m_tiles * p.n_tiles_n;
-    static unsigned long long pk_ok = 0ull;
-    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_persist_kernel), &pk_ok);
-    if (attr != hipSuccess) return (int)attr;
-    const size_t plds = (size_t)2 * (64 + 64) * BK * sizeof(float);
-    const int grid = std::min(persist_blocks(), (tiles + 7) / 8 * 8);
-    p.stamp = fgn_next_stamp_record();
-    FGN_LAUNCH_TIMED(conv_pw_persist_kernel, dim3(grid), dim3(256), plds, stream, p, tiles);
-    FGN_LAUNCH_CHECK();
-    return FGN_OK;
+    return launch_persist(p, m_tiles * p.n_tiles_n, stream);
 }
 
 extern "C" int fgn_conv1x1_dual_x3_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
@@ -1823,7 +1817,7 @@ extern "C" int fgn_winograd_gemm_f32(const float* V, const float* U, float* Mo, 
         if (fgn_exp_pointwise(p, p.n_img, 4, true, t_pad, stream, &rc2)) return rc2;
     }
 #endif
-    return launch_cfg<64, 64, 32, 32, 4>(p, p.n_img, false, stream);
+    return launch_cfg<64, 64, 32, 32, 4>(p, p.n_img, pointwise_mode(4, p.n_img, Cout, 1), stream);
 }
 
 extern "C" int fgn_winograd_gemm_x3_f32(const float* V, const void* U_x3, float* Mo, const int32_t* n_img_dev, int n_img,

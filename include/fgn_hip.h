@@ -74,7 +74,10 @@ int fgn_phase_wait(const int32_t* counter, int32_t target, int timeout_us, void*
 size_t fgn_conv2d_workspace_bytes(int n_img, int H, int W, int Cin, int Cout, int KH, int KW, int stride,
                                   int pad, int tile_hint);
 /* Which kernel the dispatcher launches for a layer (tile*10 + mode; 41 = conv_igemm_dma_kernel<64,64,32,32,2,4,1>):
- * lets a profiler attribute a launch to the kernel name rocprofv3 reports.  No reference counterpart. */
+ * lets a profiler attribute a launch to the kernel name rocprofv3 reports.  It is the decision of the launch itself (one
+ * plan serves both, given the workspace fgn_conv2d_workspace_bytes asks for): arguments fgn_conv2d_nhwc_f32 refuses on
+ * shape or hint return that refusal's code (FGN_ERR_SHAPE / FGN_ERR_ARG, negative), not an id.  fgn_conv2d_workspace_bytes
+ * is 0 for them.  No reference counterpart. */
 int fgn_conv2d_kernel_id(int n_img, int H, int W, int Cin, int Cout, int cout_pad, int KH, int KW, int stride,
                          int pad, int a_img_div, int has_in_scale, int has_residual, int tile_hint);
 int fgn_conv2d_nhwc_f32(const float* x, const float* w_packed, float* y, const float* scale,

@@ -594,3 +594,97 @@ def test_winograd_h2_is_as_close_to_fp64_as_x3():
     ops.conv3x3_winograd_multi([x, x1], lh, [o0, o1])
     assert (o0 - ops.conv3x3_winograd(x, lh)).abs().max().item() <= 1e-5 * o0.abs().max().item()
     assert (o1 - ops.conv3x3_winograd(x1, lh)).abs().max().item() <= 1e-5 * o1.abs().max().item()
+
+
+def _stamped(fn):
+    """``fn()`` with launch records armed -> (its result, the records handed out, the record buffer).
+    conv_pw_persist_kernel is the only f32 kernel that takes a record."""
+    from fgn_amd import ops
+    records = ops.new_stamp_records(4, 'cuda')
+    ops.arm_stamps(records)
+    try:
+        out = fn()
+    finally:
+        used = ops.arm_stamps(None)
+    torch.cuda.synchronize()
+    return out, used, records
+
+
+_ID_CASES = [
+    # ops.conv2d, 1x1 on [1, rows, 1, Cin]: rows, Cin, Cout, extra, id
+    ('conv', 4096, 64, 1024, None, 41), ('conv', 4097, 64, 1024, None, 44), ('conv', 4097, 64, 1024, 'residual', 44),
+    ('conv', 8194, 64, 1022, None, 41), ('conv', 4097, 64, 1024, 'in_scale', 43), ('conv', 4097, 64, 1024, 'a_img_div', 40),
+    # ops.conv1x1_dual: rows, Cin1 (= Cin2), Cout; a grid below persist_blocks() and one capped at it
+    ('dual', 128, 64, 128, None, None), ('dual', 4097, 64, 1024, None, None),
+    # ops.conv3x3_winograd, F(2x2) on [1, 32, 32, 32]: 16 groups of t_pad 256 rows -> 1024 / 1088 tiles of 64x64
+    ('wino', 256, 32, 1024, None, 41), ('wino', 256, 32, 1088, None, 44),
+]
+
+
+@pytest.mark.parametrize('kind,rows,cin,cout,extra,kid', _ID_CASES)
+def test_the_kernel_id_names_the_kernel_that_runs(kind, rows, cin, cout, extra, kid):
+    """fgn_conv2d_kernel_id against what the launch does: a launch takes a launch record exactly when its id says
+    conv_pw_persist_kernel (mode 4), and that record counts one execution - on both sides of the 1024-tile threshold, with
+    what keeps a point-wise launch off the persistent kernel (Cout % 4, a fused input scale, a shared input image), for
+    the fused conv3 + shortcut (always persistent) and the Winograd GEMM (the id ops._winograd_records asks for).  Every
+    output against fp64: the bound of this file for the 1x1 launches, that of tests/test_hip_winograd.py for F(2x2)."""
+    from fgn_amd import lib, ops
+    L = lib.load()
+    g = torch.Generator().manual_seed(rows + cout)
+    if kind == 'wino':
+        x = torch.randn(1, 32, 32, cin, generator=g)
+        wt = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
+        b = torch.randn(cout, generator=g) * 0.1
+        with ops.gemm_math('f32'):
+            layer = ops.pack_winograd(wt, bias=b, relu=True, m=2).to('cuda')
+        assert layer.groups == 16 and layer.u3 is None and layer.uh is None and L.fgn_winograd_t_pad(rows) == rows
+        got_id = L.fgn_conv2d_kernel_id(16 * rows, 1, 1, cin, cout, layer.cout_pad, 1, 1, 1, 0, 1, 0, 0, 4)
+        y, used, records = _stamped(lambda: ops.conv3x3_winograd(x.cuda(), layer))
+        ref = F.relu(F.conv2d(x.permute(0, 3, 1, 2).double(), wt.double(), b.double(), padding=1)).permute(0, 2, 3, 1)
+        bound = 5e-6 * max(ref.abs().max().item(), 1.0)
+    elif kind == 'dual':
+        x1, x2 = torch.randn(rows, cin, generator=g), torch.randn(rows, cin, generator=g)
+        w1, w2 = torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5, torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5
+        mk = lambda: dict(weight=torch.rand(cout, generator=g) + 0.5, bias=torch.randn(cout, generator=g) * 0.1,
+                          running_mean=torch.randn(cout, generator=g) * 0.1, running_var=torch.rand(cout, generator=g) + 0.5)
+        bn1, bn2 = mk(), mk()
+
+        def affine(v, bn):
+            sc = bn['weight'].double() / torch.sqrt(bn['running_var'].double() + 1e-5)
+            return v * sc + (bn['bias'].double() - bn['running_mean'].double() * sc)
+        ref = torch.relu(affine(x1.double() @ w1.reshape(cout, cin).double().T, bn1) +
+                         affine(x2.double() @ w2.reshape(cout, cin).double().T, bn2))
+        with ops.gemm_math('f32'):
+            layer = ops.pack_conv_dual(w1, bn1, w2, bn2, relu=True).to('cuda')
+        assert layer.w3 is None and layer.wh is None
+        got_id = 44                                                   # the dual entry has one kernel
+        y, used, records = _stamped(lambda: ops.conv1x1_dual(x1.cuda().view(1, rows, 1, cin), x2.cuda().view(1, rows, 1, cin), layer))
+        y = y.view(rows, cout)
+        bound = 2e-5 * ref.abs().max().item()
+    else:
+        x = torch.randn(rows, cin, generator=g)
+        wt = torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5
+        b = torch.randn(cout, generator=g)
+        res = torch.randn(rows, cout, generator=g) if extra == 'residual' else None
+        scale = (torch.rand(1, cin, generator=g) + 0.5) if extra == 'in_scale' else None
+        div = 2 if extra == 'a_img_div' else 1
+        with ops.gemm_math('f32'):
+            layer = ops.pack_conv(wt, bias=b).to('cuda')
+        assert layer.w3 is None and layer.wh is None
+        got_id = L.fgn_conv2d_kernel_id(div, rows, 1, cin, cout, layer.cout_pad, 1, 1, 1, 0, div, int(scale is not None),
+                                        int(res is not None), 0)
+        y, used, records = _stamped(lambda: ops.conv2d(
+            x.cuda().view(1, rows, 1, cin), layer, residual=None if res is None else res.cuda().view(1, rows, 1, cout),
+            in_scale=None if scale is None else scale.cuda(), a_img_div=div))
+        ref = (x.double() * (1.0 if scale is None else scale.double())) @ wt.reshape(cout, cin).double().T + b.double()
+        if res is not None:
+            ref = ref + res.double()
+        assert tuple(y.shape) == (div, rows, 1, cout)
+        y, ref = y.view(div, rows, cout), ref.expand(div, rows, cout)
+        bound = 2e-5 * ref.abs().max().item()
+    if kid is not None:
+        assert got_id == kid
+    assert used == (1 if got_id % 10 == 4 else 0)
+    if used:
+        assert ops.read_stamps(records, 1)[0]['executions'] == 1
+    assert (y.cpu().double() - ref).abs().max().item() <= bound

@@ -966,18 +966,18 @@ static int fgn_exp_launch_streamk(const ConvParams& p, int total_tiles, hipStrea
     return FGN_OK;
 }
 
-// kernel id of a point-wise launch that takes one of the experimental kernels (0: none): conv_pw_persist2_kernel =
-// tile code * 10 + 5 (the grouped Winograd GEMM asks with tile_hint 4), Stream-K = tile * 10 + 6
-static int fgn_exp_kernel_id(int mode, int tile, long long M, int Cout, int K, int tile_hint, int has_residual) {
-    if (mode == 1 && (Cout & 3) == 0 && (tile_hint == 0 || tile_hint == 4) &&
-        (tile_hint == 4 || plan_splits(M, Cout, K / BK, tile_hint, true) == 1)) {
+// kernel id of a point-wise launch (plan mode 1 / 4) that takes one of the experimental kernels (0: none):
+// conv_pw_persist2_kernel = tile code * 10 + 5 (the grouped Winograd GEMM asks with tile_hint 4), Stream-K = tile * 10 + 6
+static int fgn_exp_kernel_id(const ConvPlan& pl, int Cout, int tile_hint, int has_residual) {
+    const bool pw = pl.mode == 1 || pl.mode == 4;
+    if (pw && (Cout & 3) == 0 && (tile_hint == 4 || (tile_hint == 0 && pl.splits == 1))) {
         // (asked per group: M / 36 rows; F(2x2) launches have 16 groups and never reach the row threshold)
-        const int code = pick_persist2(M, Cout, K, tile_hint == 4, tile_hint == 4 ? (int)(M / 36) : 0, has_residual != 0);
+        const int code = pick_persist2(pl.M, Cout, pl.K, tile_hint == 4, tile_hint == 4 ? (int)(pl.M / 36) : 0, has_residual != 0);
         if (code) return (code % 10) * 10 + 5;
     }
-    if (mode == 1 && tile == 4 && (Cout & 3) == 0 && tile_hint == 0 && plan_splits(M, Cout, K / BK, tile_hint, true) == 1) {
+    if (pw && pl.tile == 4 && (Cout & 3) == 0 && tile_hint == 0 && pl.splits == 1) {
         int dp = 0, U = 0;
-        if (plan_streamk(((M + 63) / 64) * cdiv(Cout, 64), K / BK, &dp, &U)) return tile * 10 + 6;
+        if (plan_streamk(((pl.M + 63) / 64) * cdiv(Cout, 64), pl.K / BK, &dp, &U)) return pl.tile * 10 + 6;
     }
     return 0;
 }
