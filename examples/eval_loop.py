@@ -7,6 +7,7 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
     python examples/eval_loop.py --dataset OMNIISEG --episodes 16 --n-ways 3 --k-shots 1     (cfg2-shaped)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --uint8      (decoded pixels in, normalised on the GPU)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --source-size 200     (200^2 sources, resized to 128^2 on the GPU)
+    python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --source-size 200 --results-at-source     (... results in the 200^2 frame)
     python examples/eval_loop.py --episodes 8 --match-on-device     (mask overlaps counted on the GPU: the evaluator decodes no RLE)
 """
 import argparse
@@ -39,11 +40,16 @@ def main():
     ap.add_argument('--source-size', type=int, default=None, metavar='S',
                     help='character datasets: queries are generated at S x S and stay at that size in the loader; the '
                          'detector resizes image and masks to the network size on the GPU (qry_resize_to; implies --uint8)')
+    ap.add_argument('--results-at-source', action='store_true',
+                    help='with --source-size: boxes, masks, ground truth and overlap counts of the results are in the frame '
+                         'of the S x S source image (results_at_source), no ground-truth mask is resized')
     ap.add_argument('--match-on-device', action='store_true',
                     help='count the overlaps of detections and ground truth on the GPU (FGN.match_on_device): the results '
                          'carry dt_gt_inter / dt_area / gt_area and the evaluator decodes no RLE')
     args = ap.parse_args()
     args.uint8 = args.uint8 or args.source_size is not None
+    if args.results_at_source and args.source_size is None:
+        ap.error('--results-at-source needs --source-size')
     if args.uint8 and args.dataset == 'SYNTH':
         ap.error('--uint8 / --source-size need --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
 
@@ -64,7 +70,7 @@ def main():
 
     def results():
         for data in loader:
-            yield model.simple_test(**data, rescale=True)
+            yield model.simple_test(**data, rescale=True, results_at_source=args.results_at_source)
 
     with tempfile.TemporaryDirectory() as work_dir:
         out = os.path.join(work_dir, 'ResultsChunked')

@@ -267,23 +267,44 @@ __device__ inline void emit_coco_string(const uint32_t* __restrict__ tr, int T, 
     if (t == 0) { *out_len = total_chars; *overflow = 0; }
 }
 
-__global__ __launch_bounds__(RLE_THREADS) void mask_rle_kernel(
-    const float* __restrict__ prob, const float* __restrict__ boxes, int box_stride, uint32_t* __restrict__ trans,
-    uint8_t* __restrict__ out_bytes, int32_t* __restrict__ out_len, int32_t* __restrict__ overflow,
-    const int32_t* __restrict__ n_dev, int n_det, int H, int W, int MS, float thr, int trans_cap, int byte_cap,
-    int skip_empty) {
-    __shared__ float m[32 * 32];
-    __shared__ int wave_sums[RLE_THREADS / 64];
-    const int d = blockIdx.x, t = threadIdx.x;
-    int D = n_det;
-    if (n_dev) D = min(D, *n_dev);
-    if (d >= D) {
-        if (t == 0) { out_len[d] = 0; overflow[d] = 0; }
-        return;
-    }
-    for (int i = t; i < MS * MS; i += RLE_THREADS) m[i] = prob[(size_t)d * MS * MS + i];
+// Geometry of a source-size image under a network of (H, W) (results at source size): its size and the
+// scale factors of mmdet's Resize, s_x = float32(W / w), s_y = float32(H / h) - the double quotient rounded once, which
+// is numpy's np.float32(W / w) bit for bit.  At equal size both are exactly 1.  ok = the size is within 1..16384 (the
+// contract of the resize kernel of spatial.hip); nothing is computed otherwise.
+constexpr int SRC_MAX_DIM = 16384;
+struct SrcGeom {
+    int h, w;
+    float sx, sy;
+    bool ok;
+};
+__device__ __forceinline__ SrcGeom src_geom(int h, int w, int H, int W) {
+    SrcGeom g;
+    g.h = h; g.w = w;
+    g.ok = h >= 1 && h <= SRC_MAX_DIM && w >= 1 && w <= SRC_MAX_DIM;
+    g.sx = g.ok ? (float)((double)W / (double)w) : 1.f;
+    g.sy = g.ok ? (float)((double)H / (double)h) : 1.f;
+    return g;
+}
+// A network-frame box (x0, y0, x1, y1) in the source frame: each coordinate divided by its axis' scale, one correctly
+// rounded f32 division (the translation unit is built without fast-math; mmdet: bboxes / scale_factor).  No clipping.
+__device__ __forceinline__ void box_to_source(const float* __restrict__ b, const SrcGeom& g, float* __restrict__ o) {
+    o[0] = __fdiv_rn(b[0], g.sx);
+    o[1] = __fdiv_rn(b[1], g.sy);
+    o[2] = __fdiv_rn(b[2], g.sx);
+    o[3] = __fdiv_rn(b[3], g.sy);
+}
+
+// One detection, whole workgroup (RLE_THREADS): mask probabilities pm [MS][MS] pasted from box (x0, y0, x1, y1) into an
+// H x W image, thresholded and run-length encoded (steps 1-3 above).  m: MS*MS floats of LDS, wave_sums: RLE_THREADS/64
+// ints of LDS; tr / ob / out_len / overflow are the detection's own.  Every argument is workgroup-uniform.
+__device__ __forceinline__ void rle_detection(const float* __restrict__ pm, const float* box,
+                                              uint32_t* __restrict__ tr, uint8_t* __restrict__ ob, int32_t* out_len,
+                                              int32_t* overflow, int H, int W, int MS, float thr, int trans_cap,
+                                              int byte_cap, int skip_empty, float* m, int* wave_sums) {
+    const int t = threadIdx.x;
+    for (int i = t; i < MS * MS; i += RLE_THREADS) m[i] = pm[i];
     __syncthreads();
-    const PasteBox pb = make_paste_box(boxes + (size_t)d * box_stride, H, W, MS, skip_empty, thr);
+    const PasteBox pb = make_paste_box(box, H, W, MS, skip_empty, thr);
     // columns x0i .. min(x1i, W-1): one past the region closes a run that wraps a full-height column
     const int xs = pb.x0i, xe = min(pb.x1i, W - 1);
     const int ncols = max(xe - xs + 1, 0);
@@ -325,11 +346,10 @@ __global__ __launch_bounds__(RLE_THREADS) void mask_rle_kernel(
     int T;
     const int off = block_exclusive_scan(cnt, wave_sums, &T);
     if (T > trans_cap) {
-        if (t == 0) { overflow[d] = 1; out_len[d] = 0; }
+        if (t == 0) { *overflow = 1; *out_len = 0; }
         return;
     }
     // ---- 2. write positions in order ----------------------------------------------------------
-    uint32_t* tr = trans + (size_t)d * trans_cap;
     {
         int o = off;
         for (int j = 0; j < cpt; ++j) {
@@ -338,8 +358,60 @@ __global__ __launch_bounds__(RLE_THREADS) void mask_rle_kernel(
         }
     }
     __syncthreads();
-    emit_coco_string(tr, T, (long long)H * W, out_bytes + (size_t)d * byte_cap, byte_cap, out_len + d, overflow + d,
-                     wave_sums);
+    emit_coco_string(tr, T, (long long)H * W, ob, byte_cap, out_len, overflow, wave_sums);
+}
+
+__global__ __launch_bounds__(RLE_THREADS) void mask_rle_kernel(
+    const float* __restrict__ prob, const float* __restrict__ boxes, int box_stride, uint32_t* __restrict__ trans,
+    uint8_t* __restrict__ out_bytes, int32_t* __restrict__ out_len, int32_t* __restrict__ overflow,
+    const int32_t* __restrict__ n_dev, int n_det, int H, int W, int MS, float thr, int trans_cap, int byte_cap,
+    int skip_empty) {
+    __shared__ float m[32 * 32];
+    __shared__ int wave_sums[RLE_THREADS / 64];
+    const int d = blockIdx.x, t = threadIdx.x;
+    int D = n_det;
+    if (n_dev) D = min(D, *n_dev);
+    if (d >= D) {
+        if (t == 0) { out_len[d] = 0; overflow[d] = 0; }
+        return;
+    }
+    // (the network frame is the image: the box as it stands, no division)
+    rle_detection(prob + (size_t)d * MS * MS, boxes + (size_t)d * box_stride, trans + (size_t)d * trans_cap,
+                  out_bytes + (size_t)d * byte_cap, out_len + d, overflow + d, H, W, MS, thr, trans_cap, byte_cap,
+                  skip_empty, m, wave_sums);
+}
+
+// The same for a batch at SOURCE size, one launch: grid (detection, image); row r = b * n_det + d of every array.
+// Image b's size comes from the DEVICE array src_hw[b] = {h_b, w_b} and its detection count from n_dev[b] (null: n_det):
+// no launch argument and no grid dimension depends on a source size, so one captured launch serves every source size.
+// The box is divided by the image's scale (box_to_source) and pasted into h_b x w_b.  An image whose size is outside
+// 1..16384 yields out_len = 0, overflow = 0 and zero boxes_src rows, and nothing of it is read.  boxes_src (optional)
+// [B * n_det][4]: the scaled box of every row, written by one lane.  b, d and everything read at them are
+// workgroup-uniform.
+__global__ __launch_bounds__(RLE_THREADS) void mask_rle_src_kernel(
+    const float* __restrict__ prob, const float* __restrict__ boxes, int box_stride, const int32_t* __restrict__ src_hw,
+    uint32_t* __restrict__ trans, uint8_t* __restrict__ out_bytes, int32_t* __restrict__ out_len,
+    int32_t* __restrict__ overflow, float* __restrict__ boxes_src, const int32_t* __restrict__ n_dev, int n_det, int H,
+    int W, int MS, float thr, int trans_cap, int byte_cap, int skip_empty) {
+    __shared__ float m[32 * 32];
+    __shared__ int wave_sums[RLE_THREADS / 64];
+    const int d = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+    const size_t r = (size_t)b * n_det + d;
+    const SrcGeom g = src_geom(src_hw[2 * b], src_hw[2 * b + 1], H, W);
+    int D = n_det;
+    if (n_dev) D = min(D, n_dev[b]);
+    float box[4] = {0.f, 0.f, 0.f, 0.f};
+    if (g.ok) box_to_source(boxes + r * box_stride, g, box);
+    if (boxes_src && t == 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) boxes_src[r * 4 + k] = box[k];
+    }
+    if (!g.ok || d >= D) {
+        if (t == 0) { out_len[r] = 0; overflow[r] = 0; }
+        return;
+    }
+    rle_detection(prob + r * MS * MS, box, trans + r * trans_cap, out_bytes + r * byte_cap, out_len + r, overflow + r,
+                  g.h, g.w, MS, thr, trans_cap, byte_cap, skip_empty, m, wave_sums);
 }
 
 extern "C" int fgn_mask_rle(const float* prob, const float* boxes, int box_stride, uint32_t* trans_scratch,
@@ -353,6 +425,24 @@ extern "C" int fgn_mask_rle(const float* prob, const float* boxes, int box_strid
     hipLaunchKernelGGL(mask_rle_kernel, dim3(n_det), dim3(RLE_THREADS), 0, stream, prob, boxes, box_stride,
                        trans_scratch, out_bytes, out_len, overflow, n_dev, n_det, img_h, img_w, mask_size, thr,
                        trans_cap, byte_cap, skip_empty);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+extern "C" int fgn_mask_rle_src(const float* prob, const float* boxes, int box_stride, const int32_t* src_hw,
+                                uint32_t* trans_scratch, uint8_t* out_bytes, int32_t* out_len, int32_t* overflow,
+                                float* boxes_src, const int32_t* n_dev, int batch, int n_det, int net_h, int net_w,
+                                int mask_size, float thr, int trans_cap, int byte_cap, int skip_empty,
+                                hipStream_t stream) {
+    if (batch == 0 || n_det == 0) return FGN_OK;
+    if (!prob || !boxes || !src_hw || !trans_scratch || !out_bytes || !out_len || !overflow) return FGN_ERR_ARG;
+    if (batch < 0 || n_det < 0 || box_stride < 4) return FGN_ERR_ARG;
+    if (mask_size > 32 || mask_size < 1 || trans_cap < 1 || byte_cap < 8 || net_h < 1 || net_w < 1 ||
+        net_h > SRC_MAX_DIM || net_w > SRC_MAX_DIM || batch > 65535)
+        return FGN_ERR_SHAPE;
+    hipLaunchKernelGGL(mask_rle_src_kernel, dim3(n_det, batch), dim3(RLE_THREADS), 0, stream, prob, boxes, box_stride,
+                       src_hw, trans_scratch, out_bytes, out_len, overflow, boxes_src, n_dev, n_det, net_h, net_w,
+                       mask_size, thr, trans_cap, byte_cap, skip_empty);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }
@@ -639,22 +729,19 @@ extern "C" int fgn_mask_bits_u64(const uint8_t* masks, uint64_t* bits, int32_t* 
     return FGN_OK;
 }
 
-// grid: (detection, block of OVL_ROWS rows).  inter / det_area are zero on entry.
-__global__ __launch_bounds__(OVL_THREADS) void mask_overlap_kernel(
-    const float* __restrict__ prob, const float* __restrict__ boxes, int box_stride,
-    const unsigned long long* __restrict__ gt_bits, int32_t* __restrict__ inter, int32_t* __restrict__ det_area,
-    const int32_t* __restrict__ n_dev, int n_det, int G, int H, int W, int NW, int MS, float thr, int skip_empty) {
-    __shared__ float m[32 * 32];
-    __shared__ int red[OVL_WAVES][64];
-    __shared__ int red_area[OVL_WAVES];
-    const int d = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int D = n_det;
-    if (n_dev) D = min(D, *n_dev);
-    if (d >= D) return;
-    const PasteBox pb = make_paste_box(boxes + (size_t)d * box_stride, H, W, MS, skip_empty, thr);
+// One detection against the G ground-truth bit planes of an H x W image, rows of this workgroup's block (blockIdx.y):
+// pm [MS][MS] pasted from box (x0, y0, x1, y1); inter_d [G] / det_area_d are the detection's own, zero on entry.
+// m: MS*MS floats of LDS, red / red_area: the workgroup's reduction space.  Every argument is workgroup-uniform.
+__device__ __forceinline__ void overlap_detection(const float* __restrict__ pm, const float* box,
+                                                  const unsigned long long* __restrict__ gt_bits,
+                                                  int32_t* __restrict__ inter_d, int32_t* __restrict__ det_area_d, int G,
+                                                  int H, int W, int NW, int MS, float thr, int skip_empty, float* m,
+                                                  int (*red)[64], int* red_area) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const PasteBox pb = make_paste_box(box, H, W, MS, skip_empty, thr);
     const int y_lo = max(pb.y0i, (int)blockIdx.y * OVL_ROWS), y_hi = min(pb.y1i, ((int)blockIdx.y + 1) * OVL_ROWS);
     if (y_lo >= y_hi || pb.x0i >= pb.x1i) return;          // rows outside the pasted region (workgroup-uniform)
-    for (int i = t; i < MS * MS; i += OVL_THREADS) m[i] = prob[(size_t)d * MS * MS + i];
+    for (int i = t; i < MS * MS; i += OVL_THREADS) m[i] = pm[i];
     __syncthreads();
     const int w_lo = pb.x0i >> 6, w_hi = (pb.x1i - 1) >> 6;  // x-words of the region, inclusive; 0 <= x0i < x1i <= W
     for (int g0 = 0; g0 < G; g0 += 64) {                     // passes of 64 ground-truth masks (lane = mask)
@@ -681,11 +768,49 @@ __global__ __launch_bounds__(OVL_THREADS) void mask_overlap_kernel(
             int s = 0, a = 0;
 #pragma unroll
             for (int w = 0; w < OVL_WAVES; ++w) { s += red[w][lane]; a += red_area[w]; }
-            if (g < G && s) atomicAdd(inter + (size_t)d * G + g, s);
-            if (g0 == 0 && lane == 0 && a) atomicAdd(det_area + d, a);   // |d| once, not once per pass
+            if (g < G && s) atomicAdd(inter_d + g, s);
+            if (g0 == 0 && lane == 0 && a) atomicAdd(det_area_d, a);   // |d| once, not once per pass
         }
         __syncthreads();
     }
+}
+
+// grid: (detection, block of OVL_ROWS rows).  inter / det_area are zero on entry.
+__global__ __launch_bounds__(OVL_THREADS) void mask_overlap_kernel(
+    const float* __restrict__ prob, const float* __restrict__ boxes, int box_stride,
+    const unsigned long long* __restrict__ gt_bits, int32_t* __restrict__ inter, int32_t* __restrict__ det_area,
+    const int32_t* __restrict__ n_dev, int n_det, int G, int H, int W, int NW, int MS, float thr, int skip_empty) {
+    __shared__ float m[32 * 32];
+    __shared__ int red[OVL_WAVES][64];
+    __shared__ int red_area[OVL_WAVES];
+    const int d = blockIdx.x;
+    int D = n_det;
+    if (n_dev) D = min(D, *n_dev);
+    if (d >= D) return;
+    overlap_detection(prob + (size_t)d * MS * MS, boxes + (size_t)d * box_stride, gt_bits, inter + (size_t)d * G,
+                      det_area + d, G, H, W, NW, MS, thr, skip_empty, m, red, red_area);
+}
+
+// The same at SOURCE size: the boxes are network-frame boxes of an (H, W) network, divided by the scale of the h x w
+// image (src_geom / box_to_source: the scale is formed where mask_rle_src_kernel forms it) and pasted into h x w, the
+// size of gt_bits.  The launch is eager (G differs per image), so h and w are launch arguments and size the grid.
+__global__ __launch_bounds__(OVL_THREADS) void mask_overlap_src_kernel(
+    const float* __restrict__ prob, const float* __restrict__ boxes, int box_stride,
+    const unsigned long long* __restrict__ gt_bits, int32_t* __restrict__ inter, int32_t* __restrict__ det_area,
+    const int32_t* __restrict__ n_dev, int n_det, int G, int h, int w, int H, int W, int NW, int MS, float thr,
+    int skip_empty) {
+    __shared__ float m[32 * 32];
+    __shared__ int red[OVL_WAVES][64];
+    __shared__ int red_area[OVL_WAVES];
+    const int d = blockIdx.x;
+    int D = n_det;
+    if (n_dev) D = min(D, *n_dev);
+    const SrcGeom g = src_geom(h, w, H, W);
+    if (d >= D || !g.ok) return;
+    float box[4];
+    box_to_source(boxes + (size_t)d * box_stride, g, box);
+    overlap_detection(prob + (size_t)d * MS * MS, box, gt_bits, inter + (size_t)d * G, det_area + d, G, g.h, g.w, NW, MS,
+                      thr, skip_empty, m, red, red_area);
 }
 
 extern "C" int fgn_mask_overlap_i32(const float* prob, const float* boxes, int box_stride, const uint64_t* gt_bits,
@@ -704,6 +829,27 @@ extern "C" int fgn_mask_overlap_i32(const float* prob, const float* boxes, int b
     hipLaunchKernelGGL(mask_overlap_kernel, dim3(n_det, cdiv(img_h, OVL_ROWS)), dim3(OVL_THREADS), 0, stream, prob, boxes,
                        box_stride, reinterpret_cast<const unsigned long long*>(gt_bits), inter, det_area, n_dev, n_det,
                        n_gt, img_h, img_w, cdiv(img_w, 64), mask_size, thr, skip_empty);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+extern "C" int fgn_mask_overlap_src_i32(const float* prob, const float* boxes, int box_stride, const uint64_t* gt_bits,
+                                        int32_t* inter, int32_t* det_area, const int32_t* n_dev, int n_det, int n_gt,
+                                        int src_h, int src_w, int net_h, int net_w, int mask_size, float thr,
+                                        int skip_empty, hipStream_t stream) {
+    if (n_det == 0 || n_gt == 0) return FGN_OK;
+    if (!prob || !boxes || !gt_bits || !inter || !det_area) return FGN_ERR_ARG;
+    if (n_det < 0 || n_gt < 0 || box_stride < 4) return FGN_ERR_ARG;
+    if (mask_size > 32 || mask_size < 1 || src_h < 1 || src_w < 1 || src_h > SRC_MAX_DIM || src_w > SRC_MAX_DIM ||
+        net_h < 1 || net_w < 1 || net_h > SRC_MAX_DIM || net_w > SRC_MAX_DIM)
+        return FGN_ERR_SHAPE;
+    const long long n_out = (long long)n_det * n_gt;
+    hipLaunchKernelGGL(zero_i32_kernel, dim3((unsigned)std::min<long long>((n_out + n_det + 255) / 256, 1024)), dim3(256),
+                       0, stream, inter, n_out, det_area, (long long)n_det);
+    FGN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(mask_overlap_src_kernel, dim3(n_det, cdiv(src_h, OVL_ROWS)), dim3(OVL_THREADS), 0, stream, prob,
+                       boxes, box_stride, reinterpret_cast<const unsigned long long*>(gt_bits), inter, det_area, n_dev,
+                       n_det, n_gt, src_h, src_w, net_h, net_w, cdiv(src_w, 64), mask_size, thr, skip_empty);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }

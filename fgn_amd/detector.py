@@ -363,7 +363,8 @@ class _GraphedEpisode:
     ``pack_results`` may read."""
     CODE_KEYS = ('vec', 'S', 'cat_mean_mp')
 
-    def __init__(self, model, ins: dict, img_shape, support_code, dev, phase_counter=None, source=None):
+    def __init__(self, model, ins: dict, img_shape, support_code, dev, phase_counter=None, source=None,
+                 results_at_source: bool = False):
         self.static = {k: torch.empty(v.shape, dtype=v.dtype, device=dev) for k, v in ins.items()}
         resize_to = None
         if source is not None:      # source-size queries: the slot has the configured size, whatever this batch needs
@@ -385,7 +386,7 @@ class _GraphedEpisode:
         # eager pass first: packs the weights, sets kernel attributes, sizes the allocator pools
         # (the eager run that precedes the capture sends no phase mark: every ``detect_device`` call bumps the caller's
         # counter exactly once - here through the replay that follows the capture)
-        model._detect_eager(*args(), phase_counter=None)
+        model._detect_eager(*args(), phase_counter=None, results_at_source=results_at_source)
         torch.cuda.current_stream().synchronize()
         self.graph = torch.cuda.CUDAGraph()
         # launch records of the dominant kernel (``FGN.stamp_capacity``; bench.py's roofline over the whole timed window):
@@ -400,7 +401,8 @@ class _GraphedEpisode:
         # invalidate it.  (The global mode passed the same test on this torch build; FGN_GRAPH_CAPTURE_MODE selects.)
         try:
             with torch.cuda.graph(self.graph, capture_error_mode=os.environ.get('FGN_GRAPH_CAPTURE_MODE', 'thread_local')):
-                self.outs = model._detect_eager(*args(), phase_counter=phase_counter)
+                self.outs = model._detect_eager(*args(), phase_counter=phase_counter,
+                                                results_at_source=results_at_source)
         finally:
             if self.stamps is not None:
                 self.stamp_count = ops.arm_stamps(None)
@@ -1049,13 +1051,20 @@ class FGN(torch.nn.Module):
     def simple_test(self, qry_img, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None, qry_bboxes_ignore=None,
                     spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, qry_child_idx=None, img_shape=None,
                     rescale=False, cats_ids_to_sample_real=None, spp_insts_ids=None, idx=None,
-                    support_code=None, qry_resize_to=None, **kwargs) -> List[Dict]:
+                    support_code=None, qry_resize_to=None, results_at_source: bool = False, **kwargs) -> List[Dict]:
         """Test without augmentation (fgn.py:187-303).  ``support_code`` (optional, from
         ``encode_supports``) replaces the three ``spp_*`` inputs.  ``qry_resize_to`` = (H, W) (or a [B,2] tensor of
         equal rows): ``qry_img`` holds decoded images at their SOURCE size - a uint8 tensor [B,h,w,3] or a list of B
         uint8 tensors [h_i,w_i,3] - and ``qry_isegmaps`` / ``qry_bboxes`` are at source size too; image and masks are
         resized to the network size on the device (``fewshot_ds.resize_query`` bit for bit, base_fst.py:876-887), the
-        boxes on the host; needs ``set_input_norm``."""
+        boxes on the host; needs ``set_input_norm``.  ``results_at_source`` (needs ``qry_resize_to``; ``rescale`` stays
+        accepted and ignored): every quantity of a result dict is in the frame of its SOURCE image -
+        ``dt_bboxes`` divided by the image's scale (``fewshot_ds.boxes_to_source``), ``dt_isegmaps_rle`` pasted at
+        ``[h_b, w_b]`` from those boxes, the ground truth encoded and counted as given (no mask resize), ``qry_bboxes``
+        as given, ``qry_img_shape`` = ``[h_b, w_b, 3]``; the detections, their scores and their order are those of the
+        call without it."""
+        if results_at_source and qry_resize_to is None:
+            raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
         if qry_resize_to is None:
             dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
                                       qry_isegmaps=qry_isegmaps)
@@ -1063,13 +1072,15 @@ class FGN(torch.nn.Module):
         else:
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps, self._graphed())
             dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
-                                      qry_isegmaps=qry_isegmaps, qry_resize_to=rs)
+                                      qry_isegmaps=qry_isegmaps, qry_resize_to=rs, results_at_source=results_at_source)
             batch, img_shape = rs['B'], rs['img_shape']
-            qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
+            if not results_at_source:
+                qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
         return self.pack_results(dets, batch, qry_bboxes=qry_bboxes, qry_cat_ids=qry_cat_ids,
                                  qry_isegmaps=qry_isegmaps, img_shape=img_shape, qry_child_idx=qry_child_idx,
                                  cats_ids_to_sample_real=cats_ids_to_sample_real, spp_insts_ids=spp_insts_ids,
-                                 idx=idx, qry_resize_to=None if qry_resize_to is None else rs['hw'])
+                                 idx=idx, qry_resize_to=None if qry_resize_to is None else rs['hw'],
+                                 results_at_source=results_at_source)
 
     # --- support branch (fgn.py:212-215 backbone pass; fgn_ag_rpn_head.py:38-41; fgn_roi_head.py:419-449) ---
     def _support_front(self, spp_imgs, spp_bboxes, spp_isegmaps, B, dev, stream, defer_backbone: bool = False) -> dict:
@@ -1221,7 +1232,7 @@ class FGN(torch.nn.Module):
         return g
 
     def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None,
-                bits_out: Optional[list] = None, source: Optional[dict] = None):
+                bits_out: Optional[list] = None, source: Optional[dict] = None, resize_masks: bool = True):
         """``modify_input`` (fgn.py:79-108): host -> device copies of one batch, on an upload stream so that they
         overlap the previous batch's kernels (a pinned source makes them asynchronous); the compute streams wait
         on one event.  Tensors already on the device pass through.  The ground-truth masks (copied to the GPU by
@@ -1232,7 +1243,8 @@ class FGN(torch.nn.Module):
         ``bits_out`` (``match_on_device``): a list that receives, per image, the bit planes of its ground-truth masks
         (``ops.mask_bits`` on the device copy made for the RLE, right behind it on the upload stream; None for an image
         without ground truth).  ``source`` (``_source_query``): the query comes at source size - its pixels go up as
-        ``qry_src`` / ``qry_src_hw`` (``_upload_source``) and the masks are resized right behind their upload."""
+        ``qry_src`` / ``qry_src_hw`` (``_upload_source``) and the masks are resized right behind their upload - unless
+        ``resize_masks`` is off (``results_at_source``): then they are encoded and bit-packed at source size, as given."""
         gts = None
         if gt_masks is not None:
             gts = [g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
@@ -1258,7 +1270,7 @@ class FGN(torch.nn.Module):
             if gts is not None:
                 gt_out = []
                 for g in gts:
-                    g = self._resized_masks(g, source['hw'] if source else None, dev)
+                    g = self._resized_masks(g, source['hw'] if (source and resize_masks) else None, dev)
                     gt_out.append(ops.dense_mask_rle(g, packed=True))
                     if bits_out is not None:
                         bits_out.append(ops.mask_bits(g) if g.shape[0] else None)
@@ -1270,7 +1282,8 @@ class FGN(torch.nn.Module):
 
     @torch.no_grad()
     def detect_device(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
-                      qry_isegmaps=None, phase_counter=None, qry_resize_to=None) -> list:
+                      qry_isegmaps=None, phase_counter=None, qry_resize_to=None,
+                      results_at_source: bool = False) -> list:
         """Everything up to the host wait: queues the host->device copies, the whole path and the device->host
         copies of the results.  Returns, per image, a dict of device tensors (det_bboxes [D,5], det_labels [D],
         n_dets [1], mask_prob, RLE bytes) plus the pinned host slot ``pack_results`` reads.
@@ -1283,9 +1296,15 @@ class FGN(torch.nn.Module):
         set it on the model).  ``qry_resize_to``: the query comes at source size (see ``simple_test``); its pixels
         travel as ``qry_src`` (uint8 [B, slot]) and ``qry_src_hw`` (int32 [B,2]) in place of ``qry_img``, and a captured
         graph is keyed by the slot size and (H, W), not by the source sizes.  (``simple_test`` hands over the checked
-        form, the dict of ``_source_query``, instead of checking twice.)"""
+        form, the dict of ``_source_query``, instead of checking twice.)  ``results_at_source`` (needs
+        ``qry_resize_to``): the RLE strings, the ground-truth strings and the overlap counts are made at each image's
+        source size (see ``simple_test``); the record's boxes stay in the network frame - ``pack_results`` divides them -
+        and every dict carries its image's ``src_hw``.  Part of the graph key: the two modes are different launches."""
         graphed = self._graphed()
         source = None
+        results_at_source = bool(results_at_source)
+        if results_at_source and qry_resize_to is None:
+            raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
         if qry_resize_to is not None:                     # (every contract error is raised here, before anything is queued)
             source = qry_resize_to if isinstance(qry_resize_to, dict) else \
                 self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps, graphed)
@@ -1308,18 +1327,24 @@ class FGN(torch.nn.Module):
         # buffers (the caller stream orders the copy behind the previous replay that reads them) - no device-to-device hop
         into = None
         if graphed and self.use_packed_transfers and self._stream_for('upload', main) is main:
-            ge0 = self._graphs.get(self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source))
+            ge0 = self._graphs.get(self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source,
+                                                   results_at_source))
             into = ge0.static if ge0 is not None else None
         gt_bits = [] if (self.match_on_device and qry_isegmaps is not None) else None
-        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits, source=source)
+        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits, source=source,
+                                             resize_masks=not results_at_source)
         if uploaded is not None:
             main.wait_event(uploaded)
         if graphed:
-            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter, source)
+            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter, source, results_at_source)
         else:
             qry = ins['qry_img'] if source is None else _SrcQuery(ins['qry_src'], ins['qry_src_hw'], *source['hw'])
             outs = self._detect_eager(qry, ins.get('spp_imgs'), ins.get('spp_bboxes'),
-                                      ins.get('spp_isegmaps'), img_shape, support_code, phase_counter=phase_counter)
+                                      ins.get('spp_isegmaps'), img_shape, support_code, phase_counter=phase_counter,
+                                      results_at_source=results_at_source)
+        if results_at_source:
+            for d, hw in zip(outs, source['sizes']):
+                d['src_hw'] = hw
         if gt_rle is not None:
             for d, g in zip(outs, gt_rle):
                 d['gt_rle'] = g
@@ -1332,6 +1357,10 @@ class FGN(torch.nn.Module):
                     continue
                 for t in gb[:2]:
                     t.record_stream(main)                 # allocated on the upload stream
+                if results_at_source:
+                    d['overlap'] = ops.mask_overlap_src(d['mask_prob'], d['det_bboxes'], gb, d['src_hw'], d['img_hw'], thr,
+                                                        d['n_dets'], skip_empty=self._skip_empty(), packed=True)[3]
+                    continue
                 d['overlap'] = ops.mask_overlap(d['mask_prob'], d['det_bboxes'], gb, *d['img_hw'], thr, d['n_dets'],
                                                 skip_empty=self._skip_empty(), packed=True)[3]
         self._start_download(outs, main, uploaded if gt_rle is not None else None)
@@ -1342,7 +1371,8 @@ class FGN(torch.nn.Module):
     def _graphed(self) -> bool:
         return bool(self.use_graphs and self.debug_trace is None and ops.PROFILE is None)
 
-    def _graph_key(self, ins: dict, img_shape, support_code, phase_counter, main, dev, source=None) -> tuple:
+    def _graph_key(self, ins: dict, img_shape, support_code, phase_counter, main, dev, source=None,
+                   results_at_source: bool = False) -> tuple:
         hw = tuple((int(s[0]), int(s[1])) for s in img_shape)
         # everything the captured launch sequence depends on besides the weights (those drop ``_graphs`` when they
         # change): the paste semantic is an argument of the captured RLE kernel, the transfer arrangement decides which
@@ -1354,28 +1384,33 @@ class FGN(torch.nn.Module):
                 bool(self.use_side_stream), bool(self.use_packed_transfers),
                 # source-size queries: the slot and the size they are resized to - NOT the source sizes, which the kernel
                 # reads from ``qry_src_hw`` (the slot tensors are in ``ins`` only once they are uploaded: keyed here)
-                None if source is None else (source['B'], source['capacity'], source['hw'])) + \
+                # ... and whether the results are made at source size: another launch sequence (one batch-wide RLE launch
+                # that reads ``qry_src_hw``); a graph captured without it keeps its key
+                None if source is None else (source['B'], source['capacity'], source['hw']) +
+                (('at_source',) if results_at_source else ())) + \
             tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items()
                   if v is not None and k not in ('qry_src', 'qry_src_hw'))
 
-    def _detect_graphed(self, ins: dict, img_shape, support_code, phase_counter=None, source=None):
+    def _detect_graphed(self, ins: dict, img_shape, support_code, phase_counter=None, source=None,
+                        results_at_source: bool = False):
         main = torch.cuda.current_stream()
         dev = torch.device('cuda', torch.cuda.current_device())
-        key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source)
+        key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source, results_at_source)
         ge = self._graphs.get(key)
         if ge is None:
-            ge = self._graphs[key] = _GraphedEpisode(self, ins, img_shape, support_code, dev, phase_counter, source)
+            ge = self._graphs[key] = _GraphedEpisode(self, ins, img_shape, support_code, dev, phase_counter, source,
+                                                     results_at_source)
         return ge, ge.run(self, ins, support_code, main)
 
     def _detect_eager(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
-                      phase_counter=None) -> list:
+                      phase_counter=None, results_at_source: bool = False) -> list:
         dev = torch.device('cuda', torch.cuda.current_device())
         if self._packed_device != dev:
             self._pack(dev)
         self._sync_trained_shared()
         with ops.arena(dev):     # zero-initialised small outputs of this episode: one fill (caller's stream only)
             return self._detect_body(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code, dev,
-                                     phase_counter)
+                                     phase_counter, results_at_source)
 
     # Phase mark of a pipelined serving loop (bench.py): when two caller streams replay episodes side by
     # side, their relative phase settles in one of several steady states that differ by ~4 % in throughput.  A caller may
@@ -1395,7 +1430,7 @@ class FGN(torch.nn.Module):
             ops.phase_signal(counter)
 
     def _detect_body(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code, dev,
-                     phase_counter=None) -> list:
+                     phase_counter=None, results_at_source: bool = False) -> list:
         P, cfg = self._P, self.cfg
         N, K = self.n_ways, self.k_shots
         tr = self.debug_trace
@@ -1566,16 +1601,35 @@ class FGN(torch.nn.Module):
         _, mf = self._roi_feats(qry_fmap, g_map, mrois_all, nd_all)
         mlog, mprob = self._mask_head(mf, vmask, nd_all, prob_out=rec.prob.view(B * D, 2 * PS, 2 * PS))
         outs = []
+        skip_empty = self._skip_empty()
+        src_boxes = src_sizes = None
+        if results_at_source:
+            # results at source size: ONE launch for the batch, the images' sizes read from ``qry_src_hw``
+            # on the device - the launch is the same for every source size, so a captured graph serves them all
+            if not isinstance(qry, _SrcQuery):
+                raise ValueError('results_at_source needs a source-size query (qry_resize_to)')
+            if tr is not None:                  # (a trace is never captured: the host may read the sizes)
+                src_boxes = torch.empty((B * D, 4), device=dev, dtype=torch.float32)
+                src_sizes = qry.hw.cpu().tolist()
+            ops.mask_rle_src(mprob, det_all, qry.hw, (ih, iw), tc['rcnn']['mask_thr_binary'], n_det_all,
+                             skip_empty=skip_empty, boxes_src_out=src_boxes,
+                             out=(rec.rle.view(B * D, -1), rec.rle_len.view(B * D), rec.rle_ovf.view(B * D)))
         for i in range(B):
             det, lab, n_det = dets[i], labs[i], n_dets[i]
             mp_i = mprob[i * D:(i + 1) * D]
-            # paste + threshold + COCO RLE fused on device: the D x H x W masks are never written
-            skip_empty = self._skip_empty()
-            rle_bytes, rle_len, rle_ovf = ops.mask_rle(mp_i, det, ih, iw, tc['rcnn']['mask_thr_binary'], n_det,
-                                                       skip_empty=skip_empty,
-                                                       out=(rec.rle[i], rec.rle_len[i], rec.rle_ovf[i]))
+            if results_at_source:
+                rle_bytes, rle_len, rle_ovf = rec.rle[i], rec.rle_len[i], rec.rle_ovf[i]
+            else:
+                # paste + threshold + COCO RLE fused on device: the D x H x W masks are never written
+                rle_bytes, rle_len, rle_ovf = ops.mask_rle(mp_i, det, ih, iw, tc['rcnn']['mask_thr_binary'], n_det,
+                                                           skip_empty=skip_empty,
+                                                           out=(rec.rle[i], rec.rle_len[i], rec.rle_ovf[i]))
             if tr is not None:
-                masks = ops.mask_paste(mp_i, det, ih, iw, tc['rcnn']['mask_thr_binary'], n_det, skip_empty=skip_empty)
+                if results_at_source:
+                    masks = ops.mask_paste(mp_i, src_boxes[i * D:(i + 1) * D], *src_sizes[i],
+                                           tc['rcnn']['mask_thr_binary'], n_det, skip_empty=skip_empty)
+                else:
+                    masks = ops.mask_paste(mp_i, det, ih, iw, tc['rcnn']['mask_thr_binary'], n_det, skip_empty=skip_empty)
                 tr.setdefault('per_image', []).append(dict(
                     rois=rois_all[i * R:(i + 1) * R], roi_feats=feats[i * R:(i + 1) * R], Q=Q[i * R:(i + 1) * R],
                     cls_raw=cls_raw[i * R * N:(i + 1) * R * N], reg_raw=reg_raw[i * R * N:(i + 1) * R * N],
@@ -1681,13 +1735,22 @@ class FGN(torch.nn.Module):
 
     def pack_results(self, dets: list, batch: int, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None,
                      img_shape=None, qry_child_idx=None, cats_ids_to_sample_real=None, spp_insts_ids=None,
-                     idx=None, qry_resize_to=None) -> List[Dict]:
+                     idx=None, qry_resize_to=None, results_at_source: bool = False) -> List[Dict]:
         """Device->host copy and result dicts (fgn.py:240-303).  Passthrough boxes stay YXYX
         (SERVER semantics); caller tensors are never mutated.  ``qry_resize_to`` = (H, W):
         ``qry_isegmaps`` are at source size (they are read only where a device RLE overflowed or none was made, and
-        resized on the host then)."""
+        resized on the host then).  ``results_at_source``: ``dets`` come from ``detect_device`` with the same flag
+        and carry each image's (h_b, w_b), checked by ``_source_query``: boxes are divided by the image's scale
+        (``fewshot_ds.boxes_to_source``), strings carry ``size: [h_b, w_b]``, ``qry_img_shape`` is ``[h_b, w_b, 3]``
+        and no mask is resized."""
+        from .fewshot_ds import boxes_to_source
+        if results_at_source and any('src_hw' not in d for d in dets[:batch]):
+            raise ValueError('results_at_source: these detections were not made with detect_device(results_at_source=True)')
+
         def host_mask(m):
             m = np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m)
+            if results_at_source:               # as given
+                return m
             if qry_resize_to is not None and tuple(m.shape[-2:]) != tuple(qry_resize_to):
                 from .fewshot_ds import resize_masks
                 m = resize_masks(m.reshape((-1,) + m.shape[-2:]), *qry_resize_to).reshape(m.shape[:-2] + tuple(qry_resize_to))
@@ -1705,24 +1768,34 @@ class FGN(torch.nn.Module):
             lens = host['rle_len'][i, :n].numpy()
             ovf = host['rle_ovf'][i, :n].numpy()
             ih, iw = di['img_hw']
+            oh, ow = di['src_hw'] if results_at_source else (ih, iw)        # the frame of this image's results
             strings = host['rle'][i].numpy()
-            rles = [{'size': [ih, iw], 'counts': strings[j, :lens[j]].tobytes()} for j in range(n)]
+            rles = [{'size': [oh, ow], 'counts': strings[j, :lens[j]].tobytes()} for j in range(n)]
             if n and ovf.any():     # a device cap overflowed: dense paste + host RLE for those masks only
                 thr = self.cfg['test_cfg']['rcnn']['mask_thr_binary']
                 for j in np.flatnonzero(ovf):
                     # (from the HOST copies: a replayed graph may have overwritten the device tensors by now)
                     pdev = di['det_bboxes'].device
-                    dense = ops.mask_paste(host['prob'][i, j:j + 1].to(pdev).contiguous(),
-                                           host['det'][i, j:j + 1].to(pdev).contiguous(),
-                                           ih, iw, thr, skip_empty=self._skip_empty())
+                    box = host['det'][i, j:j + 1]
+                    if results_at_source:       # the box the device divided, divided here by the same rule
+                        box = torch.from_numpy(boxes_to_source(np.ascontiguousarray(box[:, :4].numpy()), (oh, ow),
+                                                               (ih, iw), order='xyxy'))
+                    dense = ops.mask_paste(host['prob'][i, j:j + 1].to(pdev).contiguous(), box.to(pdev).contiguous(),
+                                           oh, ow, thr, skip_empty=self._skip_empty())
                     rles[j] = rle.encode(dense[0].cpu().numpy())
+            boxes = db[:, [1, 0, 3, 2]].reshape(-1, 4).copy()
+            if results_at_source:
+                boxes = boxes_to_source(boxes, (oh, ow), (ih, iw), order='yxyx')
             one = {'dt_scores': db[:, 4].reshape(-1).copy(),
-                   'dt_bboxes': db[:, [1, 0, 3, 2]].reshape(-1, 4).copy(),
+                   'dt_bboxes': boxes,
                    'dt_cat_ids': host['lab'][i, :n].numpy().copy().reshape(-1),
                    'dt_isegmaps_rle': rles}
             for key, val in passthrough.items():
                 v = val[i] if val is not None else None
                 one[key] = v.cpu().numpy() if isinstance(v, torch.Tensor) else v
+            if results_at_source:
+                sh = one['qry_img_shape']
+                one['qry_img_shape'] = np.array([oh, ow, 3], sh.dtype if isinstance(sh, np.ndarray) else np.int32)
             gt = qry_isegmaps[i] if qry_isegmaps is not None else None
             if 'gt_slice' in di:                   # ground-truth masks were encoded on the device (detect_device)
                 g0, ng = di['gt_slice']
@@ -1731,7 +1804,7 @@ class FGN(torch.nn.Module):
                 glen, govf = hb[:ng * 4].view(torch.int32).numpy(), hb[ng * 4:ng * 8].view(torch.int32).numpy()
                 gstr = hb[ng * 8:].view(ng, ops.RLE_BYTE_CAP).numpy()
                 one['qry_isegmaps_rle'] = [
-                    {'size': [ih, iw], 'counts': gstr[j, :glen[j]].tobytes()} if not govf[j] else
+                    {'size': [oh, ow], 'counts': gstr[j, :glen[j]].tobytes()} if not govf[j] else
                     rle.encode(host_mask(gt[j]))
                     for j in range(ng)]
             elif gt is not None:

@@ -236,6 +236,25 @@ def scale_boxes_yxyx(bboxes_yxyx: np.ndarray, h: int, w: int, H: int, W: int) ->
     return out
 
 
+def boxes_to_source(boxes: np.ndarray, src_hw, net_hw, order: str = 'yxyx') -> np.ndarray:
+    """Boxes in the frame of a ``net_hw`` = (H, W) network in the frame of the ``src_hw`` = (h, w) image they were
+    resized from: x coordinates divided by ``float32(W / w)``, y coordinates by ``float32(H / h)`` - mmdet's
+    ``bboxes / scale_factor`` with the ``scale_factor`` its ``Resize`` forms, in float32, without clipping.  float32
+    [n,4] in, float32 out; ``order``: ``'yxyx'`` (result dicts) or ``'xyxy'`` (detection records).  At equal size the
+    same object comes back, like ``resize_query``."""
+    if order not in ('yxyx', 'xyxy'):
+        raise ValueError(f"boxes_to_source: order must be 'yxyx' or 'xyxy', got {order!r}")
+    if not isinstance(boxes, np.ndarray) or boxes.dtype != np.float32 or boxes.ndim != 2 or boxes.shape[1] != 4:
+        raise ValueError('boxes_to_source: expects a float32 [n,4] array')
+    (h, w), (H, W) = (int(v) for v in src_hw), (int(v) for v in net_hw)
+    _check_resize_dims(h, w, H, W)
+    if (h, w) == (H, W):
+        return boxes
+    sy, sx = np.float32(H / h), np.float32(W / w)
+    s = np.array([sy, sx, sy, sx] if order == 'yxyx' else [sx, sy, sx, sy], np.float32)
+    return boxes / s
+
+
 def resize_query(img: np.ndarray, bboxes_yxyx: np.ndarray, isegmaps: np.ndarray, H: int, W: int):
     """What ``get_query`` does between the decoded image and the sample (base_fst.py:876-887): image and masks to
     (H, W), boxes scaled.  At equal size everything passes through untouched (the same objects)."""

@@ -79,10 +79,12 @@ SIGNATURES = {
     'fgn_mask_logits_f32': (_i, [_p, _p, _f, _p, _p, _p, _p, _i, _i, _i, _p]),
     'fgn_mask_paste_u8': (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _f, _i, _p]),
     'fgn_mask_rle': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _i, _i, _i, _p]),
+    'fgn_mask_rle_src': (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p]),
     'fgn_dense_rle_scratch_bytes': (C.c_size_t, [_i, _i, _i, _i]),
     'fgn_dense_mask_rle': (_i, [_p, _p, C.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     'fgn_mask_bits_u64': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'fgn_mask_overlap_i32': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
+    'fgn_mask_overlap_src_i32': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
     'fgn_rpn_proposals_large_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'fgn_rpn_proposals_large_f32': (_i, [_p] * 7 + [_i, _i, _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_f),
                                                   _f, _i, _f, _f, _i, _p]),
@@ -111,7 +113,7 @@ SIGNATURES = {
     'fgn_adagrad_multi_f32': (_i, [_p, _p, _p, _p, _p, _i, _f, _f, _p]),
 }
 
-ABI_VERSION = 32
+ABI_VERSION = 33
 _lib = None
 
 

@@ -1489,6 +1489,56 @@ def mask_rle(prob: torch.Tensor, boxes: torch.Tensor, img_h: int, img_w: int, th
     return out, lens, ovf
 
 
+def mask_rle_src(prob: torch.Tensor, boxes: torch.Tensor, src_hw: torch.Tensor, net_hw, thr: float,
+                 n_dev: Optional[torch.Tensor] = None, skip_empty: bool = True, out=None, boxes_src_out=None):
+    """``mask_rle`` of a whole batch with the results at SOURCE size, one launch: ``prob`` [B*D,M,M] and ``boxes``
+    [B*D,>=4] hold D rows per image, the boxes in the frame of the ``net_hw`` = (H, W) network; ``src_hw`` int32 [B,2]
+    ON THE DEVICE holds (h_b, w_b) and is read by the kernel (the launch is the same for every source size); ``n_dev``
+    int32 [B]: the images' detection counts.  Every box is divided by its image's scale
+    (``fewshot_ds.boxes_to_source``, bit for bit) and pasted into h_b x w_b.  Returns (bytes [B*D,RLE_BYTE_CAP] u8,
+    lens [B*D] i32, overflow [B*D] i32); ``out``: caller-owned tensors of those sizes, lens / overflow ZERO on entry.
+    ``boxes_src_out``: a float32 [B*D,4] tensor that receives the divided boxes.  An image whose size is outside
+    1..16384 comes out with lengths 0."""
+    _chk(prob, 'prob')
+    _chk(boxes, 'boxes')
+    _chk(src_hw, 'src_hw', torch.int32)
+    rows, m, _ = prob.shape
+    dev = prob.device
+    if src_hw.dim() != 2 or src_hw.shape[1] != 2 or src_hw.device != dev:
+        raise _lib.FgnHipError('mask_rle_src: src_hw must be int32 [B,2] on the device of prob')
+    b = int(src_hw.shape[0])
+    if boxes.dim() != 2 or boxes.shape[0] != rows or boxes.shape[1] < 4 or (b == 0) != (rows == 0) or (b and rows % b):
+        raise _lib.FgnHipError('mask_rle_src: prob / boxes must hold the same number of rows per image of src_hw')
+    d = rows // b if b else 0
+    if n_dev is not None:
+        _chk(n_dev, 'n_dev', torch.int32)
+        if n_dev.numel() != b:
+            raise _lib.FgnHipError('mask_rle_src: n_dev must hold one count per image')
+    H, W = int(net_hw[0]), int(net_hw[1])
+    if not (1 <= H <= RESIZE_MAX_DIM and 1 <= W <= RESIZE_MAX_DIM):
+        raise _lib.FgnHipError(f'mask_rle_src: the network size must be within 1..{RESIZE_MAX_DIM}, got {(H, W)}')
+    if boxes_src_out is not None:
+        _chk(boxes_src_out, 'boxes_src_out')
+        if tuple(boxes_src_out.shape) != (rows, 4) or boxes_src_out.device != dev:
+            raise _lib.FgnHipError('mask_rle_src: boxes_src_out must be float32 [B*D,4] on the device of prob')
+    scratch = torch.empty((rows, RLE_TRANS_CAP), device=dev, dtype=torch.int32)
+    if out is not None:
+        out, lens, ovf = out
+        _chk(out, 'out bytes', torch.uint8); _chk(lens, 'out lens', torch.int32); _chk(ovf, 'out overflow', torch.int32)
+        if out.numel() != rows * RLE_BYTE_CAP or lens.numel() != rows or ovf.numel() != rows:
+            raise _lib.FgnHipError('mask_rle_src: bad out shapes')
+    else:
+        out = torch.empty((rows, RLE_BYTE_CAP), device=dev, dtype=torch.uint8)
+        lens = zeros((rows,), dev, torch.int32)
+        ovf = zeros((rows,), dev, torch.int32)
+    if rows:
+        rc = _lib.load().fgn_mask_rle_src(_ptr(prob), _ptr(boxes), boxes.shape[1], _ptr(src_hw), _ptr(scratch), _ptr(out),
+                                          _ptr(lens), _ptr(ovf), _ptr(boxes_src_out), _ptr(n_dev), b, d, H, W, m,
+                                          float(thr), RLE_TRANS_CAP, RLE_BYTE_CAP, int(bool(skip_empty)), _stream())
+        _lib.check(rc, 'fgn_mask_rle_src')
+    return out, lens, ovf
+
+
 def dense_mask_rle(masks: torch.Tensor, packed: bool = False):
     """COCO RLE of dense binary masks [n,H,W] (bool / uint8) on the device: the ground-truth masks of the query
     (``qry_isegmaps_rle``, fgn.py:298).  Returns (bytes [n,RLE_BYTE_CAP] u8, lens [n] i32, overflow [n] i32).
@@ -1569,6 +1619,41 @@ def mask_overlap(prob: torch.Tensor, boxes: torch.Tensor, gt_masks, img_h: int, 
                                           _ptr(det_area), _ptr(n_dev), d, g, img_h, img_w, m, float(thr),
                                           int(bool(skip_empty)), _stream())
     _lib.check(rc, 'fgn_mask_overlap_i32')
+    return (inter, det_area, ga, buf) if packed else (inter, det_area, ga)
+
+
+def mask_overlap_src(prob: torch.Tensor, boxes: torch.Tensor, gt_masks, src_hw, net_hw, thr: float,
+                     n_dev: Optional[torch.Tensor] = None, skip_empty: bool = True, packed: bool = False):
+    """``mask_overlap`` of one image with the detections pasted at SOURCE size: ``boxes`` are in the frame of the
+    ``net_hw`` = (H, W) network and are divided by the scale of the ``src_hw`` = (h, w) image as ``mask_rle_src`` divides
+    them; ``gt_masks`` ([G,h,w] bool / uint8, or what ``mask_bits`` returned for them) are at source size as given.
+    Returns what ``mask_overlap`` returns."""
+    _chk(prob, 'prob')
+    _chk(boxes, 'boxes')
+    d, m, _ = prob.shape
+    if boxes.shape[0] != d or boxes.shape[1] < 4:
+        raise _lib.FgnHipError('mask_overlap_src: boxes shape mismatch')
+    if n_dev is not None:
+        _chk(n_dev, 'n_dev', torch.int32)
+    h, w = int(src_hw[0]), int(src_hw[1])
+    H, W = int(net_hw[0]), int(net_hw[1])
+    if not all(1 <= v <= RESIZE_MAX_DIM for v in (h, w, H, W)):
+        raise _lib.FgnHipError(f'mask_overlap_src: sizes must be within 1..{RESIZE_MAX_DIM}, got {(h, w)} and {(H, W)}')
+    bits, gt_area, hw = gt_masks if isinstance(gt_masks, tuple) else mask_bits(gt_masks)
+    if tuple(hw) != (h, w):
+        raise _lib.FgnHipError(f'mask_overlap_src: ground-truth masks are {tuple(hw)}, the source image is {(h, w)}')
+    g = gt_area.numel()
+    buf = torch.empty(d * g + d + g, device=prob.device, dtype=torch.int32)
+    inter, det_area, ga = buf[:d * g].view(d, g), buf[d * g:d * g + d], buf[d * g + d:]
+    if g:
+        ga.copy_(gt_area)
+    if d == 0 or g == 0:
+        det_area.zero_()
+        return (inter, det_area, ga, buf) if packed else (inter, det_area, ga)
+    rc = _lib.load().fgn_mask_overlap_src_i32(_ptr(prob), _ptr(boxes), boxes.shape[1], _ptr(bits), _ptr(inter),
+                                              _ptr(det_area), _ptr(n_dev), d, g, h, w, H, W, m, float(thr),
+                                              int(bool(skip_empty)), _stream())
+    _lib.check(rc, 'fgn_mask_overlap_src_i32')
     return (inter, det_area, ga, buf) if packed else (inter, det_area, ga)
 
 

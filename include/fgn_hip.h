@@ -358,6 +358,18 @@ int fgn_mask_rle(const float* prob, const float* boxes, int box_stride, uint32_t
                  int img_h, int img_w, int mask_size, float thr, int trans_cap, int byte_cap, int skip_empty,
                  void* stream);
 
+/* fgn_mask_rle for a batch whose results are wanted at SOURCE size, one launch: row r = b * n_det + d of
+ * prob / boxes / out_* / trans_scratch is detection d of image b.  src_hw int32 [batch][2] = (h_b, w_b) IN DEVICE
+ * MEMORY, read by the kernel (the launch is the same for every source size); n_dev int32 [batch] (or null: n_det each).
+ * The boxes are network-frame boxes of a (net_h, net_w) network; each is divided by the image's scale
+ * s_x = (float)((double)net_w / w_b), s_y = (float)((double)net_h / h_b) (correctly rounded f32 division, no clipping)
+ * and pasted into h_b x w_b.  boxes_src (optional) float [batch * n_det][4]: the divided boxes.  An image whose size is
+ * outside 1..16384 yields out_len = 0, overflow = 0 and zero boxes_src rows. */
+int fgn_mask_rle_src(const float* prob, const float* boxes, int box_stride, const int32_t* src_hw,
+                     uint32_t* trans_scratch, uint8_t* out_bytes, int32_t* out_len, int32_t* overflow, float* boxes_src,
+                     const int32_t* n_dev, int batch, int n_det, int net_h, int net_w, int mask_size, float thr,
+                     int trans_cap, int byte_cap, int skip_empty, void* stream);
+
 /* COCO RLE of dense binary masks on the device: the query's ground-truth masks, which the reference copies to
  * the GPU with the batch (fgn.py:92-99) and encodes on the host with pycocotools (fgn.py:298, `qry_isegmaps_rle`).
  * masks [n][H][W] bytes (non-zero = set); out_bytes [n][byte_cap], out_len [n], overflow [n] (a cap was exceeded:
@@ -383,6 +395,13 @@ int fgn_mask_bits_u64(const uint8_t* masks, uint64_t* bits, int32_t* area, int n
 int fgn_mask_overlap_i32(const float* prob, const float* boxes, int box_stride, const uint64_t* gt_bits, int32_t* inter,
                          int32_t* det_area, const int32_t* n_dev, int n_det, int n_gt, int img_h, int img_w,
                          int mask_size, float thr, int skip_empty, void* stream);
+
+/* Step 2 at source size: the boxes are network-frame boxes of a (net_h, net_w) network, divided by the scale of the
+ * src_h x src_w image exactly as fgn_mask_rle_src divides them, and pasted into src_h x src_w, the size of gt_bits.
+ * Sizes within 1..16384. */
+int fgn_mask_overlap_src_i32(const float* prob, const float* boxes, int box_stride, const uint64_t* gt_bits,
+                             int32_t* inter, int32_t* det_area, const int32_t* n_dev, int n_det, int n_gt, int src_h,
+                             int src_w, int net_h, int net_w, int mask_size, float thr, int skip_empty, void* stream);
 
 /* ---- forward_train (fgn.py:125-185) ----------------------------------------------------- */
 
