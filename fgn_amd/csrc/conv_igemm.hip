@@ -1530,7 +1530,7 @@ static int h2_pick(long long M, int Cout, int K, int grp_rows, int grp_valid, in
     return (bm_x3 == 128 && !grp_rows) ? 64 : bm_x3;
 }
 
-template <int WMW, int WNW, int RB, int NST, bool IM2COL>
+template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1>
 static int launch_h2_cfg(ConvParams& p, const H2Im2col& q2, int M_max, hipStream_t stream) {
     constexpr int BM = 32 * RB * WMW, BN = 64 * WNW;
     const int m_tiles = cdiv(M_max, BM);
@@ -1538,13 +1538,13 @@ static int launch_h2_cfg(ConvParams& p, const H2Im2col& q2, int M_max, hipStream
     set_band(p, BM, m_tiles, (long long)BN * p.K * 4);
     const int tiles = m_tiles * p.n_tiles_n;
     static unsigned long long ok = 0ull;
-    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL>), &ok);
+    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL, KG>), &ok);
     if (attr != hipSuccess) return (int)attr;
-    const size_t lds = (size_t)NST * (BM * 128 + 2 * BN * 64);
+    const size_t lds = (size_t)KG * NST * (BM * 128 + 2 * BN * 64);            // a ring per K-group
     const int per_cu = std::min(3, (int)(160 * 1024 / lds));         // resident workgroups per CU (LDS-bound)
     const int grid = std::min(256 * per_cu, (tiles + 7) / 8 * 8);
     p.stamp = fgn_next_stamp_record();
-    FGN_LAUNCH_TIMED((conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL>), dim3(grid), dim3(64 * WMW * WNW), lds, stream, p, q2, tiles);
+    FGN_LAUNCH_TIMED((conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL, KG>), dim3(grid), dim3(64 * WMW * WNW * KG), lds, stream, p, q2, tiles);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }
@@ -1556,7 +1556,26 @@ extern "C" int fgn_h2_row_tile(long long M, int Cout, int K, int grp_rows, int g
     return h2_pick(M, Cout, K, grp_rows, grp_valid, 0);
 }
 
-// bm: 0 = choose (h2_pick), 64 / 128 / 264 = force the tile
+// K-groups of a launch (conv_pw_h2.h, KG): 2 = the 64-row tile with two sets of four waves per output tile, each on every
+// other K-tile; 1 = one set.  Two where the launch has at most one tile per CU - a workgroup is alone on its CU either
+// way, so the 96 KB of LDS cost no residency and the second set of waves takes slots nothing else would fill - the K-tile
+// count is even and the K loop long enough for half of it to outweigh the added epilogue step.  Grouped (Winograd)
+// launches and every launch of more than 256 tiles stay as they are.
+// H2_KG_MIN_KTILES: the forced-code sweep of tools/x3_probe.py on the 204 tiles of 6504 rows -> 256 channels, variants
+// taking turns, two runs (profiles/h2_kgroups_ab.json): one group -> two at 72 K-tiles (implicit GEMM) 57.7 / 55.4 -> 45.0 /
+// 43.4 us, 32: 26.4 / 25.9 -> 21.3 / 21.1, 16: 16.6 / 16.3 -> 14.0 / 13.8, 8: 11.4 / 11.4 -> 10.4 / 10.3 - the gain shrinks
+// with the K loop (22 / 19 / 16 / 9 %) but is ten times the 0.1 us between two runs of a variant at 8 K-tiles, the
+// shallowest loop measured: the threshold stands there.  (816 tiles of K 256, forced: 23.5 -> 31.8 us - hence one per CU.)
+constexpr int H2_KG_MIN_KTILES = 8;
+constexpr int H2_BM_KG2 = 1064;       // forced tile code: 64 rows, two K-groups (K / 32 even and >= 4)
+extern "C" int fgn_h2_k_groups(long long M, int Cout, int K, int grp_rows, int grp_valid) {
+    if (h2_pick(M, Cout, K, grp_rows, grp_valid, 0) != 64 || grp_rows != 0 || K % BK) return 1;
+    const int kt = K / BK;
+    if ((kt & 1) || kt < H2_KG_MIN_KTILES) return 1;
+    return cdiv(M, 64) * (long long)cdiv(Cout, H2_BN) <= 256 ? 2 : 1;
+}
+
+// bm: 0 = choose (h2_pick, fgn_h2_k_groups), 64 / 128 / 264 = force the tile (one K-group), 1064 = 64 rows, two K-groups
 static int launch_h2(const ConvParams& p0, int M_max, int n_groups, int bm, hipStream_t stream, const H2Im2col* im = nullptr) {
     ConvParams p = p0;
     if (!p.w3 || p.npad3 % H2_BN || p.npad3 < p.Cout || (p.Cout & 3) || p.K % BK || p.K < 2 * BK || p.splits != 1) return FGN_ERR_SHAPE;
@@ -1565,9 +1584,13 @@ static int launch_h2(const ConvParams& p0, int M_max, int n_groups, int bm, hipS
     p.w_inv = reinterpret_cast<const float*>(static_cast<const char*>(p.w3) + img);
     H2Im2col none;
     none.y1 = nullptr; none.x_off0 = none.x_off1 = 0u; none.M0 = none.M1 = 0; none.H1 = none.W1 = none.Ho1 = none.Wo1 = 1; none.cin_shift = 0;
-    if (bm != 0 && bm != 64 && bm != 128 && bm != 264) return FGN_ERR_SHAPE;
-    const int cfg = h2_pick(M_max, p.Cout, p.K, p.grp_rows, p.grp_valid, bm);
+    if (bm != 0 && bm != 64 && bm != 128 && bm != 264 && bm != H2_BM_KG2) return FGN_ERR_SHAPE;
+    if (bm == H2_BM_KG2 && ((p.K / BK) % 2 || p.K / BK < 4)) return FGN_ERR_SHAPE;
+    const int cfg = h2_pick(M_max, p.Cout, p.K, p.grp_rows, p.grp_valid, bm == H2_BM_KG2 ? 64 : bm);
     if (cfg == 0) return FGN_ERR_SHAPE;
+    const int kgroups = bm == H2_BM_KG2 ? 2 : (bm == 0 ? fgn_h2_k_groups(M_max, p.Cout, p.K, p.grp_rows, p.grp_valid) : 1);
+    if (kgroups == 2)
+        return im ? launch_h2_cfg<2, 2, 1, 2, true, 2>(p, *im, M_max, stream) : launch_h2_cfg<2, 2, 1, 2, false, 2>(p, none, M_max, stream);
     if (im) {
         if (cfg == 264) return launch_h2_cfg<4, 1, 1, 2, true>(p, *im, M_max, stream);
         return cfg == 128 ? launch_h2_cfg<2, 2, 2, 2, true>(p, *im, M_max, stream) : launch_h2_cfg<2, 2, 1, 2, true>(p, *im, M_max, stream);
@@ -1582,10 +1605,11 @@ static int launch_h2(const ConvParams& p0, int M_max, int n_groups, int bm, hipS
 // offset; out-of-image taps fetched out of bounds = zeros) in front of the f16-plane products.  w_h2 = ops.pack_h2 of the
 // packed weights [cout_pad][KH KW Cin] (K order: tap, channel).  Cin / 32 a power of two.  Both inputs must lie within
 // 2 GiB of each other (they do: the query map and the support maps of a layer share one buffer).
-extern "C" int fgn_conv2d_pair_h2_nhwc_f32(const float* x0, int n_img0, int H0, int W0, const float* x1, int n_img1, int H1,
-                                           int W1, const void* w_h2, float* y0, float* y1, const float* scale,
-                                           const float* shift, int Cin, int Cout, int cout_pad, int KH, int KW, int stride,
-                                           int pad, int relu, hipStream_t stream) {
+// fgn_conv2d_pair_h2_bm_nhwc_f32: the same with the tile code of fgn_gemm_h2_f32 forced (tests, tools).
+extern "C" int fgn_conv2d_pair_h2_bm_nhwc_f32(const float* x0, int n_img0, int H0, int W0, const float* x1, int n_img1, int H1,
+                                              int W1, const void* w_h2, float* y0, float* y1, const float* scale,
+                                              const float* shift, int Cin, int Cout, int cout_pad, int KH, int KW, int stride,
+                                              int pad, int relu, int bm, hipStream_t stream) {
     if (!x0 || !w_h2 || !y0 || (x1 && !y1)) return FGN_ERR_ARG;
     if (n_img0 <= 0 || (x1 && n_img1 <= 0)) return FGN_ERR_SHAPE;
     const int ct = Cin / BK;
@@ -1614,7 +1638,15 @@ extern "C" int fgn_conv2d_pair_h2_nhwc_f32(const float* x0, int n_img0, int H0, 
     q.H1 = x1 ? H1 : 1; q.W1 = x1 ? W1 : 1; q.Ho1 = Ho1; q.Wo1 = Wo1;
     q.cin_shift = 0;
     while ((1 << q.cin_shift) < ct) ++q.cin_shift;
-    return launch_h2(p, (int)(M0 + M1), 1, 0, stream, &q);
+    return launch_h2(p, (int)(M0 + M1), 1, bm, stream, &q);
+}
+
+extern "C" int fgn_conv2d_pair_h2_nhwc_f32(const float* x0, int n_img0, int H0, int W0, const float* x1, int n_img1, int H1,
+                                           int W1, const void* w_h2, float* y0, float* y1, const float* scale,
+                                           const float* shift, int Cin, int Cout, int cout_pad, int KH, int KW, int stride,
+                                           int pad, int relu, hipStream_t stream) {
+    return fgn_conv2d_pair_h2_bm_nhwc_f32(x0, n_img0, H0, W0, x1, n_img1, H1, W1, w_h2, y0, y1, scale, shift, Cin, Cout, cout_pad,
+                                          KH, KW, stride, pad, relu, 0, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -33,7 +33,7 @@
 // stage one wave row at a time: 32 RB rows x 512 bytes fit it for either row tile), the f32 activations split in
 // registers after the ds_read (2 vector instructions per element: v_fma_mixlo / mixhi_f16), the weight image
 // [group][K-tile][plane][npad][32] f16 with the k order and chunk swizzle of ops.pack_x3's 16x16x32 form.  64 rows: 48 KB
-// of LDS, three workgroups per CU; 128 rows: 64 KB, two.
+// of LDS, three workgroups per CU; 128 rows: 64 KB, two; 64 rows on two K-groups (KG = 2, below): 96 KB, one.
 #pragma once
 
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
@@ -104,9 +104,19 @@ struct H2Im2col {
     int cin_shift;            // log2(Cin / 32)
 };
 
-template <int WMW, int WNW, int RB, int NST, bool IM2COL>
-__global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const ConvParams p, const H2Im2col q2, const int total_tiles) {
-    constexpr int BM = 32 * RB * WMW, BN = 64 * WNW, NTHR = 64 * WMW * WNW, NW = WMW * WNW;
+// K-groups (KG = 2): for a grid of at most one output tile per CU, where a workgroup is alone on its CU and
+// each SIMD holds ONE wave that walks the K-tiles as a serial chain (wait, barrier, DMA issue, LDS reads, split, MFMA), a
+// second set of WMW x WNW waves works on the SAME output tile.  A K-step is KG consecutive K-tiles: group kg = wave / (WMW
+// WNW) requests K-tile step * KG + kg into a ring of NST stages of its own (behind group 0's), reads only that ring and
+// keeps its own accumulators and its own per-wave activation scale; a wave waits only for its own DMAs, and all waves meet
+// at the one workgroup barrier per step.  The chain is KT / KG steps long and each SIMD holds two waves that are out of
+// step in their phases.  In the epilogue group 0 writes its scaled accumulators to the C tile and group 1 adds its own
+// behind a barrier (a fixed order: the result is deterministic); all the threads store.  KG * NST stages of LDS.
+template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1>
+__global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_h2_kernel(const ConvParams p, const H2Im2col q2, const int total_tiles) {
+    // NW / NTHR_G: waves / threads of ONE K-group (the roles wm, wn and the DMA rows are those of the wave inside its group)
+    constexpr int BM = 32 * RB * WMW, BN = 64 * WNW, NW = WMW * WNW, NTHR_G = 64 * NW, NTHR = NTHR_G * KG;
+    static_assert(KG == 1 || KG == 2, "one or two K-groups");
     constexpr int A_LD = BM / 8 / NW;                       // activation wave-instructions per wave per K-tile (8 rows each)
     constexpr int A_STAGE = BM * 128;                       // bytes
     constexpr int B_STAGE = 2 * BN * 64;                    // bytes of one K-tile of the weight image for BN columns
@@ -116,11 +126,14 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
     static_assert(A_LD * 8 * NW == BM && B_LD * NW == 2 * BQ, "tile / wave split");
     constexpr int PER = A_LD + B_LD;                        // LDS-DMA wave-instructions per wave per K-tile
     constexpr int D = NST - 1;                              // K-tiles in flight ahead of the one being multiplied
-    constexpr int ROWS_PER_PASS = NTHR / 8;                 // A rows one pass of the workgroup's DMAs covers
+    constexpr int ROWS_PER_PASS = NTHR_G / 8;               // A rows one pass of a K-group's DMAs covers
     static_assert(NST == 2 || NST == 3, "ring of 2 or 3 stages");      // (three: measured 5-12 % slower, DESIGN appendix A row 53)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
 
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
+    const int kg = KG == 1 ? 0 : __builtin_amdgcn_readfirstlane((t >> 6) / NW);      // the wave's K-group
+    const int wv = KG == 1 ? t >> 6 : (t >> 6) % NW;                // the wave inside its group
+    const int tg = KG == 1 ? t : t % NTHR_G;                        // the thread inside its group
     const int wm = wv / WNW, wn = wv % WNW;
     const int M = IM2COL ? q2.M0 + q2.M1 : (p.n_img_dev ? min(p.n_img, *p.n_img_dev) : p.n_img) * p.Ho * p.Wo;
     int grp_valid = p.grp_valid;
@@ -128,15 +141,15 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
 
     float a_s = 1.f, a_inv = 1.f;                   // the wave's activation scale and its inverse (powers of two)
 
-    const int col4 = t & 7, row0 = t >> 3;
+    const int col4 = tg & 7, row0 = tg >> 3;
     const int src_c4 = col4 ^ ((row0 >> 1) & 7);
     const i32x4 x_rs = make_rsrc(p.x, p.x_bytes);
     const i32x4 w_rs = make_rsrc(p.w3, p.w3_bytes);
     const bool dual = !IM2COL && p.x2 != nullptr;
     const i32x4 x2_rs = make_rsrc(dual ? p.x2 : p.x, dual ? p.x2_bytes : p.x_bytes);
-    const int KT = p.K / BK;                                                  // >= D (checked by the launcher)
+    const int KT = p.K / BK / KG;                // K-steps: the K-tiles of one group; >= D, K / BK a multiple of KG (launcher)
     const unsigned kt_bytes = (unsigned)(2 * p.npad3 * 64);          // one K-tile of the image, both planes, all rows
-    const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<size_t>(smem_h2));
+    const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<size_t>(smem_h2) + kg * (NST * STAGE));   // the group's ring
     const unsigned wave_row_bytes = __builtin_amdgcn_readfirstlane(wv) * 8 * 128;
     constexpr unsigned OOB = 0x7ffffff0u;
 
@@ -216,7 +229,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
             if (dual && in) o.a2[i] = (unsigned)(((p.x2_rows ? p.x2_rows[m] : m) * p.cin2 + src_c4 * 4) * 4);
         }
         unsigned g0 = 0;
-        if (p.grp_rows) g0 = (unsigned)(m0 / p.grp_rows) * (unsigned)KT * kt_bytes;
+        if (p.grp_rows) g0 = (unsigned)(m0 / p.grp_rows) * (unsigned)(KT * KG) * kt_bytes;
 #pragma unroll
         for (int i = 0; i < B_LD; ++i) {
             const int q = wv + NW * i;
@@ -225,7 +238,8 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
         }
         return o;
     };
-    auto issue = [&](const Offs& o, int kt, int stage) {
+    auto issue = [&](const Offs& o, int step, int stage) {
+        const int kt = step * KG + kg;           // the absolute K-tile
         const unsigned st = lds_base + stage * STAGE;
         const unsigned sa = st + wave_row_bytes;
         const unsigned ko = (unsigned)(kt * BK * 4);
@@ -330,7 +344,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
             --ahead;
             issue_one();
             asm volatile("" ::: "memory");
-            const unsigned char* const S = smem_h2 + stage * STAGE;
+            const unsigned char* const S = smem_h2 + (KG == 1 ? 0 : kg * (NST * STAGE)) + stage * STAGE;
             float4 alo[2 * RB], ahi[2 * RB];
             f16x8_t bq[4][2];
 #pragma unroll
@@ -396,7 +410,8 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
             }
             stage = stage + 1 == NST ? 0 : stage + 1;
         }
-        // the stage of the last K-tile (the one before `stage` in the ring) takes the C tile once every wave has read it
+        // the stage of the last K-tile (the one before `stage` in the ring; group 0's ring) takes the C tile once every wave
+        // has read it
         float* const cbase = reinterpret_cast<float*>(smem_h2 + (stage == 0 ? NST - 1 : stage - 1) * STAGE);
         const int em0 = m0, en0 = n0;
         const float* const winv = p.w_inv + (p.grp_rows ? (size_t)(em0 / p.grp_rows) * p.npad3 : 0);
@@ -405,7 +420,7 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
 #pragma unroll
         for (int pass = 0; pass < WMW; ++pass) {
             __syncthreads();
-            if (wm == pass) {                        // 16x16 C/D layout: col = lane & 15, row = 4 * (lane >> 4) + reg
+            if (wm == pass && kg == 0) {             // 16x16 C/D layout: col = lane & 15, row = 4 * (lane >> 4) + reg
 #pragma unroll
                 for (int i = 0; i < 2 * RB; ++i)
 #pragma unroll
@@ -416,6 +431,19 @@ __global__ __launch_bounds__(64 * WMW * WNW, 2) void conv_pw_h2_kernel(const Con
                     }
             }
             __syncthreads();
+            if constexpr (KG == 2) {                 // the second group's sum on top, always in this order
+                if (wm == pass && kg == 1) {
+#pragma unroll
+                    for (int i = 0; i < 2 * RB; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            float* cw = cbase + (16 * i + 4 * g4) * BN + wn * 64 + 16 * j + r16;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) cw[r * BN] += acc[i][j][r] * a_inv;
+                        }
+                }
+                __syncthreads();
+            }
             constexpr int C4 = BN / 4, RPP = NTHR / C4, NPASS = PR / RPP, SW = NPASS < 4 ? NPASS : 4;
             static_assert(NPASS % SW == 0, "row sweeps in groups of SW");
             const int c4 = t % C4, rr = t / C4;

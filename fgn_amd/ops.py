@@ -38,8 +38,11 @@ GEMM_MATH = os.environ.get('FGN_GEMM_MATH', 'h2')
 # by row tile (fgn_x3_row_tile); template arguments: waves along M, 32-row blocks per wave, terms, LDS stages, 16x16x32 MFMA
 X3_KERNELS = {64: 'conv_pw_x3_kernel<2, 1, 6, 2, true>', 128: 'conv_pw_x3_kernel<2, 2, 6, 2, true>'}
 # by tile (fgn_h2_row_tile: 64 / 128 rows x 128 columns, 264 = 128 rows x 64 columns); template arguments: waves along M,
-# waves along N, 32-row blocks per wave, LDS stages, implicit-GEMM loader (3x3 / strided convolutions)
-H2_KERNELS = {64: 'conv_pw_h2_kernel<2, 2, 1, 2, %s>', 128: 'conv_pw_h2_kernel<2, 2, 2, 2, %s>', 264: 'conv_pw_h2_kernel<4, 1, 1, 2, %s>'}
+# waves along N, 32-row blocks per wave, LDS stages, implicit-GEMM loader (3x3 / strided convolutions), K-groups;
+# 1064 = the 64-row tile on two K-groups (fgn_h2_k_groups; also the forced tile code of gemm_h2 / conv2d_pair)
+H2_KERNELS = {64: 'conv_pw_h2_kernel<2, 2, 1, 2, %s, 1>', 128: 'conv_pw_h2_kernel<2, 2, 2, 2, %s, 1>',
+              264: 'conv_pw_h2_kernel<4, 1, 1, 2, %s, 1>', 1064: 'conv_pw_h2_kernel<2, 2, 1, 2, %s, 2>'}
+H2_BM_KG2 = 1064
 
 
 def x3_kernel(rows: int, cout: int, k: int, grp_rows: int = 0, grp_valid: int = 0) -> str:
@@ -48,8 +51,12 @@ def x3_kernel(rows: int, cout: int, k: int, grp_rows: int = 0, grp_valid: int = 
 
 
 def h2_kernel(rows: int, cout: int, k: int, grp_rows: int = 0, grp_valid: int = 0, im2col: bool = False) -> str:
-    """The same for conv_pw_h2_kernel."""
-    return H2_KERNELS.get(_lib.load().fgn_h2_row_tile(rows, cout, k, grp_rows, grp_valid), 'conv_pw_h2_kernel<?, %s>') % ('true' if im2col else 'false')
+    """The same for conv_pw_h2_kernel (the instance a launch with nothing forced runs on: tile and K-groups)."""
+    L = _lib.load()
+    tile = L.fgn_h2_row_tile(rows, cout, k, grp_rows, grp_valid)
+    if tile == 64 and L.fgn_h2_k_groups(rows, cout, k, grp_rows, grp_valid) == 2:
+        tile = H2_BM_KG2
+    return H2_KERNELS.get(tile, 'conv_pw_h2_kernel<?, %s>') % ('true' if im2col else 'false')
 
 
 class gemm_math:
@@ -537,7 +544,8 @@ def pack_h2(w: torch.Tensor) -> torch.Tensor:
 def gemm_h2(x: torch.Tensor, image: torch.Tensor, cout: int, shift: Optional[torch.Tensor] = None,
             residual: Optional[torch.Tensor] = None, relu: bool = False, groups: int = 1, grp_valid: Optional[int] = None,
             bm: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x [rows, K] (grouped: [groups, grp_rows, K]) times the ``pack_h2`` image -> [rows, cout] on conv_pw_h2_kernel."""
+    """x [rows, K] (grouped: [groups, grp_rows, K]) times the ``pack_h2`` image -> [rows, cout] on conv_pw_h2_kernel.
+    bm: 0 = the library's choice, 64 / 128 / 264 = that tile on one K-group, 1064 = 64 rows on two K-groups."""
     _chk(x, 'x')
     K = x.shape[-1]
     rows = x.numel() // K
@@ -653,10 +661,11 @@ def conv1x1_dual(x1: torch.Tensor, x2: torch.Tensor, layer: DualConvLayer, out: 
 
 
 def conv2d_pair(x0: torch.Tensor, x1: torch.Tensor, layer: ConvLayer, out0: Optional[torch.Tensor] = None,
-                out1: Optional[torch.Tensor] = None):
+                out1: Optional[torch.Tensor] = None, bm: int = 0):
     """The same convolution (weights, folded BN, ReLU) on two NHWC tensors of different geometry in ONE launch - the
     query map and the support maps of a backbone layer that strides over the spatial structure (3x3 / stride 2, the
-    1x1 / stride 2 shortcut, the stem).  Per tensor the arithmetic of ``conv2d`` without split-K.  -> (y0, y1)."""
+    1x1 / stride 2 shortcut, the stem).  Per tensor the arithmetic of ``conv2d`` without split-K.  -> (y0, y1).
+    bm != 0 (tests, tools): the implicit GEMM on conv_pw_h2_kernel with that tile code forced (``gemm_h2``)."""
     _chk(x0, 'x0')
     _chk(x1, 'x1')
     if x0.shape[3] != layer.cin or x1.shape[3] != layer.cin:
@@ -680,6 +689,15 @@ def conv2d_pair(x0: torch.Tensor, x1: torch.Tensor, layer: ConvLayer, out0: Opti
     rows = sum(o.shape[0] * o.shape[1] * o.shape[2] for o in outs)
     k = layer.kh * layer.kw * layer.cin
     span = abs(x0.data_ptr() - x1.data_ptr()) + max(x0.numel(), x1.numel()) * 4
+    if bm != 0:
+        if layer.wh is None or layer.cin == 4 or span >= 0x7fffff00 or rows * layer.cout >= (1 << 31):
+            raise _lib.FgnHipError('conv2d_pair: a forced tile code needs a layer packed for conv_pw_h2_kernel')
+        rc = L.fgn_conv2d_pair_h2_bm_nhwc_f32(_ptr(x0), x0.shape[0], x0.shape[1], x0.shape[2], _ptr(x1), x1.shape[0], x1.shape[1],
+                                              x1.shape[2], layer.wh.data_ptr(), _ptr(outs[0]), _ptr(outs[1]), _ptr(layer.scale),
+                                              _ptr(layer.shift), layer.cin, layer.cout, layer.cout_pad, layer.kh, layer.kw,
+                                              layer.stride, layer.pad, int(layer.relu), bm, _stream())
+        _lib.check(rc, 'fgn_conv2d_pair_h2_bm_nhwc_f32')
+        return outs[0], outs[1]
     if layer.wh is not None and layer.cin != 4 and span < 0x7fffff00 and rows * layer.cout < (1 << 31) and \
             L.fgn_h2_row_tile(rows, layer.cout, k, 0, 0) > 0:
         # the implicit GEMM of both tensors on conv_pw_h2_kernel

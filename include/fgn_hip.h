@@ -136,8 +136,11 @@ int fgn_winograd_gemm_x3_f32(const float* V, const void* U_x3, float* Mo, const 
  *   w_h2: [groups][K / 32][2 planes][cout_pad][32] f16 of the column-scaled weights (k order and chunk swizzle of w_x3),
  *         then [groups][cout_pad] f32 inverse column scales.  fgn_h2_image_bytes = the size of both.
  * Shapes: as the x3 entry points, and Cout 48..64 on a 64-column tile (fgn_h2_row_tile decides).  fgn_gemm_h2_f32: the direct entry (tests, tools);
- * bm 0 (= fgn_h2_row_tile) / 64 / 128 / 264 force the tile. */
+ * bm 0 (= fgn_h2_row_tile, fgn_h2_k_groups) / 64 / 128 / 264 force the tile on one K-group; 1064 = 64 rows on two K-groups
+ * (K / 32 even and >= 4).  fgn_h2_k_groups: 2 = the launch runs its 64-row tiles on two sets of four waves, each on every
+ * other K-tile (ungrouped launches of at most 256 tiles, one per CU, with an even and long enough K-tile count); 1 = one set. */
 size_t fgn_h2_image_bytes(int K, int npad, int n_groups);
+int fgn_h2_k_groups(long long M, int Cout, int K, int grp_rows, int grp_valid);
 int fgn_h2_row_tile(long long M, int Cout, int K, int grp_rows, int grp_valid);   /* 64 / 128: rows of a 128-column tile; 264: 128 rows x 64 columns (Cout 48..64); 0: use the f32 entry point */
 /* A 3x3 or 1x1 convolution of any stride / padding with folded scale / shift / ReLU on ONE or TWO NHWC tensors that share
  * the weights (x1 == NULL: one; two: the query map and the support maps of a backbone layer, fgn_conv2d_pair_nhwc_f32's
@@ -147,6 +150,10 @@ int fgn_h2_row_tile(long long M, int Cout, int K, int grp_rows, int grp_valid); 
 int fgn_conv2d_pair_h2_nhwc_f32(const float* x0, int n_img0, int H0, int W0, const float* x1, int n_img1, int H1, int W1,
                                 const void* w_h2, float* y0, float* y1, const float* scale, const float* shift, int Cin,
                                 int Cout, int cout_pad, int KH, int KW, int stride, int pad, int relu, void* stream);
+/* the same with the tile code forced (bm as for fgn_gemm_h2_f32; tests, tools) */
+int fgn_conv2d_pair_h2_bm_nhwc_f32(const float* x0, int n_img0, int H0, int W0, const float* x1, int n_img1, int H1, int W1,
+                                   const void* w_h2, float* y0, float* y1, const float* scale, const float* shift, int Cin,
+                                   int Cout, int cout_pad, int KH, int KW, int stride, int pad, int relu, int bm, void* stream);
 int fgn_gemm_h2_f32(const float* x, const void* w_h2, float* y, const float* shift, const float* residual, int rows, int K,
                     int Cout, int npad, int relu, int grp_rows, int grp_valid, int n_groups, int bm, void* stream);
 int fgn_conv1x1_h2_nhwc_f32(const float* x, const void* w_h2, float* y, const float* scale, const float* shift,

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """conv_pw_h2_kernel (two-f16-plane products) and conv_pw_x3_kernel (three-bf16-plane products) against the f32-MFMA kernels: error against fp64 and time per launch on
 the GEMM shapes of a cfg3 episode, the variants taking turns.  python tools/x3_probe.py [--reps 10]
+h2_bm64_kg2 = the 64-row tile on two K-groups (tile code 1064; skipped where K / 32 is odd or below 4); --im2col adds
+layer3.0's 3x3 / stride 2 convolution of the query map and the support maps as one implicit GEMM (6504 x 2304 -> 256).
 FGN_HIP_LIB=tools/micro/libfgn_hip_exp.so adds the instances that were measured and not chosen (128-row tiles, 16x16x32
 MFMA); FGN_HIP_LIB=tools/micro/libfgn_hip_x3ph.so --phases the phase clocks of one wave."""
 import argparse
@@ -25,7 +27,40 @@ SHAPES = [   # name, groups, rows per group (allocated), valid rows, K, N
     ('layer2 conv1 25916x512>128', 1, 25916, 25916, 512, 128),
     ('layer3 conv1 6504x1024>256', 1, 6504, 6504, 1024, 256),
     ('layer3 conv3 6504x256>1024', 1, 6504, 6504, 256, 1024),
+    # the 204-tile grid of layer3's conv1 at shallower K loops (--only kgsweep): where two K-groups start to pay
+    ('kgsweep 6504x512>256', 1, 6504, 6504, 512, 256),
+    ('kgsweep 6504x256>256', 1, 6504, 6504, 256, 256),
 ]
+
+
+def probe_im2col(dev, reps):
+    """layer3.0 conv2 (3x3 / stride 2, 256 -> 256) on the 1 x 100 x 167 query map and nine 32 x 32 support maps in one
+    launch: 4200 + 2304 = 6504 rows, 72 K-tiles, 204 tiles - one K-group against two."""
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(2)
+    c = 256
+    wt = torch.randn(c, c, 3, 3, generator=g) / (9 * c) ** 0.5
+    with ops.gemm_math('h2'):
+        layer = ops.pack_conv(wt, stride=2, pad=1, relu=False).to(dev)
+    xq, xs = torch.randn(1, 100, 167, c, generator=g).relu_(), torch.randn(9, 32, 32, c, generator=g).relu_()
+    buf = torch.cat([xq.reshape(-1), xs.reshape(-1)]).to(dev)
+    q_d, s_d = buf[:xq.numel()].view(xq.shape), buf[xq.numel():].view(xs.shape)
+    refs = [F.conv2d(x.permute(0, 3, 1, 2).double(), wt.double(), stride=2, padding=1).permute(0, 2, 3, 1) for x in (xq, xs)]
+    scale = max(r.abs().max().item() for r in refs)
+    rows = sum(r.shape[0] * r.shape[1] * r.shape[2] for r in refs)
+    rec = dict(shape='layer3.0 conv2 3x3/2 im2col %dx2304>256' % rows, gflop=2.0 * rows * 9 * c * c / 1e9)
+    fns = {}
+    for tag, bm in (('h2_bm64', 64), ('h2_bm64_kg2', 1064)):
+        o0, o1 = torch.zeros(refs[0].shape, device=dev), torch.zeros(refs[1].shape, device=dev)
+        fn = (lambda bm=bm, o0=o0, o1=o1: ops.conv2d_pair(q_d, s_d, layer, out0=o0, out1=o1, bm=bm))
+        fn()
+        torch.cuda.synchronize()
+        rec[tag] = dict(max_err=max((o.cpu().double() - r).abs().max().item() for o, r in ((o0, refs[0]), (o1, refs[1]))) / scale)
+        fns[tag] = fn
+    for k, us in timed_round_robin(fns, reps).items():
+        rec[k]['us'] = us
+        rec[k]['tflops_f32_equiv'] = round(rec['gflop'] / us * 1e-3, 1)
+    print(json.dumps(rec), flush=True)
 
 
 def timed_round_robin(fns: dict, reps: int, rounds: int = 5) -> dict:
@@ -57,10 +92,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--only', default='')
+    ap.add_argument('--im2col', action='store_true', help="layer3.0's 3x3 / stride 2 implicit GEMM, one K-group against two")
     ap.add_argument('--phases', action='store_true', help='phase clocks (FGN_HIP_LIB=tools/micro/libfgn_hip_x3ph.so)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     g = torch.Generator().manual_seed(1)
+    if args.im2col:
+        probe_im2col(dev, args.reps)
     for name, G, gr, valid, K, N in SHAPES:
         if args.only and args.only not in name:
             continue
@@ -75,8 +113,10 @@ def main():
         fns, outs = {}, {}
         # conv_pw_h2_kernel (three f16 products of scaled two-way splits): 64 / 128 rows
         imgh = ops.pack_h2(w)
-        for tag, bm in (('h2_bm64', 64), ('h2_bm128', 128)):
+        for tag, bm in (('h2_bm64', 64), ('h2_bm64_kg2', 1064), ('h2_bm128', 128)):
             if G > 1 and gr % (128 if bm == 128 else 64):
+                continue
+            if bm == 1064 and ((K // 32) % 2 or K // 32 < 4):
                 continue
             out = torch.zeros(G, gr, N, device=dev)
             fn = (lambda bm=bm, out=out: ops.gemm_h2(x, imgh, N, shift=shift, groups=G, grp_valid=valid, bm=bm, out=out))
