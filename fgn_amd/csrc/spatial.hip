@@ -240,6 +240,170 @@ extern "C" int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, 
 }
 
 // ----------------------------------------------------------------------------------
+// Supports from the source image behind the upload (BaseFewShotISEG.get_support, base_fst.py:1043-1167: get_crop with
+// reflected context, bicubic resize of the longer side to S, centre pad).  The arithmetic is the integer rule of
+// fgn_amd/fewshot_ds.py (cubic_taps / support_geometry / support_from_source) and the kernel agrees
+// with support_from_source bit for bit.
+//   tap of destination sample j on an axis of n_src -> n_dst samples (cubic convolution, A = -3/4):
+//     num = (2j+1) * n_src - n_dst, den = 2 * n_dst, i0 = floor(num / den), rem = num - i0 * den,
+//     u = (rem * 2048 + den) / (2 * den) (0..1024), v = 1024 - u; in units of 2^-32, int64:
+//     w(-1) = -3 u v^2, w(+1) = 5 v^3 - 9216 v^2 + 2^32, w(+2) = -3 u^2 v; W(k) = (w(k) + 2^20) >> 21,
+//     W(0) = 2048 - the other three; samples i0 - 1 .. i0 + 2 clamped into the crop.
+//   |W| sums to at most 2816 per axis, so |acc| <= 255 * 2816^2 < 2^31: the accumulators are int32, rows first
+//   (|row sum| <= 255 * 2816), which is exact and therefore the same number as the host's double sum.
+// The geometry of every instance - sizes, crop origin, placement, border mode, uploaded window - is a 16-int record the
+// kernel READS (no launch argument depends on it: one captured launch serves every support set).  As for the query
+// kernel a wave takes 64 consecutive pixels of one output row: instance, row, the record and the row's four y taps are
+// wave-uniform, the x taps are per lane.
+// ----------------------------------------------------------------------------------
+constexpr int SPP_REC_INTS = 16;      // H W y0 x0 ch cw nh nw top left reflect wy wx wh ww -
+constexpr int SPP_ACC_HALF = 1 << 21; // half of the weight sum 2048 * 2048
+
+struct CubicTap { int i0; int w[4]; };
+__device__ __forceinline__ CubicTap cubic_tap(int j, int n_src, int n_dst) {
+    const unsigned den = 2u * (unsigned)n_dst;
+    const unsigned nump = (2u * (unsigned)j + 1u) * (unsigned)n_src + (unsigned)n_dst;     // num + den, in [1, 2^30)
+    const unsigned q = nump / den;                                                         // i0 + 1
+    const unsigned rem = nump - q * den;
+    const long long u = (long long)((rem * 2048u + den) / (2u * den)), v = 1024 - u;
+    const long long one = 1ll << 32, half = 1ll << 20;
+    CubicTap t;
+    t.i0 = (int)q - 1;
+    t.w[0] = (int)((-3 * u * v * v + half) >> 21);
+    t.w[2] = (int)((5 * v * v * v - 9216 * v * v + one + half) >> 21);
+    t.w[3] = (int)((-3 * u * u * v + half) >> 21);
+    t.w[1] = 2048 - t.w[0] - t.w[2] - t.w[3];
+    return t;
+}
+
+// Position t of the crop's axis in the source frame -> index into the uploaded window [w_lo, w_lo + w_len) of an axis of
+// n samples, or -1 for "reads 0".  reflect: np.pad(mode='reflect') of any width = the periodic reflection of period
+// 2 (n - 1) (index 0 for n = 1); otherwise outside the image is 0.  The result is clamped into the window: the host
+// sends a window that holds every tap, a record that lies cannot make the kernel read outside its slot.
+__device__ __forceinline__ int spp_src_index(int t, int n, bool reflect, int w_lo, int w_len) {
+    if ((unsigned)t >= (unsigned)n) {
+        if (!reflect) return -1;
+        if (n == 1) {
+            t = 0;
+        } else {
+            const int p = 2 * (n - 1);
+            int m = t % p;
+            m = m < 0 ? m + p : m;
+            t = m < n ? m : p - m;
+        }
+    }
+    return min(max(t - w_lo, 0), w_len - 1);
+}
+
+// y [n,S,S,4] fp32 = u8hwc3_to_nhwc4_kernel of support_from_source's crop, m [n,S,S] = its mask as 0 / 1 bytes.  A lane
+// makes one output pixel: 16 taps x 3 image bytes and 16 mask bytes from four rows of the window (neighbouring lanes
+// share cache lines; the windows of an episode are a few hundred KB and stay in L2), three table lookups in LDS, one
+// 16-byte store (1 KB per wave, coalesced) and one mask byte (64 B per wave).  A pixel of the padding reads nothing.
+// An instance whose record is out of range (see ok below) is written as padding with an empty mask and not read.
+__global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_kernel(const uint8_t* __restrict__ src,
+                                                                           long long stride,
+                                                                           const uint8_t* __restrict__ msk,
+                                                                           long long mstride,
+                                                                           const int* __restrict__ recs,
+                                                                           const float* __restrict__ lut,
+                                                                           float4* __restrict__ y,
+                                                                           uint8_t* __restrict__ m, int S, int chunks,
+                                                                           int units) {
+    __shared__ float t[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += RESIZE_BLOCK) t[i] = lut[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int WAVES = RESIZE_BLOCK / 64;
+    const float4 pad = make_float4(t[0], t[256], t[512], 0.f);     // byte 0 through the table
+    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
+        const int r = u / chunks;                           // instance * S + row
+        const int chunk = u - r * chunks;
+        const int b = r / S, oy = r - b * S;
+        const int ox = chunk * 64 + lane;
+        if (ox >= S) continue;
+        const int* rc = recs + (size_t)b * SPP_REC_INTS;
+        const int H = rc[0], W = rc[1], y0 = rc[2], x0 = rc[3], ch = rc[4], cw = rc[5], nh = rc[6], nw = rc[7];
+        const int top = rc[8], left = rc[9], mode = rc[10], wy = rc[11], wx = rc[12], wh = rc[13], ww = rc[14];
+        const auto dim = [](int v) { return v >= 1 && v <= RESIZE_MAX_DIM; };
+        const bool ok = dim(H) && dim(W) && dim(ch) && dim(cw) && dim(nh) && dim(nw) && top >= 0 && left >= 0 &&
+                        nh <= S - top && nw <= S - left && (mode == 0 || mode == 1) &&
+                        y0 >= -2 * RESIZE_MAX_DIM && y0 < RESIZE_MAX_DIM && x0 >= -2 * RESIZE_MAX_DIM && x0 < RESIZE_MAX_DIM &&
+                        wy >= 0 && wx >= 0 && wh >= 1 && ww >= 1 && wh <= H - wy && ww <= W - wx &&
+                        (long long)wh * ww * 3 <= stride && (long long)wh * ww <= mstride;
+        float4* o = y + (size_t)r * S + ox;
+        uint8_t* om = m + (size_t)r * S + ox;
+        const int jy = oy - top, jx = ox - left;
+        if (!ok || jy < 0 || jy >= nh || jx < 0 || jx >= nw) {
+            *o = pad;
+            *om = 0;
+            continue;
+        }
+        const bool reflect = mode == 1;
+        const CubicTap ty = cubic_tap(jy, ch, nh), tx = cubic_tap(jx, cw, nw);
+        int cx[4], cm[4];                                   // window columns of the image taps / of the mask taps (-1: 0)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = x0 + min(max(tx.i0 - 1 + k, 0), cw - 1);
+            cx[k] = spp_src_index(c, W, reflect, wx, ww);
+            cm[k] = spp_src_index(c, W, false, wx, ww);
+        }
+        const uint8_t* img = src + (long long)b * stride;
+        const uint8_t* mk = msk + (long long)b * mstride;
+        int acc[3] = {0, 0, 0}, macc = 0;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int row = y0 + min(max(ty.i0 - 1 + a, 0), ch - 1);
+            const int ry = spp_src_index(row, H, reflect, wy, wh), rm = spp_src_index(row, H, false, wy, wh);
+            if (ry >= 0) {
+                const uint8_t* p = img + (size_t)ry * ww * 3;
+                int s[3] = {0, 0, 0};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (cx[k] >= 0) {
+                        s[0] += (int)p[cx[k] * 3] * tx.w[k];
+                        s[1] += (int)p[cx[k] * 3 + 1] * tx.w[k];
+                        s[2] += (int)p[cx[k] * 3 + 2] * tx.w[k];
+                    }
+                acc[0] += s[0] * ty.w[a];
+                acc[1] += s[1] * ty.w[a];
+                acc[2] += s[2] * ty.w[a];
+            }
+            if (rm >= 0) {
+                const uint8_t* p = mk + (size_t)rm * ww;
+                int s = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (cm[k] >= 0 && p[cm[k]]) s += tx.w[k];
+                macc += s * ty.w[a];
+            }
+        }
+        int v[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = min(max((acc[k] + SPP_ACC_HALF) >> 22, 0), 255);
+        *o = make_float4(t[v[0]], t[256 + v[1]], t[512 + v[2]], 0.f);
+        *om = macc > SPP_ACC_HALF ? 1 : 0;
+    }
+}
+
+extern "C" int fgn_support_from_source_f32(const unsigned char* src, long long src_stride_bytes,
+                                           const unsigned char* msk, long long msk_stride_bytes, const int* recs,
+                                           const float* lut, float* y, unsigned char* m, int n, int S,
+                                           hipStream_t stream) {
+    if (!src || !msk || !recs || !lut || !y || !m) return FGN_ERR_ARG;
+    if (n < 0 || S < 0 || S > RESIZE_MAX_DIM || src_stride_bytes < 0 || msk_stride_bytes < 0) return FGN_ERR_SHAPE;
+    if ((long long)n * S == 0) return FGN_OK;
+    const int chunks = cdiv(S, 64);
+    const long long units = (long long)n * S * chunks;
+    if (units > INT32_MAX - 4 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;       // (unit indices are int32, stride included)
+    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP);
+    hipLaunchKernelGGL(support_from_source_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes, msk,
+                       msk_stride_bytes, recs, lut, reinterpret_cast<float4*>(y), m, S, chunks, (int)units);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------
 // 3x3 / stride 2 / pad 1 max-pool, NHWC (mmdet ResNet stem; floor mode, -inf padding)
 // ----------------------------------------------------------------------------------
 __global__ void maxpool3x3s2_kernel(const float4* __restrict__ x, float4* __restrict__ y, int H, int W,

@@ -363,10 +363,15 @@ class _GraphedEpisode:
     ``pack_results`` may read."""
     CODE_KEYS = ('vec', 'S', 'cat_mean_mp')
 
+    SLOT_KEYS = ('qry_src', 'spp_src', 'spp_msk')       # rows of a configured capacity: a batch fills their fronts
+
     def __init__(self, model, ins: dict, img_shape, support_code, dev, phase_counter=None, source=None,
-                 results_at_source: bool = False):
+                 results_at_source: bool = False, spp_source=None):
         self.static = {k: torch.empty(v.shape, dtype=v.dtype, device=dev) for k, v in ins.items()}
         resize_to = None
+        if spp_source is not None:  # supports from their source images: window slots of the configured size, likewise
+            for k, cap in (('spp_src', spp_source['capacity']), ('spp_msk', spp_source['mcapacity'])):
+                self.static[k] = torch.empty((spp_source['n'], cap), dtype=torch.uint8, device=dev)
         if source is not None:      # source-size queries: the slot has the configured size, whatever this batch needs
             self.static['qry_src'] = torch.empty((source['B'], source['capacity']), dtype=torch.uint8, device=dev)
             resize_to = source['hw']
@@ -381,7 +386,9 @@ class _GraphedEpisode:
             self._copy_in(k, v)
         qry = lambda: self.static['qry_img'] if resize_to is None else \
             _SrcQuery(self.static['qry_src'], self.static['qry_src_hw'], *resize_to)
-        args = lambda: (qry(), self.static.get('spp_imgs'), self.static.get('spp_bboxes'),
+        spp = lambda: self.static.get('spp_imgs') if spp_source is None else \
+            _SrcSupports(self.static['spp_src'], self.static['spp_msk'], self.static['spp_rec'], spp_source['S'])
+        args = lambda: (qry(), spp(), self.static.get('spp_bboxes'),
                         self.static.get('spp_isegmaps'), self.img_shape, self.code)
         # eager pass first: packs the weights, sets kernel attributes, sizes the allocator pools
         # (the eager run that precedes the capture sends no phase mark: every ``detect_device`` call bumps the caller's
@@ -408,7 +415,7 @@ class _GraphedEpisode:
                 self.stamp_count = ops.arm_stamps(None)
 
     def _copy_in(self, k: str, v: torch.Tensor) -> None:
-        if k == 'qry_src':          # [B, what the batch needs] into the front of the slot rows; the rest is never read
+        if k in self.SLOT_KEYS:     # [B, what the batch needs] into the front of the slot rows; the rest is never read
             self.static[k][:, :v.shape[1]].copy_(v, non_blocking=True)
         else:
             self.static[k].copy_(v, non_blocking=True)
@@ -445,6 +452,35 @@ class _SrcQuery(NamedTuple):
 
     def to(self, dev, *a, **kw) -> '_SrcQuery':
         return _SrcQuery(self.src.to(dev, non_blocking=True), self.hw.to(dev, non_blocking=True), self.H, self.W)
+
+
+class _SrcSupports(NamedTuple):
+    """Support instances as windows of their source images on the way to ``_support_front`` (``spp_crop_to``): ``src``
+    uint8 [n, capacity], instance i's image window [wh_i, ww_i, 3] at the start of row i; ``msk`` uint8 [n, mask capacity],
+    its mask window; ``rec`` int32 [n,16], the records of ``fewshot_ds.support_geometry``; ``S`` the support size.  Stands
+    where the ``spp_imgs`` tensor stands; ``spp_isegmaps`` is None beside it (the kernel makes the masks)."""
+    src: torch.Tensor
+    msk: torch.Tensor
+    rec: torch.Tensor
+    S: int
+
+    @property
+    def shape(self) -> tuple:
+        return (self.src.shape[0], self.S, self.S, 3)
+
+    def to(self, dev, *a, **kw) -> '_SrcSupports':
+        return _SrcSupports(self.src.to(dev, non_blocking=True), self.msk.to(dev, non_blocking=True),
+                            self.rec.to(dev, non_blocking=True), self.S)
+
+
+class _StemReady(NamedTuple):
+    """An image batch that already is the NHWC4 fp32 input of the stem (``ops.support_from_source`` makes it together
+    with the masks): ``_stem_input`` hands ``x`` through."""
+    x: torch.Tensor
+
+    @property
+    def shape(self) -> tuple:
+        return tuple(self.x.shape[:3]) + (3,)
 
 
 class FGN(torch.nn.Module):
@@ -518,6 +554,9 @@ class FGN(torch.nn.Module):
         # bytes per image of the static source slot of a captured graph (``qry_resize_to`` under ``use_graphs``): the
         # graph key holds this size, not the source sizes, so every source that fits replays one graph
         self.query_source_capacity = 3 * 2_000_000
+        # the same for supports cut from their source images (``spp_crop_to`` under ``use_graphs``): bytes per INSTANCE of
+        # the image-window slot (the mask-window slot is a third of it); the default holds a 640 x 640 window
+        self.support_source_capacity = 3 * 640 * 640
         self.input_lut: Optional[np.ndarray] = None   # [3,256] fp32 normalisation table of uint8 images (set_input_norm)
         self._input_lut_dev = None                # (device, its copy there)
         self._streams: dict = {}                  # (role, caller stream) -> HIP stream: 'side', 'copy', 'upload'
@@ -864,8 +903,11 @@ class FGN(torch.nn.Module):
     def _stem_input(self, img: Union[torch.Tensor, '_SrcQuery']) -> torch.Tensor:
         """Image batch as given (host or device) -> the NHWC4 fp32 input of the stem on the current device: uint8 pixels
         [n,H,W,3] through the normalisation table, source-size pixels (``_SrcQuery``) resized and normalised in one
-        kernel, anything else cast to fp32 NCHW [n,3,H,W] and re-laid."""
+        kernel, a ready stem input (``_StemReady``: supports cut from their sources) as it is, anything else cast to fp32
+        NCHW [n,3,H,W] and re-laid."""
         dev = torch.device('cuda', torch.cuda.current_device())
+        if isinstance(img, _StemReady):
+            return img.x
         if isinstance(img, _SrcQuery):
             img = img.to(dev)
             return ops.resize_u8_to_nhwc4(img.src.contiguous(), img.hw.contiguous(), self._lut_on(dev), img.H, img.W)
@@ -946,6 +988,87 @@ class FGN(torch.nn.Module):
             else:
                 out.append(scale_boxes_yxyx(np.asarray(b), h, w, *hw))
         return out
+
+    def _source_supports(self, spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio: float = 0.8,
+                         crop_square: bool = True, graphed: bool = False) -> dict:
+        """The contract of ``spp_crop_to`` (host only, nothing is queued): S is an int, a table is set, ``spp_imgs`` is
+        a list of N*K uint8 images [h_i,w_i,3] (or B such lists), ``spp_isegmaps`` has the same nesting with every mask
+        at its image's size, ``spp_bboxes`` holds one YXYX box per instance, inside its image and not empty
+        (``fewshot_ds.support_geometry``), and every window fits the slot.  -> B, n = B*N*K, S, the records int32 [n,16],
+        the boxes in the S x S supports float32 (``support_from_instance``'s, computed here on the host) [B,N*K,4], the
+        image and mask windows as flat byte tensors, the largest of each and the slot sizes in bytes per instance."""
+        from . import fewshot_ds as fd
+        if isinstance(spp_crop_to, bool) or not isinstance(spp_crop_to, (int, np.integer)) or \
+                not 1 <= int(spp_crop_to) <= ops.RESIZE_MAX_DIM:
+            raise ValueError(f'spp_crop_to must be an int within 1..{ops.RESIZE_MAX_DIM} (the support size S), got '
+                             f'{spp_crop_to!r}')
+        S = int(spp_crop_to)
+        if self.input_lut is None:
+            raise ValueError('spp_crop_to needs the normalisation table: call set_input_norm first')
+        NK = self.n_ways * self.k_shots
+        nested = lambda v: isinstance(v, (list, tuple)) and len(v) > 0 and isinstance(v[0], (list, tuple))
+        if not isinstance(spp_imgs, (list, tuple)) or not isinstance(spp_isegmaps, (list, tuple)):
+            raise ValueError('spp_imgs / spp_isegmaps: with spp_crop_to, lists of N*K source images [h,w,3] and masks '
+                             '[h,w] (or B such lists)')
+        if nested(spp_imgs) != nested(spp_isegmaps):
+            raise ValueError('spp_imgs and spp_isegmaps must be nested alike')
+        groups = list(zip(spp_imgs, spp_isegmaps)) if nested(spp_imgs) else [(spp_imgs, spp_isegmaps)]
+        B = len(groups)
+        if len(spp_isegmaps) != len(spp_imgs) or any(len(g[0]) != NK or len(g[1]) != NK for g in groups):
+            raise ValueError(f'spp_imgs / spp_isegmaps: every support set holds N*K = {NK} images and as many masks')
+        host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        bb = host(spp_bboxes)
+        if bb.size != B * NK * 4 or bb.shape[-1] != 4:
+            raise ValueError(f'spp_bboxes: with spp_crop_to, [..,{NK},4] YXYX in the source frame for {B} support '
+                             f'set(s), got {list(bb.shape)}')
+        bb = bb.reshape(B * NK, 4)
+        recs, boxes, wins = [], [], []
+        for i, (im, mk) in enumerate((im, mk) for g in groups for im, mk in zip(*g)):
+            im, mk = host(im), host(mk)
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError(f'spp_imgs: with spp_crop_to every image is channels-last uint8 pixels [h,w,3], got '
+                                 f'{im.dtype} {list(im.shape)}')
+            if mk.shape != im.shape[:2]:
+                raise ValueError(f'spp_isegmaps: with spp_crop_to every mask is at its image\'s size '
+                                 f'{list(im.shape[:2])}, got {list(mk.shape)}')
+            rec, box = fd.support_geometry(im.shape[0], im.shape[1], bb[i], S, spp_fill_ratio, crop_square)
+            recs.append(rec); boxes.append(box); wins.append(fd.support_window(im, mk, rec))
+        need = max(w[0].size for w in wins)
+        mneed = max(w[1].size for w in wins)
+        capacity, mcapacity = need, mneed
+        if graphed:
+            capacity = int(self.support_source_capacity)
+            mcapacity = capacity // 3
+            if need > capacity or mneed > mcapacity:
+                raise ValueError(f'a support window of {need} bytes exceeds FGN.support_source_capacity = {capacity}: '
+                                 f'raise the attribute (the static window slot of the captured graph)')
+        return dict(B=B, n=B * NK, S=S, rec=torch.from_numpy(np.stack(recs)),
+                    boxes=torch.from_numpy(np.stack(boxes).reshape(B, NK, 4)),
+                    flats=[torch.from_numpy(w.reshape(-1)) for w, _ in wins],
+                    mflats=[torch.from_numpy(m.reshape(-1)) for _, m in wins], need=need, mneed=mneed,
+                    capacity=capacity, mcapacity=mcapacity, window_bytes=int(sum(w.size + m.size for w, m in wins)))
+
+    def _upload_supports(self, sp: dict, dev, into: Optional[dict] = None) -> tuple:
+        """The windows of ``_source_supports`` on the device, on the current stream: wh_i * ww_i * 3 image bytes and
+        wh_i * ww_i mask bytes of instance i into row i of ``into['spp_src']`` / ``into['spp_msk']`` (the static slots of
+        a captured graph) when those are given, else of fresh buffers as wide as the largest window of the batch - only
+        the window bytes cross the bus, and what lies behind a window in its row is never read."""
+        out = []
+        for k, flats, width, cap in (('spp_src', sp['flats'], sp['need'], sp['capacity']),
+                                     ('spp_msk', sp['mflats'], sp['mneed'], sp['mcapacity'])):
+            dst = None if into is None else into.get(k)
+            if dst is None or tuple(dst.shape) != (sp['n'], cap):
+                dst = torch.empty((sp['n'], width), dtype=torch.uint8, device=dev)
+            for i, flat in enumerate(flats):
+                dst[i, :flat.numel()].copy_(flat, non_blocking=True)
+            out.append(dst)
+        return tuple(out)
+
+    def _supports_on_device(self, sp: dict, dev) -> tuple:
+        """``_source_supports`` uploaded on the current stream, in the form ``_support_front`` takes: (``_SrcSupports``,
+        the boxes)."""
+        src, msk = self._upload_supports(sp, dev)
+        return _SrcSupports(src, msk, sp['rec'].to(dev, non_blocking=True), sp['S']), sp['boxes']
 
     # --- stages ---------------------------------------------------------------------------
     def extract_feat(self, img: Union[torch.Tensor, '_SrcQuery']) -> torch.Tensor:
@@ -1028,12 +1151,16 @@ class FGN(torch.nn.Module):
     @torch.no_grad()
     def forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                       spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
-                      **kwargs) -> Dict:
+                      spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, **kwargs) -> Dict:
         """The loss dict of one training step (fgn.py:125-185) as forward values - see ``fgn_amd.train``.  Keys and
         container types are the reference's: ``loss_rpn_cls`` / ``loss_rpn_bbox`` (lists of one tensor),
         ``loss_cls``, ``ACC-Unbalanced``, ``ACC-Balanced``, ``loss_bbox``, ``loss_mask``.  ``qry_resize_to``: source-size
-        query images, masks and boxes, as for ``simple_test``."""
+        query images, masks and boxes, as for ``simple_test``; ``spp_crop_to``: supports cut from their source images on
+        the device, as for ``simple_test``."""
         from . import train
+        sp = None
+        if spp_crop_to is not None:                       # (every contract error before anything is queued)
+            sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
         if qry_resize_to is not None:
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
             if not torch.cuda.is_available():
@@ -1043,6 +1170,11 @@ class FGN(torch.nn.Module):
             qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
             qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) for g in qry_isegmaps]
             img_shape = rs['img_shape']
+        if sp is not None:
+            if not torch.cuda.is_available():
+                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
+            (spp_imgs, spp_bboxes), spp_isegmaps = \
+                self._supports_on_device(sp, torch.device('cuda', torch.cuda.current_device())), None
         return train.forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps,
                                    qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals, spp_imgs=spp_imgs,
                                    spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps, img_shape=img_shape, **kwargs)
@@ -1051,7 +1183,8 @@ class FGN(torch.nn.Module):
     def simple_test(self, qry_img, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None, qry_bboxes_ignore=None,
                     spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, qry_child_idx=None, img_shape=None,
                     rescale=False, cats_ids_to_sample_real=None, spp_insts_ids=None, idx=None,
-                    support_code=None, qry_resize_to=None, results_at_source: bool = False, **kwargs) -> List[Dict]:
+                    support_code=None, qry_resize_to=None, results_at_source: bool = False, spp_crop_to=None,
+                    spp_fill_ratio: float = 0.8, crop_square: bool = True, **kwargs) -> List[Dict]:
         """Test without augmentation (fgn.py:187-303).  ``support_code`` (optional, from
         ``encode_supports``) replaces the three ``spp_*`` inputs.  ``qry_resize_to`` = (H, W) (or a [B,2] tensor of
         equal rows): ``qry_img`` holds decoded images at their SOURCE size - a uint8 tensor [B,h,w,3] or a list of B
@@ -1062,17 +1195,27 @@ class FGN(torch.nn.Module):
         ``dt_bboxes`` divided by the image's scale (``fewshot_ds.boxes_to_source``), ``dt_isegmaps_rle`` pasted at
         ``[h_b, w_b]`` from those boxes, the ground truth encoded and counted as given (no mask resize), ``qry_bboxes``
         as given, ``qry_img_shape`` = ``[h_b, w_b, 3]``; the detections, their scores and their order are those of the
-        call without it."""
+        call without it.  ``spp_crop_to`` = S (an int; with ``spp_fill_ratio`` and ``crop_square`` of the dataset): the
+        supports come as their SOURCE images - ``spp_imgs`` a list of N*K uint8 tensors [h_i,w_i,3] of any sizes (or B
+        such lists), ``spp_isegmaps`` the instances' masks [h_i,w_i] nested alike, ``spp_bboxes`` [..,N*K,4] YXYX in the
+        source frame - and crop, bicubic resize and centre pad of ``BaseFewShotISEG.get_support`` (base_fst.py:1043-1167)
+        run on the device in one launch (``fewshot_ds.support_from_source`` bit for bit); only the window
+        of each image that its crop reads is uploaded; needs ``set_input_norm``."""
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
+        sp = None
+        if spp_crop_to is not None and support_code is None:
+            sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square,
+                                       self._graphed())
         if qry_resize_to is None:
             dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
-                                      qry_isegmaps=qry_isegmaps)
+                                      qry_isegmaps=qry_isegmaps, spp_crop_to=sp)
             batch = qry_img.shape[0]
         else:
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps, self._graphed())
             dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
-                                      qry_isegmaps=qry_isegmaps, qry_resize_to=rs, results_at_source=results_at_source)
+                                      qry_isegmaps=qry_isegmaps, qry_resize_to=rs, results_at_source=results_at_source,
+                                      spp_crop_to=sp)
             batch, img_shape = rs['B'], rs['img_shape']
             if not results_at_source:
                 qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
@@ -1087,12 +1230,20 @@ class FGN(torch.nn.Module):
         """modify_input for the supports (fgn.py:79-108: H2D, YXYX -> XYXY on private copies), their
         backbone pass and the AG-RPN class vectors."""
         N, K = self.n_ways, self.k_shots
-        self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
-        spp = spp_imgs.to(dev, non_blocking=True).reshape(B * N * K, *spp_imgs.shape[-3:])    # (dtype: _stem_input)
+        if not isinstance(spp_imgs, _SrcSupports):
+            self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
         b = spp_bboxes.to(dev, torch.float32, non_blocking=True).reshape(B * N * K, 4)
         spp_xyxy = torch.stack((b[:, 1], b[:, 0], b[:, 3], b[:, 2]), 1)      # no host-built index tensor: graph-capturable
-        m = spp_isegmaps.to(dev, non_blocking=True).reshape(B * N * K, *spp_isegmaps.shape[-2:])
-        spp_masks = (m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)).contiguous()
+        if isinstance(spp_imgs, _SrcSupports):      # windows of the source images (``spp_crop_to``): crop, resize, pad
+            s = spp_imgs.to(dev)                    # and normalise in ONE launch, which makes the masks too
+            if s.src.shape[0] != B * N * K:
+                raise ValueError(f'{s.src.shape[0]} support instances for a batch of {B} x {N} x {K}')
+            y, spp_masks = ops.support_from_source(s.src, s.msk, s.rec, self._lut_on(dev), s.S)
+            spp = _StemReady(y)
+        else:
+            spp = spp_imgs.to(dev, non_blocking=True).reshape(B * N * K, *spp_imgs.shape[-3:])    # (dtype: _stem_input)
+            m = spp_isegmaps.to(dev, non_blocking=True).reshape(B * N * K, *spp_isegmaps.shape[-2:])
+            spp_masks = (m.view(torch.uint8) if m.dtype == torch.bool else m.to(torch.uint8)).contiguous()
         sc = dict(B=B, device=dev, spp_xyxy=spp_xyxy, spp_masks=spp_masks, spp=spp)
         if not defer_backbone:
             self._support_vectors(sc, self.extract_feat(sc.pop('spp')))         # [B*N*K,s,s,C]
@@ -1140,20 +1291,27 @@ class FGN(torch.nn.Module):
         sc['S'] = ops.conv2d(sc['cat_mean'], P['rel_s'])                              # Ws*support + bias
 
     @torch.no_grad()
-    def encode_supports(self, spp_imgs, spp_bboxes, spp_isegmaps) -> dict:
+    def encode_supports(self, spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to=None, spp_fill_ratio: float = 0.8,
+                        crop_square: bool = True) -> dict:
         """Support-feature caching across queries: everything the path derives
         from the support set alone - backbone pass, AG-RPN class vectors, count_spp, the support
         half of the relation conv - computed once on the current stream.  The returned code is
         passed as ``support_code=`` to ``simple_test`` / ``detect_device`` for every query that
         shares the support set (the reference recomputes it per query, fgn.py:212-215; results
-        are identical)."""
+        are identical).  ``spp_crop_to``: the supports come as their source images, as for ``simple_test``."""
+        sp = None
+        if spp_crop_to is not None:
+            sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
         if not torch.cuda.is_available():
             raise ops._lib.FgnHipError('FGN.encode_supports needs a GPU: the HIP path has no CPU fallback')
         dev = torch.device('cuda', torch.cuda.current_device())
         if self._packed_device != dev:
             self._pack(dev)
         self._sync_trained_shared()
-        B = spp_imgs.shape[0] if spp_imgs.dim() == 5 else 1
+        if sp is not None:
+            B, ((spp_imgs, spp_bboxes), spp_isegmaps) = sp['B'], (self._supports_on_device(sp, dev), None)
+        else:
+            B = spp_imgs.shape[0] if spp_imgs.dim() == 5 else 1
         sc = self._support_front(spp_imgs, spp_bboxes, spp_isegmaps, B, dev, torch.cuda.current_stream())
         self._support_back(sc, B, dev)
         return sc
@@ -1232,7 +1390,8 @@ class FGN(torch.nn.Module):
         return g
 
     def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None,
-                bits_out: Optional[list] = None, source: Optional[dict] = None, resize_masks: bool = True):
+                bits_out: Optional[list] = None, source: Optional[dict] = None, resize_masks: bool = True,
+                spp_source: Optional[dict] = None):
         """``modify_input`` (fgn.py:79-108): host -> device copies of one batch, on an upload stream so that they
         overlap the previous batch's kernels (a pinned source makes them asynchronous); the compute streams wait
         on one event.  Tensors already on the device pass through.  The ground-truth masks (copied to the GPU by
@@ -1244,11 +1403,14 @@ class FGN(torch.nn.Module):
         (``ops.mask_bits`` on the device copy made for the RLE, right behind it on the upload stream; None for an image
         without ground truth).  ``source`` (``_source_query``): the query comes at source size - its pixels go up as
         ``qry_src`` / ``qry_src_hw`` (``_upload_source``) and the masks are resized right behind their upload - unless
-        ``resize_masks`` is off (``results_at_source``): then they are encoded and bit-packed at source size, as given."""
+        ``resize_masks`` is off (``results_at_source``): then they are encoded and bit-packed at source size, as given.
+        ``spp_source`` (``_source_supports``): the supports come as windows of their source images - the windows go
+        up as the rows of ``spp_src`` / ``spp_msk`` (``_upload_supports``; records and boxes travel in ``tensors``)."""
         gts = None
         if gt_masks is not None:
             gts = [g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
-        on_host = [t for t in list(tensors.values()) + (gts or []) + (source['flats'] if source else [])
+        on_host = [t for t in list(tensors.values()) + (gts or []) + (source['flats'] if source else []) +
+                   (spp_source['flats'] + spp_source['mflats'] if spp_source else [])
                    if t is not None and not t.is_cuda]
         if not on_host and gts is None and source is None:
             return tensors, None, None
@@ -1267,6 +1429,8 @@ class FGN(torch.nn.Module):
             if source is not None:
                 sq = self._upload_source(source, dev, into)
                 out['qry_src'], out['qry_src_hw'] = sq.src, sq.hw
+            if spp_source is not None:
+                out['spp_src'], out['spp_msk'] = self._upload_supports(spp_source, dev, into)
             if gts is not None:
                 gt_out = []
                 for g in gts:
@@ -1283,7 +1447,8 @@ class FGN(torch.nn.Module):
     @torch.no_grad()
     def detect_device(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
                       qry_isegmaps=None, phase_counter=None, qry_resize_to=None,
-                      results_at_source: bool = False) -> list:
+                      results_at_source: bool = False, spp_crop_to=None, spp_fill_ratio: float = 0.8,
+                      crop_square: bool = True) -> list:
         """Everything up to the host wait: queues the host->device copies, the whole path and the device->host
         copies of the results.  Returns, per image, a dict of device tensors (det_bboxes [D,5], det_labels [D],
         n_dets [1], mask_prob, RLE bytes) plus the pinned host slot ``pack_results`` reads.
@@ -1299,9 +1464,18 @@ class FGN(torch.nn.Module):
         form, the dict of ``_source_query``, instead of checking twice.)  ``results_at_source`` (needs
         ``qry_resize_to``): the RLE strings, the ground-truth strings and the overlap counts are made at each image's
         source size (see ``simple_test``); the record's boxes stay in the network frame - ``pack_results`` divides them -
-        and every dict carries its image's ``src_hw``.  Part of the graph key: the two modes are different launches."""
+        and every dict carries its image's ``src_hw``.  Part of the graph key: the two modes are different launches.
+        ``spp_crop_to`` = S: the supports come as their source images (see ``simple_test``); their windows travel as
+        ``spp_src`` / ``spp_msk`` (uint8 [B*N*K, slot]) with the records ``spp_rec`` (int32 [B*N*K,16]) in place of
+        ``spp_imgs`` / ``spp_isegmaps``, the boxes are computed on the host, and a captured graph is keyed by the slot
+        size and S, not by any source, window or crop size.  (``simple_test`` hands over the dict of
+        ``_source_supports``.)  Ignored beside ``support_code``."""
         graphed = self._graphed()
-        source = None
+        source = spp_source = None
+        if spp_crop_to is not None and support_code is None:
+            spp_source = spp_crop_to if isinstance(spp_crop_to, dict) else \
+                self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square,
+                                      graphed)
         results_at_source = bool(results_at_source)
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
@@ -1318,7 +1492,9 @@ class FGN(torch.nn.Module):
             ins = {'qry_img': qry_img}
         else:
             ins = {}
-        if support_code is None:
+        if spp_source is not None:
+            ins.update(spp_bboxes=spp_source['boxes'], spp_rec=spp_source['rec'])
+        elif support_code is None:
             self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
             ins.update(spp_imgs=spp_imgs, spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps)
         if phase_counter is None:
@@ -1328,18 +1504,21 @@ class FGN(torch.nn.Module):
         into = None
         if graphed and self.use_packed_transfers and self._stream_for('upload', main) is main:
             ge0 = self._graphs.get(self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source,
-                                                   results_at_source))
+                                                   results_at_source, spp_source))
             into = ge0.static if ge0 is not None else None
         gt_bits = [] if (self.match_on_device and qry_isegmaps is not None) else None
         ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits, source=source,
-                                             resize_masks=not results_at_source)
+                                             resize_masks=not results_at_source, spp_source=spp_source)
         if uploaded is not None:
             main.wait_event(uploaded)
         if graphed:
-            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter, source, results_at_source)
+            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter, source, results_at_source,
+                                            spp_source)
         else:
             qry = ins['qry_img'] if source is None else _SrcQuery(ins['qry_src'], ins['qry_src_hw'], *source['hw'])
-            outs = self._detect_eager(qry, ins.get('spp_imgs'), ins.get('spp_bboxes'),
+            spp = ins.get('spp_imgs') if spp_source is None else \
+                _SrcSupports(ins['spp_src'], ins['spp_msk'], ins['spp_rec'], spp_source['S'])
+            outs = self._detect_eager(qry, spp, ins.get('spp_bboxes'),
                                       ins.get('spp_isegmaps'), img_shape, support_code, phase_counter=phase_counter,
                                       results_at_source=results_at_source)
         if results_at_source:
@@ -1372,7 +1551,7 @@ class FGN(torch.nn.Module):
         return bool(self.use_graphs and self.debug_trace is None and ops.PROFILE is None)
 
     def _graph_key(self, ins: dict, img_shape, support_code, phase_counter, main, dev, source=None,
-                   results_at_source: bool = False) -> tuple:
+                   results_at_source: bool = False, spp_source=None) -> tuple:
         hw = tuple((int(s[0]), int(s[1])) for s in img_shape)
         # everything the captured launch sequence depends on besides the weights (those drop ``_graphs`` when they
         # change): the paste semantic is an argument of the captured RLE kernel, the transfer arrangement decides which
@@ -1388,18 +1567,21 @@ class FGN(torch.nn.Module):
                 # that reads ``qry_src_hw``); a graph captured without it keeps its key
                 None if source is None else (source['B'], source['capacity'], source['hw']) +
                 (('at_source',) if results_at_source else ())) + \
+            (() if spp_source is None else     # supports from their sources: the window slots and S, no size of a batch
+             (('spp_source', spp_source['n'], spp_source['capacity'], spp_source['mcapacity'], spp_source['S']),)) + \
             tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items()
-                  if v is not None and k not in ('qry_src', 'qry_src_hw'))
+                  if v is not None and k not in ('qry_src', 'qry_src_hw', 'spp_src', 'spp_msk'))
 
     def _detect_graphed(self, ins: dict, img_shape, support_code, phase_counter=None, source=None,
-                        results_at_source: bool = False):
+                        results_at_source: bool = False, spp_source=None):
         main = torch.cuda.current_stream()
         dev = torch.device('cuda', torch.cuda.current_device())
-        key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source, results_at_source)
+        key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source, results_at_source,
+                              spp_source)
         ge = self._graphs.get(key)
         if ge is None:
             ge = self._graphs[key] = _GraphedEpisode(self, ins, img_shape, support_code, dev, phase_counter, source,
-                                                     results_at_source)
+                                                     results_at_source, spp_source)
         return ge, ge.run(self, ins, support_code, main)
 
     def _detect_eager(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,

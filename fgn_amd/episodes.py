@@ -82,14 +82,27 @@ def make_episode(idx: int, n_ways: int, k_shots: int, height: int, width: int,
 _LIST_KEYS = ('qry_cat_ids_real', 'qry_cat_ids', 'qry_bboxes', 'qry_isegmaps')
 
 
+_ONE_VALUE_KEYS = ('spp_crop_to', 'spp_fill_ratio', 'crop_square')     # arguments of the support cut: one per batch
+
+
 def collate(samples: list) -> dict:
     """Restatement of ``collate_fn_new`` (main.py:62-76): ragged query
-    annotations stay lists of tensors, everything else is stacked."""
+    annotations stay lists of tensors, everything else is stacked.  Supports that come as their source images
+    (``spp_source`` samples: lists of images and masks of differing sizes) stay lists, one per sample, and the
+    arguments of their cut travel as one plain value."""
     batch = {}
     for key in samples[0]:                       # default_collate of everything that stacks, in sample-dict order ...
         if key in _LIST_KEYS:
             continue
         vals = [s[key] for s in samples]
+        if key in _ONE_VALUE_KEYS:
+            if any(v != vals[0] for v in vals):
+                raise ValueError(f'{key} differs within a batch: {vals}')
+            batch[key] = vals[0]
+            continue
+        if isinstance(vals[0], list):
+            batch[key] = [[torch.as_tensor(v) for v in lst] for lst in vals]
+            continue
         if isinstance(vals[0], torch.Tensor):
             batch[key] = torch.stack(vals)
         else:

@@ -264,6 +264,184 @@ def resize_query(img: np.ndarray, bboxes_yxyx: np.ndarray, isegmaps: np.ndarray,
     return resize_image_u8(img, H, W), scale_boxes_yxyx(bboxes_yxyx, h, w, H, W), resize_masks(isegmaps, H, W)
 
 
+# ---- supports from the source image (BaseFewShotISEG.get_support, base_fst.py:1043-1167) ---------------------------
+# ``support_from_instance`` as ONE gather from the source image: crop (reflect context), bicubic resize of the longer
+# side to S and centre pad, with no padded copy of the image and no float.  The crop geometry is the golden-pinned
+# ``get_crop`` arithmetic; the resize is, like the query's, this project's own restatement in INTEGERS (imgaug's bicubic
+# is third party and pinned by no golden) so that support_from_source_kernel of csrc/spatial.hip agrees with
+# ``support_from_source`` bit for bit.  Against the float ``_resize`` of ``support_from_instance`` the
+# image bytes differ by at most 1 grey level and the masks agree (tests/test_spp_source_cpu.py).
+CUBIC_T_BITS = 10             # the fraction t = u / 1024
+CUBIC_W_BITS = 11             # weights in units of 1/2048 per axis, sum 2048, sum of magnitudes <= CUBIC_ABS_SUM
+CUBIC_ABS_SUM = 2816          # 2048 * 1.375 (t = 1/2 gives 1.25; rounding stays below): |acc| <= 255 * 2816^2 < 2^31
+SPP_REC_INTS = 16             # int32 per instance record
+SPP_REC_FIELDS = ('H', 'W', 'y0', 'x0', 'ch', 'cw', 'nh', 'nw', 'top', 'left', 'reflect', 'wy', 'wx', 'wh', 'ww')
+
+
+def cubic_taps(n_src: int, n_dst: int):
+    """Taps of one axis of the bicubic rule (cubic convolution, A = -3/4, half-pixel centres): destination sample j
+    blends source samples idx[j, 0..3] = i0-1 .. i0+2, clamped into the axis, with integer weights W[j, 0..3] that sum
+    to 2048.  num = (2j+1) * n_src - n_dst over den = 2 * n_dst is the source coordinate of j's centre, i0 its floor,
+    u the fraction rounded half up to 10 bits, v = 1024 - u; in units of 2^-32 (int64)
+        w(-1) = -3 u v^2, w(0) = 5 u^3 - 9216 u^2 + 2^32, w(+1) = 5 v^3 - 9216 v^2 + 2^32, w(+2) = -3 u^2 v,
+    each but w(0) rounded to 11 bits by a floor shift, W(0) = 2048 - the other three.  At equal size the rule is the
+    identity.  -> (idx int32 [n_dst,4], W int32 [n_dst,4])."""
+    _check_resize_dims(n_src, n_dst)
+    n_src, n_dst = int(n_src), int(n_dst)
+    j = np.arange(n_dst, dtype=np.int64)
+    den = 2 * n_dst
+    num = (2 * j + 1) * n_src - n_dst
+    i0 = num // den                                     # (floor division)
+    rem = num - i0 * den
+    u = (rem * (2 << CUBIC_T_BITS) + den) // (2 * den)
+    v = (1 << CUBIC_T_BITS) - u
+    one = np.int64(1) << 32
+    w_m1, w_p2 = -3 * u * v * v, -3 * u * u * v
+    w_p1 = 5 * v * v * v - 9216 * v * v + one
+    half, sh = np.int64(1) << (31 - CUBIC_W_BITS), 32 - CUBIC_W_BITS
+    W_m1, W_p1, W_p2 = (w_m1 + half) >> sh, (w_p1 + half) >> sh, (w_p2 + half) >> sh
+    W = np.stack([W_m1, (1 << CUBIC_W_BITS) - W_m1 - W_p1 - W_p2, W_p1, W_p2], 1).astype(np.int32)
+    idx = np.clip(i0[:, None] + np.arange(-1, 3), 0, n_src - 1).astype(np.int32)
+    return idx, W
+
+
+def reflect_index(t: np.ndarray, n: int) -> np.ndarray:
+    """Index into an axis of n samples of position t of its ``np.pad(mode='reflect')`` extension, for any t: the
+    periodic reflection of period 2 (n - 1); always 0 for n = 1 (numpy extends a single sample by its edge)."""
+    t = np.asarray(t, np.int64)
+    if n == 1:
+        return np.zeros_like(t)
+    p = 2 * (n - 1)
+    m = np.mod(t, p)
+    return np.where(m < n, m, p - m)
+
+
+def support_geometry(H: int, W: int, bbox_yxyx, S: int, spp_fill_ratio: float = 0.8, crop_square: bool = True):
+    """Everything ``support_from_instance`` decides before it touches a pixel, for an instance ``bbox_yxyx`` of an
+    [H,W] image: -> (int32 record, float32 box YXYX in the S x S support, bit-equal to ``support_from_instance``'s).
+    The record (``SPP_REC_FIELDS``, padded to ``SPP_REC_INTS``): the source size; the crop's origin (y0, x0) in the
+    source frame (negative where the context leaves the image) and its size (ch, cw), parity pixel included; the
+    resized size (nh, nw) and its place (top, left) in the support; ``reflect`` = 1 where ``get_crop`` pads by
+    reflection, 0 where by zeros (``crop_square=False`` with a non-zero offset); the WINDOW (wy, wx, wh, ww) = the
+    bounding rows and columns of the source that the crop reads after reflection - all of the image and of the mask
+    that ``support_from_source`` needs.  A box that is empty (after truncation to integers) or leaves its image raises
+    ValueError, as does a size outside 1..16384."""
+    H, W, S = int(H), int(W), int(S)
+    _check_resize_dims(H, W, S)
+    ymin, xmin, ymax, xmax = np.array(bbox_yxyx).astype(np.int32).reshape(4)
+    if not (0 <= ymin < ymax <= H and 0 <= xmin < xmax <= W):
+        raise ValueError(f'support box {[int(v) for v in (ymin, xmin, ymax, xmax)]} (YXYX) is empty or outside its '
+                         f'{H}x{W} image')
+    r = spp_offset_ratio(spp_fill_ratio)
+    w_off, h_off = int(np.floor((xmax - xmin) * r)), int(np.floor((ymax - ymin) * r))
+    # get_crop's arithmetic, without the pixels
+    h, w = ymax - ymin, xmax - xmin
+    reflect = True
+    if h_off == 0 and w_off == 0:
+        pads = ((0, int(h % 2)), (0, int(w % 2)))
+        box = (0, 0, h, w)
+    else:
+        if crop_square:
+            eh, ew = h + 2 * h_off, w + 2 * w_off
+            eh, ew = eh + eh % 2, ew + ew % 2
+            if eh > ew:
+                w_off += (eh - ew) // 2
+            elif ew > eh:
+                h_off += (ew - eh) // 2
+        else:
+            reflect = False
+        pads = ((h_off, h_off + (h + 2 * h_off) % 2), (w_off, w_off + (w + 2 * w_off) % 2))
+        box = (h_off, w_off, h_off + h, w_off + w)
+    box = np.array(box, dtype=np.int32).reshape(4)
+    y0, x0 = int(ymin) - int(pads[0][0]), int(xmin) - int(pads[1][0])
+    ch, cw = int(h) + int(sum(pads[0])), int(w) + int(sum(pads[1]))
+    _check_resize_dims(ch, cw)
+    if ch >= cw:
+        nh, nw = S, max(1, int(np.round(S * cw / ch)))
+    else:
+        nh, nw = max(1, int(np.round(S * ch / cw))), S
+    box_r = box.astype(np.float32) * np.array([nh / ch, nw / cw, nh / ch, nw / cw], np.float32)
+    top, left = (S - nh) // 2, (S - nw) // 2
+    box_out = (box_r + np.array([top, left, top, left], np.float32)).astype(np.float32)
+
+    def window(o, c, n):
+        t = o + np.arange(c, dtype=np.int64)
+        t = reflect_index(t, n) if reflect else t[(t >= 0) & (t < n)]
+        return int(t.min()), int(t.max()) - int(t.min()) + 1
+    (wy, wh), (wx, ww) = window(y0, ch, H), window(x0, cw, W)
+    rec = np.zeros(SPP_REC_INTS, np.int32)
+    rec[:len(SPP_REC_FIELDS)] = (H, W, y0, x0, ch, cw, nh, nw, top, left, int(reflect), wy, wx, wh, ww)
+    return rec, box_out
+
+
+def _spp_axis(o: int, n_crop: int, n_dst: int, n_src: int, reflect: bool, w_lo: int, w_len: int):
+    """Taps of one axis of ``support_from_source``: crop-frame taps (``cubic_taps``) + the crop's origin ``o``, mapped
+    into the source axis of ``n_src`` samples and expressed in the window [w_lo, w_lo + w_len); a tap that reads
+    nothing (zero mode, outside the image) gets index ``w_len`` - the zero sample the callers append.
+    -> (index into the window for the image, the same for the mask, weights)."""
+    idx, wts = cubic_taps(n_crop, n_dst)
+    t = idx.astype(np.int64) + o
+    inside = (t >= 0) & (t < n_src)
+    refl = reflect_index(t, n_src) - w_lo
+    raw = np.where(inside, t - w_lo, w_len)
+    if ((refl < 0) | (refl >= w_len)).any() if reflect else ((raw < 0) | (raw > w_len)).any():
+        raise ValueError('support_from_source: a tap leaves the window of support_geometry')
+    return (refl if reflect else raw), raw, wts.astype(np.int64)
+
+
+def _spp_gather(win: np.ndarray, iy, ix, wy, wx) -> np.ndarray:
+    """win [wh,ww,c] bytes -> int64 accumulators [nh,nw,c] = sum_a sum_b win[iy[:,a], ix[:,b]] * wy[:,a] * wx[:,b]; index
+    wh / ww reads 0."""
+    ext = np.zeros((win.shape[0] + 1, win.shape[1] + 1, win.shape[2]), np.int64)
+    ext[:-1, :-1] = win
+    cols = sum(ext[:, ix[:, b], :] * wx[None, :, b, None] for b in range(4))          # [wh+1,nw,c]
+    return sum(cols[iy[:, a]] * wy[:, a, None, None] for a in range(4))
+
+
+def support_from_source(img: np.ndarray, bbox_yxyx, isegmap: np.ndarray, spp_img_size: int,
+                        spp_fill_ratio: float = 0.8, crop_square: bool = True, geometry=None):
+    """``support_from_instance`` by the integer rule, as one gather from the window of ``support_geometry``: per output
+    pixel inside the resized crop the 4 x 4 taps of ``cubic_taps`` in the crop frame, moved by the crop's origin and
+    mapped into the source (``reflect_index``, or a zero outside the image in zero mode; the mask is always zero
+    outside); image byte = clamp((acc + 2^21) >> 22, 0, 255), mask set where acc > 2^21 (strictly: ``_resize`` thresholds
+    > 0.5); zeros in the padding.  img [H,W,3] uint8, isegmap [H,W] bool (or 0 / nonzero) ->
+    (crop [S,S,3] uint8, box float32 YXYX, mask [S,S] bool).  ``geometry``: the (record, box) of ``support_geometry``
+    when the caller has it already."""
+    img, isegmap = np.asarray(img), np.asarray(isegmap)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f'support_from_source: expects a uint8 [H,W,3] image, got {img.dtype} {list(img.shape)}')
+    if isegmap.shape != img.shape[:2]:
+        raise ValueError(f'support_from_source: the mask {list(isegmap.shape)} is not at its image\'s size '
+                         f'{list(img.shape[:2])}')
+    S = int(spp_img_size)
+    rec, box = geometry if geometry is not None else \
+        support_geometry(img.shape[0], img.shape[1], bbox_yxyx, S, spp_fill_ratio, crop_square)
+    g = dict(zip(SPP_REC_FIELDS, (int(v) for v in rec)))
+    iy, my, wy = _spp_axis(g['y0'], g['ch'], g['nh'], g['H'], bool(g['reflect']), g['wy'], g['wh'])
+    ix, mx, wx = _spp_axis(g['x0'], g['cw'], g['nw'], g['W'], bool(g['reflect']), g['wx'], g['ww'])
+    ys, xs = slice(g['wy'], g['wy'] + g['wh']), slice(g['wx'], g['wx'] + g['ww'])
+    half, sh = 1 << (2 * CUBIC_W_BITS - 1), 2 * CUBIC_W_BITS
+    acc = _spp_gather(img[ys, xs], iy, ix, wy, wx)
+    macc = _spp_gather((isegmap[ys, xs] != 0).astype(np.uint8)[:, :, None], my, mx, wy, wx)[:, :, 0]
+    assert np.abs(acc).max(initial=0) <= 255 * CUBIC_ABS_SUM ** 2
+    out = np.zeros((S, S, 3), np.uint8)
+    m = np.zeros((S, S), bool)
+    rows, cols = slice(g['top'], g['top'] + g['nh']), slice(g['left'], g['left'] + g['nw'])
+    out[rows, cols] = np.clip((acc + half) >> sh, 0, 255).astype(np.uint8)
+    m[rows, cols] = macc > half
+    return out, box, m
+
+
+def support_window(img: np.ndarray, isegmap: np.ndarray, rec: np.ndarray):
+    """The bytes of one instance that travel to the device: (image window [wh,ww,3] uint8, mask window [wh,ww] uint8
+    0/1), contiguous.  (A bool mask is copied as it is stored, 0 / 1 bytes, without a comparison.)"""
+    g = dict(zip(SPP_REC_FIELDS, (int(v) for v in rec)))
+    ys, xs = slice(g['wy'], g['wy'] + g['wh']), slice(g['wx'], g['wx'] + g['ww'])
+    m = isegmap[ys, xs]
+    m = np.ascontiguousarray(m) if m.dtype == np.bool_ else np.ascontiguousarray(m != 0)
+    return np.ascontiguousarray(img[ys, xs]), m.view(np.uint8)
+
+
 class SyntheticFewShotISEG(Dataset):
     def __init__(self, n_ways=3, k_shots=3, length=64, height=800, width=1333, spp_img_size=256, batch=4,
                  seed=1234, suffix='SYNTH_val_novel'):
@@ -325,16 +503,26 @@ class ClutteredCharsFewShotISEG(Dataset):
     query is NOT resized by the loader (``get_query``'s cv2.resize, base_fst.py:876-887) - ``qry_img`` [S,S,3],
     ``qry_isegmaps`` and ``qry_bboxes`` stay at source size and the sample carries ``qry_resize_to`` = (img_size,
     img_size) for a detector that resizes on the device (``FGN.simple_test(qry_resize_to=...)``); ``img_shape`` is the
-    network size.  Without it the samples are what they always were."""
+    network size.  Without it the samples are what they always were.
+    ``spp_source`` (needs ``raw_uint8``): no support crop is built by the loader (``get_support``'s crop, resize and pad,
+    base_fst.py:1043-1167) - ``spp_imgs`` is the list of the N*K instances' SOURCE images uint8 [h,w,3], ``spp_isegmaps``
+    the list of their masks [h,w] bool, ``spp_bboxes`` [N*K,4] their boxes YXYX in the source frame, and the sample
+    carries ``spp_crop_to`` = spp_img_size, ``spp_fill_ratio`` and ``crop_square`` for a detector that cuts the supports
+    on the device (``FGN.simple_test(spp_crop_to=...)``).  Off by default: the samples are then what they always were."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
                                std=(0.16037128865718842, 0.15775758028030396, 0.15985246002674103), n_cats=26)}
 
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
-                 spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None):
+                 spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None,
+                 spp_source=False):
         par = self.PARAMS[dataset]
         self.raw_uint8 = bool(raw_uint8)
+        self.spp_source = bool(spp_source)
+        if self.spp_source and not self.raw_uint8:
+            raise ValueError('spp_source needs raw_uint8=True: supports are cut from their source images by the detector, '
+                             'which takes decoded pixels')
         self.source_size = None if source_size is None else int(source_size)
         if self.source_size is not None and not self.raw_uint8:
             raise ValueError('source_size needs raw_uint8=True: source-size queries are resized by the detector, which '
@@ -401,6 +589,12 @@ class ClutteredCharsFewShotISEG(Dataset):
             for p in pick:
                 j, o = self.inst[p]
                 src = self.images[j]
+                if self.spp_source:                      # the instance as it is: image, box and mask at source size
+                    spp_imgs.append(torch.from_numpy(src['img'].copy()))
+                    spp_boxes.append(np.asarray(src['bboxes'][o], np.float32))
+                    spp_masks.append(src['isegmaps'][o].astype(bool))
+                    spp_ids.append(p)
+                    continue
                 crop, nb, m = support_from_instance(src['img'], src['bboxes'][o], src['isegmaps'][o],
                                                     self.spp_img_size, self.spp_fill_ratio)
                 spp_imgs.append(self._norm(crop)); spp_boxes.append(nb); spp_masks.append(m); spp_ids.append(p)
@@ -412,9 +606,9 @@ class ClutteredCharsFewShotISEG(Dataset):
             'qry_cat_ids': mapping[im['cat_ids'][keep]].astype(np.int64),
             'qry_bboxes': im['bboxes'][keep].astype(np.float32),
             'qry_isegmaps': im['isegmaps'][keep].astype(bool),
-            'spp_imgs': torch.stack(spp_imgs),
+            'spp_imgs': spp_imgs if self.spp_source else torch.stack(spp_imgs),
             'spp_bboxes': np.stack(spp_boxes).astype(np.float32),
-            'spp_isegmaps': np.stack(spp_masks).astype(bool),
+            'spp_isegmaps': spp_masks if self.spp_source else np.stack(spp_masks).astype(bool),
             'cats_ids_to_sample_real': real,
             'cats_ids_to_sample': np.arange(len(real), dtype=np.int64),
             'spp_insts_ids': np.asarray(spp_ids, np.int64),
@@ -422,6 +616,8 @@ class ClutteredCharsFewShotISEG(Dataset):
         }
         if self.source_size is not None:
             sample['qry_resize_to'] = np.array([self.img_size, self.img_size], dtype=np.int32)
+        if self.spp_source:
+            sample.update(spp_crop_to=int(self.spp_img_size), spp_fill_ratio=float(self.spp_fill_ratio), crop_square=True)
         return sample
 
     evaluate = SyntheticFewShotISEG.evaluate

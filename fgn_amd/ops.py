@@ -1098,6 +1098,44 @@ def resize_masks(masks: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return out
 
 
+SPP_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.SPP_REC_INTS: int32 per instance record
+
+
+def support_from_source(src: torch.Tensor, msk: torch.Tensor, recs: torch.Tensor, lut: torch.Tensor, S: int):
+    """Image and mask windows of n support instances -> (the NHWC4 fp32 stem input [n,S,S,4], the support masks
+    uint8 0/1 [n,S,S]): ``u8hwc3_to_nhwc4`` of ``fewshot_ds.support_from_source``'s crop and its mask, bit for bit, in
+    one launch.  ``src`` uint8 [n, capacity]: instance i's window [wh_i, ww_i, 3] at the start of row i; ``msk`` uint8
+    [n, mask capacity]: its mask window [wh_i, ww_i] (nonzero = set); ``recs`` int32 [n,16] ON THE DEVICE: the records
+    of ``fewshot_ds.support_geometry``, read by the kernel (the launch is the same for every support set).  An instance
+    whose record is out of range or whose window exceeds a capacity comes out as padding with an empty mask."""
+    _chk(src, 'src', torch.uint8)
+    _chk(msk, 'msk', torch.uint8)
+    _chk(recs, 'recs', torch.int32)
+    _chk(lut, 'lut')
+    n = src.shape[0] if src.dim() == 2 else -1
+    if n < 0 or msk.dim() != 2 or msk.shape[0] != n or tuple(recs.shape) != (n, SPP_REC_INTS) or \
+            msk.device != src.device or recs.device != src.device:
+        raise _lib.FgnHipError('support_from_source: expects src [n,capacity], msk [n,mask capacity] and recs [n,16] on '
+                               'one device')
+    if tuple(lut.shape) != (3, 256) or lut.device != src.device:
+        raise _lib.FgnHipError('support_from_source: lut must be [3,256] on the device of src')
+    S = int(S)
+    if not 0 <= S <= RESIZE_MAX_DIM:
+        raise _lib.FgnHipError(f'support_from_source: S must be within 0..{RESIZE_MAX_DIM}, got {S}')
+    y = torch.empty((n, S, S, 4), device=src.device, dtype=torch.float32)
+    m = torch.empty((n, S, S), device=src.device, dtype=torch.uint8)
+    if y.numel() == 0:                  # (an empty tensor has no address to hand over)
+        return y, m
+    if src.shape[1] == 0:
+        src = src.new_zeros((n, 1))     # (capacity 0: every instance is refused by the kernel; it needs an address only)
+    if msk.shape[1] == 0:
+        msk = msk.new_zeros((n, 1))
+    _lib.check(_lib.load().fgn_support_from_source_f32(_ptr(src), int(src.shape[1]), _ptr(msk), int(msk.shape[1]),
+                                                       _ptr(recs), _ptr(lut), _ptr(y), _ptr(m), n, S, _stream()),
+               'fgn_support_from_source_f32')
+    return y, m
+
+
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x, 'x')
     n, h, w, c = x.shape

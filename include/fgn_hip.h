@@ -243,6 +243,29 @@ int fgn_resize_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_strid
  * weighted sum of the four taps reaches half (cv2.resize(m.astype(uint8)).astype(bool)). */
 int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, int G, int h, int w, int H, int W, void* stream);
 
+/* Supports from the source image behind the upload (BaseFewShotISEG.get_support, base_fst.py:1043-1167: get_crop with
+ * reflected context, bicubic resize of the longer side to S, centre pad): one launch for all n = B * N * K instances of
+ * a batch.  The arithmetic is the integer rule of fgn_amd.fewshot_ds (cubic_taps: cubic convolution A = -3/4, half-pixel
+ * centres, 10-bit fraction, 11-bit weights, taps clamped into the crop; support_geometry; a restatement of imgaug's
+ * bicubic that no reference golden pins) and the outputs agree with support_from_source bit for bit.
+ *   src  instance i's image window [wh_i][ww_i][3] bytes at src + i * src_stride_bytes (no alignment needed)
+ *   msk  its mask window [wh_i][ww_i] bytes (nonzero = set) at msk + i * msk_stride_bytes
+ *   recs int32 [n][16], read ON THE DEVICE: {H, W, y0, x0, ch, cw, nh, nw, top, left, reflect, wy, wx, wh, ww, -} =
+ *        source size, crop origin in the source frame (may be negative) and crop size, resized size and its place in
+ *        the S x S support, border mode (1: periodic reflection of period 2 (n - 1), 0: zeros), and the window - the rows
+ *        [wy, wy + wh) and columns [wx, wx + ww) of the source that were uploaded.  No launch argument depends on a
+ *        source, window or crop size: one captured launch serves every support set.
+ *   y    [n][S][S][4] fp32 = fgn_u8hwc3_to_nhwc4_f32 of the support crops (the padding is byte 0 through the table)
+ *   m    [n][S][S] 0 / 1 bytes: the support masks (always zero outside the image and in the padding)
+ * Every source index is clamped into the window.  An instance whose record is out of range - a size outside 1..16384,
+ * nh / nw / top / left that do not fit S, an origin beyond +-2 * 16384, a window outside its image or larger than its
+ * slot (wh * ww * 3 > src_stride_bytes or wh * ww > msk_stride_bytes) - is written as padding with an empty mask and
+ * none of its slot is read.  A null pointer is FGN_ERR_ARG; negative n, S or strides, or S > 16384, FGN_ERR_SHAPE; an
+ * empty output FGN_OK with no launch. */
+int fgn_support_from_source_f32(const unsigned char* src, long long src_stride_bytes, const unsigned char* msk,
+                                long long msk_stride_bytes, const int* recs, const float* lut, float* y,
+                                unsigned char* m, int n, int S, void* stream);
+
 /* 3x3/2 pad 1 max-pool of the ResNet stem */
 int fgn_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n_img, int H, int W, int C, void* stream);
 
