@@ -240,6 +240,235 @@ extern "C" int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, 
 }
 
 // ----------------------------------------------------------------------------------
+// Query augmentation behind the upload (BaseFewShotISEG.augment_with_imgaug, base_fst.py:735-770, on the geometric half
+// of natural_fst.py:18-35 and its ChannelShuffle), composed with the resize above into ONE bilinear gather from the
+// source image.  The arithmetic is the integer rule of fgn_amd/fewshot_ds.py (query_augment_record / augment_image_u8 /
+// augment_masks) and both kernels agree with those host functions bit for bit.
+//   record of an image, 16 int32: h w kind flip border perm c00 c01 c10 c11 c02(lo,hi) c12(lo,hi) - -
+//   kind 0: the taps of resize_tap, of column W-1-ox under flip.
+//   kind 1: U = c00*ox + c01*oy + c02, V = c10*ox + c11*oy + c12 in int64, units of 2^-20 source samples;
+//           i0 = U >> 20, f = U & (2^20-1), w1 = (f + 256) >> 9, w0 = 2048 - w1; taps i0, i0+1 (and j0, j0+1);
+//           a tap outside the image reads its symmetric extension (border 1: r = k mod 2n, r < n ? r : 2n-1-r) or 0.
+//   |c00|,|c01|,|c10|,|c11| <= 2^26 and |c02|,|c12| <= 2^40, so |U| < 2^42 and i0 fits int32.
+// As for the resize a wave takes 64 consecutive lane items of one output row: the record, the kind and the row terms
+// c01*oy + c02, c11*oy + c12 are wave-uniform, a lane adds one 32x32->64 multiply per axis.
+// ----------------------------------------------------------------------------------
+constexpr int AUG_REC_INTS = 16;
+constexpr int AUG_FRAC_BITS = 20;
+constexpr int AUG_LIN_MAX = 1 << 26;
+constexpr long long AUG_OFF_MAX = 1ll << 40;
+
+struct AugRec {
+    int h, w, kind, flip, border, perm, c00, c01, c10, c11;
+    long long c02, c12;
+    bool ok;                                  // every field inside its set: the only records a kernel reads pixels for
+};
+__device__ __forceinline__ AugRec aug_record(const int* __restrict__ rc) {
+    AugRec r;
+    r.h = rc[0]; r.w = rc[1]; r.kind = rc[2]; r.flip = rc[3]; r.border = rc[4]; r.perm = rc[5];
+    r.c00 = rc[6]; r.c01 = rc[7]; r.c10 = rc[8]; r.c11 = rc[9];
+    r.c02 = (long long)(((unsigned long long)(unsigned)rc[11] << 32) | (unsigned)rc[10]);
+    r.c12 = (long long)(((unsigned long long)(unsigned)rc[13] << 32) | (unsigned)rc[12]);
+    const auto lin = [](int v) { return v >= -AUG_LIN_MAX && v <= AUG_LIN_MAX; };
+    const auto off = [](long long v) { return v >= -AUG_OFF_MAX && v <= AUG_OFF_MAX; };
+    r.ok = r.h >= 1 && r.h <= RESIZE_MAX_DIM && r.w >= 1 && r.w <= RESIZE_MAX_DIM && (r.kind == 0 || r.kind == 1) &&
+           (r.flip == 0 || r.flip == 1) && (r.border == 0 || r.border == 1) && r.perm >= 0 && r.perm <= 5 &&
+           lin(r.c00) && lin(r.c01) && lin(r.c10) && lin(r.c11) && off(r.c02) && off(r.c12);
+    return r;
+}
+
+// Taps of one axis of n samples at coordinate U (kind 1): indices into the axis, or -1 for "reads 0".
+__device__ __forceinline__ ResizeTap aug_tap(long long U, int n, bool symmetric) {
+    const int k = (int)(U >> AUG_FRAC_BITS);
+    const int f = (int)(U & ((1ll << AUG_FRAC_BITS) - 1));
+    ResizeTap t;
+    t.w1 = (f + 256) >> 9;
+    t.w0 = 2048 - t.w1;
+    if ((unsigned)k < (unsigned)(n - 1)) {                  // both taps inside (the common case)
+        t.i0 = k;
+        t.i1 = k + 1;
+    } else if (symmetric) {
+        const int p = 2 * n;
+        int r = k % p;
+        r = r < 0 ? r + p : r;
+        const int r1 = r + 1 == p ? 0 : r + 1;
+        t.i0 = r < n ? r : p - 1 - r;
+        t.i1 = r1 < n ? r1 : p - 1 - r1;
+    } else {
+        t.i0 = (unsigned)k < (unsigned)n ? k : -1;
+        t.i1 = (unsigned)(k + 1) < (unsigned)n ? k + 1 : -1;
+    }
+    return t;
+}
+
+__device__ __forceinline__ int aug_pick(const int v[3], int p) { return p == 0 ? v[0] : (p == 1 ? v[1] : v[2]); }
+
+// Source images as for resize_u8hwc3_to_nhwc4_kernel, records from the DEVICE array recs[b] (no launch argument depends
+// on a source size or on the augmentation) -> y [n,H,W,4] fp32 = u8hwc3_to_nhwc4_kernel of augment_image_u8's image:
+// channel c of the output is table c of byte order[c] of the blended pixel.  A lane makes one output pixel: 4 taps x 3
+// bytes - for kind 1 along a slanted line through the source (at 10 degrees a wave's 64 pixels span about 11 source
+// rows, the gathers are served by L2) - three table lookups in LDS, one 16-byte store.  A record out of range, or an
+// image that does not fit its slot, is written as zeros and none of its bytes are read.
+__global__ __launch_bounds__(RESIZE_BLOCK) void augment_u8hwc3_to_nhwc4_kernel(const uint8_t* __restrict__ src,
+                                                                               long long stride,
+                                                                               const int* __restrict__ recs,
+                                                                               const float* __restrict__ lut,
+                                                                               float4* __restrict__ y, int H, int W,
+                                                                               int chunks, int units) {
+    __shared__ float t[3 * 256];
+    for (int i = threadIdx.x; i < 3 * 256; i += RESIZE_BLOCK) t[i] = lut[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int WAVES = RESIZE_BLOCK / 64;
+    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
+        const int r = u / chunks;                           // image * H + row
+        const int chunk = u - r * chunks;
+        const int b = r / H, oy = r - b * H;
+        const AugRec g = aug_record(recs + (size_t)b * AUG_REC_INTS);
+        const int ox = chunk * 64 + lane;
+        if (ox >= W) continue;
+        float4* o = y + (size_t)r * W + ox;
+        if (!g.ok || (long long)g.h * g.w * 3 > stride) {
+            *o = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        ResizeTap ty, tx;
+        if (g.kind == 0) {
+            ty = resize_tap(oy, g.h, H);
+            tx = resize_tap(g.flip ? W - 1 - ox : ox, g.w, W);
+        } else {
+            const long long ru = (long long)g.c01 * oy + g.c02, rv = (long long)g.c11 * oy + g.c12;     // wave-uniform
+            tx = aug_tap(ru + (long long)g.c00 * ox, g.w, g.border == 1);
+            ty = aug_tap(rv + (long long)g.c10 * ox, g.h, g.border == 1);
+        }
+        const uint8_t* img = src + (long long)b * stride;
+        int acc[3] = {0, 0, 0};
+        const int iy[2] = {ty.i0, ty.i1}, wy[2] = {ty.w0, ty.w1};
+        const int ix[2] = {tx.i0, tx.i1}, wx[2] = {tx.w0, tx.w1};
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            if (iy[a] < 0) continue;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                if (ix[c] < 0) continue;
+                const uint8_t* p = img + (unsigned)((iy[a] * g.w + ix[c]) * 3);     // (< 3 * 16384^2: 32-bit offset, uniform base)
+                const int wgt = wy[a] * wx[c];
+                acc[0] += (int)p[0] * wgt;
+                acc[1] += (int)p[1] * wgt;
+                acc[2] += (int)p[2] * wgt;
+            }
+        }
+        int v[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = (acc[k] + RESIZE_HALF) >> 22;
+        // itertools.permutations(range(3))[perm] = (p0, p1, p2), two bits each
+        const int p0 = (0xA50 >> (2 * g.perm)) & 3, p1 = (0x489 >> (2 * g.perm)) & 3, p2 = (0x126 >> (2 * g.perm)) & 3;
+        *o = make_float4(t[aug_pick(v, p0)], t[256 + aug_pick(v, p1)], t[512 + aug_pick(v, p2)], 0.f);
+    }
+}
+
+extern "C" int fgn_augment_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stride_bytes, const int* recs,
+                                               const float* lut, float* y, int n_img, int H, int W,
+                                               hipStream_t stream) {
+    if (!src || !recs || !lut || !y) return FGN_ERR_ARG;
+    if (n_img < 0 || H < 0 || W < 0 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM || src_stride_bytes < 0)
+        return FGN_ERR_SHAPE;
+    if ((long long)n_img * H * W == 0) return FGN_OK;
+    const int chunks = cdiv(W, 64);
+    const long long units = (long long)n_img * H * chunks;
+    if (units > INT32_MAX - 4 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;       // (unit indices are int32, stride included)
+    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP);
+    hipLaunchKernelGGL(augment_u8hwc3_to_nhwc4_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes,
+                       recs, lut, reinterpret_cast<float4*>(y), H, W, chunks, (int)units);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// Masks [G,h,w] (bool or bytes: nonzero = set) of ONE image -> [G,H,W] 0/1 bytes by the taps of its record rec (device,
+// 16 int32) on 0/1 values, set where acc >= 2^21; a tap outside the image is 0 whatever the record's border.  Lanes,
+// dword stores and bytewise ends as in resize_mask_u8_kernel.  A record out of range, or one for another source size
+// than (h, w), gives empty masks and nothing is read.
+__global__ __launch_bounds__(RESIZE_BLOCK) void augment_mask_u8_kernel(const uint8_t* __restrict__ src,
+                                                                       uint8_t* __restrict__ dst,
+                                                                       const int* __restrict__ rec, int h, int w,
+                                                                       int H, int W, int chunks, int units) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    constexpr int WAVES = RESIZE_BLOCK / 64;
+    const AugRec g = aug_record(rec);
+    const bool ok = g.ok && g.h == h && g.w == w;
+    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
+        const int r = u / chunks;                           // mask * H + row
+        const int chunk = u - r * chunks;
+        const int m = r / H, oy = r - m * H;
+        uint8_t* row = dst + (size_t)r * W;
+        const int lead = (int)(reinterpret_cast<uintptr_t>(row) & 3u);      // bytes of the row's first dword before it
+        const int x_lo = (chunk * 64 + lane) * 4 - lead;
+        if (x_lo >= W) continue;
+        unsigned word = 0;
+        const uint8_t* base = src + (size_t)m * h * w;      // (wave-uniform; offsets below are 32-bit: h * w <= 2^28)
+        if (ok && g.kind == 0) {                            // the resize kernel's body, columns reversed under flip
+            const ResizeTap ty = resize_tap(oy, h, H);
+            const uint8_t* r0 = base + (size_t)ty.i0 * w;
+            const uint8_t* r1 = base + (size_t)ty.i1 * w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ox = x_lo + k;
+                if (ox < 0 || ox >= W) continue;
+                const ResizeTap tx = resize_tap(g.flip ? W - 1 - ox : ox, w, W);
+                const int acc = (r0[tx.i0] ? ty.w0 * tx.w0 : 0) + (r0[tx.i1] ? ty.w0 * tx.w1 : 0) +
+                                (r1[tx.i0] ? ty.w1 * tx.w0 : 0) + (r1[tx.i1] ? ty.w1 * tx.w1 : 0);
+                word |= (acc >= RESIZE_HALF ? 1u : 0u) << (8 * k);
+            }
+        } else if (ok) {
+            const long long ru = (long long)g.c01 * oy + g.c02, rv = (long long)g.c11 * oy + g.c12;     // wave-uniform
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ox = x_lo + k;
+                if (ox < 0 || ox >= W) continue;
+                const ResizeTap tx = aug_tap(ru + (long long)g.c00 * ox, w, false);
+                const ResizeTap ty = aug_tap(rv + (long long)g.c10 * ox, h, false);
+                const int iy[2] = {ty.i0, ty.i1}, wy[2] = {ty.w0, ty.w1};
+                const int ix[2] = {tx.i0, tx.i1}, wx[2] = {tx.w0, tx.w1};
+                int acc = 0;
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int c = 0; c < 2; ++c)
+                        if (iy[a] >= 0 && ix[c] >= 0 && base[(unsigned)(iy[a] * w + ix[c])]) acc += wy[a] * wx[c];
+                word |= (acc >= RESIZE_HALF ? 1u : 0u) << (8 * k);
+            }
+        }
+        if (x_lo >= 0 && x_lo + 4 <= W) {
+            *reinterpret_cast<unsigned*>(row + x_lo) = word;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x_lo + k >= 0 && x_lo + k < W) row[x_lo + k] = (uint8_t)((word >> (8 * k)) & 1u);
+        }
+    }
+}
+
+extern "C" int fgn_augment_mask_u8(const unsigned char* src, unsigned char* dst, const int* rec, int G, int h, int w,
+                                   int H, int W, hipStream_t stream) {
+    if (!src || !dst || !rec) return FGN_ERR_ARG;
+    if (G < 0 || h < 0 || w < 0 || H < 0 || W < 0 || h > RESIZE_MAX_DIM || w > RESIZE_MAX_DIM || H > RESIZE_MAX_DIM ||
+        W > RESIZE_MAX_DIM)
+        return FGN_ERR_SHAPE;
+    if ((long long)G * H * W == 0) return FGN_OK;
+    if (h == 0 || w == 0) return FGN_ERR_SHAPE;               // (pixels to make and none to make them of)
+    const int chunks = cdiv(W + 3, 256);
+    const long long units = (long long)G * H * chunks;
+    if (units > INT32_MAX - 16 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;      // (unit indices are int32, stride included)
+    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP * 4);
+    hipLaunchKernelGGL(augment_mask_u8_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, dst, rec, h, w, H, W,
+                       chunks, (int)units);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------
 // Supports from the source image behind the upload (BaseFewShotISEG.get_support, base_fst.py:1043-1167: get_crop with
 // reflected context, bicubic resize of the longer side to S, centre pad).  The arithmetic is the integer rule of
 // fgn_amd/fewshot_ds.py (cubic_taps / support_geometry / support_from_source) and the kernel agrees

@@ -454,6 +454,22 @@ class _SrcQuery(NamedTuple):
         return _SrcQuery(self.src.to(dev, non_blocking=True), self.hw.to(dev, non_blocking=True), self.H, self.W)
 
 
+class _AugQuery(NamedTuple):
+    """``_SrcQuery`` with an augmentation (``qry_augment``): ``rec`` int32 [B,16], the records of
+    ``fewshot_ds.query_augment_record`` (source size included), in place of ``hw``."""
+    src: torch.Tensor
+    rec: torch.Tensor
+    H: int
+    W: int
+
+    @property
+    def shape(self) -> tuple:
+        return (self.src.shape[0], self.H, self.W, 3)
+
+    def to(self, dev, *a, **kw) -> '_AugQuery':
+        return _AugQuery(self.src.to(dev, non_blocking=True), self.rec.to(dev, non_blocking=True), self.H, self.W)
+
+
 class _SrcSupports(NamedTuple):
     """Support instances as windows of their source images on the way to ``_support_front`` (``spp_crop_to``): ``src``
     uint8 [n, capacity], instance i's image window [wh_i, ww_i, 3] at the start of row i; ``msk`` uint8 [n, mask capacity],
@@ -890,7 +906,7 @@ class FGN(torch.nn.Module):
         """(leading dimensions, H, W) of an image tensor as given: channels-last pixels when it is uint8 and a table is
         set (``set_input_norm``), NCHW otherwise; source-size pixels (``_SrcQuery``) count with the size they are resized
         to.  ``lead``: the numbers of leading dimensions allowed."""
-        if isinstance(img, _SrcQuery):
+        if isinstance(img, (_SrcQuery, _AugQuery)):
             return (int(img.src.shape[0]),), img.H, img.W
         if self.input_lut is not None and img.dtype == torch.uint8:
             if img.dim() - 3 not in lead or img.shape[-1] != 3:
@@ -911,6 +927,9 @@ class FGN(torch.nn.Module):
         if isinstance(img, _SrcQuery):
             img = img.to(dev)
             return ops.resize_u8_to_nhwc4(img.src.contiguous(), img.hw.contiguous(), self._lut_on(dev), img.H, img.W)
+        if isinstance(img, _AugQuery):
+            img = img.to(dev)
+            return ops.augment_u8_to_nhwc4(img.src.contiguous(), img.rec.contiguous(), self._lut_on(dev), img.H, img.W)
         if self.input_lut is not None and img.dtype == torch.uint8:
             self._image_dims(img, 'image')
             return ops.u8hwc3_to_nhwc4(img.to(dev, non_blocking=True).contiguous(), self._lut_on(dev))
@@ -971,6 +990,70 @@ class FGN(torch.nn.Module):
                                  f'the attribute (the static source slot of the captured graph)')
         return dict(B=B, hw=(H, W), flats=[im.contiguous().reshape(-1) for im in imgs], sizes=sizes, need=need,
                     capacity=capacity, img_shape=img_shape)
+
+    @staticmethod
+    def _augment_plans(qry_augment, qry_bboxes, rs: dict) -> tuple:
+        """The contract of ``qry_augment`` (host only, nothing is queued): [B,8] finite rows of
+        ``fewshot_ds.AUG_PARAMS`` with flip, border and channel order inside their sets and coefficients inside the bounds
+        of the integer rule.  -> (records int32 [B,16], the boxes at the network size): per image
+        ``fewshot_ds.augment_plan`` - the boxes through the forward matrix, or, where a box leaves the image, the neutral
+        record and the plain boxes (the fallback of base_fst.py:751-768)."""
+        from . import fewshot_ds as fd
+        rows = qry_augment.detach().cpu().numpy() if isinstance(qry_augment, torch.Tensor) else np.asarray(qry_augment)
+        if rows.dtype.kind not in 'iuf' or rows.shape != (rs['B'], len(fd.AUG_PARAMS)):
+            raise ValueError(f'qry_augment must be [B,{len(fd.AUG_PARAMS)}] numbers {fd.AUG_PARAMS} for {rs["B"]} images, '
+                             f'got {rows.dtype} {list(rows.shape)}')
+        if qry_bboxes is None or len(qry_bboxes) != rs['B']:
+            raise ValueError(f'qry_augment: qry_bboxes must hold the boxes of {rs["B"]} images')
+        recs, boxes = [], []
+        for row, b, hw in zip(rows, qry_bboxes, rs['sizes']):
+            as_tensor = isinstance(b, torch.Tensor)
+            rec, nb = fd.augment_plan(row, b.detach().cpu().numpy() if as_tensor else np.asarray(b), hw, rs['hw'])
+            recs.append(rec)
+            boxes.append(torch.from_numpy(nb) if as_tensor else nb)
+        return torch.from_numpy(np.stack(recs)), boxes
+
+    def _train_front(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
+                     spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
+                     spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
+                     **kwargs) -> dict:
+        """The front of a training batch, shared by ``forward_train`` and ``train.Trainer``: the contracts of
+        ``qry_resize_to``, ``spp_crop_to`` and ``qry_augment`` (every error before anything is queued), then the uploads
+        and the kernels behind them.  -> the keyword arguments of ``train.forward_train``."""
+        if qry_augment is not None and qry_resize_to is None:
+            raise ValueError('qry_augment needs qry_resize_to: the query is augmented together with its resize from the '
+                             'source size')
+        sp = None
+        if spp_crop_to is not None:                       # (every contract error before anything is queued)
+            sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
+        if qry_resize_to is not None:
+            rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
+            if qry_augment is not None:
+                recs, boxes = self._augment_plans(qry_augment, qry_bboxes, rs)
+            if not torch.cuda.is_available():
+                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
+            dev = torch.device('cuda', torch.cuda.current_device())
+            qry_img = self._upload_source(rs, dev)
+            if qry_augment is None:
+                qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
+                qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) for g in qry_isegmaps]
+            else:
+                rec_dev = recs.to(dev, non_blocking=True)
+                qry_img = _AugQuery(qry_img.src, rec_dev, *rs['hw'])
+                qry_bboxes = boxes
+                plain = [not bool(r[2:6].any()) for r in recs.numpy()]          # neutral, or fallen back
+                qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) if p else
+                                self._augmented_masks(g, rec_dev[i], rs['hw'], dev)
+                                for i, (g, p) in enumerate(zip(qry_isegmaps, plain))]
+            img_shape = rs['img_shape']
+        if sp is not None:
+            if not torch.cuda.is_available():
+                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
+            (spp_imgs, spp_bboxes), spp_isegmaps = \
+                self._supports_on_device(sp, torch.device('cuda', torch.cuda.current_device())), None
+        return dict(qry_img=qry_img, qry_bboxes=qry_bboxes, qry_cat_ids=qry_cat_ids, qry_isegmaps=qry_isegmaps,
+                    qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals, spp_imgs=spp_imgs, spp_bboxes=spp_bboxes,
+                    spp_isegmaps=spp_isegmaps, img_shape=img_shape, **kwargs)
 
     @staticmethod
     def _scaled_boxes(qry_bboxes, sizes, hw):
@@ -1151,41 +1234,31 @@ class FGN(torch.nn.Module):
     @torch.no_grad()
     def forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                       spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
-                      spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, **kwargs) -> Dict:
+                      spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
+                      **kwargs) -> Dict:
         """The loss dict of one training step (fgn.py:125-185) as forward values - see ``fgn_amd.train``.  Keys and
         container types are the reference's: ``loss_rpn_cls`` / ``loss_rpn_bbox`` (lists of one tensor),
         ``loss_cls``, ``ACC-Unbalanced``, ``ACC-Balanced``, ``loss_bbox``, ``loss_mask``.  ``qry_resize_to``: source-size
         query images, masks and boxes, as for ``simple_test``; ``spp_crop_to``: supports cut from their source images on
-        the device, as for ``simple_test``."""
+        the device, as for ``simple_test``.  ``qry_augment`` (needs ``qry_resize_to``): [B,8] rows of
+        ``fewshot_ds.AUG_PARAMS`` - flip, rotation, scale, shear, translation, border, channel order - applied to image
+        and masks on the device together with the resize (``fewshot_ds.augment_query`` bit for bit; ``get_query`` with
+        ``augment_qry``, base_fst.py:889-891), to the boxes on the host; an image whose boxes leave it is
+        used un-augmented, as in the reference."""
         from . import train
-        sp = None
-        if spp_crop_to is not None:                       # (every contract error before anything is queued)
-            sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
-        if qry_resize_to is not None:
-            rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
-            if not torch.cuda.is_available():
-                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
-            dev = torch.device('cuda', torch.cuda.current_device())
-            qry_img = self._upload_source(rs, dev)
-            qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
-            qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) for g in qry_isegmaps]
-            img_shape = rs['img_shape']
-        if sp is not None:
-            if not torch.cuda.is_available():
-                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
-            (spp_imgs, spp_bboxes), spp_isegmaps = \
-                self._supports_on_device(sp, torch.device('cuda', torch.cuda.current_device())), None
-        return train.forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps,
-                                   qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals, spp_imgs=spp_imgs,
-                                   spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps, img_shape=img_shape, **kwargs)
+        return train.forward_train(self, **self._train_front(
+            qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals,
+            spp_imgs=spp_imgs, spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps, img_shape=img_shape,
+            qry_resize_to=qry_resize_to, spp_crop_to=spp_crop_to, spp_fill_ratio=spp_fill_ratio, crop_square=crop_square,
+            qry_augment=qry_augment, **kwargs))
 
     @torch.no_grad()
     def simple_test(self, qry_img, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None, qry_bboxes_ignore=None,
                     spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, qry_child_idx=None, img_shape=None,
                     rescale=False, cats_ids_to_sample_real=None, spp_insts_ids=None, idx=None,
                     support_code=None, qry_resize_to=None, results_at_source: bool = False, spp_crop_to=None,
-                    spp_fill_ratio: float = 0.8, crop_square: bool = True, **kwargs) -> List[Dict]:
-        """Test without augmentation (fgn.py:187-303).  ``support_code`` (optional, from
+                    spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None, **kwargs) -> List[Dict]:
+        """Test without augmentation (fgn.py:187-303; ``qry_augment`` is refused).  ``support_code`` (optional, from
         ``encode_supports``) replaces the three ``spp_*`` inputs.  ``qry_resize_to`` = (H, W) (or a [B,2] tensor of
         equal rows): ``qry_img`` holds decoded images at their SOURCE size - a uint8 tensor [B,h,w,3] or a list of B
         uint8 tensors [h_i,w_i,3] - and ``qry_isegmaps`` / ``qry_bboxes`` are at source size too; image and masks are
@@ -1201,6 +1274,8 @@ class FGN(torch.nn.Module):
         source frame - and crop, bicubic resize and centre pad of ``BaseFewShotISEG.get_support`` (base_fst.py:1043-1167)
         run on the device in one launch (``fewshot_ds.support_from_source`` bit for bit); only the window
         of each image that its crop reads is uploaded; needs ``set_input_norm``."""
+        if qry_augment is not None:
+            raise ValueError('qry_augment is for forward_train: the test is without augmentation')
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
         sp = None
@@ -1388,6 +1463,15 @@ class FGN(torch.nn.Module):
         if hw is not None and tuple(g.shape[1:]) != tuple(hw):
             g = ops.resize_masks(g, *hw)
         return g
+
+    @staticmethod
+    def _augmented_masks(g, rec: torch.Tensor, hw, dev) -> torch.Tensor:
+        """Ground-truth masks of one image on the device, warped there by its record (``ops.augment_masks``): uint8
+        [n,H,W]."""
+        g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
+        g = g.to(dev, non_blocking=True)
+        g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
+        return ops.augment_masks(g.contiguous(), rec, *hw)
 
     def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None,
                 bits_out: Optional[list] = None, source: Optional[dict] = None, resize_masks: bool = True,

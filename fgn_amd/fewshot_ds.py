@@ -9,6 +9,7 @@ reproduced.
 """
 from __future__ import annotations
 
+import itertools
 import os
 import pickle
 import random
@@ -264,6 +265,242 @@ def resize_query(img: np.ndarray, bboxes_yxyx: np.ndarray, isegmaps: np.ndarray,
     return resize_image_u8(img, H, W), scale_boxes_yxyx(bboxes_yxyx, h, w, H, W), resize_masks(isegmaps, H, W)
 
 
+# ---- query augmentation (BaseFewShotISEG.augment_with_imgaug, base_fst.py:735-770; natural_fst.py:18-35) -----------
+# The geometric half of the reference's ``augs_seq`` (Fliplr, Affine rotate / scale / shear / translate_px) and its
+# ChannelShuffle, composed with the resize of ``get_query`` into ONE bilinear gather from the source image.  imgaug and
+# cv2 are third party and pinned by no golden: like ``resize_taps`` this is the project's own restatement in INTEGERS, so
+# that augment_u8hwc3_to_nhwc4_kernel and augment_mask_u8_kernel of csrc/spatial.hip agree with these functions bit for
+# bit (which also lists the conventions of imgaug that were taken from memory).
+AUG_PARAMS = ('flip', 'rotate', 'scale', 'shear', 'translate_x', 'translate_y', 'border', 'channel_order')
+AUG_FRAC_BITS = 20            # coefficients of the source map in units of 2^-20 source pixels
+AUG_LIN_MAX = 1 << 26         # |c00|, |c01|, |c10|, |c11| at most this (64 source pixels per output pixel)
+AUG_OFF_MAX = 1 << 40         # |c02|, |c12| at most this; then |U| < 2^42 for ox, oy < 16384 and U >> 20 fits int32
+AUG_REC_INTS = 16             # int32 per image record
+AUG_REC_FIELDS = ('h', 'w', 'kind', 'flip', 'border', 'perm', 'c00', 'c01', 'c10', 'c11', 'c02_lo', 'c02_hi', 'c12_lo',
+                  'c12_hi')
+CHANNEL_ORDERS = tuple(itertools.permutations(range(3)))      # out[c] = in[CHANNEL_ORDERS[k][c]]; 0 = identity
+AUG_NEUTRAL = (0., 0., 1., 0., 0., 0., 0., 0.)
+
+
+def check_augment_params(params) -> np.ndarray:
+    """One image's row ``AUG_PARAMS`` as float64 [8]; ValueError for a wrong shape, a non-finite entry, a scale that is
+    not positive, or flip / border / channel order outside {0,1} / {0,1} / 0..5."""
+    p = np.asarray(params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else params)
+    if p.dtype.kind not in 'iuf' or p.shape != (len(AUG_PARAMS),):
+        raise ValueError(f'qry_augment: one image\'s row is {len(AUG_PARAMS)} numbers {AUG_PARAMS}, got '
+                         f'{p.dtype} {list(p.shape)}')
+    p = p.astype(np.float64)
+    if not np.isfinite(p).all():
+        raise ValueError(f'qry_augment: non-finite entries in {p.tolist()}')
+    if p[0] not in (0., 1.) or p[6] not in (0., 1.) or p[7] not in (0., 1., 2., 3., 4., 5.):
+        raise ValueError(f'qry_augment: flip and border are 0 or 1 and the channel order is 0..5, got flip {p[0]}, '
+                         f'border {p[6]}, channel order {p[7]}')
+    if not p[2] > 0:
+        raise ValueError(f'qry_augment: the scale must be positive, got {p[2]}')
+    return p
+
+
+def augment_kind(p: np.ndarray) -> int:
+    """0: rotation, shear and translation are 0 and the scale is 1 (the resize's own taps, reversed under flip);
+    1: an affine gather."""
+    return int(not (p[1] == 0 and p[2] == 1 and p[3] == 0 and p[4] == 0 and p[5] == 0))
+
+
+def augment_is_neutral(p: np.ndarray) -> bool:
+    return augment_kind(p) == 0 and p[0] == 0 and p[7] == 0
+
+
+def augment_forward_matrix(p: np.ndarray, net_hw) -> np.ndarray:
+    """A = T(c) T(t) Rot(rotate) ShearX(shear) Scale(scale) FlipX T(-c), c = (W/2, H/2), float64 [3,3] on (x, y, 1)
+    in the network frame (pixel j covers [j, j+1)).  Rot = [[cos, -sin], [sin, cos]] (y points down: positive angles
+    turn clockwise on the screen), ShearX = [[1, -tan], [0, 1]], FlipX = diag(-1, 1)."""
+    H, W = (float(v) for v in net_hw)
+    T = lambda x, y: np.array([[1., 0., x], [0., 1., y], [0., 0., 1.]])
+    th, ph = np.deg2rad(p[1]), np.deg2rad(p[3])
+    rot = np.array([[np.cos(th), -np.sin(th), 0.], [np.sin(th), np.cos(th), 0.], [0., 0., 1.]])
+    shear = np.array([[1., -np.tan(ph), 0.], [0., 1., 0.], [0., 0., 1.]])
+    scale = np.diag([p[2], p[2], 1.])
+    flip = np.diag([-1. if p[0] else 1., 1., 1.])
+    return T(W / 2, H / 2) @ T(p[4], p[5]) @ rot @ shear @ scale @ flip @ T(-W / 2, -H / 2)
+
+
+def augment_source_matrix(p: np.ndarray, src_hw, net_hw) -> np.ndarray:
+    """M = Rz A^-1 P, float64 [2,3]: source sample coordinate (sample j at j) of output pixel (ox, oy) = M (ox, oy, 1).
+    P shifts to the pixel's centre, Rz scales by (w / W, h / H) and shifts back by half a source pixel."""
+    (h, w), (H, W) = (float(v) for v in src_hw), (float(v) for v in net_hw)
+    P = np.array([[1., 0., .5], [0., 1., .5], [0., 0., 1.]])
+    Rz = np.array([[w / W, 0., -.5], [0., h / H, -.5], [0., 0., 1.]])
+    return (Rz @ np.linalg.inv(augment_forward_matrix(p, net_hw)) @ P)[:2]
+
+
+def query_augment_record(params, src_hw, net_hw) -> np.ndarray:
+    """What the kernels read for one image, int32 [16] (``AUG_REC_FIELDS``): source size, kind, flip, border, channel
+    order and, for kind 1, c = rint(M * 2^20) with the two offsets as (low, high) halves of an int64.  ``params`` None:
+    the neutral record.  ValueError for parameters outside their sets, sizes outside 1..16384 and coefficients beyond
+    ``AUG_LIN_MAX`` / ``AUG_OFF_MAX``."""
+    p = check_augment_params(AUG_NEUTRAL if params is None else params)
+    (h, w), (H, W) = (int(v) for v in src_hw), (int(v) for v in net_hw)
+    _check_resize_dims(h, w, H, W)
+    rec = np.zeros(AUG_REC_INTS, np.int32)
+    kind = augment_kind(p)
+    rec[:6] = (h, w, kind, int(p[0]), int(p[6]), int(p[7]))
+    if kind == 1:
+        M = augment_source_matrix(p, (h, w), (H, W)) * float(1 << AUG_FRAC_BITS)
+        if not np.isfinite(M).all() or np.abs(M[:, :2]).max() > AUG_LIN_MAX or np.abs(M[:, 2]).max() > AUG_OFF_MAX:
+            raise ValueError(f'qry_augment: the source map of {p.tolist()} at {(h, w)} -> {(H, W)} exceeds the bounds of '
+                             f'the integer rule (|linear| <= 2^6, |offset| <= 2^20 source pixels)')
+        c = np.rint(M).astype(np.int64)
+        rec[6:10] = (c[0, 0], c[0, 1], c[1, 0], c[1, 1])
+        rec[10:14] = np.array([c[0, 2], c[1, 2]], np.int64).view(np.int32)       # (little endian: low, high)
+    return rec
+
+
+def _record_fields(rec) -> dict:
+    rec = np.asarray(rec)
+    if rec.dtype != np.int32 or rec.shape != (AUG_REC_INTS,):
+        raise ValueError(f'an augmentation record is int32 [{AUG_REC_INTS}], got {rec.dtype} {list(rec.shape)}')
+    g = dict(zip(AUG_REC_FIELDS[:10], (int(v) for v in rec[:10])))
+    g['c02'], g['c12'] = (int(v) for v in np.ascontiguousarray(rec[10:14]).view(np.int64))
+    if g['kind'] not in (0, 1) or g['flip'] not in (0, 1) or g['border'] not in (0, 1) or not 0 <= g['perm'] <= 5 or \
+            max(abs(g[k]) for k in ('c00', 'c01', 'c10', 'c11')) > AUG_LIN_MAX or \
+            max(abs(g['c02']), abs(g['c12'])) > AUG_OFF_MAX:
+        raise ValueError(f'augmentation record out of range: {g}')
+    return g
+
+
+def _augment_acc(planes: np.ndarray, g: dict, H: int, W: int, symmetric: bool) -> np.ndarray:
+    """planes uint8 [C,h,w] -> the int32 accumulators [C,H,W] of record ``g`` (weights sum to 2^22).  Kind 1 taps that
+    leave the image read the symmetric extension (``symmetric``) or 0."""
+    C, h, w = planes.shape
+    if (h, w) != (g['h'], g['w']):
+        raise ValueError(f'the record is for a {(g["h"], g["w"])} source, got {(h, w)}')
+    _check_resize_dims(H, W)
+    if g['kind'] == 0:
+        acc = _resize_acc(planes, H, W)
+        return acc[..., ::-1] if g['flip'] else acc
+    ox, oy = np.arange(W, dtype=np.int64)[None, :], np.arange(H, dtype=np.int64)[:, None]
+    one = 1 << AUG_FRAC_BITS
+
+    def taps(c_x, c_y, c_o, n):
+        U = c_x * ox + c_y * oy + c_o
+        i0, f = U >> AUG_FRAC_BITS, U & (one - 1)
+        w1 = (f + (1 << (AUG_FRAC_BITS - RESIZE_W_BITS - 1))) >> (AUG_FRAC_BITS - RESIZE_W_BITS)
+        idx = np.stack([i0, i0 + 1])
+        if symmetric:
+            r = np.mod(idx, 2 * n)
+            idx = np.where(r < n, r, 2 * n - 1 - r)
+        else:
+            idx = np.where((idx >= 0) & (idx < n), idx, n)                  # n: the zero sample appended below
+        return idx, np.stack([(1 << RESIZE_W_BITS) - w1, w1]).astype(np.int32)
+    ix, wx = taps(g['c00'], g['c01'], g['c02'], w)
+    iy, wy = taps(g['c10'], g['c11'], g['c12'], h)
+    ext = np.zeros((C, h + 1, w + 1), np.int32)
+    ext[:, :h, :w] = planes
+    acc = np.zeros((C, H, W), np.int32)
+    for a in range(2):
+        for b in range(2):
+            wgt = wy[a] * wx[b]
+            for c in range(C):                                              # (one plane at a time: masks come by the dozen)
+                acc[c] += ext[c][iy[a], ix[b]] * wgt
+    return acc
+
+
+def augment_image_u8(img: np.ndarray, rec: np.ndarray, H: int, W: int) -> np.ndarray:
+    """uint8 [h,w,3] -> uint8 [H,W,3] by record ``rec``: per channel (acc + 2^21) >> 22, then out[..., c] =
+    in[..., order[c]].  Kind 0 without flip and with the identity order is ``resize_image_u8``."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f'augment_image_u8: expects a uint8 [h,w,3] image, got {img.dtype} {list(img.shape)}')
+    g = _record_fields(rec)
+    acc = _augment_acc(np.moveaxis(img, 2, 0), g, int(H), int(W), bool(g['border']))
+    out = np.moveaxis((acc + (1 << (2 * RESIZE_W_BITS - 1))) >> (2 * RESIZE_W_BITS), 0, 2).astype(np.uint8)
+    return np.ascontiguousarray(out[..., list(CHANNEL_ORDERS[g['perm']])])
+
+
+def augment_masks(m: np.ndarray, rec: np.ndarray, H: int, W: int) -> np.ndarray:
+    """bool (or 0 / nonzero) [G,h,w] -> bool [G,H,W]: the image's taps on 0/1 values, set where acc >= 2^21; a tap
+    outside the image is 0 whatever the record's border.  Kind 0 without flip is ``resize_masks``."""
+    m = np.asarray(m)
+    if m.ndim != 3:
+        raise ValueError(f'augment_masks: expects [G,h,w], got {list(m.shape)}')
+    g = _record_fields(rec)
+    _check_resize_dims(H, W)
+    if m.shape[0] == 0:
+        return np.zeros((0, int(H), int(W)), bool)
+    return _augment_acc((m != 0).astype(np.uint8), g, int(H), int(W), False) >= (1 << (2 * RESIZE_W_BITS - 1))
+
+
+def augment_boxes_yxyx(bboxes_yxyx: np.ndarray, params, H: int, W: int):
+    """Boxes YXYX in the network frame through A: the four corners in float64, their axis-aligned hull, cast to float32
+    -> (boxes float32 [n,4] clipped to the image, True), or (None, False) when a hull lies fully outside the image
+    (``bad_augment``, base_fst.py:751-768: the sample is then used un-augmented)."""
+    p = check_augment_params(params)
+    A = augment_forward_matrix(p, (H, W))
+    b = np.asarray(bboxes_yxyx, np.float64).reshape(-1, 4)
+    xs, ys = b[:, [1, 3, 1, 3]], b[:, [0, 0, 2, 2]]
+    X = A[0, 0] * xs + A[0, 1] * ys + A[0, 2]
+    Y = A[1, 0] * xs + A[1, 1] * ys + A[1, 2]
+    hull = np.stack([Y.min(1), X.min(1), Y.max(1), X.max(1)], 1).astype(np.float32).reshape(-1, 4)
+    out = (hull[:, 3] <= 0) | (hull[:, 1] >= W) | (hull[:, 2] <= 0) | (hull[:, 0] >= H)
+    if out.any():
+        return None, False
+    hull[:, [0, 2]] = hull[:, [0, 2]].clip(0, H)
+    hull[:, [1, 3]] = hull[:, [1, 3]].clip(0, W)
+    return hull, True
+
+
+def augment_plan(params, bboxes_yxyx, src_hw, net_hw):
+    """Everything of one image's augmentation that is decided before a pixel is touched: -> (record int32 [16], boxes
+    at the network size).  A neutral row (or None) and a row whose boxes leave the image (the fallback) give the neutral
+    record and the boxes of ``resize_query``; every contract error of the row is raised here."""
+    (h, w), (H, W) = (int(v) for v in src_hw), (int(v) for v in net_hw)
+    plain = bboxes_yxyx if (h, w) == (H, W) or bboxes_yxyx is None else scale_boxes_yxyx(bboxes_yxyx, h, w, H, W)
+    rec = query_augment_record(params, (h, w), (H, W))
+    if params is None or augment_is_neutral(check_augment_params(params)):
+        return query_augment_record(None, (h, w), (H, W)), plain
+    if plain is None:
+        return rec, None
+    boxes, ok = augment_boxes_yxyx(plain, params, H, W)
+    if not ok:
+        return query_augment_record(None, (h, w), (H, W)), plain
+    return rec, boxes
+
+
+def augment_query(img: np.ndarray, bboxes_yxyx: np.ndarray, isegmaps: np.ndarray, H: int, W: int, params=None):
+    """``get_query`` with ``augment_qry`` between the decoded image and the sample (base_fst.py:876-891): resize and
+    augmentation as one gather of image and masks, boxes through the forward matrix.  ``params`` None or neutral, or a
+    box that leaves the image: exactly ``resize_query``."""
+    h, w = img.shape[:2]
+    rec, boxes = augment_plan(params, bboxes_yxyx, (h, w), (H, W))
+    if not rec[2:6].any():
+        return resize_query(img, bboxes_yxyx, isegmaps, H, W)
+    return augment_image_u8(img, rec, H, W), boxes, augment_masks(isegmaps, rec, H, W)
+
+
+def draw_query_augment(rng) -> np.ndarray:
+    """One row of ``AUG_PARAMS`` drawn like the geometric half of ``augs_seq`` and its ChannelShuffle
+    (natural_fst.py:18-35): with p = 1/2 one of Fliplr, rotation by 10 degrees (symmetric border), scale uniform in
+    [0.8, 1.2], shear uniform in [-10, 10] degrees (symmetric border), translation by integers uniform in [-20, 20] per
+    axis; with p = 1/14 (1/2 x one photometric operator of seven) a uniformly drawn channel order.  ``rng``: a numpy
+    Generator or RandomState (``random`` and ``uniform`` are used)."""
+    p = np.array(AUG_NEUTRAL, np.float64)
+    if rng.random() < 0.5:
+        op = min(int(rng.random() * 5), 4)
+        if op == 0:
+            p[0] = 1
+        elif op == 1:
+            p[1], p[6] = 10, 1
+        elif op == 2:
+            p[2] = rng.uniform(0.8, 1.2)
+        elif op == 3:
+            p[3], p[6] = rng.uniform(-10, 10), 1
+        else:
+            p[4], p[5] = (min(int(rng.random() * 41), 40) - 20 for _ in range(2))
+    if rng.random() < 1 / 14:
+        p[7] = min(int(rng.random() * 6), 5)
+    return p
+
+
 # ---- supports from the source image (BaseFewShotISEG.get_support, base_fst.py:1043-1167) ---------------------------
 # ``support_from_instance`` as ONE gather from the source image: crop (reflect context), bicubic resize of the longer
 # side to S and centre pad, with no padded copy of the image and no float.  The crop geometry is the golden-pinned
@@ -508,7 +745,12 @@ class ClutteredCharsFewShotISEG(Dataset):
     base_fst.py:1043-1167) - ``spp_imgs`` is the list of the N*K instances' SOURCE images uint8 [h,w,3], ``spp_isegmaps``
     the list of their masks [h,w] bool, ``spp_bboxes`` [N*K,4] their boxes YXYX in the source frame, and the sample
     carries ``spp_crop_to`` = spp_img_size, ``spp_fill_ratio`` and ``crop_square`` for a detector that cuts the supports
-    on the device (``FGN.simple_test(spp_crop_to=...)``).  Off by default: the samples are then what they always were."""
+    on the device (``FGN.simple_test(spp_crop_to=...)``).  Off by default: the samples are then what they always were.
+    ``augment_qry`` (needs ``source_size``): the sample carries ``qry_augment``, one row of ``AUG_PARAMS`` float64 [8]
+    drawn by ``draw_query_augment`` per (seed, child, epoch of ``reshuffle``), for a detector that augments the query on
+    the device (``FGN.forward_train(qry_augment=...)``; ``get_query`` with ``augment_qry``, base_fst.py:889-891); the
+    pixels, masks and boxes of the sample are NOT augmented.  Off by default: the samples are then what they always
+    were."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
@@ -516,7 +758,7 @@ class ClutteredCharsFewShotISEG(Dataset):
 
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
                  spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None,
-                 spp_source=False):
+                 spp_source=False, augment_qry=False):
         par = self.PARAMS[dataset]
         self.raw_uint8 = bool(raw_uint8)
         self.spp_source = bool(spp_source)
@@ -527,6 +769,11 @@ class ClutteredCharsFewShotISEG(Dataset):
         if self.source_size is not None and not self.raw_uint8:
             raise ValueError('source_size needs raw_uint8=True: source-size queries are resized by the detector, which '
                              'takes decoded pixels')
+        self.augment_qry = bool(augment_qry)
+        if self.augment_qry and self.source_size is None:
+            raise ValueError('augment_qry needs source_size: the query is augmented by the detector together with its '
+                             'resize from the source size')
+        self.epoch = 0                               # the ``e`` of the last ``reshuffle``: one augmentation draw per epoch
         self.n_ways, self.k_shots, self.batch, self.shuffle = n_ways, k_shots, batch, shuffle
         self.img_size, self.spp_img_size, self.spp_fill_ratio = img_size, spp_img_size, spp_fill_ratio
         self.sampling_origin_ds, self.sampling_origin_ds_subset = dataset, 'val'
@@ -553,6 +800,7 @@ class ClutteredCharsFewShotISEG(Dataset):
         if self.shuffle:
             random.Random((2 ** e) % 1000).shuffle(order)
         self.order = np.array(order, dtype=np.int32)
+        self.epoch = int(e)
 
     @property
     def input_norm(self) -> dict:
@@ -616,6 +864,8 @@ class ClutteredCharsFewShotISEG(Dataset):
         }
         if self.source_size is not None:
             sample['qry_resize_to'] = np.array([self.img_size, self.img_size], dtype=np.int32)
+        if self.augment_qry:
+            sample['qry_augment'] = draw_query_augment(np.random.default_rng([int(self.seed), child, self.epoch]))
         if self.spp_source:
             sample.update(spp_crop_to=int(self.spp_img_size), spp_fill_ratio=float(self.spp_fill_ratio), crop_square=True)
         return sample

@@ -40,6 +40,8 @@ SIGNATURES = {
     'fgn_u8hwc3_to_nhwc4_f32': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'fgn_resize_u8hwc3_to_nhwc4_f32': (_i, [_p, C.c_longlong, _p, _p, _p, _i, _i, _i, _p]),
     'fgn_resize_mask_u8': (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
+    'fgn_augment_u8hwc3_to_nhwc4_f32': (_i, [_p, C.c_longlong, _p, _p, _p, _i, _i, _i, _p]),
+    'fgn_augment_mask_u8': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     'fgn_support_from_source_f32': (_i, [_p, C.c_longlong, _p, C.c_longlong, _p, _p, _p, _p, _i, _i, _p]),
     'fgn_maxpool3x3s2_nhwc_f32': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgn_group_norm_workspace_bytes': (C.c_size_t, [_i] * 4),

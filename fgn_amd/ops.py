@@ -1098,6 +1098,63 @@ def resize_masks(masks: torch.Tensor, H: int, W: int) -> torch.Tensor:
     return out
 
 
+AUG_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.AUG_REC_INTS: int32 per image record
+
+
+def augment_u8_to_nhwc4(src: torch.Tensor, recs: torch.Tensor, lut: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Source-size images -> the augmented NHWC4 fp32 stem input at (H, W): ``u8hwc3_to_nhwc4`` of
+    ``fewshot_ds.augment_image_u8`` of every image, bit for bit, in one launch.  ``src`` as for ``resize_u8_to_nhwc4``;
+    ``recs`` int32 [n,16] ON THE DEVICE: the records of ``fewshot_ds.query_augment_record``, read by the kernel (the
+    launch is the same for every source size and augmentation).  An image whose record is out of range or whose size
+    exceeds the capacity comes out as zeros."""
+    _chk(src, 'src', torch.uint8)
+    _chk(recs, 'recs', torch.int32)
+    _chk(lut, 'lut')
+    if src.dim() != 2 or tuple(recs.shape) != (src.shape[0], AUG_REC_INTS) or recs.device != src.device:
+        raise _lib.FgnHipError('augment_u8_to_nhwc4: expects src [n,capacity] and recs [n,16] on one device')
+    if tuple(lut.shape) != (3, 256) or lut.device != src.device:
+        raise _lib.FgnHipError('augment_u8_to_nhwc4: lut must be [3,256] on the device of src')
+    H, W = int(H), int(W)
+    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM):
+        raise _lib.FgnHipError(f'augment_u8_to_nhwc4: output size must be within 0..{RESIZE_MAX_DIM}, got {(H, W)}')
+    n = src.shape[0]
+    y = torch.empty((n, H, W, 4), device=src.device, dtype=torch.float32)
+    if y.numel() == 0:                  # (an empty tensor has no address to hand over)
+        return y
+    if src.shape[1] == 0:
+        src = src.new_zeros((n, 1))     # (capacity 0: every image is refused by the kernel; it needs an address only)
+    _lib.check(_lib.load().fgn_augment_u8hwc3_to_nhwc4_f32(_ptr(src), int(src.shape[1]), _ptr(recs), _ptr(lut),
+                                                            _ptr(y), n, H, W, _stream()),
+               'fgn_augment_u8hwc3_to_nhwc4_f32')
+    return y
+
+
+def augment_masks(masks: torch.Tensor, rec: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Dense binary masks [G,h,w] (bool / uint8, non-zero = set) of one image -> uint8 0/1 [G,H,W] by the image's record
+    ``rec`` (int32 [16] ON THE DEVICE): ``fewshot_ds.augment_masks`` bit for bit.  A record out of range, or one for
+    another source size, gives empty masks."""
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    _chk(masks, 'masks', torch.uint8)
+    _chk(rec, 'rec', torch.int32)
+    if masks.dim() != 3:
+        raise _lib.FgnHipError('augment_masks: masks must be [G,h,w]')
+    if tuple(rec.shape) != (AUG_REC_INTS,) or rec.device != masks.device:
+        raise _lib.FgnHipError('augment_masks: rec must be int32 [16] on the device of masks')
+    g, h, w = masks.shape
+    H, W = int(H), int(W)
+    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM and h <= RESIZE_MAX_DIM and w <= RESIZE_MAX_DIM):
+        raise _lib.FgnHipError(f'augment_masks: every dimension must be at most {RESIZE_MAX_DIM}')
+    out = torch.empty((g, H, W), device=masks.device, dtype=torch.uint8)
+    if out.numel() == 0:
+        return out
+    if h == 0 or w == 0:
+        raise _lib.FgnHipError('augment_masks: empty source masks')
+    _lib.check(_lib.load().fgn_augment_mask_u8(_ptr(masks), _ptr(out), _ptr(rec), g, h, w, H, W, _stream()),
+               'fgn_augment_mask_u8')
+    return out
+
+
 SPP_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.SPP_REC_INTS: int32 per instance record
 
 

@@ -950,7 +950,8 @@ class Trainer:
         m._tape = {}
         try:
             with ops.gemm_math('f32'):      # the transposed-weight layers packed inside backward() live for one call
-                losses = forward_train(m, perm_fn=perm_fn, bn_momentum=self.bn_momentum, **batch)
+                # (the detector's front: source-size queries, supports cut from their sources, augmentation)
+                losses = forward_train(m, perm_fn=perm_fn, bn_momentum=self.bn_momentum, **m._train_front(**batch))
                 self._bn_calls += 1 + (m._tape.get('roi') is not None)
                 g = backward(m, self.W, m._tape)
         finally:

@@ -243,6 +243,30 @@ int fgn_resize_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_strid
  * weighted sum of the four taps reaches half (cv2.resize(m.astype(uint8)).astype(bool)). */
 int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, int G, int h, int w, int H, int W, void* stream);
 
+/* Query augmentation behind the upload (BaseFewShotISEG.augment_with_imgaug, base_fst.py:735-770: flip, affine warp and
+ * channel order of natural_fst.py:18-35), composed with the resize above into one bilinear gather from the source image.
+ * Both entries compute the integer rule of fgn_amd.fewshot_ds (query_augment_record; a restatement of imgaug's operators
+ * that no reference golden pins) and agree with augment_image_u8 / augment_masks bit for bit.  Return codes as above.
+ *   record, int32 [16]: {h, w, kind, flip, border, perm, c00, c01, c10, c11, c02 lo, c02 hi, c12 lo, c12 hi, -, -}
+ *     kind 0: the taps of the resize, of column W-1-ox under flip.
+ *     kind 1: source coordinate (U, V) = c (ox, oy, 1) in int64, units of 2^-20 samples; i0 = U >> 20, w1 =
+ *             ((U & (2^20-1)) + 256) >> 9, w0 = 2048 - w1, taps i0 and i0 + 1; a tap outside the image reads the
+ *             symmetric extension (border 1: r = k mod 2n, r < n ? r : 2n-1-r) or 0 (border 0).
+ *     perm: index into itertools.permutations(range(3)); output channel c is table c of blended byte p[c].
+ *   A record is out of range when h or w is outside 1..16384, kind, flip, border or perm outside its set, a linear
+ *   coefficient beyond +-2^26 or an offset beyond +-2^40.
+ *
+ * fgn_augment_u8hwc3_to_nhwc4_f32: the contract of fgn_resize_u8hwc3_to_nhwc4_f32 with recs int32 [n_img][16] read ON THE
+ * DEVICE in place of src_hw: no launch argument depends on a source size or on the augmentation.  An image whose record
+ * is out of range or with h * w * 3 > src_stride_bytes is written as +0.0f and not read. */
+int fgn_augment_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stride_bytes, const int* recs,
+                                    const float* lut, float* y, int n_img, int H, int W, void* stream);
+/* fgn_augment_mask_u8: the contract of fgn_resize_mask_u8 with one record (device, int32 [16]) for the G masks of an
+ * image; taps outside the image are 0 whatever the border.  A record out of range, or one whose (h, w) is not the
+ * launch's, gives empty masks and src is not read. */
+int fgn_augment_mask_u8(const unsigned char* src, unsigned char* dst, const int* rec, int G, int h, int w, int H, int W,
+                        void* stream);
+
 /* Supports from the source image behind the upload (BaseFewShotISEG.get_support, base_fst.py:1043-1167: get_crop with
  * reflected context, bicubic resize of the longer side to S, centre pad): one launch for all n = B * N * K instances of
  * a batch.  The arithmetic is the integer rule of fgn_amd.fewshot_ds (cubic_taps: cubic convolution A = -3/4, half-pixel
