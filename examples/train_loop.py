@@ -7,12 +7,15 @@ warm-up 100 iterations, 3 epochs) on the MI355X path: DataLoader(ds, collate_fn_
     python examples/train_loop.py --dataset OMNIISEG --episodes 32 --epochs 3
     python examples/train_loop.py --dataset SYNTH --height 320 --width 480 --episodes 16
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment
+    python examples/train_loop.py --dataset OMNIISEG --source-size 320 --augment --photometric
 
 ``--source-size S``: the loader hands over decoded S x S pixels and the detector resizes them on the GPU
 (``qry_resize_to``); ``--spp-source``: the supports are cut from their source images on the GPU (``spp_crop_to``);
 ``--augment`` (needs ``--source-size``): the queries are augmented on the GPU together with the resize
 (``qry_augment``: flip, affine warp, channel order, drawn per image and epoch - ``augment_qry=True`` of the reference's
-training configurations).  The evaluation at the end is without augmentation.
+training configurations); ``--photometric`` (needs ``--augment``): the other six operators of the reference's
+``augs_seq`` - Gaussian and impulse noise, blur, hue, saturation, brightness - run on the source pixels on the GPU as
+well (``qry_photometric``), and both rows come from one joint draw.  The evaluation at the end is without augmentation.
 
 The backbone is frozen as in fgn_r50_c4_densecl.py:31; with no pretrained checkpoint here it is randomly
 initialised, so this demonstrates the loop (losses fall on the training episodes), not a trained detector.
@@ -49,7 +52,11 @@ def main():
     ap.add_argument('--source-size', type=int, default=None, help='decoded S x S query images, resized on the GPU')
     ap.add_argument('--spp-source', action='store_true', help='supports cut from their source images on the GPU')
     ap.add_argument('--augment', action='store_true', help='augment the queries on the GPU (needs --source-size)')
+    ap.add_argument('--photometric', action='store_true',
+                    help='noise, blur, hue, saturation, brightness on the GPU as well (needs --augment)')
     args = ap.parse_args()
+    if args.photometric and not args.augment:
+        ap.error('--photometric needs --augment: the two are one joint draw of the reference\'s augs_seq')
     source = args.source_size is not None or args.spp_source
     if (source or args.augment) and args.dataset == 'SYNTH':
         ap.error('--source-size / --spp-source / --augment need a character dataset (MNISTISEG, OMNIISEG)')
@@ -61,7 +68,7 @@ def main():
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,
                                        raw_uint8=source, source_size=args.source_size, spp_source=args.spp_source,
-                                       augment_qry=args.augment)
+                                       augment_qry=args.augment, photometric_qry=args.photometric)
     model = FGN(args.n_ways, args.k_shots)
     if source:
         model.set_input_norm(**ds.input_norm)
@@ -92,7 +99,8 @@ def main():
     with tempfile.TemporaryDirectory() as work_dir:
         loader = DataLoader(ds, batch_size=ds.batch, num_workers=2, collate_fn=collate)
         results = [r for data in loader
-                   for r in model.simple_test(**{k: v for k, v in data.items() if k != 'qry_augment'}, rescale=True)]
+                   for r in model.simple_test(**{k: v for k, v in data.items()
+                                                 if k not in ('qry_augment', 'qry_photometric')}, rescale=True)]
         print(ds.evaluate(results=results, model_dir=work_dir))
 
 

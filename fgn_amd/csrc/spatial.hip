@@ -469,6 +469,274 @@ extern "C" int fgn_augment_mask_u8(const unsigned char* src, unsigned char* dst,
 }
 
 // ----------------------------------------------------------------------------------
+// Photometric query augmentation on the source bytes, ahead of the resize / augment gathers above (the other six
+// operators of augs_seq, natural_fst.py:18-35: AdditiveGaussianNoise, ImpulseNoise, GaussianBlur, AddToHue,
+// AddToSaturation, AddToBrightness).  One out-of-place pass src -> dst in the slot layout of the kernels it feeds.  The
+// arithmetic is the integer rule of fgn_amd/fewshot_ds.py (query_photometric_record / photometric_image_u8; DESIGN.md
+// 4.4.6) and the kernel agrees with photometric_image_u8 bit for bit: every table that depends on a float (blur weights,
+// noise thresholds) is made on the host and travels in the record, the device evaluates no transcendental.
+//   record of an image, 64 int32: h w op seed a0 a1 rx ry | payload from 8
+//   op 0 copy.
+//   op 1 noise:   u = word 0 of Philox4x32-10 at counter (pixel, 0, 0, op), key (seed, 0); thresholds L[0..11] at 8;
+//                 k = #{L[j] <= u} - 12 + #{~u < L[j]}; the three bytes of the pixel become clip(byte + k, 0, 255).
+//   op 2 impulse: byte c is replaced where word c < a1 * 2^32 + a0, by 255 where bit c of word 3 is set, else by 0.
+//   op 3 blur:    radii rx, ry in 1..16, weights w[0..rx] at 8 and w[0..ry] at 25 (offset |k|; w[0] + 2 sum w[1..] =
+//                 2048); byte = (sum of byte * wy * wx + 2^21) >> 22, reflect-101 border (r = k mod (2n-2), r < n ? r :
+//                 2n-2-r; 0 for n = 1).
+//   op 4 / 5 / 6 hue / saturation / brightness: photo_hsv below (a0: the amount in the operator's fixed point).
+// The grid is (tiles, images) and depends on the slot stride alone; record and operator are workgroup-uniform, a
+// workgroup branches once on the operator and then loops over its tiles of the image.
+// ----------------------------------------------------------------------------------
+constexpr int PHOTO_REC_INTS = 64;
+constexpr int PHOTO_PAYLOAD = 8;
+constexpr int PHOTO_NOISE_K = 12;
+constexpr int PHOTO_R_MAX = 16;
+constexpr int PHOTO_BLOCK = 256;
+constexpr int PHOTO_RUN = 4;                          // pixels per lane of a point operator: 12 bytes, three dwords
+constexpr int PHOTO_TILE = 32;                        // blur: a workgroup makes 32 x 32 output pixels at a time
+constexpr int PHOTO_IN = PHOTO_TILE + 2 * PHOTO_R_MAX;        // its input tile with the largest halo: 64 x 64 pixels
+constexpr int PHOTO_GRID_CAP = 2048;                  // workgroups per image; further tiles take further passes
+constexpr int PHOTO_ONE = 1 << 16;                    // hue and ramp in units of 2^-16; value and chroma in 2^-7 levels
+constexpr int PHOTO_SIX = 6 << 16;
+
+__device__ __forceinline__ bool photo_axis_ok(const int* __restrict__ wt, int r) {
+    if (r < 1 || r > PHOTO_R_MAX) return false;
+    int sum = 0;
+    bool ok = true;
+    for (int k = 0; k <= r; ++k) {
+        const int v = wt[k];
+        ok = ok && v >= 0 && v <= 2048;
+        sum += (k ? 2 : 1) * (ok ? v : 0);
+    }
+    return ok && sum == 2048;
+}
+
+// Every field inside its set and the image inside its slot: the only records a workgroup reads pixels for.
+__device__ __forceinline__ bool photo_record_ok(const int* __restrict__ rc, long long stride) {
+    const int h = rc[0], w = rc[1], op = rc[2], a0 = rc[4], a1 = rc[5];
+    if (h < 1 || h > RESIZE_MAX_DIM || w < 1 || w > RESIZE_MAX_DIM || op < 0 || op > 6) return false;
+    if ((long long)h * w * 3 > stride) return false;
+    switch (op) {
+        case 2: return a1 == 0 || (a1 == 1 && a0 == 0);
+        case 3: return photo_axis_ok(rc + PHOTO_PAYLOAD, rc[6]) && photo_axis_ok(rc + PHOTO_PAYLOAD + PHOTO_R_MAX + 1, rc[7]);
+        case 4: return a0 >= 0 && a0 < PHOTO_SIX;
+        case 5: return a0 >= -(1 << 23) && a0 <= (1 << 23);
+        case 6: return a0 >= -(255 << 7) && a0 <= (255 << 7);
+        default: return true;
+    }
+}
+
+__device__ __forceinline__ void photo_philox(unsigned c0, unsigned c3, unsigned k0, unsigned out[4]) {
+    unsigned c1 = 0u, c2 = 0u, k1 = 0u;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// Hue (OP 4), saturation (5), brightness (6) of one pixel.  V = max, d = V - min; the hue H in units of 2^-16 sextants
+// from one rounded unsigned division by d; value V7 and chroma C7 in units of 2^-7 grey levels; channel n of (5, 3, 1)
+// for (R, G, B) = (V7 * 2^16 - C7 * f + 2^22) >> 23, f = clip(min(k, 4 - k), 0, 1) of k = (n + H) mod 6.  All int32:
+// V7 * 2^16 + 2^22 <= 255 * 2^23 + 2^22 < 2^31, V * |a0| <= 255 * 2^23.
+template <int OP>
+__device__ __forceinline__ void photo_hsv(int a0, int px[3]) {
+    const int r = px[0], g = px[1], b = px[2];
+    const int V = max(max(r, g), b), d = V - min(min(r, g), b);
+    const bool is_r = V == r, is_g = !is_r && V == g;
+    const int num = is_r ? g - b : (is_g ? b - r : r - g);
+    const int q = d ? (int)((2u * (unsigned)abs(num) * (unsigned)PHOTO_ONE + (unsigned)d) / (2u * (unsigned)d)) : 0;
+    int H = (is_r ? 0 : (is_g ? 2 : 4)) * PHOTO_ONE + (num >= 0 ? q : -q);
+    H = d == 0 ? 0 : (H < 0 ? H + PHOTO_SIX : H);
+    int V7 = V << 7, C7 = d << 7;
+    if constexpr (OP == 4) {
+        H += a0;
+        H = H >= PHOTO_SIX ? H - PHOTO_SIX : H;
+    } else if constexpr (OP == 5) {
+        const int t = (int)(((unsigned)V * (unsigned)abs(a0) + (1u << 15)) >> 16);
+        C7 = min(max(C7 + (a0 >= 0 ? t : -t), 0), V7);
+    } else {
+        V7 = min(max(V7 + a0, 0), 255 << 7);
+        C7 = V ? (int)((2u * (unsigned)V7 * (unsigned)d + (unsigned)V) / (2u * (unsigned)V)) : 0;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int k = (5 - 2 * c) * PHOTO_ONE + H;
+        k = k >= PHOTO_SIX ? k - PHOTO_SIX : k;
+        const int f = min(max(min(k, 4 * PHOTO_ONE - k), 0), PHOTO_ONE);
+        px[c] = (V7 * PHOTO_ONE - C7 * f + (1 << 22)) >> 23;
+    }
+}
+
+template <int OP>
+__device__ __forceinline__ void photo_pixel(const int* __restrict__ rc, int p, int px[3]) {
+    if constexpr (OP == 1) {
+        unsigned wd[4];
+        photo_philox((unsigned)p, 1u, (unsigned)rc[3], wd);
+        const unsigned u = wd[0];
+        int k = -PHOTO_NOISE_K;
+#pragma unroll
+        for (int j = 0; j < PHOTO_NOISE_K; ++j) {
+            const unsigned L = (unsigned)rc[PHOTO_PAYLOAD + j];
+            k += (L <= u ? 1 : 0) + (~u < L ? 1 : 0);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) px[c] = min(max(px[c] + k, 0), 255);
+    } else if constexpr (OP == 2) {
+        unsigned wd[4];
+        photo_philox((unsigned)p, 2u, (unsigned)rc[3], wd);
+        const unsigned lo = (unsigned)rc[4];
+        const bool all = rc[5] != 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            if (all || wd[c] < lo) px[c] = ((wd[3] >> c) & 1u) ? 255 : 0;
+    } else if constexpr (OP >= 4) {
+        photo_hsv<OP>(rc[4], px);
+    }
+}
+
+// A point operator on tiles of PHOTO_BLOCK * PHOTO_RUN pixels of the flat pixel array: a lane takes PHOTO_RUN
+// consecutive pixels, as three dwords each way where both slots are dword-aligned and the run is whole, bytewise
+// otherwise (odd slots, the image's last pixels).
+template <int OP>
+__device__ __forceinline__ void photo_point(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                            const int* __restrict__ rc, int npix) {
+    const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 3u) == 0;
+    const int tiles = (npix + PHOTO_BLOCK * PHOTO_RUN - 1) / (PHOTO_BLOCK * PHOTO_RUN);
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int p0 = (t * PHOTO_BLOCK + (int)threadIdx.x) * PHOTO_RUN;
+        if (p0 >= npix) continue;
+        const int n = min(PHOTO_RUN, npix - p0);
+        const bool wide = aligned && n == PHOTO_RUN;
+        int v[3 * PHOTO_RUN];
+        if (wide) {
+            const uint3 d = *reinterpret_cast<const uint3*>(in + 3 * (size_t)p0);
+            const unsigned wd[3] = {d.x, d.y, d.z};
+#pragma unroll
+            for (int i = 0; i < 3 * PHOTO_RUN; ++i) v[i] = (int)((wd[i >> 2] >> (8 * (i & 3))) & 255u);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3 * PHOTO_RUN; ++i) v[i] = i < 3 * n ? (int)in[3 * (size_t)p0 + i] : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < PHOTO_RUN; ++j)
+            if (j < n) photo_pixel<OP>(rc, p0 + j, v + 3 * j);
+        if (wide) {
+            unsigned wd[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int i = 0; i < 3 * PHOTO_RUN; ++i) wd[i >> 2] |= (unsigned)v[i] << (8 * (i & 3));
+            *reinterpret_cast<uint3*>(out + 3 * (size_t)p0) = make_uint3(wd[0], wd[1], wd[2]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3 * PHOTO_RUN; ++i)
+                if (i < 3 * n) out[3 * (size_t)p0 + i] = (uint8_t)v[i];
+        }
+    }
+}
+
+__device__ __forceinline__ int photo_reflect101(int k, int n) {
+    if ((unsigned)k < (unsigned)n) return k;
+    if (n == 1) return 0;
+    const int p = 2 * n - 2;
+    int r = k % p;
+    r = r < 0 ? r + p : r;
+    return r < n ? r : p - r;
+}
+
+// src [n_img][stride] bytes, image b as [h_b, w_b, 3] at the start of its slot (any byte alignment), records from the
+// DEVICE array recs[b] (no launch argument depends on a source size or on an operator) -> dst in the same layout: bytes
+// [0, 3 h w) of the slot are written, the rest of it is left alone.  A record out of range, or an image that does not fit
+// its slot, gets its WHOLE slot written as zeros and none of its source bytes are read.
+// Blur: the 32 x 32 tile's input with a halo of the record's radii goes to LDS as bytes (reflected indices, so every
+// read is inside the image), a horizontal pass leaves int32 sums (<= 255 * 2^11) of its 32 + 2 ry rows in LDS, a vertical
+// pass makes the bytes.  No rounding between the passes: the separable form is the 2D rule bit for bit.  36 KB of LDS.
+__global__ __launch_bounds__(PHOTO_BLOCK) void photometric_u8hwc3_kernel(const uint8_t* __restrict__ src,
+                                                                         uint8_t* __restrict__ dst, long long stride,
+                                                                         const int* __restrict__ recs) {
+    __shared__ uint8_t tin[PHOTO_IN][PHOTO_IN * 3];
+    __shared__ int hsum[PHOTO_IN][PHOTO_TILE * 3];
+    __shared__ int wgt[2][PHOTO_R_MAX + 1];
+    const int b = blockIdx.y;
+    const int tid = threadIdx.x;
+    const int* rc = recs + (size_t)b * PHOTO_REC_INTS;
+    const uint8_t* in = src + (long long)b * stride;
+    uint8_t* out = dst + (long long)b * stride;
+    if (!photo_record_ok(rc, stride)) {
+        for (long long o = ((long long)blockIdx.x * PHOTO_BLOCK + tid) * 16; o < stride;
+             o += (long long)gridDim.x * PHOTO_BLOCK * 16)
+            for (int k = 0; k < 16; ++k)
+                if (o + k < stride) out[o + k] = 0;
+        return;
+    }
+    const int h = rc[0], w = rc[1], op = rc[2];
+    switch (op) {
+        case 0: photo_point<0>(in, out, rc, h * w); return;
+        case 1: photo_point<1>(in, out, rc, h * w); return;
+        case 2: photo_point<2>(in, out, rc, h * w); return;
+        case 4: photo_point<4>(in, out, rc, h * w); return;
+        case 5: photo_point<5>(in, out, rc, h * w); return;
+        case 6: photo_point<6>(in, out, rc, h * w); return;
+        default: break;
+    }
+    const int rx = rc[6], ry = rc[7];
+    if (tid <= rx) wgt[0][tid] = rc[PHOTO_PAYLOAD + tid];
+    if (tid <= ry) wgt[1][tid] = rc[PHOTO_PAYLOAD + PHOTO_R_MAX + 1 + tid];
+    const int tiles_x = (w + PHOTO_TILE - 1) / PHOTO_TILE, tiles = tiles_x * ((h + PHOTO_TILE - 1) / PHOTO_TILE);
+    const int iw = PHOTO_TILE + 2 * rx, ih = PHOTO_TILE + 2 * ry;
+    constexpr int ROW = PHOTO_TILE * 3;                     // ints of a row of hsum, bytes of a tile's row of pixels
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int ty = t / tiles_x;
+        const int y0 = ty * PHOTO_TILE, x0 = (t - ty * tiles_x) * PHOTO_TILE;
+        __syncthreads();                                    // (the weights; the last tile's reads of tin and hsum)
+#pragma unroll 4
+        for (int i = tid; i < ih * iw; i += PHOTO_BLOCK) {             // (unrolled: several pixels' loads in flight)
+            const int ly = i / iw, lx = i - ly * iw;
+            const int sy = photo_reflect101(y0 - ry + ly, h), sx = photo_reflect101(x0 - rx + lx, w);
+            const uint8_t* p = in + (unsigned)((sy * w + sx) * 3);              // (< 3 * 16384^2: a 32-bit offset)
+            tin[ly][3 * lx] = p[0];
+            tin[ly][3 * lx + 1] = p[1];
+            tin[ly][3 * lx + 2] = p[2];
+        }
+        __syncthreads();
+        for (int i = tid; i < ih * ROW; i += PHOTO_BLOCK) {
+            const int ly = i / ROW, x3 = i - ly * ROW;      // x3 = 3 * column + channel
+            const uint8_t* c = &tin[ly][x3 + 3 * rx];
+            int acc = (int)c[0] * wgt[0][0];
+            for (int k = 1; k <= rx; ++k) acc += ((int)c[-3 * k] + (int)c[3 * k]) * wgt[0][k];
+            hsum[ly][x3] = acc;
+        }
+        __syncthreads();
+        for (int i = tid; i < PHOTO_TILE * ROW; i += PHOTO_BLOCK) {
+            const int oy = i / ROW, x3 = i - oy * ROW;
+            const int y = y0 + oy, x = x0 + x3 / 3;
+            if (y >= h || x >= w) continue;
+            int acc = hsum[oy + ry][x3] * wgt[1][0];
+            for (int k = 1; k <= ry; ++k) acc += (hsum[oy + ry - k][x3] + hsum[oy + ry + k][x3]) * wgt[1][k];
+            out[(unsigned)((y * w + x0) * 3 + x3)] = (uint8_t)((acc + RESIZE_HALF) >> 22);
+        }
+    }
+}
+
+extern "C" int fgn_photometric_u8hwc3(const unsigned char* src, unsigned char* dst, long long stride_bytes,
+                                      const int* recs, int n_img, hipStream_t stream) {
+    if (!src || !dst || !recs) return FGN_ERR_ARG;
+    if (n_img < 0 || n_img > 65535 || stride_bytes < 0 || stride_bytes > (1ll << 40)) return FGN_ERR_SHAPE;
+    if (n_img == 0 || stride_bytes == 0) return FGN_OK;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src), d = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t span = (uintptr_t)n_img * (uintptr_t)stride_bytes;
+    if (a < d + span && d < a + span) return FGN_ERR_ARG;     // (the blur reads neighbours: never in place)
+    const long long tile_bytes = 3ll * PHOTO_BLOCK * PHOTO_RUN;
+    const int grid = (int)std::min<long long>((stride_bytes + tile_bytes - 1) / tile_bytes, PHOTO_GRID_CAP);
+    hipLaunchKernelGGL(photometric_u8hwc3_kernel, dim3(grid, n_img), dim3(PHOTO_BLOCK), 0, stream, src, dst,
+                       stride_bytes, recs);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------
 // Supports from the source image behind the upload (BaseFewShotISEG.get_support, base_fst.py:1043-1167: get_crop with
 // reflected context, bicubic resize of the longer side to S, centre pad).  The arithmetic is the integer rule of
 // fgn_amd/fewshot_ds.py (cubic_taps / support_geometry / support_from_source) and the kernel agrees

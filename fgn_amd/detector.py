@@ -1013,16 +1013,40 @@ class FGN(torch.nn.Module):
             boxes.append(torch.from_numpy(nb) if as_tensor else nb)
         return torch.from_numpy(np.stack(recs)), boxes
 
+    @staticmethod
+    def _photometric_records(qry_photometric, rs: dict, qry_augment=None, aug_recs=None):
+        """The contract of ``qry_photometric`` (host only, nothing is queued): [B,3] finite rows of
+        ``fewshot_ds.PHOTO_PARAMS`` with operator, amount and seed inside their sets and a blur radius of at most 16 source
+        pixels.  -> records int32 [B,64] (``fewshot_ds.query_photometric_record``), or None when every row is neutral.
+        An image whose geometric row fell back to the plain sample (``aug_recs``: a neutral record for a row that is
+        not) gets the neutral record here too: ``bad_augment`` drops both halves (base_fst.py:751-768)."""
+        from . import fewshot_ds as fd
+        rows = qry_photometric.detach().cpu().numpy() if isinstance(qry_photometric, torch.Tensor) \
+            else np.asarray(qry_photometric)
+        if rows.dtype.kind not in 'iuf' or rows.shape != (rs['B'], len(fd.PHOTO_PARAMS)):
+            raise ValueError(f'qry_photometric must be [B,{len(fd.PHOTO_PARAMS)}] numbers {fd.PHOTO_PARAMS} for '
+                             f'{rs["B"]} images, got {rows.dtype} {list(rows.shape)}')
+        recs = np.stack([fd.query_photometric_record(row, hw, rs['hw']) for row, hw in zip(rows, rs['sizes'])])
+        if qry_augment is not None:
+            geo = qry_augment.detach().cpu().numpy() if isinstance(qry_augment, torch.Tensor) else np.asarray(qry_augment)
+            for i, (g, hw) in enumerate(zip(geo, rs['sizes'])):
+                if not fd.augment_is_neutral(fd.check_augment_params(g)) and not aug_recs[i, 2:6].any():
+                    recs[i] = fd.query_photometric_record(None, hw, rs['hw'])
+        return torch.from_numpy(recs) if recs[:, 2].any() else None
+
     def _train_front(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                      spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
                      spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
-                     **kwargs) -> dict:
+                     qry_photometric=None, **kwargs) -> dict:
         """The front of a training batch, shared by ``forward_train`` and ``train.Trainer``: the contracts of
-        ``qry_resize_to``, ``spp_crop_to`` and ``qry_augment`` (every error before anything is queued), then the uploads
-        and the kernels behind them.  -> the keyword arguments of ``train.forward_train``."""
+        ``qry_resize_to``, ``spp_crop_to``, ``qry_augment`` and ``qry_photometric`` (every error before anything is
+        queued), then the uploads and the kernels behind them.  -> the keyword arguments of ``train.forward_train``."""
         if qry_augment is not None and qry_resize_to is None:
             raise ValueError('qry_augment needs qry_resize_to: the query is augmented together with its resize from the '
                              'source size')
+        if qry_photometric is not None and qry_resize_to is None:
+            raise ValueError('qry_photometric needs qry_resize_to: the photometric operators run on the source pixels, '
+                             'ahead of their resize')
         sp = None
         if spp_crop_to is not None:                       # (every contract error before anything is queued)
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
@@ -1030,10 +1054,16 @@ class FGN(torch.nn.Module):
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
             if qry_augment is not None:
                 recs, boxes = self._augment_plans(qry_augment, qry_bboxes, rs)
+            precs = None
+            if qry_photometric is not None:
+                precs = self._photometric_records(qry_photometric, rs, qry_augment,
+                                                  recs.numpy() if qry_augment is not None else None)
             if not torch.cuda.is_available():
                 raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
             dev = torch.device('cuda', torch.cuda.current_device())
             qry_img = self._upload_source(rs, dev)
+            if precs is not None:                          # (all rows neutral after the fallback: no launch)
+                qry_img = qry_img._replace(src=ops.photometric_u8(qry_img.src, precs.to(dev, non_blocking=True)))
             if qry_augment is None:
                 qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
                 qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) for g in qry_isegmaps]
@@ -1235,7 +1265,7 @@ class FGN(torch.nn.Module):
     def forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                       spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
                       spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
-                      **kwargs) -> Dict:
+                      qry_photometric=None, **kwargs) -> Dict:
         """The loss dict of one training step (fgn.py:125-185) as forward values - see ``fgn_amd.train``.  Keys and
         container types are the reference's: ``loss_rpn_cls`` / ``loss_rpn_bbox`` (lists of one tensor),
         ``loss_cls``, ``ACC-Unbalanced``, ``ACC-Balanced``, ``loss_bbox``, ``loss_mask``.  ``qry_resize_to``: source-size
@@ -1244,21 +1274,26 @@ class FGN(torch.nn.Module):
         ``fewshot_ds.AUG_PARAMS`` - flip, rotation, scale, shear, translation, border, channel order - applied to image
         and masks on the device together with the resize (``fewshot_ds.augment_query`` bit for bit; ``get_query`` with
         ``augment_qry``, base_fst.py:889-891), to the boxes on the host; an image whose boxes leave it is
-        used un-augmented, as in the reference."""
+        used un-augmented, as in the reference.  ``qry_photometric`` (needs ``qry_resize_to``, with or without
+        ``qry_augment``): [B,3] rows of ``fewshot_ds.PHOTO_PARAMS`` - one of Gaussian noise, impulse noise, Gaussian blur,
+        hue, saturation, brightness per image, applied to the source pixels on the device ahead of the resize
+        (``fewshot_ds.photometric_image_u8`` bit for bit); an image whose boxes leave it under
+        ``qry_augment`` is used without either."""
         from . import train
         return train.forward_train(self, **self._train_front(
             qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals,
             spp_imgs=spp_imgs, spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps, img_shape=img_shape,
             qry_resize_to=qry_resize_to, spp_crop_to=spp_crop_to, spp_fill_ratio=spp_fill_ratio, crop_square=crop_square,
-            qry_augment=qry_augment, **kwargs))
+            qry_augment=qry_augment, qry_photometric=qry_photometric, **kwargs))
 
     @torch.no_grad()
     def simple_test(self, qry_img, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None, qry_bboxes_ignore=None,
                     spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, qry_child_idx=None, img_shape=None,
                     rescale=False, cats_ids_to_sample_real=None, spp_insts_ids=None, idx=None,
                     support_code=None, qry_resize_to=None, results_at_source: bool = False, spp_crop_to=None,
-                    spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None, **kwargs) -> List[Dict]:
-        """Test without augmentation (fgn.py:187-303; ``qry_augment`` is refused).  ``support_code`` (optional, from
+                    spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None, qry_photometric=None,
+                    **kwargs) -> List[Dict]:
+        """Test without augmentation (fgn.py:187-303; ``qry_augment`` and ``qry_photometric`` are refused).  ``support_code`` (optional, from
         ``encode_supports``) replaces the three ``spp_*`` inputs.  ``qry_resize_to`` = (H, W) (or a [B,2] tensor of
         equal rows): ``qry_img`` holds decoded images at their SOURCE size - a uint8 tensor [B,h,w,3] or a list of B
         uint8 tensors [h_i,w_i,3] - and ``qry_isegmaps`` / ``qry_bboxes`` are at source size too; image and masks are
@@ -1276,6 +1311,8 @@ class FGN(torch.nn.Module):
         of each image that its crop reads is uploaded; needs ``set_input_norm``."""
         if qry_augment is not None:
             raise ValueError('qry_augment is for forward_train: the test is without augmentation')
+        if qry_photometric is not None:
+            raise ValueError('qry_photometric is for forward_train: the test is without augmentation')
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
         sp = None

@@ -10,6 +10,7 @@ reproduced.
 from __future__ import annotations
 
 import itertools
+import math
 import os
 import pickle
 import random
@@ -501,6 +502,288 @@ def draw_query_augment(rng) -> np.ndarray:
     return p
 
 
+# ---- photometric query augmentation (the other six operators of ``augs_seq``, natural_fst.py:18-35) ----------------
+# AdditiveGaussianNoise, ImpulseNoise, GaussianBlur, AddToHue, AddToSaturation, AddToBrightness as ONE out-of-place pass
+# over the SOURCE bytes, ahead of the resize / geometric gather above (in ``augs_seq`` the photometric half acts first).
+# Like the rules above this is the project's own restatement in INTEGERS (imgaug is third party, no golden pins its
+# bytes), so that photometric_u8hwc3_kernel of csrc/spatial.hip agrees with ``photometric_image_u8`` bit for bit; every
+# table that depends on a float (blur weights, noise thresholds) is made here in float64 and travels in the record
+# (which derives the fixed-point widths and lists the conventions of imgaug taken from memory).
+PHOTO_PARAMS = ('operator', 'amount', 'seed')
+PHOTO_OPS = ('none', 'gaussian_noise', 'impulse_noise', 'gaussian_blur', 'hue', 'saturation', 'brightness')
+PHOTO_NEUTRAL = (0., 0., 0.)
+PHOTO_REC_INTS = 64           # int32 per image record: 8 of header, then the operator's payload
+PHOTO_REC_HEADER = ('h', 'w', 'operator', 'seed', 'a0', 'a1', 'rx', 'ry')
+PHOTO_PAYLOAD = 8             # noise: 12 thresholds; blur: x weights w[0..16] at 8, y weights w[0..16] at 25
+PHOTO_NOISE_K = 12            # the integer noise k lies in -12..12: six sigma at the largest scale
+PHOTO_NOISE_SCALE_MAX = 2.0
+PHOTO_BLUR_R_MAX = 16
+PHOTO_HUE_BITS = 16           # hue in units of 2^-16 sextants; the ramp f of a channel in units of 2^-16
+PHOTO_CHROMA_BITS = 7         # value and chroma in units of 2^-7 grey levels: 255 * 2^7 * 2^16 < 2^31
+PHOTO_SAT_BITS = 23           # the saturation amount / 255 in units of 2^-23: 255 * 2^23 < 2^31
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32(counter, key) -> np.ndarray:
+    """Philox4x32-10 (Salmon et al., SC'11).  ``counter`` [...,4], ``key`` [...,2] (broadcast against each other),
+    values in [0, 2^32) -> uint32 [...,4]."""
+    c = np.asarray(counter, np.uint64)
+    k = np.asarray(key, np.uint64)
+    lead = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], lead) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], lead) for i in range(2))
+    m32 = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(_PHILOX_M[0]) * c0, np.uint64(_PHILOX_M[1]) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m32
+        k0, k1 = (k0 + np.uint64(_PHILOX_W[0])) & m32, (k1 + np.uint64(_PHILOX_W[1])) & m32
+    return np.stack([c0, c1, c2, c3], -1).astype(np.uint32)
+
+
+def check_photometric_params(params) -> np.ndarray:
+    """One image's row ``PHOTO_PARAMS`` as float64 [3]; ValueError for a wrong shape, a non-finite entry, an operator
+    outside 0..6, a seed that is no integer in [0, 2^32) or an amount outside its operator's set: noise scale in (0, 2],
+    impulse p in [0, 1], blur sigma >= 0, hue / saturation / brightness in [-255, 255]."""
+    p = np.asarray(params.detach().cpu().numpy() if isinstance(params, torch.Tensor) else params)
+    if p.dtype.kind not in 'iuf' or p.shape != (len(PHOTO_PARAMS),):
+        raise ValueError(f'qry_photometric: one image\'s row is {len(PHOTO_PARAMS)} numbers {PHOTO_PARAMS}, got '
+                         f'{p.dtype} {list(p.shape)}')
+    p = p.astype(np.float64)
+    if not np.isfinite(p).all():
+        raise ValueError(f'qry_photometric: non-finite entries in {p.tolist()}')
+    op, a, seed = p
+    if op not in (0., 1., 2., 3., 4., 5., 6.):
+        raise ValueError(f'qry_photometric: the operator is 0..6 {PHOTO_OPS}, got {op}')
+    if seed != np.floor(seed) or not 0 <= seed < 2.0 ** 32:
+        raise ValueError(f'qry_photometric: the seed is an integer in [0, 2^32), got {seed}')
+    ok = {0: True, 1: 0 < a <= PHOTO_NOISE_SCALE_MAX, 2: 0 <= a <= 1, 3: a >= 0}.get(int(op), -255 <= a <= 255)
+    if not ok:
+        raise ValueError(f'qry_photometric: amount {a} is outside the set of operator {int(op)} ({PHOTO_OPS[int(op)]}): '
+                         f'noise scale in (0, {PHOTO_NOISE_SCALE_MAX}], impulse p in [0, 1], blur sigma >= 0, hue / '
+                         f'saturation / brightness in [-255, 255]')
+    return p
+
+
+def photometric_is_neutral(p: np.ndarray) -> bool:
+    """Operator 0, or an amount of 0 for operators 2 to 6."""
+    return p[0] == 0 or (p[0] >= 2 and p[1] == 0)
+
+
+def noise_thresholds(scale: float) -> np.ndarray:
+    """The lower half of the thresholds of the integer noise, int64 [12]: L_j = floor(Phi((j - 12 + 1/2) / scale) *
+    2^32) from ``erfc`` (the float64 ``erf`` saturates in the tails); the upper half is 2^32 - L_j by symmetry.  For a
+    uniform 32-bit word u, k = #{j : L_j <= u} - 12 + #{j : 2^32 - L_j <= u} is N(0, scale^2) rounded to an integer,
+    with the mass beyond +-12.5 on +-12."""
+    return np.array([int(math.floor(0.5 * math.erfc(-(j - PHOTO_NOISE_K + 0.5) / (scale * math.sqrt(2.0))) * 2.0 ** 32))
+                     for j in range(PHOTO_NOISE_K)], np.int64)
+
+
+def blur_weights(sigma_axis: float):
+    """One axis of the blur: radius r = max(1, ceil(3 sigma)) and the weights w[0..r] of offsets 0..r (symmetric) =
+    rint(2048 g_k / sum g), the centre adjusted so that w[0] + 2 sum w[1..r] = 2048 exactly.  ValueError for r > 16."""
+    s = float(sigma_axis)
+    r = max(1, int(np.ceil(3.0 * s))) if np.isfinite(s) and s > 0 else -1
+    if not 1 <= r <= PHOTO_BLUR_R_MAX:
+        raise ValueError(f'qry_photometric: a blur of sigma {s} source pixels needs a radius beyond {PHOTO_BLUR_R_MAX}')
+    k = np.arange(r + 1, dtype=np.float64)
+    with np.errstate(over='ignore', under='ignore'):
+        g = np.exp(-(k * k) / (2.0 * s * s))
+    w = np.rint(2048.0 * g / (g[0] + 2.0 * g[1:].sum())).astype(np.int64)
+    w[0] = 2048 - 2 * int(w[1:].sum())
+    return r, w
+
+
+def query_photometric_record(params, src_hw, net_hw) -> np.ndarray:
+    """What photometric_u8hwc3_kernel reads for one image, int32 [64]: the header ``PHOTO_REC_HEADER`` and the
+    operator's payload.  ``params`` None or a neutral row: operator 0 (a copy).
+      noise:      12 thresholds (``noise_thresholds``) at 8.
+      impulse:    (a0, a1) = low and high half of floor(p * 2^32).
+      blur:       sigma per axis in SOURCE pixels, sigma * w / W and sigma * h / H; (rx, ry) and w[0..rx] at 8, w[0..ry]
+                  at 25 (``blur_weights``).
+      hue:        a0 = rint(amount * 3 / 255 * 2^16) mod 6 * 2^16.
+      saturation: a0 = rint(amount / 255 * 2^23).        brightness: a0 = rint(amount * 2^7).
+    ValueError for a row outside its sets, sizes outside 1..16384 and a blur radius beyond 16."""
+    p = check_photometric_params(PHOTO_NEUTRAL if params is None else params)
+    (h, w), (H, W) = (int(v) for v in src_hw), (int(v) for v in net_hw)
+    _check_resize_dims(h, w, H, W)
+    rec = np.zeros(PHOTO_REC_INTS, np.int64)
+    rec[:2] = (h, w)
+    op, a = int(p[0]), float(p[1])
+    if not photometric_is_neutral(p):
+        rec[2] = op
+        if op in (1, 2):
+            rec[3] = int(p[2])
+        if op == 1:
+            rec[PHOTO_PAYLOAD:PHOTO_PAYLOAD + PHOTO_NOISE_K] = noise_thresholds(a)
+        elif op == 2:
+            P = int(np.floor(a * 2.0 ** 32))
+            rec[4:6] = (P & 0xFFFFFFFF, P >> 32)
+        elif op == 3:
+            (rx, wx), (ry, wy) = blur_weights(a * w / W), blur_weights(a * h / H)
+            rec[6:8] = (rx, ry)
+            rec[PHOTO_PAYLOAD:PHOTO_PAYLOAD + rx + 1] = wx
+            rec[PHOTO_PAYLOAD + PHOTO_BLUR_R_MAX + 1:PHOTO_PAYLOAD + PHOTO_BLUR_R_MAX + 2 + ry] = wy
+        elif op == 4:
+            rec[4] = int(np.rint(a * 3.0 / 255.0 * (1 << PHOTO_HUE_BITS))) % (6 << PHOTO_HUE_BITS)
+        elif op == 5:
+            rec[4] = int(np.rint(a / 255.0 * (1 << PHOTO_SAT_BITS)))
+        else:
+            rec[4] = int(np.rint(a * (1 << PHOTO_CHROMA_BITS)))
+    return (rec & 0xFFFFFFFF).astype(np.uint32).view(np.int32)            # (seed and thresholds: the low 32 bits as they are)
+
+
+def _photo_fields(rec) -> dict:
+    """The fields of a record, checked as the kernel checks them; ValueError where the kernel writes zeros."""
+    rec = np.asarray(rec)
+    if rec.dtype != np.int32 or rec.shape != (PHOTO_REC_INTS,):
+        raise ValueError(f'a photometric record is int32 [{PHOTO_REC_INTS}], got {rec.dtype} {list(rec.shape)}')
+    g = dict(zip(PHOTO_REC_HEADER, (int(v) for v in rec[:8])))
+    g['seed'] &= 0xFFFFFFFF
+    op, a0, a1 = g['operator'], g['a0'], g['a1']
+    ok = 1 <= g['h'] <= RESIZE_MAX_DIM and 1 <= g['w'] <= RESIZE_MAX_DIM and 0 <= op <= 6
+    if ok and op == 1:
+        g['thresholds'] = rec[PHOTO_PAYLOAD:PHOTO_PAYLOAD + PHOTO_NOISE_K].view(np.uint32).astype(np.int64)
+    elif ok and op == 2:
+        ok = a1 == 0 or (a1 == 1 and a0 == 0)
+        g['P'] = (a1 << 32) | (a0 & 0xFFFFFFFF)
+    elif ok and op == 3:
+        ok = 1 <= g['rx'] <= PHOTO_BLUR_R_MAX and 1 <= g['ry'] <= PHOTO_BLUR_R_MAX
+        if ok:
+            g['wx'] = rec[PHOTO_PAYLOAD:PHOTO_PAYLOAD + g['rx'] + 1].astype(np.int64)
+            y0 = PHOTO_PAYLOAD + PHOTO_BLUR_R_MAX + 1
+            g['wy'] = rec[y0:y0 + g['ry'] + 1].astype(np.int64)
+            ok = all(wt.min() >= 0 and wt.max() <= 2048 and wt[0] + 2 * wt[1:].sum() == 2048 for wt in (g['wx'], g['wy']))
+    elif ok and op == 4:
+        ok = 0 <= a0 < (6 << PHOTO_HUE_BITS)
+    elif ok and op == 5:
+        ok = abs(a0) <= (1 << PHOTO_SAT_BITS)
+    elif ok and op == 6:
+        ok = abs(a0) <= (255 << PHOTO_CHROMA_BITS)
+    if not ok:
+        raise ValueError(f'photometric record out of range: {g}')
+    return g
+
+
+def reflect101(k: np.ndarray, n: int) -> np.ndarray:
+    """Indices k (any integers) into an axis of n samples under reflect-101 (the edge sample is not repeated): r = k mod
+    (2n - 2), r < n ? r : 2n - 2 - r; always 0 for n = 1."""
+    k = np.asarray(k, np.int64)
+    if n == 1:
+        return np.zeros_like(k)
+    r = np.mod(k, 2 * n - 2)
+    return np.where(r < n, r, 2 * n - 2 - r)
+
+
+def _photo_hsv(img: np.ndarray, op: int, a0: int) -> np.ndarray:
+    """Hue, saturation and brightness of the record in integers.  V = max, d = V - min; the hue H in units of 2^-16
+    sextants from one rounded non-negative division by d; value V7 and chroma C7 in units of 2^-7 grey levels; channel n
+    of (5, 3, 1) for (R, G, B) = (V7 * 2^16 - C7 * f + 2^22) >> 23 with the ramp f = clip(min(k, 4 - k), 0, 1) of
+    k = (n + H) mod 6 in units of 2^-16."""
+    one, six = 1 << PHOTO_HUE_BITS, 6 << PHOTO_HUE_BITS
+    r, g, b = (img[..., c].astype(np.int64) for c in range(3))
+    V = np.maximum(np.maximum(r, g), b)
+    d = V - np.minimum(np.minimum(r, g), b)
+    is_r = V == r
+    is_g = ~is_r & (V == g)
+    num = np.where(is_r, g - b, np.where(is_g, b - r, r - g))
+    q = (2 * np.abs(num) * one + d) // np.maximum(2 * d, 1)
+    Hh = np.where(is_r, 0, np.where(is_g, 2, 4)) * one + np.where(num >= 0, q, -q)
+    Hh = np.where(d == 0, 0, np.where(Hh < 0, Hh + six, Hh))
+    V7, C7 = V << PHOTO_CHROMA_BITS, d << PHOTO_CHROMA_BITS
+    if op == 4:
+        Hh = Hh + a0
+        Hh = np.where(Hh >= six, Hh - six, Hh)
+    elif op == 5:
+        t = (V * abs(a0) + (1 << (PHOTO_SAT_BITS - PHOTO_CHROMA_BITS - 1))) >> (PHOTO_SAT_BITS - PHOTO_CHROMA_BITS)
+        C7 = np.clip(C7 + (t if a0 >= 0 else -t), 0, V7)
+    else:
+        V7 = np.clip(V7 + a0, 0, 255 << PHOTO_CHROMA_BITS)
+        C7 = (2 * V7 * d + V) // np.maximum(2 * V, 1)
+    out = np.empty(img.shape, np.uint8)
+    for c, n in enumerate((5, 3, 1)):
+        k = n * one + Hh
+        k = np.where(k >= six, k - six, k)
+        f = np.clip(np.minimum(k, 4 * one - k), 0, one)
+        out[..., c] = (V7 * one - C7 * f + (1 << (PHOTO_HUE_BITS + PHOTO_CHROMA_BITS - 1))) >> \
+            (PHOTO_HUE_BITS + PHOTO_CHROMA_BITS)
+    return out
+
+
+def photometric_image_u8(img: np.ndarray, rec: np.ndarray) -> np.ndarray:
+    """uint8 [h,w,3] -> uint8 [h,w,3] by record ``rec`` (``query_photometric_record``); the image is not changed.
+      noise:   Philox4x32-10 at counter (y * w + x, 0, 0, operator), key (seed, 0); k from word 0 and the thresholds, the
+               same k on the three channels, byte = clip(byte + k, 0, 255).
+      impulse: channel c is replaced where word c < floor(p * 2^32), by 255 where bit c of word 3 is set, else by 0.
+      blur:    (sum over the window of byte * wy * wx + 2^21) >> 22 with reflect-101 borders.
+      hue, saturation, brightness: ``_photo_hsv``."""
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError(f'photometric_image_u8: expects a uint8 [h,w,3] image, got {img.dtype} {list(img.shape)}')
+    g = _photo_fields(rec)
+    h, w = img.shape[:2]
+    if (h, w) != (g['h'], g['w']):
+        raise ValueError(f'the record is for a {(g["h"], g["w"])} source, got {(h, w)}')
+    op = g['operator']
+    if op == 0:
+        return img.copy()
+    if op in (1, 2):
+        ctr = np.zeros((h * w, 4), np.uint64)
+        ctr[:, 0], ctr[:, 3] = np.arange(h * w), op
+        words = philox4x32(ctr, (g['seed'], 0)).astype(np.int64).reshape(h, w, 4)
+        if op == 1:
+            u, L = words[..., 0, None], g['thresholds']
+            k = (L <= u).sum(-1) - PHOTO_NOISE_K + (0xFFFFFFFF - u < L).sum(-1)
+            return np.clip(img.astype(np.int64) + k[..., None], 0, 255).astype(np.uint8)
+        hit = words[..., :3] < g['P']
+        val = np.where((words[..., 3, None] >> np.arange(3)) & 1, 255, 0)
+        return np.where(hit, val, img).astype(np.uint8)
+    if op == 3:
+        rx, ry, wx, wy = g['rx'], g['ry'], g['wx'], g['wy']
+        ix, iy = reflect101(np.arange(-rx, w + rx), w), reflect101(np.arange(-ry, h + ry), h)
+        p = img.astype(np.int64)
+        hor = sum(p[:, ix[rx + k:rx + k + w]] * wx[abs(k)] for k in range(-rx, rx + 1))
+        acc = sum(hor[iy[ry + k:ry + k + h]] * wy[abs(k)] for k in range(-ry, ry + 1))
+        return ((acc + (1 << (2 * RESIZE_W_BITS - 1))) >> (2 * RESIZE_W_BITS)).astype(np.uint8)
+    return _photo_hsv(img, op, g['a0'])
+
+
+def augment_query_full(img: np.ndarray, bboxes_yxyx: np.ndarray, isegmaps: np.ndarray, H: int, W: int, params=None,
+                       photometric=None):
+    """``augment_query`` behind the photometric pass - ``augs_seq`` in the reference's order, photometric half first:
+    ``photometric_image_u8`` on the SOURCE image (its blur's sigma is given in network pixels), then resize and geometry
+    as one gather.  A sample whose boxes leave the image is used un-augmented in BOTH halves (``bad_augment``,
+    base_fst.py:751-768)."""
+    h, w = img.shape[:2]
+    rec, _ = augment_plan(params, bboxes_yxyx, (h, w), (H, W))
+    fell_back = params is not None and not augment_is_neutral(check_augment_params(params)) and not rec[2:6].any()
+    prec = query_photometric_record(photometric, (h, w), (H, W))            # (its contract errors, fallback or not)
+    if not fell_back and prec[2] != 0:
+        img = photometric_image_u8(img, prec)
+    return augment_query(img, bboxes_yxyx, isegmaps, H, W, params)
+
+
+def draw_query_augment_full(rng):
+    """(row of ``AUG_PARAMS``, row of ``PHOTO_PARAMS``) drawn like the whole ``augs_seq`` (natural_fst.py:18-35): the
+    geometric half as ``draw_query_augment`` draws it; with p = 1/2 one photometric operator of seven - noise of scale 1,
+    impulse noise with p uniform in [0, 0.03], blur with sigma uniform in [0, 3], hue uniform in [-50, 50], saturation
+    uniform in [-75, 75], brightness uniform in [-30, 30], or a uniformly drawn channel order, which goes into the first
+    row.  Never both a channel order and an operator of the second row."""
+    p = draw_query_augment(rng)
+    p[7] = 0                                        # (the channel order is one of the seven operators below)
+    q = np.array(PHOTO_NEUTRAL, np.float64)
+    if rng.random() < 0.5:
+        op = min(int(rng.random() * 7), 6)
+        if op == 6:
+            p[7] = min(int(rng.random() * 6), 5)
+        else:
+            lo, hi = ((1., 1.), (0., 0.03), (0., 3.), (-50., 50.), (-75., 75.), (-30., 30.))[op]
+            q[0] = op + 1
+            q[1] = lo if lo == hi else rng.uniform(lo, hi)
+            q[2] = min(int(rng.random() * 2.0 ** 32), 2 ** 32 - 1)
+    return p, q
+
+
 # ---- supports from the source image (BaseFewShotISEG.get_support, base_fst.py:1043-1167) ---------------------------
 # ``support_from_instance`` as ONE gather from the source image: crop (reflect context), bicubic resize of the longer
 # side to S and centre pad, with no padded copy of the image and no float.  The crop geometry is the golden-pinned
@@ -750,7 +1033,10 @@ class ClutteredCharsFewShotISEG(Dataset):
     drawn by ``draw_query_augment`` per (seed, child, epoch of ``reshuffle``), for a detector that augments the query on
     the device (``FGN.forward_train(qry_augment=...)``; ``get_query`` with ``augment_qry``, base_fst.py:889-891); the
     pixels, masks and boxes of the sample are NOT augmented.  Off by default: the samples are then what they always
-    were."""
+    were.  ``photometric_qry`` (needs ``augment_qry``): the sample also carries ``qry_photometric``, one row of
+    ``PHOTO_PARAMS`` float64 [3], and both rows come from the joint draw ``draw_query_augment_full`` (the whole
+    ``augs_seq``), seeded the same way, for ``FGN.forward_train(qry_photometric=...)``.  Off by default: the samples
+    are then key for key what they are without it."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
@@ -758,7 +1044,7 @@ class ClutteredCharsFewShotISEG(Dataset):
 
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
                  spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None,
-                 spp_source=False, augment_qry=False):
+                 spp_source=False, augment_qry=False, photometric_qry=False):
         par = self.PARAMS[dataset]
         self.raw_uint8 = bool(raw_uint8)
         self.spp_source = bool(spp_source)
@@ -773,6 +1059,10 @@ class ClutteredCharsFewShotISEG(Dataset):
         if self.augment_qry and self.source_size is None:
             raise ValueError('augment_qry needs source_size: the query is augmented by the detector together with its '
                              'resize from the source size')
+        self.photometric_qry = bool(photometric_qry)
+        if self.photometric_qry and not self.augment_qry:
+            raise ValueError('photometric_qry needs augment_qry: the two rows are one joint draw of the reference\'s '
+                             'augs_seq')
         self.epoch = 0                               # the ``e`` of the last ``reshuffle``: one augmentation draw per epoch
         self.n_ways, self.k_shots, self.batch, self.shuffle = n_ways, k_shots, batch, shuffle
         self.img_size, self.spp_img_size, self.spp_fill_ratio = img_size, spp_img_size, spp_fill_ratio
@@ -864,7 +1154,10 @@ class ClutteredCharsFewShotISEG(Dataset):
         }
         if self.source_size is not None:
             sample['qry_resize_to'] = np.array([self.img_size, self.img_size], dtype=np.int32)
-        if self.augment_qry:
+        if self.photometric_qry:
+            sample['qry_augment'], sample['qry_photometric'] = \
+                draw_query_augment_full(np.random.default_rng([int(self.seed), child, self.epoch]))
+        elif self.augment_qry:
             sample['qry_augment'] = draw_query_augment(np.random.default_rng([int(self.seed), child, self.epoch]))
         if self.spp_source:
             sample.update(spp_crop_to=int(self.spp_img_size), spp_fill_ratio=float(self.spp_fill_ratio), crop_square=True)

@@ -1155,6 +1155,27 @@ def augment_masks(masks: torch.Tensor, rec: torch.Tensor, H: int, W: int) -> tor
     return out
 
 
+PHOTO_REC_INTS = 64          # csrc/spatial.hip; fewshot_ds.PHOTO_REC_INTS: int32 per image record
+
+
+def photometric_u8(src: torch.Tensor, recs: torch.Tensor) -> torch.Tensor:
+    """Source-size images -> the same slots after their photometric operator: ``fewshot_ds.photometric_image_u8`` of
+    every image, bit for bit, in one launch.  ``src`` uint8 [n,capacity] as for ``resize_u8_to_nhwc4``; ``recs`` int32
+    [n,64] ON THE DEVICE: the records of ``fewshot_ds.query_photometric_record``, read by the kernel.  -> a new uint8
+    [n,capacity]: the h * w * 3 bytes of every image are written, what lies behind them in a slot is not.  An image whose
+    record is out of range or whose size exceeds the capacity has its slot written as zeros."""
+    _chk(src, 'src', torch.uint8)
+    _chk(recs, 'recs', torch.int32)
+    if src.dim() != 2 or tuple(recs.shape) != (src.shape[0], PHOTO_REC_INTS) or recs.device != src.device:
+        raise _lib.FgnHipError('photometric_u8: expects src [n,capacity] and recs [n,64] on one device')
+    dst = torch.empty_like(src)
+    if src.numel() == 0:                # (an empty tensor has no address to hand over)
+        return dst
+    _lib.check(_lib.load().fgn_photometric_u8hwc3(_ptr(src), _ptr(dst), int(src.shape[1]), _ptr(recs),
+                                                  int(src.shape[0]), _stream()), 'fgn_photometric_u8hwc3')
+    return dst
+
+
 SPP_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.SPP_REC_INTS: int32 per instance record
 
 

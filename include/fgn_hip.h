@@ -267,6 +267,27 @@ int fgn_augment_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stri
 int fgn_augment_mask_u8(const unsigned char* src, unsigned char* dst, const int* rec, int G, int h, int w, int H, int W,
                         void* stream);
 
+/* Photometric query augmentation on the source bytes, ahead of the two gathers above (the other six operators of
+ * augs_seq, natural_fst.py:18-35: Gaussian noise, impulse noise, Gaussian blur, hue, saturation, brightness): one
+ * out-of-place pass src -> dst, both [n_img][stride_bytes] with image b as [h_b, w_b, 3] bytes at the start of slot b
+ * (any byte alignment).  It computes the integer rule of fgn_amd.fewshot_ds (query_photometric_record; a restatement of
+ * imgaug's operators that no reference golden pins) and agrees with photometric_image_u8 bit for bit.
+ *   recs int32 [n_img][64], read ON THE DEVICE (no launch argument depends on a source size or on an operator):
+ *     {h, w, op, seed, a0, a1, rx, ry, payload ...}
+ *     op 0: copy.
+ *     op 1: Gaussian noise.  u = word 0 of Philox4x32-10 at counter (y * w + x, 0, 0, op), key (seed, 0); payload 12
+ *           thresholds L; k = #{L[j] <= u} - 12 + #{~u < L[j]}; the pixel's three bytes become clip(byte + k, 0, 255).
+ *     op 2: impulse noise.  Byte c is replaced where word c < a1 * 2^32 + a0, by 255 where bit c of word 3 is set, else 0.
+ *     op 3: Gaussian blur.  Radii rx, ry in 1..16; weights of offset |k|: w[0..rx] at 8, w[0..ry] at 25, each axis summing
+ *           to 2048; byte = (sum of byte * wy * wx + 2^21) >> 22; reflect-101 border.
+ *     op 4 / 5 / 6: hue / saturation / brightness with a0 = the amount as rint(a * 3 / 255 * 2^16) mod 6 * 2^16 /
+ *           rint(a / 255 * 2^23) / rint(a * 2^7) (DESIGN.md 4.4.6 for the fixed-point rule).
+ *   Bytes [0, 3 h w) of a slot are written.  A record out of range (size outside 1..16384, operator, radius, weights not
+ *   summing to 2048, amount outside its set) or with h * w * 3 > stride_bytes gets its whole slot written as zeros and none
+ *   of its source bytes are read.  src and dst must not overlap (FGN_ERR_ARG): the blur reads neighbours. */
+int fgn_photometric_u8hwc3(const unsigned char* src, unsigned char* dst, long long stride_bytes, const int* recs,
+                           int n_img, void* stream);
+
 /* Supports from the source image behind the upload (BaseFewShotISEG.get_support, base_fst.py:1043-1167: get_crop with
  * reflected context, bicubic resize of the longer side to S, centre pad): one launch for all n = B * N * K instances of
  * a batch.  The arithmetic is the integer rule of fgn_amd.fewshot_ds (cubic_taps: cubic convolution A = -3/4, half-pixel
