@@ -183,6 +183,13 @@ __device__ __forceinline__ vf<V> vfma(float k, vf<V> a, vf<V> acc) {
     for (int i = 0; i < V; ++i) r[i] = fmaf(k, a[i], acc[i]);
     return r;
 }
+// The in_scale product a * s, rounded on its own: contracted into the first difference of wg4_bt (fma(d3, s, -(d1 * s)))
+// it leaves x s - round(x s) where equal inputs must cancel to exactly 0 (tests/test_hip_wg_bound.py, the guided case).
+template <int V>
+__device__ __forceinline__ vf<V> vmul_rn(vf<V> a, vf<V> s) {
+#pragma clang fp contract(off)
+    return a * s;
+}
 template <int V>
 __device__ __forceinline__ vf<V> vzero() {
     vf<V> r;
@@ -278,7 +285,7 @@ __global__ __launch_bounds__(256) void wg4_input_kernel(const float* __restrict_
             for (int b = 0; b < 6; ++b) {             // tt[.][b] = B^T (d * s)[.][b], in place
                 T d[6], rr[6];
 #pragma unroll
-                for (int a = 0; a < 6; ++a) d[a] = tt[a][b] * s;
+                for (int a = 0; a < 6; ++a) d[a] = vmul_rn<V>(tt[a][b], s);
                 wg4_bt<V>(d, rr);
 #pragma unroll
                 for (int a = 0; a < 6; ++a) tt[a][b] = rr[a];
@@ -292,7 +299,7 @@ __global__ __launch_bounds__(256) void wg4_input_kernel(const float* __restrict_
                 for (int a = 0; a < 6; ++a) {
                     const int iy = iy0 + a;
                     d[a] = ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)
-                               ? src[((size_t)iy * W + ix) * CV] * s : vzero<V>();
+                               ? vmul_rn<V>(src[((size_t)iy * W + ix) * CV], s) : vzero<V>();
                 }
                 wg4_bt<V>(d, rr);
 #pragma unroll
