@@ -93,11 +93,10 @@ extern "C" int fgn_u8hwc3_to_nhwc4_f32(const unsigned char* x, const float* lut,
 //     num = (2j+1) * n_src - n_dst, den = 2 * n_dst, i0 = floor(num / den), rem = num - i0 * den,
 //     w1 = (rem * 4096 + den) / (2 * den), w1 = 0 where i0 < 0, i1 = min(i0 + 1, n_src - 1), i0 clamped, w0 = 2048 - w1
 // num > -den, so the floor division is one unsigned division of num + den; w1 costs a second one (divisor 2 * den).
-// The unit of work is one wave on 64 consecutive lane items of ONE output row: image, row and the row's y taps are
-// wave-uniform (scalar registers, one scalar division pair per unit), the x taps are per lane.
 // ----------------------------------------------------------------------------------
 constexpr int RESIZE_MAX_DIM = 16384;
 constexpr int RESIZE_BLOCK = 256;
+constexpr int RESIZE_WAVES = RESIZE_BLOCK / 64;
 constexpr int RESIZE_GRID_CAP = 256 * 8;      // workgroups; waves loop over further units
 constexpr int RESIZE_HALF = 1 << 21;          // half of the weight sum 2048 * 2048
 
@@ -115,130 +114,6 @@ __device__ __forceinline__ ResizeTap resize_tap(int j, int n_src, int n_dst) {
     return t;
 }
 
-// Source images [h_b, w_b, 3] uint8 at src + b * stride (any byte alignment), sizes from the DEVICE array src_hw[b] =
-// {h_b, w_b} (no launch argument depends on a source size: one captured launch serves every source size) ->
-// y [n,H,W,4] fp32 = {lut[0][r], lut[1][g], lut[2][b], +0}: u8hwc3_to_nhwc4_kernel of the resized image.  A lane makes
-// one output pixel: 4 taps x 3 bytes from two source rows (neighbouring lanes share cache lines; the source is a few MB
-// and stays in L2), three table lookups in LDS, one 16-byte store - 1 KB per wave, coalesced; like the kernel above it
-// waits on those stores.  Every index is clamped into [0,h) x [0,w); an image whose size is outside 1..RESIZE_MAX_DIM
-// or does not fit its slot is written as zeros and none of its bytes are read.
-__global__ __launch_bounds__(RESIZE_BLOCK) void resize_u8hwc3_to_nhwc4_kernel(const uint8_t* __restrict__ src,
-                                                                              long long stride,
-                                                                              const int* __restrict__ src_hw,
-                                                                              const float* __restrict__ lut,
-                                                                              float4* __restrict__ y, int H, int W,
-                                                                              int chunks, int units) {
-    __shared__ float t[3 * 256];
-    for (int i = threadIdx.x; i < 3 * 256; i += RESIZE_BLOCK) t[i] = lut[i];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int WAVES = RESIZE_BLOCK / 64;
-    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
-        const int r = u / chunks;                           // image * H + row
-        const int chunk = u - r * chunks;
-        const int b = r / H, oy = r - b * H;
-        const int h = src_hw[2 * b], w = src_hw[2 * b + 1];
-        const int ox = chunk * 64 + lane;
-        if (ox >= W) continue;
-        float4* o = y + (size_t)r * W + ox;
-        const bool ok = h >= 1 && h <= RESIZE_MAX_DIM && w >= 1 && w <= RESIZE_MAX_DIM && (long long)h * w * 3 <= stride;
-        if (!ok) {
-            *o = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        const ResizeTap ty = resize_tap(oy, h, H), tx = resize_tap(ox, w, W);
-        const uint8_t* img = src + (long long)b * stride;
-        const uint8_t* r0 = img + (size_t)ty.i0 * w * 3;
-        const uint8_t* r1 = img + (size_t)ty.i1 * w * 3;
-        const int a = tx.i0 * 3, c = tx.i1 * 3;
-        const int w00 = ty.w0 * tx.w0, w01 = ty.w0 * tx.w1, w10 = ty.w1 * tx.w0, w11 = ty.w1 * tx.w1;
-        int v[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            v[k] = ((int)r0[a + k] * w00 + (int)r0[c + k] * w01 + (int)r1[a + k] * w10 + (int)r1[c + k] * w11 +
-                    RESIZE_HALF) >> 22;
-        *o = make_float4(t[v[0]], t[256 + v[1]], t[512 + v[2]], 0.f);
-    }
-}
-
-extern "C" int fgn_resize_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stride_bytes, const int* src_hw,
-                                              const float* lut, float* y, int n_img, int H, int W,
-                                              hipStream_t stream) {
-    if (!src || !src_hw || !lut || !y) return FGN_ERR_ARG;
-    if (n_img < 0 || H < 0 || W < 0 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM || src_stride_bytes < 0)
-        return FGN_ERR_SHAPE;
-    if ((long long)n_img * H * W == 0) return FGN_OK;
-    const int chunks = cdiv(W, 64);
-    const long long units = (long long)n_img * H * chunks;
-    if (units > INT32_MAX - 4 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;       // (unit indices are int32, stride included)
-    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP);
-    hipLaunchKernelGGL(resize_u8hwc3_to_nhwc4_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes,
-                       src_hw, lut, reinterpret_cast<float4*>(y), H, W, chunks, (int)units);
-    FGN_LAUNCH_CHECK();
-    return FGN_OK;
-}
-
-// Masks [G,h,w] (bool or bytes: nonzero = set) -> [G,H,W] 0/1 bytes by the same taps on 0/1 values, set where
-// acc >= 2^21 (half counts as set): cv2.resize(m.astype(uint8)).astype(bool) of base_fst.py:885.  A lane makes the
-// four pixels of one ALIGNED dword of the output row (the first group of a row starts up to 3 bytes before the row, so
-// that dst + 4 * k is dword-aligned whatever W and the row are) and stores it whole; a group that the row's ends cut
-// goes bytewise.  Dimensions are launch arguments: the ground-truth work of an episode is eager (G differs per image).
-__global__ __launch_bounds__(RESIZE_BLOCK) void resize_mask_u8_kernel(const uint8_t* __restrict__ src,
-                                                                      uint8_t* __restrict__ dst, int h, int w, int H,
-                                                                      int W, int chunks, int units) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int WAVES = RESIZE_BLOCK / 64;
-    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
-        const int r = u / chunks;                           // mask * H + row
-        const int chunk = u - r * chunks;
-        const int g = r / H, oy = r - g * H;
-        uint8_t* row = dst + (size_t)r * W;
-        const int lead = (int)(reinterpret_cast<uintptr_t>(row) & 3u);      // bytes of the row's first dword before it
-        const int x_lo = (chunk * 64 + lane) * 4 - lead;
-        if (x_lo >= W) continue;
-        const ResizeTap ty = resize_tap(oy, h, H);
-        const uint8_t* r0 = src + ((size_t)g * h + ty.i0) * w;
-        const uint8_t* r1 = src + ((size_t)g * h + ty.i1) * w;
-        unsigned word = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int ox = x_lo + k;
-            if (ox < 0 || ox >= W) continue;
-            const ResizeTap tx = resize_tap(ox, w, W);
-            const int acc = (r0[tx.i0] ? ty.w0 * tx.w0 : 0) + (r0[tx.i1] ? ty.w0 * tx.w1 : 0) +
-                            (r1[tx.i0] ? ty.w1 * tx.w0 : 0) + (r1[tx.i1] ? ty.w1 * tx.w1 : 0);
-            word |= (acc >= RESIZE_HALF ? 1u : 0u) << (8 * k);
-        }
-        if (x_lo >= 0 && x_lo + 4 <= W) {
-            *reinterpret_cast<unsigned*>(row + x_lo) = word;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (x_lo + k >= 0 && x_lo + k < W) row[x_lo + k] = (uint8_t)((word >> (8 * k)) & 1u);
-        }
-    }
-}
-
-extern "C" int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, int G, int h, int w, int H, int W,
-                                  hipStream_t stream) {
-    if (!src || !dst) return FGN_ERR_ARG;
-    if (G < 0 || h < 0 || w < 0 || H < 0 || W < 0 || h > RESIZE_MAX_DIM || w > RESIZE_MAX_DIM || H > RESIZE_MAX_DIM ||
-        W > RESIZE_MAX_DIM)
-        return FGN_ERR_SHAPE;
-    if ((long long)G * H * W == 0) return FGN_OK;
-    if (h == 0 || w == 0) return FGN_ERR_SHAPE;               // (pixels to make and none to make them of)
-    const int chunks = cdiv(W + 3, 256);
-    const long long units = (long long)G * H * chunks;
-    if (units > INT32_MAX - 16 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;      // (unit indices are int32, stride included)
-    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP * 4);
-    hipLaunchKernelGGL(resize_mask_u8_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, dst, h, w, H, W, chunks,
-                       (int)units);
-    FGN_LAUNCH_CHECK();
-    return FGN_OK;
-}
-
 // ----------------------------------------------------------------------------------
 // Query augmentation behind the upload (BaseFewShotISEG.augment_with_imgaug, base_fst.py:735-770, on the geometric half
 // of natural_fst.py:18-35 and its ChannelShuffle), composed with the resize above into ONE bilinear gather from the
@@ -250,8 +125,8 @@ extern "C" int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, 
 //           i0 = U >> 20, f = U & (2^20-1), w1 = (f + 256) >> 9, w0 = 2048 - w1; taps i0, i0+1 (and j0, j0+1);
 //           a tap outside the image reads its symmetric extension (border 1: r = k mod 2n, r < n ? r : 2n-1-r) or 0.
 //   |c00|,|c01|,|c10|,|c11| <= 2^26 and |c02|,|c12| <= 2^40, so |U| < 2^42 and i0 fits int32.
-// As for the resize a wave takes 64 consecutive lane items of one output row: the record, the kind and the row terms
-// c01*oy + c02, c11*oy + c12 are wave-uniform, a lane adds one 32x32->64 multiply per axis.
+// As fewshot_ds._augment_acc calls _resize_acc for kind 0, the resize kernels are the gathers below without a record:
+// kind 0, no flip, channel order 0, all of it known to the compiler.
 // ----------------------------------------------------------------------------------
 constexpr int AUG_REC_INTS = 16;
 constexpr int AUG_FRAC_BITS = 20;
@@ -263,12 +138,17 @@ struct AugRec {
     long long c02, c12;
     bool ok;                                  // every field inside its set: the only records a kernel reads pixels for
 };
+// REC: rc is a record; without it rc is {h, w} alone, read as the neutral record of that size (the plain resize).
+template <bool REC>
 __device__ __forceinline__ AugRec aug_record(const int* __restrict__ rc) {
-    AugRec r;
-    r.h = rc[0]; r.w = rc[1]; r.kind = rc[2]; r.flip = rc[3]; r.border = rc[4]; r.perm = rc[5];
-    r.c00 = rc[6]; r.c01 = rc[7]; r.c10 = rc[8]; r.c11 = rc[9];
-    r.c02 = (long long)(((unsigned long long)(unsigned)rc[11] << 32) | (unsigned)rc[10]);
-    r.c12 = (long long)(((unsigned long long)(unsigned)rc[13] << 32) | (unsigned)rc[12]);
+    AugRec r = {};
+    r.h = rc[0]; r.w = rc[1];
+    if constexpr (REC) {
+        r.kind = rc[2]; r.flip = rc[3]; r.border = rc[4]; r.perm = rc[5];
+        r.c00 = rc[6]; r.c01 = rc[7]; r.c10 = rc[8]; r.c11 = rc[9];
+        r.c02 = (long long)(((unsigned long long)(unsigned)rc[11] << 32) | (unsigned)rc[10]);
+        r.c12 = (long long)(((unsigned long long)(unsigned)rc[13] << 32) | (unsigned)rc[12]);
+    }
     const auto lin = [](int v) { return v >= -AUG_LIN_MAX && v <= AUG_LIN_MAX; };
     const auto off = [](long long v) { return v >= -AUG_OFF_MAX && v <= AUG_OFF_MAX; };
     r.ok = r.h >= 1 && r.h <= RESIZE_MAX_DIM && r.w >= 1 && r.w <= RESIZE_MAX_DIM && (r.kind == 0 || r.kind == 1) &&
@@ -303,169 +183,279 @@ __device__ __forceinline__ ResizeTap aug_tap(long long U, int n, bool symmetric)
 
 __device__ __forceinline__ int aug_pick(const int v[3], int p) { return p == 0 ? v[0] : (p == 1 ? v[1] : v[2]); }
 
-// Source images as for resize_u8hwc3_to_nhwc4_kernel, records from the DEVICE array recs[b] (no launch argument depends
-// on a source size or on the augmentation) -> y [n,H,W,4] fp32 = u8hwc3_to_nhwc4_kernel of augment_image_u8's image:
-// channel c of the output is table c of byte order[c] of the blended pixel.  A lane makes one output pixel: 4 taps x 3
-// bytes - for kind 1 along a slanted line through the source (at 10 degrees a wave's 64 pixels span about 11 source
-// rows, the gathers are served by L2) - three table lookups in LDS, one 16-byte store.  A record out of range, or an
-// image that does not fit its slot, is written as zeros and none of its bytes are read.
+// The four taps (ty.i0 | ty.i1) x (tx.i0 | tx.i1) of an image of rows of w pixels of NCH bytes, blended with wy * wx
+// (which sum to 2^22): acc[k] += byte k of the tap * weight - or, with BITS, the weight where the byte is nonzero (masks).
+// GUARD: a tap index may be -1, "reads 0" (kind 1); without it every index is inside the image (kind 0).  The offsets are
+// 32-bit on a wave-uniform base: (i * w + j) * NCH < 3 * 16384^2.
+template <int NCH, bool BITS, bool GUARD>
+__device__ __forceinline__ void blend4(const uint8_t* __restrict__ img, int w, const ResizeTap& ty, const ResizeTap& tx,
+                                       int acc[NCH]) {
+    const int iy[2] = {ty.i0, ty.i1}, wy[2] = {ty.w0, ty.w1};
+    const int ix[2] = {tx.i0, tx.i1}, wx[2] = {tx.w0, tx.w1};
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        if (GUARD && iy[a] < 0) continue;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            if (GUARD && ix[c] < 0) continue;
+            const uint8_t* p = img + (unsigned)((iy[a] * w + ix[c]) * NCH);
+            const int wgt = wy[a] * wx[c];
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) acc[k] += BITS ? (p[k] ? wgt : 0) : (int)p[k] * wgt;
+        }
+    }
+}
+
+// The unit of work of the row kernels (these gathers and support_from_source_kernel): one wave on 64 consecutive lane
+// items of ONE output row.  Item (image, mask or instance), row, the row's y taps or row terms and a record are
+// wave-uniform (scalar registers, one scalar division pair per unit for resize_tap), the x taps are per lane; for kind 1
+// a lane adds one 32x32->64 multiply per axis to the row terms c01*oy + c02, c11*oy + c12.
+struct WaveUnits { int lane, first, step; };              // the units first, first + step, ... of this lane's wave
+__device__ __forceinline__ WaveUnits wave_units() {
+    WaveUnits q;
+    q.lane = threadIdx.x & 63;
+    q.first = blockIdx.x * RESIZE_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    q.step = gridDim.x * RESIZE_WAVES;
+    return q;
+}
+struct RowUnit { int r, item, row, chunk; };              // r = item * rows + row
+__device__ __forceinline__ RowUnit row_unit(int u, int chunks, int rows) {
+    RowUnit q;
+    q.r = u / chunks;
+    q.chunk = u - q.r * chunks;
+    q.item = q.r / rows;
+    q.row = q.r - q.item * rows;
+    return q;
+}
+
+// The normalisation table into LDS (3 KB), as in u8hwc3_to_nhwc4_kernel.
+__device__ __forceinline__ void lut_to_lds(float* __restrict__ t, const float* __restrict__ lut) {
+    for (int i = threadIdx.x; i < 3 * 256; i += RESIZE_BLOCK) t[i] = lut[i];
+    __syncthreads();
+}
+
+// Launch geometry of the row kernels: `rows` output rows of `items` lane items, `chunk` of them to a wave's unit, at most
+// `grid_cap` workgroups.  Unit indices are int32, the stride of wave_units (grid_cap workgroups of RESIZE_WAVES)
+// included: more units than that is FGN_ERR_SHAPE.
+struct RowGrid { int chunks, units, grid; };
+static int row_grid(long long rows, int items, int chunk, int grid_cap, RowGrid* g) {
+    g->chunks = cdiv(items, chunk);
+    const long long units = rows * g->chunks;
+    if (units > INT32_MAX - RESIZE_WAVES * grid_cap) return FGN_ERR_SHAPE;
+    g->units = (int)units;
+    g->grid = (int)std::min<long long>((units + RESIZE_WAVES - 1) / RESIZE_WAVES, grid_cap);
+    return FGN_OK;
+}
+
+// Source images [h_b, w_b, 3] uint8 at src + b * stride (any byte alignment), described by the DEVICE array desc - the
+// records recs[b] (REC), or src_hw[b] = {h_b, w_b} - so that no launch argument depends on a source size or on the
+// augmentation: one captured launch serves them all.  -> y [n,H,W,4] fp32 = u8hwc3_to_nhwc4_kernel of augment_image_u8's
+// image (resize_image_u8's without a record): channel c of the output is table c of byte order[c] of the blended pixel,
+// {lut[0][r], lut[1][g], lut[2][b], +0} for order 0.  A lane makes one output pixel: 4 taps x 3 bytes - for kind 0 from
+// two source rows (neighbouring lanes share cache lines; the source is a few MB and stays in L2), for kind 1 along a
+// slanted line through the source (at 10 degrees a wave's 64 pixels span about 11 source rows, the gathers are served by
+// L2) - three table lookups in LDS, one 16-byte store: 1 KB per wave, coalesced; like u8hwc3_to_nhwc4_kernel it waits on
+// those stores.  Every index of kind 0 is clamped into [0,h) x [0,w).  A record out of range, a size outside
+// 1..RESIZE_MAX_DIM or an image that does not fit its slot is written as zeros and none of its bytes are read.
+// Without a record, kind, flip, channel order and "every tap is inside" are compile-time: no int64 coordinates, no tap
+// guards, no selects.
+template <bool REC>
+__device__ __forceinline__ void image_gather(const uint8_t* __restrict__ src, long long stride,
+                                             const int* __restrict__ desc, const float* __restrict__ lut,
+                                             float4* __restrict__ y, int H, int W, int chunks, int units) {
+    __shared__ float t[3 * 256];
+    lut_to_lds(t, lut);
+    const WaveUnits wu = wave_units();
+    for (int u = wu.first; u < units; u += wu.step) {
+        const RowUnit q = row_unit(u, chunks, H);           // item: the image
+        const AugRec g = aug_record<REC>(desc + (size_t)q.item * (REC ? AUG_REC_INTS : 2));
+        const int ox = q.chunk * 64 + wu.lane, oy = q.row;
+        if (ox >= W) continue;
+        float4* o = y + (size_t)q.r * W + ox;
+        if (!g.ok || (long long)g.h * g.w * 3 > stride) {
+            *o = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        ResizeTap ty, tx;
+        if (!REC || g.kind == 0) {
+            ty = resize_tap(oy, g.h, H);
+            tx = resize_tap(REC && g.flip ? W - 1 - ox : ox, g.w, W);
+        } else {
+            const long long ru = (long long)g.c01 * oy + g.c02, rv = (long long)g.c11 * oy + g.c12;     // wave-uniform
+            tx = aug_tap(ru + (long long)g.c00 * ox, g.w, g.border == 1);
+            ty = aug_tap(rv + (long long)g.c10 * ox, g.h, g.border == 1);
+        }
+        int acc[3] = {0, 0, 0};
+        blend4<3, false, REC>(src + (long long)q.item * stride, g.w, ty, tx, acc);
+        int v[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = (acc[k] + RESIZE_HALF) >> 22;
+        if constexpr (REC) {
+            // itertools.permutations(range(3))[perm] = (p0, p1, p2), two bits each
+            const int p0 = (0xA50 >> (2 * g.perm)) & 3, p1 = (0x489 >> (2 * g.perm)) & 3, p2 = (0x126 >> (2 * g.perm)) & 3;
+            *o = make_float4(t[aug_pick(v, p0)], t[256 + aug_pick(v, p1)], t[512 + aug_pick(v, p2)], 0.f);
+        } else {
+            *o = make_float4(t[v[0]], t[256 + v[1]], t[512 + v[2]], 0.f);
+        }
+    }
+}
+
+__global__ __launch_bounds__(RESIZE_BLOCK) void resize_u8hwc3_to_nhwc4_kernel(const uint8_t* __restrict__ src,
+                                                                              long long stride,
+                                                                              const int* __restrict__ src_hw,
+                                                                              const float* __restrict__ lut,
+                                                                              float4* __restrict__ y, int H, int W,
+                                                                              int chunks, int units) {
+    image_gather<false>(src, stride, src_hw, lut, y, H, W, chunks, units);
+}
+
 __global__ __launch_bounds__(RESIZE_BLOCK) void augment_u8hwc3_to_nhwc4_kernel(const uint8_t* __restrict__ src,
                                                                                long long stride,
                                                                                const int* __restrict__ recs,
                                                                                const float* __restrict__ lut,
                                                                                float4* __restrict__ y, int H, int W,
                                                                                int chunks, int units) {
-    __shared__ float t[3 * 256];
-    for (int i = threadIdx.x; i < 3 * 256; i += RESIZE_BLOCK) t[i] = lut[i];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int WAVES = RESIZE_BLOCK / 64;
-    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
-        const int r = u / chunks;                           // image * H + row
-        const int chunk = u - r * chunks;
-        const int b = r / H, oy = r - b * H;
-        const AugRec g = aug_record(recs + (size_t)b * AUG_REC_INTS);
-        const int ox = chunk * 64 + lane;
-        if (ox >= W) continue;
-        float4* o = y + (size_t)r * W + ox;
-        if (!g.ok || (long long)g.h * g.w * 3 > stride) {
-            *o = make_float4(0.f, 0.f, 0.f, 0.f);
-            continue;
-        }
-        ResizeTap ty, tx;
-        if (g.kind == 0) {
-            ty = resize_tap(oy, g.h, H);
-            tx = resize_tap(g.flip ? W - 1 - ox : ox, g.w, W);
-        } else {
-            const long long ru = (long long)g.c01 * oy + g.c02, rv = (long long)g.c11 * oy + g.c12;     // wave-uniform
-            tx = aug_tap(ru + (long long)g.c00 * ox, g.w, g.border == 1);
-            ty = aug_tap(rv + (long long)g.c10 * ox, g.h, g.border == 1);
-        }
-        const uint8_t* img = src + (long long)b * stride;
-        int acc[3] = {0, 0, 0};
-        const int iy[2] = {ty.i0, ty.i1}, wy[2] = {ty.w0, ty.w1};
-        const int ix[2] = {tx.i0, tx.i1}, wx[2] = {tx.w0, tx.w1};
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            if (iy[a] < 0) continue;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                if (ix[c] < 0) continue;
-                const uint8_t* p = img + (unsigned)((iy[a] * g.w + ix[c]) * 3);     // (< 3 * 16384^2: 32-bit offset, uniform base)
-                const int wgt = wy[a] * wx[c];
-                acc[0] += (int)p[0] * wgt;
-                acc[1] += (int)p[1] * wgt;
-                acc[2] += (int)p[2] * wgt;
-            }
-        }
-        int v[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = (acc[k] + RESIZE_HALF) >> 22;
-        // itertools.permutations(range(3))[perm] = (p0, p1, p2), two bits each
-        const int p0 = (0xA50 >> (2 * g.perm)) & 3, p1 = (0x489 >> (2 * g.perm)) & 3, p2 = (0x126 >> (2 * g.perm)) & 3;
-        *o = make_float4(t[aug_pick(v, p0)], t[256 + aug_pick(v, p1)], t[512 + aug_pick(v, p2)], 0.f);
-    }
+    image_gather<true>(src, stride, recs, lut, y, H, W, chunks, units);
+}
+
+template <class Kernel>
+static int image_gather_launch(Kernel kernel, const unsigned char* src, long long src_stride_bytes, const int* desc,
+                               const float* lut, float* y, int n_img, int H, int W, hipStream_t stream) {
+    if (!src || !desc || !lut || !y) return FGN_ERR_ARG;
+    if (n_img < 0 || H < 0 || W < 0 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM || src_stride_bytes < 0)
+        return FGN_ERR_SHAPE;
+    if ((long long)n_img * H * W == 0) return FGN_OK;
+    RowGrid g;
+    if (row_grid((long long)n_img * H, W, 64, RESIZE_GRID_CAP, &g) != FGN_OK) return FGN_ERR_SHAPE;
+    hipLaunchKernelGGL(kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes, desc, lut,
+                       reinterpret_cast<float4*>(y), H, W, g.chunks, g.units);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+extern "C" int fgn_resize_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stride_bytes, const int* src_hw,
+                                              const float* lut, float* y, int n_img, int H, int W,
+                                              hipStream_t stream) {
+    return image_gather_launch(resize_u8hwc3_to_nhwc4_kernel, src, src_stride_bytes, src_hw, lut, y, n_img, H, W, stream);
 }
 
 extern "C" int fgn_augment_u8hwc3_to_nhwc4_f32(const unsigned char* src, long long src_stride_bytes, const int* recs,
                                                const float* lut, float* y, int n_img, int H, int W,
                                                hipStream_t stream) {
-    if (!src || !recs || !lut || !y) return FGN_ERR_ARG;
-    if (n_img < 0 || H < 0 || W < 0 || H > RESIZE_MAX_DIM || W > RESIZE_MAX_DIM || src_stride_bytes < 0)
-        return FGN_ERR_SHAPE;
-    if ((long long)n_img * H * W == 0) return FGN_OK;
-    const int chunks = cdiv(W, 64);
-    const long long units = (long long)n_img * H * chunks;
-    if (units > INT32_MAX - 4 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;       // (unit indices are int32, stride included)
-    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP);
-    hipLaunchKernelGGL(augment_u8hwc3_to_nhwc4_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes,
-                       recs, lut, reinterpret_cast<float4*>(y), H, W, chunks, (int)units);
-    FGN_LAUNCH_CHECK();
-    return FGN_OK;
+    return image_gather_launch(augment_u8hwc3_to_nhwc4_kernel, src, src_stride_bytes, recs, lut, y, n_img, H, W, stream);
 }
 
-// Masks [G,h,w] (bool or bytes: nonzero = set) of ONE image -> [G,H,W] 0/1 bytes by the taps of its record rec (device,
-// 16 int32) on 0/1 values, set where acc >= 2^21; a tap outside the image is 0 whatever the record's border.  Lanes,
-// dword stores and bytewise ends as in resize_mask_u8_kernel.  A record out of range, or one for another source size
-// than (h, w), gives empty masks and nothing is read.
-__global__ __launch_bounds__(RESIZE_BLOCK) void augment_mask_u8_kernel(const uint8_t* __restrict__ src,
-                                                                       uint8_t* __restrict__ dst,
-                                                                       const int* __restrict__ rec, int h, int w,
-                                                                       int H, int W, int chunks, int units) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int WAVES = RESIZE_BLOCK / 64;
-    const AugRec g = aug_record(rec);
-    const bool ok = g.ok && g.h == h && g.w == w;
-    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
-        const int r = u / chunks;                           // mask * H + row
-        const int chunk = u - r * chunks;
-        const int m = r / H, oy = r - m * H;
-        uint8_t* row = dst + (size_t)r * W;
+// Masks [G,h,w] (bool or bytes: nonzero = set) of ONE image -> [G,H,W] 0/1 bytes by the same taps on 0/1 values, set
+// where acc >= 2^21 (half counts as set): cv2.resize(m.astype(uint8)).astype(bool) of base_fst.py:885, with a record rec
+// (REC; device, 16 int32) by the taps of the record, where a tap outside the image is 0 whatever the record's border.  A
+// lane makes the four pixels of one ALIGNED dword of the output row (the first group of a row starts up to 3 bytes before
+// the row, so that dst + 4 * k is dword-aligned whatever W and the row are) and stores it whole; a group that the row's
+// ends cut goes bytewise.  Dimensions are launch arguments: the ground-truth work of an episode is eager (G differs per
+// image).  A record out of range, or one for another source size than (h, w), gives empty masks and nothing is read.
+constexpr int MASK_LANE_BYTES = 4;
+constexpr int MASK_GRID_CAP = 4 * RESIZE_GRID_CAP;        // (a mask unit writes 256 B, a quarter of an image unit's 1 KB)
+
+// The pixels x_lo .. x_lo + 3 of a row as the bytes of a dword (those outside [0, W) stay 0); taps(ox, ty, tx) gives
+// the taps of column ox, blend4's GUARD says whether they can be absent.
+template <bool GUARD, class Taps>
+__device__ __forceinline__ unsigned mask_word(const uint8_t* __restrict__ base, int w, int W, int x_lo, Taps taps) {
+    unsigned word = 0;
+#pragma unroll
+    for (int k = 0; k < MASK_LANE_BYTES; ++k) {
+        const int ox = x_lo + k;
+        if (ox < 0 || ox >= W) continue;
+        ResizeTap ty, tx;
+        taps(ox, ty, tx);
+        int acc = 0;
+        blend4<1, true, GUARD>(base, w, ty, tx, &acc);
+        word |= (acc >= RESIZE_HALF ? 1u : 0u) << (8 * k);
+    }
+    return word;
+}
+
+template <bool REC>
+__device__ __forceinline__ void mask_gather(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                            const int* __restrict__ rec, int h, int w, int H, int W, int chunks,
+                                            int units) {
+    AugRec g = {};
+    if constexpr (REC) g = aug_record<true>(rec);
+    const bool ok = !REC || (g.ok && g.h == h && g.w == w);
+    const WaveUnits wu = wave_units();
+    for (int u = wu.first; u < units; u += wu.step) {
+        const RowUnit q = row_unit(u, chunks, H);           // item: the mask
+        const int oy = q.row;
+        uint8_t* row = dst + (size_t)q.r * W;
         const int lead = (int)(reinterpret_cast<uintptr_t>(row) & 3u);      // bytes of the row's first dword before it
-        const int x_lo = (chunk * 64 + lane) * 4 - lead;
+        const int x_lo = (q.chunk * 64 + wu.lane) * MASK_LANE_BYTES - lead;
         if (x_lo >= W) continue;
         unsigned word = 0;
-        const uint8_t* base = src + (size_t)m * h * w;      // (wave-uniform; offsets below are 32-bit: h * w <= 2^28)
-        if (ok && g.kind == 0) {                            // the resize kernel's body, columns reversed under flip
-            const ResizeTap ty = resize_tap(oy, h, H);
-            const uint8_t* r0 = base + (size_t)ty.i0 * w;
-            const uint8_t* r1 = base + (size_t)ty.i1 * w;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ox = x_lo + k;
-                if (ox < 0 || ox >= W) continue;
-                const ResizeTap tx = resize_tap(g.flip ? W - 1 - ox : ox, w, W);
-                const int acc = (r0[tx.i0] ? ty.w0 * tx.w0 : 0) + (r0[tx.i1] ? ty.w0 * tx.w1 : 0) +
-                                (r1[tx.i0] ? ty.w1 * tx.w0 : 0) + (r1[tx.i1] ? ty.w1 * tx.w1 : 0);
-                word |= (acc >= RESIZE_HALF ? 1u : 0u) << (8 * k);
-            }
+        const uint8_t* base = src + (size_t)q.item * h * w;             // (wave-uniform; the taps' offsets are 32-bit)
+        if (!REC || (ok && g.kind == 0)) {
+            const ResizeTap ry = resize_tap(oy, h, H);
+            word = mask_word<false>(base, w, W, x_lo, [&](int ox, ResizeTap& ty, ResizeTap& tx) {
+                ty = ry;
+                tx = resize_tap(REC && g.flip ? W - 1 - ox : ox, w, W);
+            });
         } else if (ok) {
             const long long ru = (long long)g.c01 * oy + g.c02, rv = (long long)g.c11 * oy + g.c12;     // wave-uniform
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ox = x_lo + k;
-                if (ox < 0 || ox >= W) continue;
-                const ResizeTap tx = aug_tap(ru + (long long)g.c00 * ox, w, false);
-                const ResizeTap ty = aug_tap(rv + (long long)g.c10 * ox, h, false);
-                const int iy[2] = {ty.i0, ty.i1}, wy[2] = {ty.w0, ty.w1};
-                const int ix[2] = {tx.i0, tx.i1}, wx[2] = {tx.w0, tx.w1};
-                int acc = 0;
-#pragma unroll
-                for (int a = 0; a < 2; ++a)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c)
-                        if (iy[a] >= 0 && ix[c] >= 0 && base[(unsigned)(iy[a] * w + ix[c])]) acc += wy[a] * wx[c];
-                word |= (acc >= RESIZE_HALF ? 1u : 0u) << (8 * k);
-            }
+            word = mask_word<true>(base, w, W, x_lo, [&](int ox, ResizeTap& ty, ResizeTap& tx) {
+                tx = aug_tap(ru + (long long)g.c00 * ox, w, false);
+                ty = aug_tap(rv + (long long)g.c10 * ox, h, false);
+            });
         }
-        if (x_lo >= 0 && x_lo + 4 <= W) {
+        if (x_lo >= 0 && x_lo + MASK_LANE_BYTES <= W) {
             *reinterpret_cast<unsigned*>(row + x_lo) = word;
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
+            for (int k = 0; k < MASK_LANE_BYTES; ++k)
                 if (x_lo + k >= 0 && x_lo + k < W) row[x_lo + k] = (uint8_t)((word >> (8 * k)) & 1u);
         }
     }
 }
 
-extern "C" int fgn_augment_mask_u8(const unsigned char* src, unsigned char* dst, const int* rec, int G, int h, int w,
-                                   int H, int W, hipStream_t stream) {
-    if (!src || !dst || !rec) return FGN_ERR_ARG;
+__global__ __launch_bounds__(RESIZE_BLOCK) void resize_mask_u8_kernel(const uint8_t* __restrict__ src,
+                                                                      uint8_t* __restrict__ dst, int h, int w, int H,
+                                                                      int W, int chunks, int units) {
+    mask_gather<false>(src, dst, nullptr, h, w, H, W, chunks, units);
+}
+
+__global__ __launch_bounds__(RESIZE_BLOCK) void augment_mask_u8_kernel(const uint8_t* __restrict__ src,
+                                                                       uint8_t* __restrict__ dst,
+                                                                       const int* __restrict__ rec, int h, int w,
+                                                                       int H, int W, int chunks, int units) {
+    mask_gather<true>(src, dst, rec, h, w, H, W, chunks, units);
+}
+
+template <class Launch>
+static int mask_gather_launch(bool pointers, int G, int h, int w, int H, int W, Launch launch) {
+    if (!pointers) return FGN_ERR_ARG;
     if (G < 0 || h < 0 || w < 0 || H < 0 || W < 0 || h > RESIZE_MAX_DIM || w > RESIZE_MAX_DIM || H > RESIZE_MAX_DIM ||
         W > RESIZE_MAX_DIM)
         return FGN_ERR_SHAPE;
     if ((long long)G * H * W == 0) return FGN_OK;
     if (h == 0 || w == 0) return FGN_ERR_SHAPE;               // (pixels to make and none to make them of)
-    const int chunks = cdiv(W + 3, 256);
-    const long long units = (long long)G * H * chunks;
-    if (units > INT32_MAX - 16 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;      // (unit indices are int32, stride included)
-    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP * 4);
-    hipLaunchKernelGGL(augment_mask_u8_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, dst, rec, h, w, H, W,
-                       chunks, (int)units);
+    RowGrid g;
+    if (row_grid((long long)G * H, W + MASK_LANE_BYTES - 1, 64 * MASK_LANE_BYTES, MASK_GRID_CAP, &g) != FGN_OK)
+        return FGN_ERR_SHAPE;
+    launch(g);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
+}
+
+extern "C" int fgn_resize_mask_u8(const unsigned char* src, unsigned char* dst, int G, int h, int w, int H, int W,
+                                  hipStream_t stream) {
+    return mask_gather_launch(src && dst, G, h, w, H, W, [&](const RowGrid& g) {
+        hipLaunchKernelGGL(resize_mask_u8_kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, src, dst, h, w, H, W,
+                           g.chunks, g.units);
+    });
+}
+
+extern "C" int fgn_augment_mask_u8(const unsigned char* src, unsigned char* dst, const int* rec, int G, int h, int w,
+                                   int H, int W, hipStream_t stream) {
+    return mask_gather_launch(src && dst && rec, G, h, w, H, W, [&](const RowGrid& g) {
+        hipLaunchKernelGGL(augment_mask_u8_kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, src, dst, rec, h, w, H,
+                           W, g.chunks, g.units);
+    });
 }
 
 // ----------------------------------------------------------------------------------
@@ -754,7 +744,6 @@ extern "C" int fgn_photometric_u8hwc3(const unsigned char* src, unsigned char* d
 // wave-uniform, the x taps are per lane.
 // ----------------------------------------------------------------------------------
 constexpr int SPP_REC_INTS = 16;      // H W y0 x0 ch cw nh nw top left reflect wy wx wh ww -
-constexpr int SPP_ACC_HALF = 1 << 21; // half of the weight sum 2048 * 2048
 
 struct CubicTap { int i0; int w[4]; };
 __device__ __forceinline__ CubicTap cubic_tap(int j, int n_src, int n_dst) {
@@ -807,17 +796,13 @@ __global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_kernel(const
                                                                            uint8_t* __restrict__ m, int S, int chunks,
                                                                            int units) {
     __shared__ float t[3 * 256];
-    for (int i = threadIdx.x; i < 3 * 256; i += RESIZE_BLOCK) t[i] = lut[i];
-    __syncthreads();
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr int WAVES = RESIZE_BLOCK / 64;
+    lut_to_lds(t, lut);
+    const WaveUnits wu = wave_units();
     const float4 pad = make_float4(t[0], t[256], t[512], 0.f);     // byte 0 through the table
-    for (int u = blockIdx.x * WAVES + wave; u < units; u += gridDim.x * WAVES) {
-        const int r = u / chunks;                           // instance * S + row
-        const int chunk = u - r * chunks;
-        const int b = r / S, oy = r - b * S;
-        const int ox = chunk * 64 + lane;
+    for (int u = wu.first; u < units; u += wu.step) {
+        const RowUnit q = row_unit(u, chunks, S);           // item: the instance
+        const int r = q.r, b = q.item, oy = q.row;
+        const int ox = q.chunk * 64 + wu.lane;
         if (ox >= S) continue;
         const int* rc = recs + (size_t)b * SPP_REC_INTS;
         const int H = rc[0], W = rc[1], y0 = rc[2], x0 = rc[3], ch = rc[4], cw = rc[5], nh = rc[6], nw = rc[7];
@@ -877,9 +862,9 @@ __global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_kernel(const
         }
         int v[3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) v[k] = min(max((acc[k] + SPP_ACC_HALF) >> 22, 0), 255);
+        for (int k = 0; k < 3; ++k) v[k] = min(max((acc[k] + RESIZE_HALF) >> 22, 0), 255);
         *o = make_float4(t[v[0]], t[256 + v[1]], t[512 + v[2]], 0.f);
-        *om = macc > SPP_ACC_HALF ? 1 : 0;
+        *om = macc > RESIZE_HALF ? 1 : 0;
     }
 }
 
@@ -890,12 +875,10 @@ extern "C" int fgn_support_from_source_f32(const unsigned char* src, long long s
     if (!src || !msk || !recs || !lut || !y || !m) return FGN_ERR_ARG;
     if (n < 0 || S < 0 || S > RESIZE_MAX_DIM || src_stride_bytes < 0 || msk_stride_bytes < 0) return FGN_ERR_SHAPE;
     if ((long long)n * S == 0) return FGN_OK;
-    const int chunks = cdiv(S, 64);
-    const long long units = (long long)n * S * chunks;
-    if (units > INT32_MAX - 4 * RESIZE_GRID_CAP) return FGN_ERR_SHAPE;       // (unit indices are int32, stride included)
-    const int grid = (int)std::min<long long>((units + RESIZE_BLOCK / 64 - 1) / (RESIZE_BLOCK / 64), RESIZE_GRID_CAP);
-    hipLaunchKernelGGL(support_from_source_kernel, dim3(grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes, msk,
-                       msk_stride_bytes, recs, lut, reinterpret_cast<float4*>(y), m, S, chunks, (int)units);
+    RowGrid g;
+    if (row_grid((long long)n * S, S, 64, RESIZE_GRID_CAP, &g) != FGN_OK) return FGN_ERR_SHAPE;
+    hipLaunchKernelGGL(support_from_source_kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes, msk,
+                       msk_stride_bytes, recs, lut, reinterpret_cast<float4*>(y), m, S, g.chunks, g.units);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }

@@ -1490,13 +1490,18 @@ class FGN(torch.nn.Module):
         return _SrcQuery(dst, dhw, *rs['hw'])
 
     @staticmethod
-    def _resized_masks(g, hw, dev) -> torch.Tensor:
-        """Ground-truth masks of one image on the device as bool / uint8 [n,H,W]; at another size than ``hw`` (not None)
-        they are resized there (``ops.resize_masks``)."""
+    def _device_masks(g, dev) -> torch.Tensor:
+        """Ground-truth masks of one image (array or tensor) on the device as contiguous bool / uint8 [n,h,w]."""
         g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
         g = g.to(dev, non_blocking=True)
         g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
-        g = g.contiguous()
+        return g.contiguous()
+
+    @staticmethod
+    def _resized_masks(g, hw, dev) -> torch.Tensor:
+        """Ground-truth masks of one image on the device as bool / uint8 [n,H,W]; at another size than ``hw`` (not None)
+        they are resized there (``ops.resize_masks``)."""
+        g = FGN._device_masks(g, dev)
         if hw is not None and tuple(g.shape[1:]) != tuple(hw):
             g = ops.resize_masks(g, *hw)
         return g
@@ -1505,10 +1510,7 @@ class FGN(torch.nn.Module):
     def _augmented_masks(g, rec: torch.Tensor, hw, dev) -> torch.Tensor:
         """Ground-truth masks of one image on the device, warped there by its record (``ops.augment_masks``): uint8
         [n,H,W]."""
-        g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
-        g = g.to(dev, non_blocking=True)
-        g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
-        return ops.augment_masks(g.contiguous(), rec, *hw)
+        return ops.augment_masks(FGN._device_masks(g, dev), rec, *hw)
 
     def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None,
                 bits_out: Optional[list] = None, source: Optional[dict] = None, resize_masks: bool = True,

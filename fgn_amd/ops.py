@@ -1047,6 +1047,41 @@ def u8hwc3_to_nhwc4(x_u8: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
 
 
 RESIZE_MAX_DIM = 16384       # csrc/spatial.hip; fewshot_ds.RESIZE_MAX_DIM: int32 arithmetic of the resize rule
+AUG_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.AUG_REC_INTS: int32 per image record
+SPP_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.SPP_REC_INTS: int32 per instance record
+
+
+def _gather_from_slots(fn: str, entry: str, slots, desc, expects: str, lut: torch.Tensor, size, size_name: str,
+                       with_mask: bool = False):
+    """The wrapper of the gathers from source slots into a stem input (``fn``, over the library's ``entry``).  ``slots``:
+    (name, uint8 [n,capacity]) pairs, row i the bytes of item i; ``desc`` = (name, int32 [n,ints] ON THE DEVICE, ints):
+    what the kernel reads about every item; ``lut`` [3,256]; ``size``: (H, W), or (S,) for a square output.  -> fp32
+    [n,H,W,4], ``with_mask`` also uint8 [n,H,W]."""
+    for name, t in slots:
+        _chk(t, name, torch.uint8)
+    desc_name, desc, desc_ints = desc
+    _chk(desc, desc_name, torch.int32)
+    _chk(lut, 'lut')
+    src = slots[0][1]
+    n = src.shape[0] if src.dim() == 2 else -1
+    if n < 0 or tuple(desc.shape) != (n, desc_ints) or desc.device != src.device or \
+            any(t.dim() != 2 or t.shape[0] != n or t.device != src.device for _, t in slots[1:]):
+        raise _lib.FgnHipError(f'{fn}: expects {expects} on one device')
+    if tuple(lut.shape) != (3, 256) or lut.device != src.device:
+        raise _lib.FgnHipError(f'{fn}: lut must be [3,256] on the device of src')
+    size = tuple(int(v) for v in size)
+    if not all(0 <= v <= RESIZE_MAX_DIM for v in size):
+        raise _lib.FgnHipError(f'{fn}: {size_name} must be within 0..{RESIZE_MAX_DIM}, '
+                               f'got {size if len(size) > 1 else size[0]}')
+    hw = size if len(size) > 1 else size * 2
+    y = torch.empty((n,) + hw + (4,), device=src.device, dtype=torch.float32)
+    m = torch.empty((n,) + hw, device=src.device, dtype=torch.uint8) if with_mask else None
+    if y.numel():                       # (an empty tensor has no address to hand over)
+        # (capacity 0: every item is refused by the kernel; it needs an address only)
+        slots = [t if t.shape[1] else t.new_zeros((n, 1)) for _, t in slots]
+        args = [a for t in slots for a in (_ptr(t), int(t.shape[1]))] + [_ptr(desc), _ptr(lut), _ptr(y)]
+        _lib.check(getattr(_lib.load(), entry)(*args, *([_ptr(m)] if with_mask else []), n, *size, _stream()), entry)
+    return (y, m) if with_mask else y
 
 
 def resize_u8_to_nhwc4(src: torch.Tensor, src_hw: torch.Tensor, lut: torch.Tensor, H: int, W: int) -> torch.Tensor:
@@ -1055,50 +1090,8 @@ def resize_u8_to_nhwc4(src: torch.Tensor, src_hw: torch.Tensor, lut: torch.Tenso
     [h_b, w_b, 3] pixels at the start of row b; ``src_hw`` int32 [n,2] ON THE DEVICE holds (h_b, w_b) and is read by
     the kernel (the launch is the same for every source size).  An image whose size is outside 1..16384 or exceeds the
     capacity comes out as zeros."""
-    _chk(src, 'src', torch.uint8)
-    _chk(src_hw, 'src_hw', torch.int32)
-    _chk(lut, 'lut')
-    if src.dim() != 2 or tuple(src_hw.shape) != (src.shape[0], 2) or src_hw.device != src.device:
-        raise _lib.FgnHipError('resize_u8_to_nhwc4: expects src [n,capacity] and src_hw [n,2] on one device')
-    if tuple(lut.shape) != (3, 256) or lut.device != src.device:
-        raise _lib.FgnHipError('resize_u8_to_nhwc4: lut must be [3,256] on the device of src')
-    H, W = int(H), int(W)
-    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM):
-        raise _lib.FgnHipError(f'resize_u8_to_nhwc4: output size must be within 0..{RESIZE_MAX_DIM}, got {(H, W)}')
-    n = src.shape[0]
-    y = torch.empty((n, H, W, 4), device=src.device, dtype=torch.float32)
-    if y.numel() == 0:                  # (an empty tensor has no address to hand over)
-        return y
-    if src.shape[1] == 0:
-        src = src.new_zeros((n, 1))     # (capacity 0: every image is refused by the kernel; it needs an address only)
-    _lib.check(_lib.load().fgn_resize_u8hwc3_to_nhwc4_f32(_ptr(src), int(src.shape[1]), _ptr(src_hw), _ptr(lut),
-                                                           _ptr(y), n, H, W, _stream()),
-               'fgn_resize_u8hwc3_to_nhwc4_f32')
-    return y
-
-
-def resize_masks(masks: torch.Tensor, H: int, W: int) -> torch.Tensor:
-    """Dense binary masks [G,h,w] (bool / uint8, non-zero = set) -> uint8 0/1 [G,H,W]: ``fewshot_ds.resize_masks`` bit
-    for bit (the ground-truth side of the query resize)."""
-    if masks.dtype == torch.bool:
-        masks = masks.view(torch.uint8)
-    _chk(masks, 'masks', torch.uint8)
-    if masks.dim() != 3:
-        raise _lib.FgnHipError('resize_masks: masks must be [G,h,w]')
-    g, h, w = masks.shape
-    H, W = int(H), int(W)
-    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM and h <= RESIZE_MAX_DIM and w <= RESIZE_MAX_DIM):
-        raise _lib.FgnHipError(f'resize_masks: every dimension must be at most {RESIZE_MAX_DIM}')
-    out = torch.empty((g, H, W), device=masks.device, dtype=torch.uint8)
-    if out.numel() == 0:
-        return out
-    if h == 0 or w == 0:
-        raise _lib.FgnHipError('resize_masks: empty source masks')
-    _lib.check(_lib.load().fgn_resize_mask_u8(_ptr(masks), _ptr(out), g, h, w, H, W, _stream()), 'fgn_resize_mask_u8')
-    return out
-
-
-AUG_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.AUG_REC_INTS: int32 per image record
+    return _gather_from_slots('resize_u8_to_nhwc4', 'fgn_resize_u8hwc3_to_nhwc4_f32', [('src', src)],
+                              ('src_hw', src_hw, 2), 'src [n,capacity] and src_hw [n,2]', lut, (H, W), 'output size')
 
 
 def augment_u8_to_nhwc4(src: torch.Tensor, recs: torch.Tensor, lut: torch.Tensor, H: int, W: int) -> torch.Tensor:
@@ -1107,52 +1100,62 @@ def augment_u8_to_nhwc4(src: torch.Tensor, recs: torch.Tensor, lut: torch.Tensor
     ``recs`` int32 [n,16] ON THE DEVICE: the records of ``fewshot_ds.query_augment_record``, read by the kernel (the
     launch is the same for every source size and augmentation).  An image whose record is out of range or whose size
     exceeds the capacity comes out as zeros."""
-    _chk(src, 'src', torch.uint8)
-    _chk(recs, 'recs', torch.int32)
-    _chk(lut, 'lut')
-    if src.dim() != 2 or tuple(recs.shape) != (src.shape[0], AUG_REC_INTS) or recs.device != src.device:
-        raise _lib.FgnHipError('augment_u8_to_nhwc4: expects src [n,capacity] and recs [n,16] on one device')
-    if tuple(lut.shape) != (3, 256) or lut.device != src.device:
-        raise _lib.FgnHipError('augment_u8_to_nhwc4: lut must be [3,256] on the device of src')
+    return _gather_from_slots('augment_u8_to_nhwc4', 'fgn_augment_u8hwc3_to_nhwc4_f32', [('src', src)],
+                              ('recs', recs, AUG_REC_INTS), 'src [n,capacity] and recs [n,16]', lut, (H, W),
+                              'output size')
+
+
+def support_from_source(src: torch.Tensor, msk: torch.Tensor, recs: torch.Tensor, lut: torch.Tensor, S: int):
+    """Image and mask windows of n support instances -> (the NHWC4 fp32 stem input [n,S,S,4], the support masks
+    uint8 0/1 [n,S,S]): ``u8hwc3_to_nhwc4`` of ``fewshot_ds.support_from_source``'s crop and its mask, bit for bit, in
+    one launch.  ``src`` uint8 [n, capacity]: instance i's window [wh_i, ww_i, 3] at the start of row i; ``msk`` uint8
+    [n, mask capacity]: its mask window [wh_i, ww_i] (nonzero = set); ``recs`` int32 [n,16] ON THE DEVICE: the records
+    of ``fewshot_ds.support_geometry``, read by the kernel (the launch is the same for every support set).  An instance
+    whose record is out of range or whose window exceeds a capacity comes out as padding with an empty mask."""
+    return _gather_from_slots('support_from_source', 'fgn_support_from_source_f32', [('src', src), ('msk', msk)],
+                              ('recs', recs, SPP_REC_INTS), 'src [n,capacity], msk [n,mask capacity] and recs [n,16]', lut,
+                              (S,), 'S', with_mask=True)
+
+
+def _gather_masks(fn: str, entry: str, masks: torch.Tensor, rec: Optional[torch.Tensor], H: int, W: int) -> torch.Tensor:
+    """The wrapper of the two mask gathers (``fn``, over the library's ``entry``): masks [G,h,w] bool / uint8, with or
+    without the record of their image -> uint8 0/1 [G,H,W]."""
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    _chk(masks, 'masks', torch.uint8)
+    if rec is not None:
+        _chk(rec, 'rec', torch.int32)
+    if masks.dim() != 3:
+        raise _lib.FgnHipError(f'{fn}: masks must be [G,h,w]')
+    if rec is not None and (tuple(rec.shape) != (AUG_REC_INTS,) or rec.device != masks.device):
+        raise _lib.FgnHipError(f'{fn}: rec must be int32 [16] on the device of masks')
+    g, h, w = masks.shape
     H, W = int(H), int(W)
-    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM):
-        raise _lib.FgnHipError(f'augment_u8_to_nhwc4: output size must be within 0..{RESIZE_MAX_DIM}, got {(H, W)}')
-    n = src.shape[0]
-    y = torch.empty((n, H, W, 4), device=src.device, dtype=torch.float32)
-    if y.numel() == 0:                  # (an empty tensor has no address to hand over)
-        return y
-    if src.shape[1] == 0:
-        src = src.new_zeros((n, 1))     # (capacity 0: every image is refused by the kernel; it needs an address only)
-    _lib.check(_lib.load().fgn_augment_u8hwc3_to_nhwc4_f32(_ptr(src), int(src.shape[1]), _ptr(recs), _ptr(lut),
-                                                            _ptr(y), n, H, W, _stream()),
-               'fgn_augment_u8hwc3_to_nhwc4_f32')
-    return y
+    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM and h <= RESIZE_MAX_DIM and w <= RESIZE_MAX_DIM):
+        raise _lib.FgnHipError(f'{fn}: every dimension must be at most {RESIZE_MAX_DIM}')
+    out = torch.empty((g, H, W), device=masks.device, dtype=torch.uint8)
+    if out.numel() == 0:
+        return out
+    if h == 0 or w == 0:
+        raise _lib.FgnHipError(f'{fn}: empty source masks')
+    _lib.check(getattr(_lib.load(), entry)(_ptr(masks), _ptr(out), *([] if rec is None else [_ptr(rec)]), g, h, w, H, W,
+                                           _stream()), entry)
+    return out
+
+
+def resize_masks(masks: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """Dense binary masks [G,h,w] (bool / uint8, non-zero = set) -> uint8 0/1 [G,H,W]: ``fewshot_ds.resize_masks`` bit
+    for bit (the ground-truth side of the query resize)."""
+    return _gather_masks('resize_masks', 'fgn_resize_mask_u8', masks, None, H, W)
 
 
 def augment_masks(masks: torch.Tensor, rec: torch.Tensor, H: int, W: int) -> torch.Tensor:
     """Dense binary masks [G,h,w] (bool / uint8, non-zero = set) of one image -> uint8 0/1 [G,H,W] by the image's record
     ``rec`` (int32 [16] ON THE DEVICE): ``fewshot_ds.augment_masks`` bit for bit.  A record out of range, or one for
     another source size, gives empty masks."""
-    if masks.dtype == torch.bool:
-        masks = masks.view(torch.uint8)
-    _chk(masks, 'masks', torch.uint8)
-    _chk(rec, 'rec', torch.int32)
-    if masks.dim() != 3:
-        raise _lib.FgnHipError('augment_masks: masks must be [G,h,w]')
-    if tuple(rec.shape) != (AUG_REC_INTS,) or rec.device != masks.device:
+    if rec is None:
         raise _lib.FgnHipError('augment_masks: rec must be int32 [16] on the device of masks')
-    g, h, w = masks.shape
-    H, W = int(H), int(W)
-    if not (0 <= H <= RESIZE_MAX_DIM and 0 <= W <= RESIZE_MAX_DIM and h <= RESIZE_MAX_DIM and w <= RESIZE_MAX_DIM):
-        raise _lib.FgnHipError(f'augment_masks: every dimension must be at most {RESIZE_MAX_DIM}')
-    out = torch.empty((g, H, W), device=masks.device, dtype=torch.uint8)
-    if out.numel() == 0:
-        return out
-    if h == 0 or w == 0:
-        raise _lib.FgnHipError('augment_masks: empty source masks')
-    _lib.check(_lib.load().fgn_augment_mask_u8(_ptr(masks), _ptr(out), _ptr(rec), g, h, w, H, W, _stream()),
-               'fgn_augment_mask_u8')
-    return out
+    return _gather_masks('augment_masks', 'fgn_augment_mask_u8', masks, rec, H, W)
 
 
 PHOTO_REC_INTS = 64          # csrc/spatial.hip; fewshot_ds.PHOTO_REC_INTS: int32 per image record
@@ -1174,44 +1177,6 @@ def photometric_u8(src: torch.Tensor, recs: torch.Tensor) -> torch.Tensor:
     _lib.check(_lib.load().fgn_photometric_u8hwc3(_ptr(src), _ptr(dst), int(src.shape[1]), _ptr(recs),
                                                   int(src.shape[0]), _stream()), 'fgn_photometric_u8hwc3')
     return dst
-
-
-SPP_REC_INTS = 16            # csrc/spatial.hip; fewshot_ds.SPP_REC_INTS: int32 per instance record
-
-
-def support_from_source(src: torch.Tensor, msk: torch.Tensor, recs: torch.Tensor, lut: torch.Tensor, S: int):
-    """Image and mask windows of n support instances -> (the NHWC4 fp32 stem input [n,S,S,4], the support masks
-    uint8 0/1 [n,S,S]): ``u8hwc3_to_nhwc4`` of ``fewshot_ds.support_from_source``'s crop and its mask, bit for bit, in
-    one launch.  ``src`` uint8 [n, capacity]: instance i's window [wh_i, ww_i, 3] at the start of row i; ``msk`` uint8
-    [n, mask capacity]: its mask window [wh_i, ww_i] (nonzero = set); ``recs`` int32 [n,16] ON THE DEVICE: the records
-    of ``fewshot_ds.support_geometry``, read by the kernel (the launch is the same for every support set).  An instance
-    whose record is out of range or whose window exceeds a capacity comes out as padding with an empty mask."""
-    _chk(src, 'src', torch.uint8)
-    _chk(msk, 'msk', torch.uint8)
-    _chk(recs, 'recs', torch.int32)
-    _chk(lut, 'lut')
-    n = src.shape[0] if src.dim() == 2 else -1
-    if n < 0 or msk.dim() != 2 or msk.shape[0] != n or tuple(recs.shape) != (n, SPP_REC_INTS) or \
-            msk.device != src.device or recs.device != src.device:
-        raise _lib.FgnHipError('support_from_source: expects src [n,capacity], msk [n,mask capacity] and recs [n,16] on '
-                               'one device')
-    if tuple(lut.shape) != (3, 256) or lut.device != src.device:
-        raise _lib.FgnHipError('support_from_source: lut must be [3,256] on the device of src')
-    S = int(S)
-    if not 0 <= S <= RESIZE_MAX_DIM:
-        raise _lib.FgnHipError(f'support_from_source: S must be within 0..{RESIZE_MAX_DIM}, got {S}')
-    y = torch.empty((n, S, S, 4), device=src.device, dtype=torch.float32)
-    m = torch.empty((n, S, S), device=src.device, dtype=torch.uint8)
-    if y.numel() == 0:                  # (an empty tensor has no address to hand over)
-        return y, m
-    if src.shape[1] == 0:
-        src = src.new_zeros((n, 1))     # (capacity 0: every instance is refused by the kernel; it needs an address only)
-    if msk.shape[1] == 0:
-        msk = msk.new_zeros((n, 1))
-    _lib.check(_lib.load().fgn_support_from_source_f32(_ptr(src), int(src.shape[1]), _ptr(msk), int(msk.shape[1]),
-                                                       _ptr(recs), _ptr(lut), _ptr(y), _ptr(m), n, S, _stream()),
-               'fgn_support_from_source_f32')
-    return y, m
 
 
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -134,6 +134,10 @@ def test_a_kind_0_record_gives_the_bytes_of_the_resize_kernel(src, dst):
         assert rec[2] == 0
         assert torch.equal(_ibits(ops.augment_u8_to_nhwc4(slot, torch.from_numpy(rec[None]).cuda(), lut, *dst)),
                            _ibits(want))
+    rec = fd.query_augment_record(row(flip=1), src, dst)
+    assert rec[2] == 0 and rec[3] == 1
+    assert torch.equal(_ibits(ops.augment_u8_to_nhwc4(slot, torch.from_numpy(rec[None]).cuda(), lut, *dst)),
+                       _ibits(torch.flip(want, dims=(2,))))                         # the resize, flipped along W
 
 
 def test_a_refused_record_or_size_comes_out_as_zeros_and_is_not_read():
@@ -220,6 +224,23 @@ def test_mask_kernel_is_bitwise_the_host_rule(src, dst, G):
         assert got.dtype == torch.uint8 and tuple(got.shape) == (G,) + dst
         assert np.array_equal(got.cpu().numpy(), want.astype(np.uint8)), name       # 0 / 1 bytes
         assert torch.equal(ops.augment_masks(d8, drec, *dst), got), name
+
+
+@pytest.mark.parametrize('G', [1, 3])
+@pytest.mark.parametrize('src,dst', [((7, 9), (16, 12)), ((9, 300), (5, 519)), ((3, 5), (3, 5))])
+def test_a_kind_0_record_gives_the_masks_of_the_resize_kernel(src, dst, G):
+    """The two mask kernels against each other, byte for byte.  W of 12, 519 and 5: a row of whole dwords, a row of more
+    than one 256-pixel chunk with a ragged end, a row shorter than two dwords."""
+    dm = torch.from_numpy(_masks(G, src, G * 10 + dst[1])).cuda()
+    want = ops.resize_masks(dm, *dst)
+    assert want.dtype == torch.uint8 and tuple(want.shape) == (G,) + dst
+    for params in (None, row(), row(border=1)):
+        rec = fd.query_augment_record(params, src, dst)
+        assert rec[2] == 0 and rec[3] == 0
+        assert torch.equal(ops.augment_masks(dm, torch.from_numpy(rec).cuda(), *dst), want)
+    rec = fd.query_augment_record(row(flip=1), src, dst)
+    assert rec[2] == 0 and rec[3] == 1
+    assert torch.equal(ops.augment_masks(dm, torch.from_numpy(rec).cuda(), *dst), torch.flip(want, dims=(2,)))
 
 
 @pytest.mark.parametrize('offset', [1, 2, 3])
