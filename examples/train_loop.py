@@ -8,6 +8,7 @@ warm-up 100 iterations, 3 epochs) on the MI355X path: DataLoader(ds, collate_fn_
     python examples/train_loop.py --dataset SYNTH --height 320 --width 480 --episodes 16
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --augment --photometric
+    python examples/train_loop.py --dataset OMNIISEG --spp-source --augment-spp --photometric-spp
 
 ``--source-size S``: the loader hands over decoded S x S pixels and the detector resizes them on the GPU
 (``qry_resize_to``); ``--spp-source``: the supports are cut from their source images on the GPU (``spp_crop_to``);
@@ -15,7 +16,10 @@ warm-up 100 iterations, 3 epochs) on the MI355X path: DataLoader(ds, collate_fn_
 (``qry_augment``: flip, affine warp, channel order, drawn per image and epoch - ``augment_qry=True`` of the reference's
 training configurations); ``--photometric`` (needs ``--augment``): the other six operators of the reference's
 ``augs_seq`` - Gaussian and impulse noise, blur, hue, saturation, brightness - run on the source pixels on the GPU as
-well (``qry_photometric``), and both rows come from one joint draw.  The evaluation at the end is without augmentation.
+well (``qry_photometric``), and both rows come from one joint draw.  ``--augment-spp`` (needs ``--spp-source``): every
+support instance is augmented on the GPU behind its cut (``spp_augment``, one row per instance and epoch -
+``augment_spp=True`` of the reference's training configurations); ``--photometric-spp`` (needs ``--augment-spp``): the
+photometric operators as well (``spp_photometric``).  The evaluation at the end is without augmentation.
 
 The backbone is frozen as in fgn_r50_c4_densecl.py:31; with no pretrained checkpoint here it is randomly
 initialised, so this demonstrates the loop (losses fall on the training episodes), not a trained detector.
@@ -54,7 +58,15 @@ def main():
     ap.add_argument('--augment', action='store_true', help='augment the queries on the GPU (needs --source-size)')
     ap.add_argument('--photometric', action='store_true',
                     help='noise, blur, hue, saturation, brightness on the GPU as well (needs --augment)')
+    ap.add_argument('--augment-spp', action='store_true',
+                    help='augment every support instance on the GPU behind its cut (needs --spp-source)')
+    ap.add_argument('--photometric-spp', action='store_true',
+                    help='the photometric operators on the supports as well (needs --augment-spp)')
     args = ap.parse_args()
+    if args.augment_spp and not args.spp_source:
+        ap.error('--augment-spp needs --spp-source: the supports are augmented behind their cut from the source images')
+    if args.photometric_spp and not args.augment_spp:
+        ap.error('--photometric-spp needs --augment-spp: the two rows of an instance are one joint draw')
     if args.photometric and not args.augment:
         ap.error('--photometric needs --augment: the two are one joint draw of the reference\'s augs_seq')
     source = args.source_size is not None or args.spp_source
@@ -68,7 +80,8 @@ def main():
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,
                                        raw_uint8=source, source_size=args.source_size, spp_source=args.spp_source,
-                                       augment_qry=args.augment, photometric_qry=args.photometric)
+                                       augment_qry=args.augment, photometric_qry=args.photometric,
+                                       augment_spp=args.augment_spp, photometric_spp=args.photometric_spp)
     model = FGN(args.n_ways, args.k_shots)
     if source:
         model.set_input_norm(**ds.input_norm)
@@ -77,7 +90,7 @@ def main():
     trainer = Trainer(model, lr=args.lr)
     it = 0
     for epoch in range(args.epochs):
-        if args.augment:
+        if args.augment or args.augment_spp:
             ds.reshuffle(e=epoch)                             # (another epoch, another draw of the augmentation)
         else:
             ds.reshuffle()
@@ -100,7 +113,8 @@ def main():
         loader = DataLoader(ds, batch_size=ds.batch, num_workers=2, collate_fn=collate)
         results = [r for data in loader
                    for r in model.simple_test(**{k: v for k, v in data.items()
-                                                 if k not in ('qry_augment', 'qry_photometric')}, rescale=True)]
+                                                 if k not in ('qry_augment', 'qry_photometric', 'spp_augment',
+                                                              'spp_photometric')}, rescale=True)]
         print(ds.evaluate(results=results, model_dir=work_dir))
 
 

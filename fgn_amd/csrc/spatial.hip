@@ -786,19 +786,19 @@ __device__ __forceinline__ int spp_src_index(int t, int n, bool reflect, int w_l
 // share cache lines; the windows of an episode are a few hundred KB and stay in L2), three table lookups in LDS, one
 // 16-byte store (1 KB per wave, coalesced) and one mask byte (64 B per wave).  A pixel of the padding reads nothing.
 // An instance whose record is out of range (see ok below) is written as padding with an empty mask and not read.
-__global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_kernel(const uint8_t* __restrict__ src,
-                                                                           long long stride,
-                                                                           const uint8_t* __restrict__ msk,
-                                                                           long long mstride,
-                                                                           const int* __restrict__ recs,
-                                                                           const float* __restrict__ lut,
-                                                                           float4* __restrict__ y,
-                                                                           uint8_t* __restrict__ m, int S, int chunks,
-                                                                           int units) {
-    __shared__ float t[3 * 256];
-    lut_to_lds(t, lut);
+// U8: the byte-output form - the clamped bytes themselves go to crop [n,S,S,3] uint8 (three byte stores per lane, 192
+// contiguous bytes per wave), the padding and an instance with a bad record as byte 0; no table, no LDS.  It feeds the
+// support augmentation below, which works on bytes.  Record, taps, window reads, validity rule and mask are one body;
+// t is the f32 form's table in LDS (lut_to_lds), unused by the byte form.
+template <bool U8>
+__device__ __forceinline__ void support_gather(const uint8_t* __restrict__ src, long long stride,
+                                               const uint8_t* __restrict__ msk, long long mstride,
+                                               const int* __restrict__ recs, const float* __restrict__ t,
+                                               float4* __restrict__ y, uint8_t* __restrict__ crop,
+                                               uint8_t* __restrict__ m, int S, int chunks, int units) {
+    float4 pad = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (!U8) pad = make_float4(t[0], t[256], t[512], 0.f);               // byte 0 through the table
     const WaveUnits wu = wave_units();
-    const float4 pad = make_float4(t[0], t[256], t[512], 0.f);     // byte 0 through the table
     for (int u = wu.first; u < units; u += wu.step) {
         const RowUnit q = row_unit(u, chunks, S);           // item: the instance
         const int r = q.r, b = q.item, oy = q.row;
@@ -813,11 +813,16 @@ __global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_kernel(const
                         y0 >= -2 * RESIZE_MAX_DIM && y0 < RESIZE_MAX_DIM && x0 >= -2 * RESIZE_MAX_DIM && x0 < RESIZE_MAX_DIM &&
                         wy >= 0 && wx >= 0 && wh >= 1 && ww >= 1 && wh <= H - wy && ww <= W - wx &&
                         (long long)wh * ww * 3 <= stride && (long long)wh * ww <= mstride;
-        float4* o = y + (size_t)r * S + ox;
+        float4* o = U8 ? nullptr : y + (size_t)r * S + ox;
+        uint8_t* ob = U8 ? crop + ((size_t)r * S + ox) * 3 : nullptr;
         uint8_t* om = m + (size_t)r * S + ox;
         const int jy = oy - top, jx = ox - left;
         if (!ok || jy < 0 || jy >= nh || jx < 0 || jx >= nw) {
-            *o = pad;
+            if constexpr (U8) {
+                ob[0] = 0; ob[1] = 0; ob[2] = 0;
+            } else {
+                *o = pad;
+            }
             *om = 0;
             continue;
         }
@@ -863,22 +868,156 @@ __global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_kernel(const
         int v[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) v[k] = min(max((acc[k] + RESIZE_HALF) >> 22, 0), 255);
-        *o = make_float4(t[v[0]], t[256 + v[1]], t[512 + v[2]], 0.f);
+        if constexpr (U8) {
+            ob[0] = (uint8_t)v[0]; ob[1] = (uint8_t)v[1]; ob[2] = (uint8_t)v[2];
+        } else {
+            *o = make_float4(t[v[0]], t[256 + v[1]], t[512 + v[2]], 0.f);
+        }
         *om = macc > RESIZE_HALF ? 1 : 0;
     }
+}
+
+__global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_kernel(const uint8_t* __restrict__ src,
+                                                                           long long stride,
+                                                                           const uint8_t* __restrict__ msk,
+                                                                           long long mstride,
+                                                                           const int* __restrict__ recs,
+                                                                           const float* __restrict__ lut,
+                                                                           float4* __restrict__ y,
+                                                                           uint8_t* __restrict__ m, int S, int chunks,
+                                                                           int units) {
+    __shared__ float t[3 * 256];
+    lut_to_lds(t, lut);
+    support_gather<false>(src, stride, msk, mstride, recs, t, y, nullptr, m, S, chunks, units);
+}
+
+__global__ __launch_bounds__(RESIZE_BLOCK) void support_from_source_u8_kernel(const uint8_t* __restrict__ src,
+                                                                              long long stride,
+                                                                              const uint8_t* __restrict__ msk,
+                                                                              long long mstride,
+                                                                              const int* __restrict__ recs,
+                                                                              uint8_t* __restrict__ crop,
+                                                                              uint8_t* __restrict__ m, int S, int chunks,
+                                                                              int units) {
+    support_gather<true>(src, stride, msk, mstride, recs, nullptr, nullptr, crop, m, S, chunks, units);
+}
+
+template <class Launch>
+static int support_gather_launch(bool pointers, long long src_stride_bytes, long long msk_stride_bytes, int n, int S,
+                                 Launch launch) {
+    if (!pointers) return FGN_ERR_ARG;
+    if (n < 0 || S < 0 || S > RESIZE_MAX_DIM || src_stride_bytes < 0 || msk_stride_bytes < 0) return FGN_ERR_SHAPE;
+    if ((long long)n * S == 0) return FGN_OK;
+    RowGrid g;
+    if (row_grid((long long)n * S, S, 64, RESIZE_GRID_CAP, &g) != FGN_OK) return FGN_ERR_SHAPE;
+    launch(g);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
 }
 
 extern "C" int fgn_support_from_source_f32(const unsigned char* src, long long src_stride_bytes,
                                            const unsigned char* msk, long long msk_stride_bytes, const int* recs,
                                            const float* lut, float* y, unsigned char* m, int n, int S,
                                            hipStream_t stream) {
-    if (!src || !msk || !recs || !lut || !y || !m) return FGN_ERR_ARG;
-    if (n < 0 || S < 0 || S > RESIZE_MAX_DIM || src_stride_bytes < 0 || msk_stride_bytes < 0) return FGN_ERR_SHAPE;
+    return support_gather_launch(src && msk && recs && lut && y && m, src_stride_bytes, msk_stride_bytes, n, S,
+                                 [&](const RowGrid& g) {
+        hipLaunchKernelGGL(support_from_source_kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes,
+                           msk, msk_stride_bytes, recs, lut, reinterpret_cast<float4*>(y), m, S, g.chunks, g.units);
+    });
+}
+
+extern "C" int fgn_support_from_source_u8(const unsigned char* src, long long src_stride_bytes, const unsigned char* msk,
+                                          long long msk_stride_bytes, const int* recs, unsigned char* crop,
+                                          unsigned char* m, int n, int S, hipStream_t stream) {
+    return support_gather_launch(src && msk && recs && crop && m, src_stride_bytes, msk_stride_bytes, n, S,
+                                 [&](const RowGrid& g) {
+        hipLaunchKernelGGL(support_from_source_u8_kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, src,
+                           src_stride_bytes, msk, msk_stride_bytes, recs, crop, m, S, g.chunks, g.units);
+    });
+}
+
+// ----------------------------------------------------------------------------------
+// Support augmentation behind the cut (BaseFewShotISEG.get_support with augment_spp, base_fst.py:1151-1153:
+// augment_with_imgaug once per instance on the S x S crop, its mask and its box, AFTER resize and pad).  The rule is the
+// query's at equal size (fgn_amd/fewshot_ds.py augment_support): the photometric pass above on the n
+// crops as n slots of 3 S S bytes, then this gather, which agrees with augment_image_u8 / augment_masks at S -> S
+// followed by the table bit for bit.
+//   crop [n,S,S,3] uint8, msk [n,S,S] (nonzero = set), recs [n][16] the records of query_augment_record with h = w = S,
+//   READ on the device (no launch argument depends on an augmentation: one launch serves all n instances)
+//   -> y [n,S,S,4] fp32 through the table and m [n,S,S] 0 / 1 bytes.
+// Unit of work as above: a wave on 64 consecutive pixels of one output row; instance, row, record and the row terms are
+// wave-uniform.  Kind 0: the equal-size taps of resize_tap are the identity (w1 = 0), so a lane copies pixel and mask
+// byte of column ox, or S-1-ox under flip - one tap, no blend.  Kind 1: the taps of aug_tap per axis are computed once;
+// image and mask share indices and weights, except that a mask tap outside the frame reads 0 whatever the border.  The
+// symmetric border reflects the S x S frame, its pad bands included.  Stores as support_from_source_kernel's: one
+// 16-byte store and one mask byte per lane.  An instance whose record is out of range (the sets of aug_record) or is
+// for another size than S x S is written as the table's byte-0 pixel with an empty mask, and none of its bytes are read.
+// ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(RESIZE_BLOCK) void support_augment_kernel(const uint8_t* __restrict__ crop,
+                                                                       const uint8_t* __restrict__ msk,
+                                                                       const int* __restrict__ recs,
+                                                                       const float* __restrict__ lut,
+                                                                       float4* __restrict__ y, uint8_t* __restrict__ m,
+                                                                       int S, int chunks, int units) {
+    __shared__ float t[3 * 256];
+    lut_to_lds(t, lut);
+    const float4 pad = make_float4(t[0], t[256], t[512], 0.f);
+    const WaveUnits wu = wave_units();
+    for (int u = wu.first; u < units; u += wu.step) {
+        const RowUnit q = row_unit(u, chunks, S);           // item: the instance
+        const AugRec g = aug_record<true>(recs + (size_t)q.item * AUG_REC_INTS);
+        const int ox = q.chunk * 64 + wu.lane, oy = q.row;
+        if (ox >= S) continue;
+        float4* o = y + (size_t)q.r * S + ox;
+        uint8_t* om = m + (size_t)q.r * S + ox;
+        if (!g.ok || g.h != S || g.w != S) {
+            *o = pad;
+            *om = 0;
+            continue;
+        }
+        const uint8_t* img = crop + (size_t)q.item * S * S * 3;         // (wave-uniform; the taps' offsets are 32-bit)
+        const uint8_t* mk = msk + (size_t)q.item * S * S;
+        int v[3];
+        bool set;
+        if (g.kind == 0) {
+            const unsigned at = (unsigned)(oy * S + (g.flip ? S - 1 - ox : ox));
+            const uint8_t* p = img + at * 3u;
+            v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
+            set = mk[at] != 0;
+        } else {
+            const long long ru = (long long)g.c01 * oy + g.c02, rv = (long long)g.c11 * oy + g.c12;     // wave-uniform
+            const long long U = ru + (long long)g.c00 * ox, V = rv + (long long)g.c10 * ox;
+            const ResizeTap mx = aug_tap(U, S, false), my = aug_tap(V, S, false);          // the mask's: outside reads 0
+            const ResizeTap tx = g.border == 1 ? aug_tap(U, S, true) : mx, ty = g.border == 1 ? aug_tap(V, S, true) : my;
+            int acc[3] = {0, 0, 0}, macc = 0;
+            blend4<3, false, true>(img, S, ty, tx, acc);
+            blend4<1, true, true>(mk, S, my, mx, &macc);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = (acc[k] + RESIZE_HALF) >> 22;
+            set = macc >= RESIZE_HALF;
+        }
+        // itertools.permutations(range(3))[perm] = (p0, p1, p2), two bits each
+        const int p0 = (0xA50 >> (2 * g.perm)) & 3, p1 = (0x489 >> (2 * g.perm)) & 3, p2 = (0x126 >> (2 * g.perm)) & 3;
+        *o = make_float4(t[aug_pick(v, p0)], t[256 + aug_pick(v, p1)], t[512 + aug_pick(v, p2)], 0.f);
+        *om = set ? 1 : 0;
+    }
+}
+
+extern "C" int fgn_support_augment_f32(const unsigned char* crop, const unsigned char* msk, const int* recs,
+                                       const float* lut, float* y, unsigned char* m, int n, int S, hipStream_t stream) {
+    if (!crop || !msk || !recs || !lut || !y || !m) return FGN_ERR_ARG;
+    if (n < 0 || S < 0 || S > RESIZE_MAX_DIM) return FGN_ERR_SHAPE;
     if ((long long)n * S == 0) return FGN_OK;
+    const uintptr_t px = (uintptr_t)n * S * S;              // pixels: 3 bytes of crop, 16 of y, 1 of msk and of m each
+    const auto meet = [](const void* a, uintptr_t na, const void* b, uintptr_t nb) {
+        const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+        return pa < pb + nb && pb < pa + na;
+    };
+    if (meet(crop, 3 * px, y, 16 * px) || meet(msk, px, m, px)) return FGN_ERR_ARG;       // (a gather: never in place)
     RowGrid g;
     if (row_grid((long long)n * S, S, 64, RESIZE_GRID_CAP, &g) != FGN_OK) return FGN_ERR_SHAPE;
-    hipLaunchKernelGGL(support_from_source_kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, src, src_stride_bytes, msk,
-                       msk_stride_bytes, recs, lut, reinterpret_cast<float4*>(y), m, S, g.chunks, g.units);
+    hipLaunchKernelGGL(support_augment_kernel, dim3(g.grid), dim3(RESIZE_BLOCK), 0, stream, crop, msk, recs, lut,
+                       reinterpret_cast<float4*>(y), m, S, g.chunks, g.units);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }

@@ -489,6 +489,27 @@ class _SrcSupports(NamedTuple):
                             self.rec.to(dev, non_blocking=True), self.S)
 
 
+class _AugSupports(NamedTuple):
+    """``_SrcSupports`` with an augmentation (``spp_augment`` / ``spp_photometric``): ``aug`` int32 [n,16], the records of
+    ``fewshot_ds.query_augment_record`` at S -> S, and ``photo`` int32 [n,64], the records of
+    ``fewshot_ds.query_photometric_record`` - or None where every instance's is neutral (no photometric launch)."""
+    src: torch.Tensor
+    msk: torch.Tensor
+    rec: torch.Tensor
+    S: int
+    aug: torch.Tensor
+    photo: Optional[torch.Tensor]
+
+    @property
+    def shape(self) -> tuple:
+        return (self.src.shape[0], self.S, self.S, 3)
+
+    def to(self, dev, *a, **kw) -> '_AugSupports':
+        return _AugSupports(self.src.to(dev, non_blocking=True), self.msk.to(dev, non_blocking=True),
+                            self.rec.to(dev, non_blocking=True), self.S, self.aug.to(dev, non_blocking=True),
+                            None if self.photo is None else self.photo.to(dev, non_blocking=True))
+
+
 class _StemReady(NamedTuple):
     """An image batch that already is the NHWC4 fp32 input of the stem (``ops.support_from_source`` makes it together
     with the masks): ``_stem_input`` hands ``x`` through."""
@@ -1034,13 +1055,55 @@ class FGN(torch.nn.Module):
                     recs[i] = fd.query_photometric_record(None, hw, rs['hw'])
         return torch.from_numpy(recs) if recs[:, 2].any() else None
 
+    @staticmethod
+    def _refuse_support_augment(spp_augment, spp_photometric) -> None:
+        for name, v in (('spp_augment', spp_augment), ('spp_photometric', spp_photometric)):
+            if v is not None:
+                raise ValueError(f'{name} is for forward_train: the test is without augmentation')
+
+    @staticmethod
+    def _support_plans(spp_augment, spp_photometric, sp: dict) -> dict:
+        """The contract of ``spp_augment`` / ``spp_photometric`` (host only, nothing is queued): [B,N*K,8] / [B,N*K,3]
+        finite rows ([N*K,.] for a single support set) inside the sets and bounds of the queries' rows, at S -> S.  ``sp``:
+        the dict of ``_source_supports``, whose boxes the plan starts from.  -> ``sp`` with ``boxes`` replaced by
+        ``fewshot_ds.support_augment_plan``'s and, unless every instance is neutral after the per-instance fallback,
+        ``aug`` int32 [n,16] and ``photo`` int32 [n,64] (None where every photometric record is neutral)."""
+        from . import fewshot_ds as fd
+        B, n, S = sp['B'], sp['n'], sp['S']
+        rows = {}
+        for name, v, width, fields in (('spp_augment', spp_augment, len(fd.AUG_PARAMS), fd.AUG_PARAMS),
+                                       ('spp_photometric', spp_photometric, len(fd.PHOTO_PARAMS), fd.PHOTO_PARAMS)):
+            if v is None:
+                rows[name] = None
+                continue
+            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+            if a.dtype.kind not in 'iuf' or a.shape not in ((B, n // B, width),) + (((n, width),) if B == 1 else ()):
+                raise ValueError(f'{name} must be [B,N*K,{width}] numbers {fields} for {B} support set(s) of {n // B} '
+                                 f'instances ([N*K,{width}] for a single set), got {a.dtype} {list(a.shape)}')
+            rows[name] = a.reshape(n, width)
+        try:
+            recs, precs, boxes, _ = fd.support_augment_plan(rows['spp_augment'], rows['spp_photometric'],
+                                                            sp['boxes'].numpy().reshape(n, 4), S)
+        except ValueError as e:             # (the rows' sets and bounds are the queries': name the supports' arguments)
+            raise ValueError(str(e).replace('qry_augment', 'spp_augment').replace('qry_photometric', 'spp_photometric')
+                             ) from None
+        sp = dict(sp, boxes=torch.from_numpy(boxes.reshape(B, n // B, 4)))
+        if recs[:, 2:6].any() or precs[:, 2].any():
+            sp.update(aug=torch.from_numpy(recs), photo=torch.from_numpy(precs) if precs[:, 2].any() else None)
+        return sp
+
     def _train_front(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                      spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
                      spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
-                     qry_photometric=None, **kwargs) -> dict:
+                     qry_photometric=None, spp_augment=None, spp_photometric=None, **kwargs) -> dict:
         """The front of a training batch, shared by ``forward_train`` and ``train.Trainer``: the contracts of
-        ``qry_resize_to``, ``spp_crop_to``, ``qry_augment`` and ``qry_photometric`` (every error before anything is
-        queued), then the uploads and the kernels behind them.  -> the keyword arguments of ``train.forward_train``."""
+        ``qry_resize_to``, ``spp_crop_to``, ``qry_augment``, ``qry_photometric``, ``spp_augment`` and ``spp_photometric``
+        (every error before anything is queued), then the uploads and the kernels behind them.  -> the keyword arguments
+        of ``train.forward_train``."""
+        for name, v in (('spp_augment', spp_augment), ('spp_photometric', spp_photometric)):
+            if v is not None and spp_crop_to is None:
+                raise ValueError(f'{name} needs spp_crop_to: the supports are augmented on the device behind their cut '
+                                 f'from the source images')
         if qry_augment is not None and qry_resize_to is None:
             raise ValueError('qry_augment needs qry_resize_to: the query is augmented together with its resize from the '
                              'source size')
@@ -1050,6 +1113,8 @@ class FGN(torch.nn.Module):
         sp = None
         if spp_crop_to is not None:                       # (every contract error before anything is queued)
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
+            if spp_augment is not None or spp_photometric is not None:
+                sp = self._support_plans(spp_augment, spp_photometric, sp)
         if qry_resize_to is not None:
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
             if qry_augment is not None:
@@ -1181,7 +1246,10 @@ class FGN(torch.nn.Module):
         """``_source_supports`` uploaded on the current stream, in the form ``_support_front`` takes: (``_SrcSupports``,
         the boxes)."""
         src, msk = self._upload_supports(sp, dev)
-        return _SrcSupports(src, msk, sp['rec'].to(dev, non_blocking=True), sp['S']), sp['boxes']
+        rec = sp['rec'].to(dev, non_blocking=True)
+        if sp.get('aug') is None:           # (no augmentation, or every instance neutral after the fallback)
+            return _SrcSupports(src, msk, rec, sp['S']), sp['boxes']
+        return _AugSupports(src, msk, rec, sp['S'], sp['aug'], sp['photo']).to(dev), sp['boxes']
 
     # --- stages ---------------------------------------------------------------------------
     def extract_feat(self, img: Union[torch.Tensor, '_SrcQuery']) -> torch.Tensor:
@@ -1265,7 +1333,7 @@ class FGN(torch.nn.Module):
     def forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                       spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
                       spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
-                      qry_photometric=None, **kwargs) -> Dict:
+                      qry_photometric=None, spp_augment=None, spp_photometric=None, **kwargs) -> Dict:
         """The loss dict of one training step (fgn.py:125-185) as forward values - see ``fgn_amd.train``.  Keys and
         container types are the reference's: ``loss_rpn_cls`` / ``loss_rpn_bbox`` (lists of one tensor),
         ``loss_cls``, ``ACC-Unbalanced``, ``ACC-Balanced``, ``loss_bbox``, ``loss_mask``.  ``qry_resize_to``: source-size
@@ -1278,13 +1346,19 @@ class FGN(torch.nn.Module):
         ``qry_augment``): [B,3] rows of ``fewshot_ds.PHOTO_PARAMS`` - one of Gaussian noise, impulse noise, Gaussian blur,
         hue, saturation, brightness per image, applied to the source pixels on the device ahead of the resize
         (``fewshot_ds.photometric_image_u8`` bit for bit); an image whose boxes leave it under
-        ``qry_augment`` is used without either."""
+        ``qry_augment`` is used without either.  ``spp_augment`` / ``spp_photometric`` (need ``spp_crop_to``; either
+        without the other): [B,N*K,8] / [B,N*K,3] rows of the same two formats, one pair per support INSTANCE, applied on
+        the device to the S x S crop behind its cut - after resize and pad, the reference's own order
+        (``fewshot_ds.augment_support`` bit for bit; ``get_support`` with ``augment_spp``, base_fst.py:1151-1153;
+        DESIGN 4.4.7) - and to ``spp_bboxes`` on the host; an instance whose box leaves its crop is used un-augmented,
+        that instance alone.  At most three launches make the supports, whatever N*K."""
         from . import train
         return train.forward_train(self, **self._train_front(
             qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals,
             spp_imgs=spp_imgs, spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps, img_shape=img_shape,
             qry_resize_to=qry_resize_to, spp_crop_to=spp_crop_to, spp_fill_ratio=spp_fill_ratio, crop_square=crop_square,
-            qry_augment=qry_augment, qry_photometric=qry_photometric, **kwargs))
+            qry_augment=qry_augment, qry_photometric=qry_photometric, spp_augment=spp_augment,
+            spp_photometric=spp_photometric, **kwargs))
 
     @torch.no_grad()
     def simple_test(self, qry_img, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None, qry_bboxes_ignore=None,
@@ -1292,8 +1366,9 @@ class FGN(torch.nn.Module):
                     rescale=False, cats_ids_to_sample_real=None, spp_insts_ids=None, idx=None,
                     support_code=None, qry_resize_to=None, results_at_source: bool = False, spp_crop_to=None,
                     spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None, qry_photometric=None,
-                    **kwargs) -> List[Dict]:
-        """Test without augmentation (fgn.py:187-303; ``qry_augment`` and ``qry_photometric`` are refused).  ``support_code`` (optional, from
+                    spp_augment=None, spp_photometric=None, **kwargs) -> List[Dict]:
+        """Test without augmentation (fgn.py:187-303; ``qry_augment``, ``qry_photometric``, ``spp_augment`` and
+        ``spp_photometric`` are refused).  ``support_code`` (optional, from
         ``encode_supports``) replaces the three ``spp_*`` inputs.  ``qry_resize_to`` = (H, W) (or a [B,2] tensor of
         equal rows): ``qry_img`` holds decoded images at their SOURCE size - a uint8 tensor [B,h,w,3] or a list of B
         uint8 tensors [h_i,w_i,3] - and ``qry_isegmaps`` / ``qry_bboxes`` are at source size too; image and masks are
@@ -1313,6 +1388,7 @@ class FGN(torch.nn.Module):
             raise ValueError('qry_augment is for forward_train: the test is without augmentation')
         if qry_photometric is not None:
             raise ValueError('qry_photometric is for forward_train: the test is without augmentation')
+        self._refuse_support_augment(spp_augment, spp_photometric)
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
         sp = None
@@ -1342,15 +1418,21 @@ class FGN(torch.nn.Module):
         """modify_input for the supports (fgn.py:79-108: H2D, YXYX -> XYXY on private copies), their
         backbone pass and the AG-RPN class vectors."""
         N, K = self.n_ways, self.k_shots
-        if not isinstance(spp_imgs, _SrcSupports):
+        if not isinstance(spp_imgs, (_SrcSupports, _AugSupports)):
             self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
         b = spp_bboxes.to(dev, torch.float32, non_blocking=True).reshape(B * N * K, 4)
         spp_xyxy = torch.stack((b[:, 1], b[:, 0], b[:, 3], b[:, 2]), 1)      # no host-built index tensor: graph-capturable
-        if isinstance(spp_imgs, _SrcSupports):      # windows of the source images (``spp_crop_to``): crop, resize, pad
-            s = spp_imgs.to(dev)                    # and normalise in ONE launch, which makes the masks too
+        if isinstance(spp_imgs, (_SrcSupports, _AugSupports)):  # windows of the source images (``spp_crop_to``): crop,
+            s = spp_imgs.to(dev)                    # resize, pad and normalise in ONE launch, which makes the masks too
             if s.src.shape[0] != B * N * K:
                 raise ValueError(f'{s.src.shape[0]} support instances for a batch of {B} x {N} x {K}')
-            y, spp_masks = ops.support_from_source(s.src, s.msk, s.rec, self._lut_on(dev), s.S)
+            if isinstance(s, _AugSupports):         # (``spp_augment``: the cut as bytes, the photometric pass where an
+                crop, msk = ops.support_from_source_u8(s.src, s.msk, s.rec, s.S)        # instance has one, the gather)
+                if s.photo is not None:
+                    crop = ops.photometric_u8(crop.view(crop.shape[0], -1), s.photo).view(crop.shape)
+                y, spp_masks = ops.support_augment(crop, msk, s.aug, self._lut_on(dev), s.S)
+            else:
+                y, spp_masks = ops.support_from_source(s.src, s.msk, s.rec, self._lut_on(dev), s.S)
             spp = _StemReady(y)
         else:
             spp = spp_imgs.to(dev, non_blocking=True).reshape(B * N * K, *spp_imgs.shape[-3:])    # (dtype: _stem_input)
@@ -1404,13 +1486,15 @@ class FGN(torch.nn.Module):
 
     @torch.no_grad()
     def encode_supports(self, spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to=None, spp_fill_ratio: float = 0.8,
-                        crop_square: bool = True) -> dict:
+                        crop_square: bool = True, spp_augment=None, spp_photometric=None) -> dict:
         """Support-feature caching across queries: everything the path derives
         from the support set alone - backbone pass, AG-RPN class vectors, count_spp, the support
         half of the relation conv - computed once on the current stream.  The returned code is
         passed as ``support_code=`` to ``simple_test`` / ``detect_device`` for every query that
         shares the support set (the reference recomputes it per query, fgn.py:212-215; results
-        are identical).  ``spp_crop_to``: the supports come as their source images, as for ``simple_test``."""
+        are identical).  ``spp_crop_to``: the supports come as their source images, as for ``simple_test``.
+        ``spp_augment`` / ``spp_photometric`` are refused: the test path is without augmentation."""
+        self._refuse_support_augment(spp_augment, spp_photometric)
         sp = None
         if spp_crop_to is not None:
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
@@ -1571,7 +1655,7 @@ class FGN(torch.nn.Module):
     def detect_device(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
                       qry_isegmaps=None, phase_counter=None, qry_resize_to=None,
                       results_at_source: bool = False, spp_crop_to=None, spp_fill_ratio: float = 0.8,
-                      crop_square: bool = True) -> list:
+                      crop_square: bool = True, spp_augment=None, spp_photometric=None) -> list:
         """Everything up to the host wait: queues the host->device copies, the whole path and the device->host
         copies of the results.  Returns, per image, a dict of device tensors (det_bboxes [D,5], det_labels [D],
         n_dets [1], mask_prob, RLE bytes) plus the pinned host slot ``pack_results`` reads.
@@ -1592,7 +1676,9 @@ class FGN(torch.nn.Module):
         ``spp_src`` / ``spp_msk`` (uint8 [B*N*K, slot]) with the records ``spp_rec`` (int32 [B*N*K,16]) in place of
         ``spp_imgs`` / ``spp_isegmaps``, the boxes are computed on the host, and a captured graph is keyed by the slot
         size and S, not by any source, window or crop size.  (``simple_test`` hands over the dict of
-        ``_source_supports``.)  Ignored beside ``support_code``."""
+        ``_source_supports``.)  Ignored beside ``support_code``.  ``spp_augment`` / ``spp_photometric`` are refused: the
+        test path is without augmentation."""
+        self._refuse_support_augment(spp_augment, spp_photometric)
         graphed = self._graphed()
         source = spp_source = None
         if spp_crop_to is not None and support_code is None:

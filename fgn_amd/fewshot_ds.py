@@ -962,6 +962,71 @@ def support_window(img: np.ndarray, isegmap: np.ndarray, rec: np.ndarray):
     return np.ascontiguousarray(img[ys, xs]), m.view(np.uint8)
 
 
+# ---- support augmentation (BaseFewShotISEG.get_support with augment_spp, base_fst.py:1151-1153) --------------------
+# ``augment_with_imgaug(self.augs_spp, img_crop_pad, box_crop_pad, isegmap_crop_pad)`` once per instance, on the S x S
+# crop AFTER resize and pad, with one mask and one box.  The few-shot dataset classes assign ``augs_spp = augs_seq``, the
+# queries' sequence, so the rule is the queries' by composition, at equal size: nothing new is restated here
+# (DESIGN.md 4.4.7).  Unlike the queries the supports see the operators in the reference's own place, after the resize.
+def augment_support(crop: np.ndarray, box, mask: np.ndarray, params=None, photometric=None):
+    """One support instance of ``support_from_source`` (crop uint8 [S,S,3], box float32 YXYX in the S x S frame, mask
+    [S,S]) through one row pair (``AUG_PARAMS``, ``PHOTO_PARAMS``): ``augment_query_full`` at equal size with one box
+    and one mask - ``photometric_image_u8`` (the blur's sigma in crop pixels), the gather of ``query_augment_record``
+    whose symmetric border reflects the S x S frame, pad bands included, and the box through ``augment_boxes_yxyx``.  A
+    box that leaves the open S x S rectangle: the instance is used un-augmented in both halves.
+    -> (crop', box' [4], mask' [S,S])."""
+    crop, mask = np.asarray(crop), np.asarray(mask)
+    if crop.ndim != 3 or crop.shape[0] != crop.shape[1] or mask.shape != crop.shape[:2]:
+        raise ValueError(f'augment_support: expects a crop [S,S,3] and its mask [S,S], got {list(crop.shape)} and '
+                         f'{list(mask.shape)}')
+    S = crop.shape[0]
+    box = np.asarray(box).reshape(1, 4)
+    img, boxes, masks = augment_query_full(crop, box, mask[None], S, S, params, photometric)
+    return img, boxes[0], masks[0]
+
+
+def support_augment_plan(rows, photo_rows, boxes, S: int):
+    """Everything of the augmentation of n support instances that is decided before a pixel is touched.  ``rows``
+    [n,8] rows of ``AUG_PARAMS`` and ``photo_rows`` [n,3] rows of ``PHOTO_PARAMS`` (either may be None: neutral),
+    ``boxes`` [n,4] YXYX in the S x S frame (``support_geometry``'s) -> (geometric records int32 [n,16] of
+    ``query_augment_record(row, (S,S), (S,S))``, photometric records int32 [n,64] of ``query_photometric_record``,
+    boxes [n,4] after the matrix in the dtype of ``boxes``, fallback flags bool [n]).  The fallback is per instance: where
+    the transformed box has no overlap with the open S x S rectangle, that instance alone gets both neutral records and
+    keeps its box (base_fst.py:751-768).  Every contract error of a row is raised here, fallback or not."""
+    S = int(S)
+    boxes = np.asarray(boxes)
+    if boxes.ndim != 2 or boxes.shape[1] != 4:
+        raise ValueError(f'support_augment_plan: boxes must be [n,4], got {list(boxes.shape)}')
+    n = boxes.shape[0]
+    rows = [None] * n if rows is None else rows
+    photo_rows = [None] * n if photo_rows is None else photo_rows
+    if len(rows) != n or len(photo_rows) != n:
+        raise ValueError(f'support_augment_plan: {n} boxes, {len(rows)} geometric and {len(photo_rows)} photometric rows')
+    recs = np.zeros((n, AUG_REC_INTS), np.int32)
+    precs = np.zeros((n, PHOTO_REC_INTS), np.int32)
+    out = np.array(boxes, copy=True)
+    fell_back = np.zeros(n, bool)
+    for i, (row, prow) in enumerate(zip(rows, photo_rows)):
+        recs[i] = query_augment_record(row, (S, S), (S, S))
+        precs[i] = query_photometric_record(prow, (S, S), (S, S))
+        if row is None or augment_is_neutral(check_augment_params(row)):
+            recs[i] = query_augment_record(None, (S, S), (S, S))          # (a neutral row's border is of no account)
+            continue
+        nb, ok = augment_boxes_yxyx(boxes[i:i + 1], row, S, S)
+        if ok:
+            out[i] = nb[0]
+        else:
+            fell_back[i] = True
+            recs[i] = query_augment_record(None, (S, S), (S, S))
+            precs[i] = query_photometric_record(None, (S, S), (S, S))
+    return recs, precs, out, fell_back
+
+
+def draw_support_augment(rng):
+    """One support instance's row pair (row of ``AUG_PARAMS``, row of ``PHOTO_PARAMS``), drawn as
+    ``draw_query_augment_full`` draws a query's: the few-shot dataset classes assign ``augs_spp = augs_seq``."""
+    return draw_query_augment_full(rng)
+
+
 class SyntheticFewShotISEG(Dataset):
     def __init__(self, n_ways=3, k_shots=3, length=64, height=800, width=1333, spp_img_size=256, batch=4,
                  seed=1234, suffix='SYNTH_val_novel'):
@@ -1036,7 +1101,15 @@ class ClutteredCharsFewShotISEG(Dataset):
     were.  ``photometric_qry`` (needs ``augment_qry``): the sample also carries ``qry_photometric``, one row of
     ``PHOTO_PARAMS`` float64 [3], and both rows come from the joint draw ``draw_query_augment_full`` (the whole
     ``augs_seq``), seeded the same way, for ``FGN.forward_train(qry_photometric=...)``.  Off by default: the samples
-    are then key for key what they are without it."""
+    are then key for key what they are without it.
+    ``augment_spp`` (needs ``spp_source``): the sample carries ``spp_augment``, float64 [N*K,8], one row of ``AUG_PARAMS``
+    per support instance, for a detector that augments the supports on the device behind their cut
+    (``FGN.forward_train(spp_augment=...)``; ``get_support`` with ``augment_spp``, base_fst.py:1151-1153).  Instance i
+    is drawn from ``np.random.default_rng([seed, child, epoch, 1 + i])`` - four words, disjoint from the query's three -
+    by ``draw_query_augment``; the pixels, masks and boxes of the sample are NOT augmented.  ``photometric_spp`` (needs
+    ``augment_spp``): the sample also carries ``spp_photometric`` [N*K,3] and both rows of an instance come from the
+    joint draw ``draw_support_augment``, seeded the same way.  Off by default: the samples are then key for key what
+    they are without them, and ``qry_augment`` / ``qry_photometric`` are the same with or without them."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
@@ -1044,7 +1117,7 @@ class ClutteredCharsFewShotISEG(Dataset):
 
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
                  spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None,
-                 spp_source=False, augment_qry=False, photometric_qry=False):
+                 spp_source=False, augment_qry=False, photometric_qry=False, augment_spp=False, photometric_spp=False):
         par = self.PARAMS[dataset]
         self.raw_uint8 = bool(raw_uint8)
         self.spp_source = bool(spp_source)
@@ -1063,6 +1136,14 @@ class ClutteredCharsFewShotISEG(Dataset):
         if self.photometric_qry and not self.augment_qry:
             raise ValueError('photometric_qry needs augment_qry: the two rows are one joint draw of the reference\'s '
                              'augs_seq')
+        self.augment_spp = bool(augment_spp)
+        if self.augment_spp and not self.spp_source:
+            raise ValueError('augment_spp needs spp_source: the supports are augmented by the detector behind their cut '
+                             'from the source images')
+        self.photometric_spp = bool(photometric_spp)
+        if self.photometric_spp and not self.augment_spp:
+            raise ValueError('photometric_spp needs augment_spp: the two rows of an instance are one joint draw of the '
+                             'reference\'s augs_seq')
         self.epoch = 0                               # the ``e`` of the last ``reshuffle``: one augmentation draw per epoch
         self.n_ways, self.k_shots, self.batch, self.shuffle = n_ways, k_shots, batch, shuffle
         self.img_size, self.spp_img_size, self.spp_fill_ratio = img_size, spp_img_size, spp_fill_ratio
@@ -1161,6 +1242,14 @@ class ClutteredCharsFewShotISEG(Dataset):
             sample['qry_augment'] = draw_query_augment(np.random.default_rng([int(self.seed), child, self.epoch]))
         if self.spp_source:
             sample.update(spp_crop_to=int(self.spp_img_size), spp_fill_ratio=float(self.spp_fill_ratio), crop_square=True)
+        if self.augment_spp:                     # instance i: its own stream, disjoint from the query's three-word seed
+            rngs = [np.random.default_rng([int(self.seed), child, self.epoch, 1 + i]) for i in range(len(spp_ids))]
+            if self.photometric_spp:
+                pairs = [draw_support_augment(r) for r in rngs]
+                sample['spp_augment'] = np.stack([p for p, _ in pairs])
+                sample['spp_photometric'] = np.stack([q for _, q in pairs])
+            else:
+                sample['spp_augment'] = np.stack([draw_query_augment(r) for r in rngs])
         return sample
 
     evaluate = SyntheticFewShotISEG.evaluate

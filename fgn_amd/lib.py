@@ -44,6 +44,8 @@ SIGNATURES = {
     'fgn_augment_mask_u8': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     'fgn_photometric_u8hwc3': (_i, [_p, _p, C.c_longlong, _p, _i, _p]),
     'fgn_support_from_source_f32': (_i, [_p, C.c_longlong, _p, C.c_longlong, _p, _p, _p, _p, _i, _i, _p]),
+    'fgn_support_from_source_u8': (_i, [_p, C.c_longlong, _p, C.c_longlong, _p, _p, _p, _i, _i, _p]),
+    'fgn_support_augment_f32': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
     'fgn_maxpool3x3s2_nhwc_f32': (_i, [_p, _p, _i, _i, _i, _i, _p]),
     'fgn_group_norm_workspace_bytes': (C.c_size_t, [_i] * 4),
     'fgn_group_norm_nhwc_f32': (_i, [_p] * 6 + [C.c_size_t, _i, _i, _i, _i, _f, _i, _p]),

@@ -1117,6 +1117,64 @@ def support_from_source(src: torch.Tensor, msk: torch.Tensor, recs: torch.Tensor
                               (S,), 'S', with_mask=True)
 
 
+def support_from_source_u8(src: torch.Tensor, msk: torch.Tensor, recs: torch.Tensor, S: int):
+    """``support_from_source`` with the crops as BYTES: -> (uint8 [n,S,S,3], the support masks uint8 0/1 [n,S,S]) =
+    ``fewshot_ds.support_from_source``'s crop and mask themselves, bit for bit, in one launch; no table.  Arguments and
+    the treatment of a bad record as for ``support_from_source`` (the padding and a refused instance are byte 0).  The
+    crops feed ``photometric_u8`` (as [n, 3*S*S] slots) and ``support_augment``."""
+    for name, t in (('src', src), ('msk', msk)):
+        _chk(t, name, torch.uint8)
+    _chk(recs, 'recs', torch.int32)
+    n = src.shape[0] if src.dim() == 2 else -1
+    if n < 0 or msk.dim() != 2 or msk.shape[0] != n or tuple(recs.shape) != (n, SPP_REC_INTS) or \
+            msk.device != src.device or recs.device != src.device:
+        raise _lib.FgnHipError('support_from_source_u8: expects src [n,capacity], msk [n,mask capacity] and recs [n,16] '
+                               'on one device')
+    S = int(S)
+    if not 0 <= S <= RESIZE_MAX_DIM:
+        raise _lib.FgnHipError(f'support_from_source_u8: S must be within 0..{RESIZE_MAX_DIM}, got {S}')
+    crop = torch.empty((n, S, S, 3), device=src.device, dtype=torch.uint8)
+    m = torch.empty((n, S, S), device=src.device, dtype=torch.uint8)
+    if crop.numel():                    # (an empty tensor has no address to hand over)
+        # (capacity 0: every item is refused by the kernel; it needs an address only)
+        src, msk = (t if t.shape[1] else t.new_zeros((n, 1)) for t in (src, msk))
+        _lib.check(_lib.load().fgn_support_from_source_u8(_ptr(src), int(src.shape[1]), _ptr(msk), int(msk.shape[1]),
+                                                          _ptr(recs), _ptr(crop), _ptr(m), n, S, _stream()),
+                   'fgn_support_from_source_u8')
+    return crop, m
+
+
+def support_augment(crop: torch.Tensor, msk: torch.Tensor, recs: torch.Tensor, lut: torch.Tensor, S: int):
+    """n support crops and their masks -> (the augmented NHWC4 fp32 stem input [n,S,S,4], the augmented masks uint8 0/1
+    [n,S,S]): ``u8hwc3_to_nhwc4`` of ``fewshot_ds.augment_image_u8`` and ``fewshot_ds.augment_masks`` at S -> S of
+    every instance, bit for bit, in ONE launch (``get_support`` with ``augment_spp``, base_fst.py:1151-1153).  ``crop``
+    uint8 [n,S,S,3] and ``msk`` uint8 / bool [n,S,S] (nonzero = set) as ``support_from_source_u8`` makes them; ``recs``
+    int32 [n,16] ON THE DEVICE: the records of ``fewshot_ds.query_augment_record(row, (S,S), (S,S))``, read by the kernel.
+    An instance whose record is out of range or for another size than S comes out as padding with an empty mask."""
+    if msk.dtype == torch.bool:
+        msk = msk.view(torch.uint8)
+    _chk(crop, 'crop', torch.uint8)
+    _chk(msk, 'msk', torch.uint8)
+    _chk(recs, 'recs', torch.int32)
+    _chk(lut, 'lut')
+    S = int(S)
+    if not 0 <= S <= RESIZE_MAX_DIM:
+        raise _lib.FgnHipError(f'support_augment: S must be within 0..{RESIZE_MAX_DIM}, got {S}')
+    n = crop.shape[0] if crop.dim() == 4 else -1
+    if n < 0 or tuple(crop.shape) != (n, S, S, 3) or tuple(msk.shape) != (n, S, S) or \
+            tuple(recs.shape) != (n, AUG_REC_INTS) or msk.device != crop.device or recs.device != crop.device:
+        raise _lib.FgnHipError(f'support_augment: expects crop [n,{S},{S},3], msk [n,{S},{S}] and recs [n,16] on one '
+                               f'device')
+    if tuple(lut.shape) != (3, 256) or lut.device != crop.device:
+        raise _lib.FgnHipError('support_augment: lut must be [3,256] on the device of crop')
+    y = torch.empty((n, S, S, 4), device=crop.device, dtype=torch.float32)
+    m = torch.empty((n, S, S), device=crop.device, dtype=torch.uint8)
+    if y.numel():                       # (an empty tensor has no address to hand over)
+        _lib.check(_lib.load().fgn_support_augment_f32(_ptr(crop), _ptr(msk), _ptr(recs), _ptr(lut), _ptr(y), _ptr(m),
+                                                       n, S, _stream()), 'fgn_support_augment_f32')
+    return y, m
+
+
 def _gather_masks(fn: str, entry: str, masks: torch.Tensor, rec: Optional[torch.Tensor], H: int, W: int) -> torch.Tensor:
     """The wrapper of the two mask gathers (``fn``, over the library's ``entry``): masks [G,h,w] bool / uint8, with or
     without the record of their image -> uint8 0/1 [G,H,W]."""

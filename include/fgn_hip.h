@@ -311,6 +311,31 @@ int fgn_support_from_source_f32(const unsigned char* src, long long src_stride_b
                                 long long msk_stride_bytes, const int* recs, const float* lut, float* y,
                                 unsigned char* m, int n, int S, void* stream);
 
+/* The byte-output form of fgn_support_from_source_f32 (the same kernel body: record, taps, window reads, validity rule
+ * and mask are those above): crop [n][S][S][3] uint8 = fewshot_ds.support_from_source's crop itself, bit for bit - the
+ * clamped bytes, byte 0 in the padding and for an instance whose record is out of range - and m as above.  No table.
+ * It feeds fgn_photometric_u8hwc3 (n slots of stride 3 * S * S) and fgn_support_augment_f32.  Return codes as above. */
+int fgn_support_from_source_u8(const unsigned char* src, long long src_stride_bytes, const unsigned char* msk,
+                               long long msk_stride_bytes, const int* recs, unsigned char* crop, unsigned char* m,
+                               int n, int S, void* stream);
+
+/* Support augmentation behind the cut (get_support with augment_spp, base_fst.py:1151-1153: per instance, on the S x S
+ * crop after resize and pad), ONE launch for all n instances: fewshot_ds.augment_image_u8 / augment_masks at S -> S
+ * followed by the table, bit for bit.
+ *   crop [n][S][S][3] uint8, msk [n][S][S] bytes (nonzero = set): what fgn_support_from_source_u8 makes
+ *   recs int32 [n][16], read ON THE DEVICE: the records of fgn_augment_u8hwc3_to_nhwc4_f32 with h = w = S.  No launch
+ *        argument depends on an augmentation.
+ *   lut  [3][256] fp32;  y [n][S][S][4] fp32: channel c = table c of byte order[c] of the gathered pixel;  m [n][S][S]
+ *        0 / 1 bytes: the mask by the image's taps, a tap outside the frame reading 0 whatever the border, set where
+ *        acc >= 2^21.
+ * Kind 0 copies column ox (S-1-ox under flip); kind 1 is the bilinear gather, whose symmetric border reflects the S x S
+ * frame, pad bands included.  An instance whose record is out of range, or whose h or w is not S, is written as the
+ * table's byte-0 pixel with an empty mask and none of its bytes are read; its neighbours are untouched.  A null pointer,
+ * or crop / y or msk / m overlapping, is FGN_ERR_ARG; n < 0 or S outside 0..16384 FGN_ERR_SHAPE; n * S == 0 FGN_OK with
+ * no launch. */
+int fgn_support_augment_f32(const unsigned char* crop, const unsigned char* msk, const int* recs, const float* lut,
+                            float* y, unsigned char* m, int n, int S, void* stream);
+
 /* 3x3/2 pad 1 max-pool of the ResNet stem */
 int fgn_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n_img, int H, int W, int C, void* stream);
 
