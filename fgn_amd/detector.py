@@ -363,18 +363,11 @@ class _GraphedEpisode:
     ``pack_results`` may read."""
     CODE_KEYS = ('vec', 'S', 'cat_mean_mp')
 
-    SLOT_KEYS = ('qry_src', 'spp_src', 'spp_msk')       # rows of a configured capacity: a batch fills their fronts
-
-    def __init__(self, model, ins: dict, img_shape, support_code, dev, phase_counter=None, source=None,
-                 results_at_source: bool = False, spp_source=None):
+    def __init__(self, model, ins: dict, img_shape, support_code, dev, phase_counter, form: '_InputForm'):
         self.static = {k: torch.empty(v.shape, dtype=v.dtype, device=dev) for k, v in ins.items()}
-        resize_to = None
-        if spp_source is not None:  # supports from their source images: window slots of the configured size, likewise
-            for k, cap in (('spp_src', spp_source['capacity']), ('spp_msk', spp_source['mcapacity'])):
-                self.static[k] = torch.empty((spp_source['n'], cap), dtype=torch.uint8, device=dev)
-        if source is not None:      # source-size queries: the slot has the configured size, whatever this batch needs
-            self.static['qry_src'] = torch.empty((source['B'], source['capacity']), dtype=torch.uint8, device=dev)
-            resize_to = source['hw']
+        self.slots = form.slots()   # rows of a configured capacity, whatever this batch needs: a batch fills their fronts
+        for k, shape in self.slots.items():
+            self.static[k] = torch.empty(shape, dtype=torch.uint8, device=dev)
         self.img_shape = torch.as_tensor(img_shape).cpu().clone()
         self.code = None
         if support_code is not None:
@@ -384,16 +377,12 @@ class _GraphedEpisode:
         self.last_download = None
         for k, v in ins.items():
             self._copy_in(k, v)
-        qry = lambda: self.static['qry_img'] if resize_to is None else \
-            _SrcQuery(self.static['qry_src'], self.static['qry_src_hw'], *resize_to)
-        spp = lambda: self.static.get('spp_imgs') if spp_source is None else \
-            _SrcSupports(self.static['spp_src'], self.static['spp_msk'], self.static['spp_rec'], spp_source['S'])
-        args = lambda: (qry(), spp(), self.static.get('spp_bboxes'),
+        args = lambda: (form.query(self.static), form.supports(self.static), self.static.get('spp_bboxes'),
                         self.static.get('spp_isegmaps'), self.img_shape, self.code)
         # eager pass first: packs the weights, sets kernel attributes, sizes the allocator pools
         # (the eager run that precedes the capture sends no phase mark: every ``detect_device`` call bumps the caller's
         # counter exactly once - here through the replay that follows the capture)
-        model._detect_eager(*args(), phase_counter=None, results_at_source=results_at_source)
+        model._detect_eager(*args(), phase_counter=None, results_at_source=form.at_source)
         torch.cuda.current_stream().synchronize()
         self.graph = torch.cuda.CUDAGraph()
         # launch records of the dominant kernel (``FGN.stamp_capacity``; bench.py's roofline over the whole timed window):
@@ -409,13 +398,13 @@ class _GraphedEpisode:
         try:
             with torch.cuda.graph(self.graph, capture_error_mode=os.environ.get('FGN_GRAPH_CAPTURE_MODE', 'thread_local')):
                 self.outs = model._detect_eager(*args(), phase_counter=phase_counter,
-                                                results_at_source=results_at_source)
+                                                results_at_source=form.at_source)
         finally:
             if self.stamps is not None:
                 self.stamp_count = ops.arm_stamps(None)
 
     def _copy_in(self, k: str, v: torch.Tensor) -> None:
-        if k in self.SLOT_KEYS:     # [B, what the batch needs] into the front of the slot rows; the rest is never read
+        if k in self.slots:         # [B, what the batch needs] into the front of the slot rows; the rest is never read
             self.static[k][:, :v.shape[1]].copy_(v, non_blocking=True)
         else:
             self.static[k].copy_(v, non_blocking=True)
@@ -436,88 +425,152 @@ class _GraphedEpisode:
         return [dict(d) for d in self.outs]          # detect_device queues the download and sets ``last_download``
 
 
-class _SrcQuery(NamedTuple):
+def _host(v) -> np.ndarray:
+    """A tensor, array or nested list as a host array."""
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
+def _number_rows(v, shapes: tuple, must: str) -> np.ndarray:
+    """The rows of an augmentation argument as a host array: numbers, in one of ``shapes``."""
+    a = _host(v)
+    if a.dtype.kind not in 'iuf' or a.shape not in shapes:
+        raise ValueError(f'{must}, got {a.dtype} {list(a.shape)}')
+    return a
+
+
+def _moved(t: tuple, dev):
+    """A carrier with every tensor it holds on ``dev`` (None and the plain numbers stay)."""
+    return t._make(v.to(dev, non_blocking=True) if isinstance(v, torch.Tensor) else v for v in t)
+
+
+class _QueryPixels(NamedTuple):
     """Query images at their source size on the way to the stem (``qry_resize_to``): ``src`` uint8 [B, capacity], image b
-    = [h_b, w_b, 3] pixels at the start of row b; ``hw`` int32 [B,2] = (h_b, w_b); (H, W) the network size.  Stands where
-    the ``qry_img`` tensor stands between ``detect_device`` / ``forward_train`` and ``_stem_input``; on that way only
-    ``shape[0]``, ``to(device)`` and ``FGN._image_dims`` are asked of a query, and those it answers."""
+    = [h_b, w_b, 3] pixels at the start of row b; ``hw`` int32 [B,2] = (h_b, w_b); (H, W) the network size; ``rec``
+    (``qry_augment``) int32 [B,16], the records of ``fewshot_ds.query_augment_record`` (source size included), or None
+    for the plain resize.  Stands where the ``qry_img`` tensor stands between ``detect_device`` / ``forward_train`` and
+    ``_stem_input``; on that way only ``shape[0]``, ``to(device)``, ``dims`` (``FGN._image_dims``) and ``stem_input``
+    (``FGN._stem_input``) are asked of a query, and those it answers."""
     src: torch.Tensor
     hw: torch.Tensor
     H: int
     W: int
+    rec: Optional[torch.Tensor] = None
 
     @property
     def shape(self) -> tuple:
         return (self.src.shape[0], self.H, self.W, 3)
 
-    def to(self, dev, *a, **kw) -> '_SrcQuery':
-        return _SrcQuery(self.src.to(dev, non_blocking=True), self.hw.to(dev, non_blocking=True), self.H, self.W)
-
-
-class _AugQuery(NamedTuple):
-    """``_SrcQuery`` with an augmentation (``qry_augment``): ``rec`` int32 [B,16], the records of
-    ``fewshot_ds.query_augment_record`` (source size included), in place of ``hw``."""
-    src: torch.Tensor
-    rec: torch.Tensor
-    H: int
-    W: int
-
     @property
-    def shape(self) -> tuple:
-        return (self.src.shape[0], self.H, self.W, 3)
+    def dims(self) -> tuple:
+        return (int(self.src.shape[0]),), self.H, self.W
 
-    def to(self, dev, *a, **kw) -> '_AugQuery':
-        return _AugQuery(self.src.to(dev, non_blocking=True), self.rec.to(dev, non_blocking=True), self.H, self.W)
+    def to(self, dev, *a, **kw) -> '_QueryPixels':
+        return _moved(self, dev)
+
+    def stem_input(self, lut: torch.Tensor) -> torch.Tensor:
+        """The NHWC4 fp32 input of the stem, in one launch: resized, or warped by ``rec``, and normalised."""
+        if self.rec is None:
+            return ops.resize_u8_to_nhwc4(self.src.contiguous(), self.hw.contiguous(), lut, self.H, self.W)
+        return ops.augment_u8_to_nhwc4(self.src.contiguous(), self.rec.contiguous(), lut, self.H, self.W)
 
 
-class _SrcSupports(NamedTuple):
+class _SupportWindows(NamedTuple):
     """Support instances as windows of their source images on the way to ``_support_front`` (``spp_crop_to``): ``src``
     uint8 [n, capacity], instance i's image window [wh_i, ww_i, 3] at the start of row i; ``msk`` uint8 [n, mask capacity],
     its mask window; ``rec`` int32 [n,16], the records of ``fewshot_ds.support_geometry``; ``S`` the support size.  Stands
-    where the ``spp_imgs`` tensor stands; ``spp_isegmaps`` is None beside it (the kernel makes the masks)."""
-    src: torch.Tensor
-    msk: torch.Tensor
-    rec: torch.Tensor
-    S: int
-
-    @property
-    def shape(self) -> tuple:
-        return (self.src.shape[0], self.S, self.S, 3)
-
-    def to(self, dev, *a, **kw) -> '_SrcSupports':
-        return _SrcSupports(self.src.to(dev, non_blocking=True), self.msk.to(dev, non_blocking=True),
-                            self.rec.to(dev, non_blocking=True), self.S)
-
-
-class _AugSupports(NamedTuple):
-    """``_SrcSupports`` with an augmentation (``spp_augment`` / ``spp_photometric``): ``aug`` int32 [n,16], the records of
+    where the ``spp_imgs`` tensor stands; ``spp_isegmaps`` is None beside it (the kernel makes the masks).  With an
+    augmentation (``spp_augment`` / ``spp_photometric``): ``aug`` int32 [n,16], the records of
     ``fewshot_ds.query_augment_record`` at S -> S, and ``photo`` int32 [n,64], the records of
     ``fewshot_ds.query_photometric_record`` - or None where every instance's is neutral (no photometric launch)."""
     src: torch.Tensor
     msk: torch.Tensor
     rec: torch.Tensor
     S: int
-    aug: torch.Tensor
-    photo: Optional[torch.Tensor]
+    aug: Optional[torch.Tensor] = None
+    photo: Optional[torch.Tensor] = None
 
     @property
     def shape(self) -> tuple:
         return (self.src.shape[0], self.S, self.S, 3)
 
-    def to(self, dev, *a, **kw) -> '_AugSupports':
-        return _AugSupports(self.src.to(dev, non_blocking=True), self.msk.to(dev, non_blocking=True),
-                            self.rec.to(dev, non_blocking=True), self.S, self.aug.to(dev, non_blocking=True),
-                            None if self.photo is None else self.photo.to(dev, non_blocking=True))
+    def to(self, dev, *a, **kw) -> '_SupportWindows':
+        return _moved(self, dev)
+
+    def stem_input(self, lut: torch.Tensor) -> tuple:
+        """(the NHWC4 fp32 input of the stem, the masks uint8 [n,S,S]): crop, resize, pad and normalise in ONE launch,
+        which makes the masks too; with ``aug`` the cut as bytes, the photometric pass where an instance has one, the
+        gather."""
+        if self.aug is None:
+            return ops.support_from_source(self.src, self.msk, self.rec, lut, self.S)
+        crop, msk = ops.support_from_source_u8(self.src, self.msk, self.rec, self.S)
+        if self.photo is not None:
+            crop = ops.photometric_u8(crop.view(crop.shape[0], -1), self.photo).view(crop.shape)
+        return ops.support_augment(crop, msk, self.aug, lut, self.S)
 
 
 class _StemReady(NamedTuple):
-    """An image batch that already is the NHWC4 fp32 input of the stem (``ops.support_from_source`` makes it together
+    """An image batch that already is the NHWC4 fp32 input of the stem (``_SupportWindows.stem_input`` makes it together
     with the masks): ``_stem_input`` hands ``x`` through."""
     x: torch.Tensor
 
     @property
     def shape(self) -> tuple:
         return tuple(self.x.shape[:3]) + (3,)
+
+    def to(self, dev, *a, **kw) -> '_StemReady':
+        return self
+
+    def stem_input(self, lut: torch.Tensor) -> torch.Tensor:
+        return self.x
+
+
+class _InputForm(NamedTuple):
+    """The form in which one ``detect_device`` call brought its images: ``source``, the checked dict of
+    ``FGN._source_query`` (None: ``qry_img`` is a tensor); ``spp_source``, the checked dict of ``FGN._source_supports``
+    (None: ``spp_imgs`` is a tensor, or a support code stands in); ``at_source``, results at source size.  The one place
+    that names the slot tensors these forms travel in - ``qry_src`` uint8 [B, slot] with ``qry_src_hw`` int32 [B,2],
+    ``spp_src`` / ``spp_msk`` uint8 [B*N*K, slot] beside ``spp_rec`` - between ``_upload``, which fills them
+    (``_upload_source`` / ``_upload_supports``), the static buffers of a captured graph and the carriers of the stem."""
+    source: Optional[dict] = None
+    spp_source: Optional[dict] = None
+    at_source: bool = False
+
+    def slots(self) -> dict:
+        """name -> (rows, capacity) of the uint8 tensors whose rows have a configured capacity: a captured graph holds
+        them at that size, a batch fills the fronts of their rows."""
+        out = {}
+        if self.source is not None:
+            out['qry_src'] = (self.source['B'], self.source['capacity'])
+        if self.spp_source is not None:
+            out['spp_src'] = (self.spp_source['n'], self.spp_source['capacity'])
+            out['spp_msk'] = (self.spp_source['n'], self.spp_source['mcapacity'])
+        return out
+
+    def key(self, ins: dict) -> tuple:
+        """This form's part of a graph key, and the (name, shape, dtype) of every other tensor of ``ins``."""
+        q, s = self.source, self.spp_source
+        # source-size queries: the slot and the size they are resized to - NOT the source sizes, which the kernel
+        # reads from ``qry_src_hw`` (the slot tensors are in ``ins`` only once they are uploaded: keyed here)
+        # ... and whether the results are made at source size: another launch sequence (one batch-wide RLE launch
+        # that reads ``qry_src_hw``); a graph captured without it keeps its key
+        return (None if q is None else (q['B'], q['capacity'], q['hw']) + (('at_source',) if self.at_source else ()),) + \
+            (() if s is None else     # supports from their sources: the window slots and S, no size of a batch
+             (('spp_source', s['n'], s['capacity'], s['mcapacity'], s['S']),)) + \
+            tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items()
+                  if v is not None and k not in ('qry_src', 'qry_src_hw', 'spp_src', 'spp_msk'))
+
+    def query(self, t: dict):
+        """The query of a dict of tensors (the uploaded ``ins``, or the static buffers of a graph) as ``_stem_input``
+        takes it."""
+        if self.source is None:
+            return t.get('qry_img')
+        return _QueryPixels(t['qry_src'], t['qry_src_hw'], *self.source['hw'])
+
+    def supports(self, t: dict):
+        """Likewise the supports as ``_support_front`` takes them."""
+        if self.spp_source is None:
+            return t.get('spp_imgs')
+        return _SupportWindows(t['spp_src'], t['spp_msk'], t['spp_rec'], self.spp_source['S'])
 
 
 class FGN(torch.nn.Module):
@@ -923,12 +976,12 @@ class FGN(torch.nn.Module):
             self._input_lut_dev = (dev, torch.from_numpy(self.input_lut).to(dev))
         return self._input_lut_dev[1]
 
-    def _image_dims(self, img: Union[torch.Tensor, '_SrcQuery'], what: str, lead=(1,)) -> tuple:
+    def _image_dims(self, img: Union[torch.Tensor, '_QueryPixels'], what: str, lead=(1,)) -> tuple:
         """(leading dimensions, H, W) of an image tensor as given: channels-last pixels when it is uint8 and a table is
-        set (``set_input_norm``), NCHW otherwise; source-size pixels (``_SrcQuery``) count with the size they are resized
-        to.  ``lead``: the numbers of leading dimensions allowed."""
-        if isinstance(img, (_SrcQuery, _AugQuery)):
-            return (int(img.src.shape[0]),), img.H, img.W
+        set (``set_input_norm``), NCHW otherwise; source-size pixels (``_QueryPixels``) count with the size they are
+        resized to.  ``lead``: the numbers of leading dimensions allowed."""
+        if not isinstance(img, torch.Tensor):
+            return img.dims
         if self.input_lut is not None and img.dtype == torch.uint8:
             if img.dim() - 3 not in lead or img.shape[-1] != 3:
                 raise ValueError(f'{what}: with set_input_norm in effect a uint8 image tensor is channels-last pixels '
@@ -937,20 +990,14 @@ class FGN(torch.nn.Module):
             return tuple(img.shape[:-3]), int(img.shape[-3]), int(img.shape[-2])
         return tuple(img.shape[:-3]), int(img.shape[-2]), int(img.shape[-1])
 
-    def _stem_input(self, img: Union[torch.Tensor, '_SrcQuery']) -> torch.Tensor:
+    def _stem_input(self, img: Union[torch.Tensor, '_QueryPixels', '_StemReady']) -> torch.Tensor:
         """Image batch as given (host or device) -> the NHWC4 fp32 input of the stem on the current device: uint8 pixels
-        [n,H,W,3] through the normalisation table, source-size pixels (``_SrcQuery``) resized and normalised in one
+        [n,H,W,3] through the normalisation table, source-size pixels (``_QueryPixels``) resized and normalised in one
         kernel, a ready stem input (``_StemReady``: supports cut from their sources) as it is, anything else cast to fp32
         NCHW [n,3,H,W] and re-laid."""
         dev = torch.device('cuda', torch.cuda.current_device())
-        if isinstance(img, _StemReady):
-            return img.x
-        if isinstance(img, _SrcQuery):
-            img = img.to(dev)
-            return ops.resize_u8_to_nhwc4(img.src.contiguous(), img.hw.contiguous(), self._lut_on(dev), img.H, img.W)
-        if isinstance(img, _AugQuery):
-            img = img.to(dev)
-            return ops.augment_u8_to_nhwc4(img.src.contiguous(), img.rec.contiguous(), self._lut_on(dev), img.H, img.W)
+        if not isinstance(img, torch.Tensor):       # (a carrier answers for itself)
+            return img.to(dev).stem_input(self._lut_on(dev))
         if self.input_lut is not None and img.dtype == torch.uint8:
             self._image_dims(img, 'image')
             return ops.u8hwc3_to_nhwc4(img.to(dev, non_blocking=True).contiguous(), self._lut_on(dev))
@@ -962,7 +1009,7 @@ class FGN(torch.nn.Module):
         rows, ``img_shape`` (default (H, W, 3) per image) agrees with it, the masks are at their image's source size and
         every image fits the slot.  -> B, (H, W), the images as flat byte tensors, their sizes, the slot size in bytes
         per image and ``img_shape``."""
-        rt = np.asarray(qry_resize_to.cpu() if isinstance(qry_resize_to, torch.Tensor) else qry_resize_to)
+        rt = _host(qry_resize_to)
         ok = rt.dtype.kind in 'iuf' and (rt.shape == (2,) or (rt.ndim == 2 and rt.shape[1] == 2 and rt.shape[0] >= 1))
         if ok:
             rt = rt.reshape(-1, 2)
@@ -1020,16 +1067,14 @@ class FGN(torch.nn.Module):
         ``fewshot_ds.augment_plan`` - the boxes through the forward matrix, or, where a box leaves the image, the neutral
         record and the plain boxes (the fallback of base_fst.py:751-768)."""
         from . import fewshot_ds as fd
-        rows = qry_augment.detach().cpu().numpy() if isinstance(qry_augment, torch.Tensor) else np.asarray(qry_augment)
-        if rows.dtype.kind not in 'iuf' or rows.shape != (rs['B'], len(fd.AUG_PARAMS)):
-            raise ValueError(f'qry_augment must be [B,{len(fd.AUG_PARAMS)}] numbers {fd.AUG_PARAMS} for {rs["B"]} images, '
-                             f'got {rows.dtype} {list(rows.shape)}')
+        rows = _number_rows(qry_augment, ((rs['B'], len(fd.AUG_PARAMS)),),
+                            f'qry_augment must be [B,{len(fd.AUG_PARAMS)}] numbers {fd.AUG_PARAMS} for {rs["B"]} images')
         if qry_bboxes is None or len(qry_bboxes) != rs['B']:
             raise ValueError(f'qry_augment: qry_bboxes must hold the boxes of {rs["B"]} images')
         recs, boxes = [], []
         for row, b, hw in zip(rows, qry_bboxes, rs['sizes']):
             as_tensor = isinstance(b, torch.Tensor)
-            rec, nb = fd.augment_plan(row, b.detach().cpu().numpy() if as_tensor else np.asarray(b), hw, rs['hw'])
+            rec, nb = fd.augment_plan(row, _host(b), hw, rs['hw'])
             recs.append(rec)
             boxes.append(torch.from_numpy(nb) if as_tensor else nb)
         return torch.from_numpy(np.stack(recs)), boxes
@@ -1042,22 +1087,20 @@ class FGN(torch.nn.Module):
         An image whose geometric row fell back to the plain sample (``aug_recs``: a neutral record for a row that is
         not) gets the neutral record here too: ``bad_augment`` drops both halves (base_fst.py:751-768)."""
         from . import fewshot_ds as fd
-        rows = qry_photometric.detach().cpu().numpy() if isinstance(qry_photometric, torch.Tensor) \
-            else np.asarray(qry_photometric)
-        if rows.dtype.kind not in 'iuf' or rows.shape != (rs['B'], len(fd.PHOTO_PARAMS)):
-            raise ValueError(f'qry_photometric must be [B,{len(fd.PHOTO_PARAMS)}] numbers {fd.PHOTO_PARAMS} for '
-                             f'{rs["B"]} images, got {rows.dtype} {list(rows.shape)}')
+        rows = _number_rows(qry_photometric, ((rs['B'], len(fd.PHOTO_PARAMS)),),
+                            f'qry_photometric must be [B,{len(fd.PHOTO_PARAMS)}] numbers {fd.PHOTO_PARAMS} for '
+                            f'{rs["B"]} images')
         recs = np.stack([fd.query_photometric_record(row, hw, rs['hw']) for row, hw in zip(rows, rs['sizes'])])
         if qry_augment is not None:
-            geo = qry_augment.detach().cpu().numpy() if isinstance(qry_augment, torch.Tensor) else np.asarray(qry_augment)
-            for i, (g, hw) in enumerate(zip(geo, rs['sizes'])):
+            for i, (g, hw) in enumerate(zip(_host(qry_augment), rs['sizes'])):
                 if not fd.augment_is_neutral(fd.check_augment_params(g)) and not aug_recs[i, 2:6].any():
                     recs[i] = fd.query_photometric_record(None, hw, rs['hw'])
         return torch.from_numpy(recs) if recs[:, 2].any() else None
 
     @staticmethod
-    def _refuse_support_augment(spp_augment, spp_photometric) -> None:
-        for name, v in (('spp_augment', spp_augment), ('spp_photometric', spp_photometric)):
+    def _refuse_augment(**given) -> None:
+        """The test path takes none of the augmentation arguments (by keyword, refused in the order given)."""
+        for name, v in given.items():
             if v is not None:
                 raise ValueError(f'{name} is for forward_train: the test is without augmentation')
 
@@ -1076,11 +1119,10 @@ class FGN(torch.nn.Module):
             if v is None:
                 rows[name] = None
                 continue
-            a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
-            if a.dtype.kind not in 'iuf' or a.shape not in ((B, n // B, width),) + (((n, width),) if B == 1 else ()):
-                raise ValueError(f'{name} must be [B,N*K,{width}] numbers {fields} for {B} support set(s) of {n // B} '
-                                 f'instances ([N*K,{width}] for a single set), got {a.dtype} {list(a.shape)}')
-            rows[name] = a.reshape(n, width)
+            rows[name] = _number_rows(
+                v, ((B, n // B, width),) + (((n, width),) if B == 1 else ()),
+                f'{name} must be [B,N*K,{width}] numbers {fields} for {B} support set(s) of {n // B} instances '
+                f'([N*K,{width}] for a single set)').reshape(n, width)
         try:
             recs, precs, boxes, _ = fd.support_augment_plan(rows['spp_augment'], rows['spp_photometric'],
                                                             sp['boxes'].numpy().reshape(n, 4), S)
@@ -1115,40 +1157,43 @@ class FGN(torch.nn.Module):
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
             if spp_augment is not None or spp_photometric is not None:
                 sp = self._support_plans(spp_augment, spp_photometric, sp)
+        rs = recs = precs = None
         if qry_resize_to is not None:
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
             if qry_augment is not None:
                 recs, boxes = self._augment_plans(qry_augment, qry_bboxes, rs)
-            precs = None
             if qry_photometric is not None:
                 precs = self._photometric_records(qry_photometric, rs, qry_augment,
-                                                  recs.numpy() if qry_augment is not None else None)
-            if not torch.cuda.is_available():
-                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
-            dev = torch.device('cuda', torch.cuda.current_device())
-            qry_img = self._upload_source(rs, dev)
+                                                  None if recs is None else recs.numpy())
+        if rs is not None or sp is not None:
+            dev = self._gpu('forward_train')
+        if rs is not None:
+            qry_img = _InputForm(source=rs).query(self._upload_source(rs, dev))
             if precs is not None:                          # (all rows neutral after the fallback: no launch)
                 qry_img = qry_img._replace(src=ops.photometric_u8(qry_img.src, precs.to(dev, non_blocking=True)))
-            if qry_augment is None:
+            if recs is None:
                 qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
                 qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) for g in qry_isegmaps]
             else:
-                rec_dev = recs.to(dev, non_blocking=True)
-                qry_img = _AugQuery(qry_img.src, rec_dev, *rs['hw'])
+                qry_img = qry_img._replace(rec=recs.to(dev, non_blocking=True))
                 qry_bboxes = boxes
                 plain = [not bool(r[2:6].any()) for r in recs.numpy()]          # neutral, or fallen back
                 qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) if p else
-                                self._augmented_masks(g, rec_dev[i], rs['hw'], dev)
+                                self._augmented_masks(g, qry_img.rec[i], rs['hw'], dev)
                                 for i, (g, p) in enumerate(zip(qry_isegmaps, plain))]
             img_shape = rs['img_shape']
         if sp is not None:
-            if not torch.cuda.is_available():
-                raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
-            (spp_imgs, spp_bboxes), spp_isegmaps = \
-                self._supports_on_device(sp, torch.device('cuda', torch.cuda.current_device())), None
+            (spp_imgs, spp_bboxes), spp_isegmaps = self._supports_on_device(sp, dev), None
         return dict(qry_img=qry_img, qry_bboxes=qry_bboxes, qry_cat_ids=qry_cat_ids, qry_isegmaps=qry_isegmaps,
                     qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals, spp_imgs=spp_imgs, spp_bboxes=spp_bboxes,
                     spp_isegmaps=spp_isegmaps, img_shape=img_shape, **kwargs)
+
+    @staticmethod
+    def _gpu(entry: str) -> torch.device:
+        """The current device of an entry point that is about to queue work (every contract error comes before)."""
+        if not torch.cuda.is_available():
+            raise ops._lib.FgnHipError(f'FGN.{entry} needs a GPU: the HIP path has no CPU fallback')
+        return torch.device('cuda', torch.cuda.current_device())
 
     @staticmethod
     def _scaled_boxes(qry_bboxes, sizes, hw):
@@ -1161,10 +1206,9 @@ class FGN(torch.nn.Module):
         for b, (h, w) in zip(qry_bboxes, sizes):
             if (h, w) == tuple(hw) or b is None:
                 out.append(b)
-            elif isinstance(b, torch.Tensor):
-                out.append(torch.from_numpy(scale_boxes_yxyx(b.detach().cpu().numpy(), h, w, *hw)))
             else:
-                out.append(scale_boxes_yxyx(np.asarray(b), h, w, *hw))
+                nb = scale_boxes_yxyx(_host(b), h, w, *hw)
+                out.append(torch.from_numpy(nb) if isinstance(b, torch.Tensor) else nb)
         return out
 
     def _source_supports(self, spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio: float = 0.8,
@@ -1194,15 +1238,14 @@ class FGN(torch.nn.Module):
         B = len(groups)
         if len(spp_isegmaps) != len(spp_imgs) or any(len(g[0]) != NK or len(g[1]) != NK for g in groups):
             raise ValueError(f'spp_imgs / spp_isegmaps: every support set holds N*K = {NK} images and as many masks')
-        host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-        bb = host(spp_bboxes)
+        bb = _host(spp_bboxes)
         if bb.size != B * NK * 4 or bb.shape[-1] != 4:
             raise ValueError(f'spp_bboxes: with spp_crop_to, [..,{NK},4] YXYX in the source frame for {B} support '
                              f'set(s), got {list(bb.shape)}')
         bb = bb.reshape(B * NK, 4)
         recs, boxes, wins = [], [], []
         for i, (im, mk) in enumerate((im, mk) for g in groups for im, mk in zip(*g)):
-            im, mk = host(im), host(mk)
+            im, mk = _host(im), _host(mk)
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise ValueError(f'spp_imgs: with spp_crop_to every image is channels-last uint8 pixels [h,w,3], got '
                                  f'{im.dtype} {list(im.shape)}')
@@ -1226,33 +1269,33 @@ class FGN(torch.nn.Module):
                     mflats=[torch.from_numpy(m.reshape(-1)) for _, m in wins], need=need, mneed=mneed,
                     capacity=capacity, mcapacity=mcapacity, window_bytes=int(sum(w.size + m.size for w, m in wins)))
 
-    def _upload_supports(self, sp: dict, dev, into: Optional[dict] = None) -> tuple:
+    @staticmethod
+    def _slot_rows(flats: list, width: int, capacity: int, dev, slot: Optional[torch.Tensor]) -> torch.Tensor:
+        """Flat byte tensors into the fronts of the rows of ``slot`` (a static slot of a captured graph) when that is
+        given at [len(flats), capacity], else of a fresh buffer ``width`` wide, on the current stream."""
+        if slot is None or tuple(slot.shape) != (len(flats), capacity):
+            slot = torch.empty((len(flats), width), dtype=torch.uint8, device=dev)
+        for i, flat in enumerate(flats):
+            slot[i, :flat.numel()].copy_(flat, non_blocking=True)
+        return slot
+
+    def _upload_supports(self, sp: dict, dev, into: Optional[dict] = None) -> dict:
         """The windows of ``_source_supports`` on the device, on the current stream: wh_i * ww_i * 3 image bytes and
         wh_i * ww_i mask bytes of instance i into row i of ``into['spp_src']`` / ``into['spp_msk']`` (the static slots of
         a captured graph) when those are given, else of fresh buffers as wide as the largest window of the batch - only
-        the window bytes cross the bus, and what lies behind a window in its row is never read."""
-        out = []
-        for k, flats, width, cap in (('spp_src', sp['flats'], sp['need'], sp['capacity']),
-                                     ('spp_msk', sp['mflats'], sp['mneed'], sp['mcapacity'])):
-            dst = None if into is None else into.get(k)
-            if dst is None or tuple(dst.shape) != (sp['n'], cap):
-                dst = torch.empty((sp['n'], width), dtype=torch.uint8, device=dev)
-            for i, flat in enumerate(flats):
-                dst[i, :flat.numel()].copy_(flat, non_blocking=True)
-            out.append(dst)
-        return tuple(out)
+        the window bytes cross the bus, and what lies behind a window in its row is never read.  -> the two by name."""
+        into = into or {}
+        return {'spp_src': self._slot_rows(sp['flats'], sp['need'], sp['capacity'], dev, into.get('spp_src')),
+                'spp_msk': self._slot_rows(sp['mflats'], sp['mneed'], sp['mcapacity'], dev, into.get('spp_msk'))}
 
     def _supports_on_device(self, sp: dict, dev) -> tuple:
-        """``_source_supports`` uploaded on the current stream, in the form ``_support_front`` takes: (``_SrcSupports``,
-        the boxes)."""
-        src, msk = self._upload_supports(sp, dev)
-        rec = sp['rec'].to(dev, non_blocking=True)
-        if sp.get('aug') is None:           # (no augmentation, or every instance neutral after the fallback)
-            return _SrcSupports(src, msk, rec, sp['S']), sp['boxes']
-        return _AugSupports(src, msk, rec, sp['S'], sp['aug'], sp['photo']).to(dev), sp['boxes']
+        """``_source_supports`` uploaded on the current stream, in the form ``_support_front`` takes:
+        (``_SupportWindows``, the boxes) - with the records of ``_support_plans`` where an instance is augmented."""
+        s = _InputForm(spp_source=sp).supports(dict(self._upload_supports(sp, dev), spp_rec=sp['rec']))
+        return s._replace(aug=sp.get('aug'), photo=sp.get('photo')).to(dev), sp['boxes']
 
     # --- stages ---------------------------------------------------------------------------
-    def extract_feat(self, img: Union[torch.Tensor, '_SrcQuery']) -> torch.Tensor:
+    def extract_feat(self, img: Union[torch.Tensor, '_QueryPixels']) -> torch.Tensor:
         """ResNet-50 stages 1-3 (fgn.py:67-77): NCHW fp32 (or uint8 pixels, ``set_input_norm``) in, NHWC [B,h,w,1024]
         out."""
         P = self._P
@@ -1268,7 +1311,7 @@ class FGN(torch.nn.Module):
                 x = blk(x)
         return x
 
-    def extract_feat_pair(self, qry: Union[torch.Tensor, '_SrcQuery'], spp: torch.Tensor, phase_counter=None):
+    def extract_feat_pair(self, qry: Union[torch.Tensor, '_QueryPixels'], spp: torch.Tensor, phase_counter=None):
         """Both backbone passes of an episode (fgn.py:212-215) through SHARED launches wherever a layer does not look at
         the spatial structure (``use_merged_backbone``; frozen-BN bottleneck backbones only)."""
         P = self._P
@@ -1384,11 +1427,8 @@ class FGN(torch.nn.Module):
         source frame - and crop, bicubic resize and centre pad of ``BaseFewShotISEG.get_support`` (base_fst.py:1043-1167)
         run on the device in one launch (``fewshot_ds.support_from_source`` bit for bit); only the window
         of each image that its crop reads is uploaded; needs ``set_input_norm``."""
-        if qry_augment is not None:
-            raise ValueError('qry_augment is for forward_train: the test is without augmentation')
-        if qry_photometric is not None:
-            raise ValueError('qry_photometric is for forward_train: the test is without augmentation')
-        self._refuse_support_augment(spp_augment, spp_photometric)
+        self._refuse_augment(qry_augment=qry_augment, qry_photometric=qry_photometric, spp_augment=spp_augment,
+                             spp_photometric=spp_photometric)
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
         sp = None
@@ -1418,21 +1458,16 @@ class FGN(torch.nn.Module):
         """modify_input for the supports (fgn.py:79-108: H2D, YXYX -> XYXY on private copies), their
         backbone pass and the AG-RPN class vectors."""
         N, K = self.n_ways, self.k_shots
-        if not isinstance(spp_imgs, (_SrcSupports, _AugSupports)):
+        windows = isinstance(spp_imgs, _SupportWindows)         # windows of the source images (``spp_crop_to``)
+        if not windows:
             self._image_dims(spp_imgs, 'spp_imgs', lead=(1, 2))
         b = spp_bboxes.to(dev, torch.float32, non_blocking=True).reshape(B * N * K, 4)
         spp_xyxy = torch.stack((b[:, 1], b[:, 0], b[:, 3], b[:, 2]), 1)      # no host-built index tensor: graph-capturable
-        if isinstance(spp_imgs, (_SrcSupports, _AugSupports)):  # windows of the source images (``spp_crop_to``): crop,
-            s = spp_imgs.to(dev)                    # resize, pad and normalise in ONE launch, which makes the masks too
+        if windows:
+            s = spp_imgs.to(dev)
             if s.src.shape[0] != B * N * K:
                 raise ValueError(f'{s.src.shape[0]} support instances for a batch of {B} x {N} x {K}')
-            if isinstance(s, _AugSupports):         # (``spp_augment``: the cut as bytes, the photometric pass where an
-                crop, msk = ops.support_from_source_u8(s.src, s.msk, s.rec, s.S)        # instance has one, the gather)
-                if s.photo is not None:
-                    crop = ops.photometric_u8(crop.view(crop.shape[0], -1), s.photo).view(crop.shape)
-                y, spp_masks = ops.support_augment(crop, msk, s.aug, self._lut_on(dev), s.S)
-            else:
-                y, spp_masks = ops.support_from_source(s.src, s.msk, s.rec, self._lut_on(dev), s.S)
+            y, spp_masks = s.stem_input(self._lut_on(dev))
             spp = _StemReady(y)
         else:
             spp = spp_imgs.to(dev, non_blocking=True).reshape(B * N * K, *spp_imgs.shape[-3:])    # (dtype: _stem_input)
@@ -1450,31 +1485,28 @@ class FGN(torch.nn.Module):
     def _support_back(self, sc: dict, B, dev, shared=None) -> None:
         """count_spp (fgn_roi_head.py:419-449) and the support half of the relation conv.  ``shared``: the shared-head
         callable (forward_train passes the train-mode BatchNorm variant)."""
-        P, rh = self._P, self.cfg['roi_head']
-        N, K, PS = self.n_ways, self.k_shots, rh['roi_out_size']
-        bidx = torch.arange(B * N * K, device=dev, dtype=torch.float32)[:, None]
+        sfeat = self._support_pool(sc, B, dev)
+        self._support_finish(sc, self._shared_head(sfeat) if shared is None else shared(sfeat), B)
+
+    def _support_pool(self, sc: dict, B, dev, out=None) -> torch.Tensor:
+        """The support RoIs (image index | XYXY), the masks pooled on them (``sc['masks7']``) and the support maps pooled
+        on them (into ``out`` when given)."""
+        rh = self.cfg['roi_head']
+        bidx = torch.arange(B * self.n_ways * self.k_shots, device=dev, dtype=torch.float32)[:, None]
         spp_rois = torch.cat([bidx, sc['spp_xyxy']], 1).contiguous()
-        sc['masks7'] = ops.roi_align_mask(sc['spp_masks'], spp_rois, PS, 1.0, -1, False)
+        sc['masks7'] = ops.roi_align_mask(sc['spp_masks'], spp_rois, rh['roi_out_size'], 1.0, -1, False)
         # `spp_bboxes /= 16` then roi_align(scale=1) == roi_align(scale=1/16): /16 is exact in fp32
-        sfeat = ops.roi_align(sc['spp_fmaps'], spp_rois, PS, 1.0 / rh['featmap_stride'], -1, False)
-        sfeat = self._shared_head(sfeat) if shared is None else shared(sfeat)
-        sc['cat_mean'] = ops.support_kmean(sfeat, B * N, K)                           # [B*N,7,7,C]
-        sc['cat_mean_mp'] = ops.support_class_vectors(sfeat, sc['masks7'], B * N, K)  # [B*N,C]
-        sc['S'] = ops.conv2d(sc['cat_mean'], P['rel_s'])                              # Ws*support + bias
+        return ops.roi_align(sc['spp_fmaps'], spp_rois, rh['roi_out_size'], 1.0 / rh['featmap_stride'], -1, False,
+                             out=out)
 
     def _support_rois(self, sc: dict, B, dev, x_out, y1_out) -> None:
         """First half of count_spp for the MERGED shared head: the support masks and maps are pooled (into the first rows
         of the RoI batch the box head will run, ``x_out``), and - the first 1x1 conv of the shared head being taken on
         the feature map for the query's RoIs - the same conv on the pooled support features fills their rows of
         ``y1_out``."""
-        P, rh = self._P, self.cfg['roi_head']
-        N, K, PS = self.n_ways, self.k_shots, rh['roi_out_size']
-        bidx = torch.arange(B * N * K, device=dev, dtype=torch.float32)[:, None]
-        spp_rois = torch.cat([bidx, sc['spp_xyxy']], 1).contiguous()
-        sc['masks7'] = ops.roi_align_mask(sc['spp_masks'], spp_rois, PS, 1.0, -1, False)
-        ops.roi_align(sc['spp_fmaps'], spp_rois, PS, 1.0 / rh['featmap_stride'], -1, False, out=x_out)
+        self._support_pool(sc, B, dev, out=x_out)
         if y1_out is not None:
-            ops.conv2d(x_out, P['shared'][0].conv1, out=y1_out)
+            ops.conv2d(x_out, self._P['shared'][0].conv1, out=y1_out)
 
     def _support_finish(self, sc: dict, sfeat, B) -> None:
         """Second half of count_spp (fgn_roi_head.py:439-447) + the support half of the relation conv, on the support
@@ -1494,13 +1526,11 @@ class FGN(torch.nn.Module):
         shares the support set (the reference recomputes it per query, fgn.py:212-215; results
         are identical).  ``spp_crop_to``: the supports come as their source images, as for ``simple_test``.
         ``spp_augment`` / ``spp_photometric`` are refused: the test path is without augmentation."""
-        self._refuse_support_augment(spp_augment, spp_photometric)
+        self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric)
         sp = None
         if spp_crop_to is not None:
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
-        if not torch.cuda.is_available():
-            raise ops._lib.FgnHipError('FGN.encode_supports needs a GPU: the HIP path has no CPU fallback')
-        dev = torch.device('cuda', torch.cuda.current_device())
+        dev = self._gpu('encode_supports')
         if self._packed_device != dev:
             self._pack(dev)
         self._sync_trained_shared()
@@ -1555,23 +1585,20 @@ class FGN(torch.nn.Module):
         self.transfer_mode = int(mode)
         return self._stream_for('upload', torch.cuda.current_stream())
 
-    def _upload_source(self, rs: dict, dev, into: Optional[dict] = None) -> '_SrcQuery':
+    def _upload_source(self, rs: dict, dev, into: Optional[dict] = None) -> dict:
         """The source pixels of ``_source_query`` on the device, on the current stream: h_i * w_i * 3 bytes per image
         into row i of ``into['qry_src']`` (the [B, capacity] static slot of a captured graph) when that is given, else of
         a fresh buffer as wide as the largest image of the batch - what lies behind an image in its row is never read -
-        and the sizes as int32 [B,2]."""
-        dst = None if into is None else into.get('qry_src')
-        if dst is None or tuple(dst.shape) != (rs['B'], rs['capacity']):
-            dst = torch.empty((rs['B'], rs['need']), dtype=torch.uint8, device=dev)
-        for i, flat in enumerate(rs['flats']):
-            dst[i, :flat.numel()].copy_(flat, non_blocking=True)
+        and the sizes as int32 [B,2].  -> the two by name."""
+        into = into or {}
+        src = self._slot_rows(rs['flats'], rs['need'], rs['capacity'], dev, into.get('qry_src'))
         hw = torch.tensor(rs['sizes'], dtype=torch.int32).reshape(-1, 2)
-        dhw = None if into is None else into.get('qry_src_hw')
+        dhw = into.get('qry_src_hw')
         if dhw is not None and tuple(dhw.shape) == tuple(hw.shape):
             dhw.copy_(hw, non_blocking=True)
         else:
             dhw = hw.to(dev, non_blocking=True)
-        return _SrcQuery(dst, dhw, *rs['hw'])
+        return {'qry_src': src, 'qry_src_hw': dhw}
 
     @staticmethod
     def _device_masks(g, dev) -> torch.Tensor:
@@ -1597,8 +1624,7 @@ class FGN(torch.nn.Module):
         return ops.augment_masks(FGN._device_masks(g, dev), rec, *hw)
 
     def _upload(self, tensors: dict, gt_masks, dev, main, into: Optional[dict] = None,
-                bits_out: Optional[list] = None, source: Optional[dict] = None, resize_masks: bool = True,
-                spp_source: Optional[dict] = None):
+                bits_out: Optional[list] = None, form: _InputForm = _InputForm()):
         """``modify_input`` (fgn.py:79-108): host -> device copies of one batch, on an upload stream so that they
         overlap the previous batch's kernels (a pinned source makes them asynchronous); the compute streams wait
         on one event.  Tensors already on the device pass through.  The ground-truth masks (copied to the GPU by
@@ -1608,11 +1634,12 @@ class FGN(torch.nn.Module):
         stream itself and so ordered behind the previous replay that reads them) instead of fresh allocations.
         ``bits_out`` (``match_on_device``): a list that receives, per image, the bit planes of its ground-truth masks
         (``ops.mask_bits`` on the device copy made for the RLE, right behind it on the upload stream; None for an image
-        without ground truth).  ``source`` (``_source_query``): the query comes at source size - its pixels go up as
+        without ground truth).  ``form.source`` (``_source_query``): the query comes at source size - its pixels go up as
         ``qry_src`` / ``qry_src_hw`` (``_upload_source``) and the masks are resized right behind their upload - unless
-        ``resize_masks`` is off (``results_at_source``): then they are encoded and bit-packed at source size, as given.
-        ``spp_source`` (``_source_supports``): the supports come as windows of their source images - the windows go
+        ``form.at_source`` (``results_at_source``): then they are encoded and bit-packed at source size, as given.
+        ``form.spp_source`` (``_source_supports``): the supports come as windows of their source images - the windows go
         up as the rows of ``spp_src`` / ``spp_msk`` (``_upload_supports``; records and boxes travel in ``tensors``)."""
+        source, spp_source = form.source, form.spp_source
         gts = None
         if gt_masks is not None:
             gts = [g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
@@ -1634,14 +1661,13 @@ class FGN(torch.nn.Module):
                 else:
                     out[k] = None if t is None else t.to(dev, non_blocking=True)
             if source is not None:
-                sq = self._upload_source(source, dev, into)
-                out['qry_src'], out['qry_src_hw'] = sq.src, sq.hw
+                out.update(self._upload_source(source, dev, into))
             if spp_source is not None:
-                out['spp_src'], out['spp_msk'] = self._upload_supports(spp_source, dev, into)
+                out.update(self._upload_supports(spp_source, dev, into))
             if gts is not None:
                 gt_out = []
                 for g in gts:
-                    g = self._resized_masks(g, source['hw'] if (source and resize_masks) else None, dev)
+                    g = self._resized_masks(g, source['hw'] if (source and not form.at_source) else None, dev)
                     gt_out.append(ops.dense_mask_rle(g, packed=True))
                     if bits_out is not None:
                         bits_out.append(ops.mask_bits(g) if g.shape[0] else None)
@@ -1678,7 +1704,7 @@ class FGN(torch.nn.Module):
         size and S, not by any source, window or crop size.  (``simple_test`` hands over the dict of
         ``_source_supports``.)  Ignored beside ``support_code``.  ``spp_augment`` / ``spp_photometric`` are refused: the
         test path is without augmentation."""
-        self._refuse_support_augment(spp_augment, spp_photometric)
+        self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric)
         graphed = self._graphed()
         source = spp_source = None
         if spp_crop_to is not None and support_code is None:
@@ -1692,9 +1718,8 @@ class FGN(torch.nn.Module):
             source = qry_resize_to if isinstance(qry_resize_to, dict) else \
                 self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps, graphed)
             img_shape = source['img_shape']
-        if not torch.cuda.is_available():
-            raise ops._lib.FgnHipError('FGN.simple_test needs a GPU: the HIP path has no CPU fallback')
-        dev = torch.device('cuda', torch.cuda.current_device())
+        form = _InputForm(source, spp_source, results_at_source)
+        dev = self._gpu('simple_test')
         main = torch.cuda.current_stream()
         if source is None:
             self._image_dims(qry_img, 'qry_img')          # (a wrong uint8 layout is refused before anything is queued)
@@ -1710,24 +1735,21 @@ class FGN(torch.nn.Module):
             phase_counter = self.phase_counter
         # graph replay with the transfers on the caller stream: host tensors go straight into the graph's static input
         # buffers (the caller stream orders the copy behind the previous replay that reads them) - no device-to-device hop
-        into = None
-        if graphed and self.use_packed_transfers and self._stream_for('upload', main) is main:
-            ge0 = self._graphs.get(self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source,
-                                                   results_at_source, spp_source))
-            into = ge0.static if ge0 is not None else None
+        # (the key is taken once, ahead of the upload: that adds the slot tensors, which the key leaves out, and moves the
+        # others to the device at their shapes and dtypes)
+        into = key = None
+        if graphed:
+            key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, form)
+            if self.use_packed_transfers and self._stream_for('upload', main) is main and key in self._graphs:
+                into = self._graphs[key].static
         gt_bits = [] if (self.match_on_device and qry_isegmaps is not None) else None
-        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits, source=source,
-                                             resize_masks=not results_at_source, spp_source=spp_source)
+        ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits, form=form)
         if uploaded is not None:
             main.wait_event(uploaded)
         if graphed:
-            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter, source, results_at_source,
-                                            spp_source)
+            ge, outs = self._detect_graphed(ins, img_shape, support_code, phase_counter, form, key)
         else:
-            qry = ins['qry_img'] if source is None else _SrcQuery(ins['qry_src'], ins['qry_src_hw'], *source['hw'])
-            spp = ins.get('spp_imgs') if spp_source is None else \
-                _SrcSupports(ins['spp_src'], ins['spp_msk'], ins['spp_rec'], spp_source['S'])
-            outs = self._detect_eager(qry, spp, ins.get('spp_bboxes'),
+            outs = self._detect_eager(form.query(ins), form.supports(ins), ins.get('spp_bboxes'),
                                       ins.get('spp_isegmaps'), img_shape, support_code, phase_counter=phase_counter,
                                       results_at_source=results_at_source)
         if results_at_source:
@@ -1759,8 +1781,8 @@ class FGN(torch.nn.Module):
     def _graphed(self) -> bool:
         return bool(self.use_graphs and self.debug_trace is None and ops.PROFILE is None)
 
-    def _graph_key(self, ins: dict, img_shape, support_code, phase_counter, main, dev, source=None,
-                   results_at_source: bool = False, spp_source=None) -> tuple:
+    def _graph_key(self, ins: dict, img_shape, support_code, phase_counter, main, dev,
+                   form: _InputForm = _InputForm()) -> tuple:
         hw = tuple((int(s[0]), int(s[1])) for s in img_shape)
         # everything the captured launch sequence depends on besides the weights (those drop ``_graphs`` when they
         # change): the paste semantic is an argument of the captured RLE kernel, the transfer arrangement decides which
@@ -1769,29 +1791,16 @@ class FGN(torch.nn.Module):
         mark = None if (phase_counter is None or not self.phase_point) else (phase_counter.data_ptr(), self.phase_point)
         return (main.cuda_stream, dev.index, hw, support_code is not None, bool(self.use_merged_backbone),
                 bool(self.use_merged_support_head), self.paste_semantics, int(self.transfer_mode), mark,
-                bool(self.use_side_stream), bool(self.use_packed_transfers),
-                # source-size queries: the slot and the size they are resized to - NOT the source sizes, which the kernel
-                # reads from ``qry_src_hw`` (the slot tensors are in ``ins`` only once they are uploaded: keyed here)
-                # ... and whether the results are made at source size: another launch sequence (one batch-wide RLE launch
-                # that reads ``qry_src_hw``); a graph captured without it keeps its key
-                None if source is None else (source['B'], source['capacity'], source['hw']) +
-                (('at_source',) if results_at_source else ())) + \
-            (() if spp_source is None else     # supports from their sources: the window slots and S, no size of a batch
-             (('spp_source', spp_source['n'], spp_source['capacity'], spp_source['mcapacity'], spp_source['S']),)) + \
-            tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items()
-                  if v is not None and k not in ('qry_src', 'qry_src_hw', 'spp_src', 'spp_msk'))
+                bool(self.use_side_stream), bool(self.use_packed_transfers)) + form.key(ins)
 
-    def _detect_graphed(self, ins: dict, img_shape, support_code, phase_counter=None, source=None,
-                        results_at_source: bool = False, spp_source=None):
-        main = torch.cuda.current_stream()
-        dev = torch.device('cuda', torch.cuda.current_device())
-        key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, source, results_at_source,
-                              spp_source)
+    def _detect_graphed(self, ins: dict, img_shape, support_code, phase_counter, form: _InputForm, key: tuple):
+        """Replay the graph of ``key`` (``_graph_key``, taken by ``detect_device``), capturing it first where this is
+        the first call of its kind."""
         ge = self._graphs.get(key)
         if ge is None:
-            ge = self._graphs[key] = _GraphedEpisode(self, ins, img_shape, support_code, dev, phase_counter, source,
-                                                     results_at_source, spp_source)
-        return ge, ge.run(self, ins, support_code, main)
+            dev = torch.device('cuda', torch.cuda.current_device())
+            ge = self._graphs[key] = _GraphedEpisode(self, ins, img_shape, support_code, dev, phase_counter, form)
+        return ge, ge.run(self, ins, support_code, torch.cuda.current_stream())
 
     def _detect_eager(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
                       phase_counter=None, results_at_source: bool = False) -> list:
@@ -1997,7 +2006,7 @@ class FGN(torch.nn.Module):
         if results_at_source:
             # results at source size: ONE launch for the batch, the images' sizes read from ``qry_src_hw``
             # on the device - the launch is the same for every source size, so a captured graph serves them all
-            if not isinstance(qry, _SrcQuery):
+            if getattr(qry, 'hw', None) is None:
                 raise ValueError('results_at_source needs a source-size query (qry_resize_to)')
             if tr is not None:                  # (a trace is never captured: the host may read the sizes)
                 src_boxes = torch.empty((B * D, 4), device=dev, dtype=torch.float32)

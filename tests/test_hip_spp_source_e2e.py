@@ -228,8 +228,10 @@ def test_pinned_inputs_go_straight_into_the_static_slots(env):
     # the upload itself: the static tensors come back, holding the other support set
     dev, main = torch.device('cuda', torch.cuda.current_device()), torch.cuda.current_stream()
     sp1 = m._source_supports(b1['spp_imgs'], b1['spp_bboxes'], b1['spp_isegmaps'], SPP, graphed=True)
+    from fgn_amd.detector import _InputForm
     out, _, _ = m._upload({'qry_img': b1['qry_img'], 'spp_bboxes': sp1['boxes'].pin_memory(),
-                           'spp_rec': sp1['rec'].pin_memory()}, None, dev, main, into=ge.static, spp_source=sp1)
+                           'spp_rec': sp1['rec'].pin_memory()}, None, dev, main, into=ge.static,
+                          form=_InputForm(spp_source=sp1))
     for k in ('qry_img', 'spp_bboxes', 'spp_rec', 'spp_src', 'spp_msk'):
         assert out[k] is ge.static[k], k
     torch.cuda.synchronize()

@@ -180,7 +180,9 @@ def test_pinned_source_pixels_go_straight_into_the_static_slot(env):
     # the upload itself: the static tensors come back, holding the other batch
     dev, main = torch.device('cuda', torch.cuda.current_device()), torch.cuda.current_stream()
     source = m._source_query(b1['qry_img'], b1['qry_resize_to'], None, graphed=True)
-    out, _, _ = m._upload({'spp_imgs': b1['spp_imgs']}, None, dev, main, into=ge.static, source=source)
+    from fgn_amd.detector import _InputForm
+    out, _, _ = m._upload({'spp_imgs': b1['spp_imgs']}, None, dev, main, into=ge.static,
+                          form=_InputForm(source=source))
     assert out['qry_src'] is ge.static['qry_src'] and out['qry_src_hw'] is ge.static['qry_src_hw']
     torch.cuda.synchronize()
     assert torch.equal(ge.static['qry_src'][0, :64 * 160 * 3].cpu(), b1['qry_img'].reshape(-1))

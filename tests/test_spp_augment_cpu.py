@@ -273,7 +273,7 @@ def test_every_contract_error_is_raised_with_no_gpu_present():
 
 
 def test_the_plan_of_the_detector_and_its_carrier():
-    from fgn_amd.detector import FGN, _AugSupports, _SrcSupports
+    from fgn_amd.detector import FGN, _SupportWindows
     m = _model()
     S, NK = 32, 3
     rs = np.random.RandomState(1)
@@ -298,10 +298,12 @@ def test_the_plan_of_the_detector_and_its_carrier():
                                                            np.array([(0, 0, 0), (1, 1, 3), (6, 0, 0)], np.float64))):
         out = FGN._support_plans(g, p, sp)
         assert 'aug' not in out and 'photo' not in out and torch.equal(out['boxes'], sp['boxes'])
-    assert _AugSupports._fields == _SrcSupports._fields + ('aug', 'photo')
-    a = _AugSupports(torch.zeros((3, 8), dtype=torch.uint8), torch.zeros((3, 4), dtype=torch.uint8), sp['rec'], S,
-                     torch.from_numpy(want[0]), None)
+    assert _SupportWindows._fields == ('src', 'msk', 'rec', 'S', 'aug', 'photo')
+    assert _SupportWindows._field_defaults == dict(aug=None, photo=None)
+    src, msk = torch.zeros((3, 8), dtype=torch.uint8), torch.zeros((3, 4), dtype=torch.uint8)
+    a = _SupportWindows(src, msk, sp['rec'], S, torch.from_numpy(want[0]), None)
     assert a.shape == (3, S, S, 3) and a.to('cpu').photo is None
+    assert _SupportWindows(src, msk, sp['rec'], S) == _SupportWindows(src, msk, sp['rec'], S, None, None)
 
 
 def test_header_and_signatures_agree_on_the_two_entries_and_the_abi_stays_33():
