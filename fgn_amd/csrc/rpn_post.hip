@@ -335,8 +335,11 @@ __global__ __launch_bounds__(POST_THREADS) void rpn_proposals_kernel(const Propo
         RPN_STAMP(4);
 
         // ---- 3. decode (delta2bbox), min-size filter, order-preserving compaction --------------
-        float4* out_boxes = p.sorted_boxes + (size_t)b * cap;
-        float* out_scores = p.sorted_scores + (size_t)b * cap;
+        // image b owns [b * p.cap, (b + 1) * p.cap) of the scratch on BOTH attempts (the fast one fills at most
+        // RPN_FAST_CAP <= p.cap of it): with the fast attempt's own cap as the pitch, image b's attempt 0 lay inside the
+        // range another image's attempt 1 was sorting into (tests/test_hip_sel_routes.py, the shared-scratch batch)
+        float4* out_boxes = p.sorted_boxes + (size_t)b * p.cap;
+        float* out_scores = p.sorted_scores + (size_t)b * p.cap;
         const int per_thread = cap / POST_THREADS > 0 ? cap / POST_THREADS : 1;
         const int i0 = t * per_thread;
         float4 bx[8];

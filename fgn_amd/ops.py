@@ -1479,9 +1479,13 @@ def rpn_merge(head: torch.Tensor, batch: int, n_ways: int, n_anchors: int):
 
 def rpn_proposals(scores: torch.Tensor, deltas: torch.Tensor, anchors_base: torch.Tensor, feat_h: int, feat_w: int,
                   stride: int, img_h: int, img_w: int, means, stds, nms_pre: int, min_bbox_size: float,
-                  iou_thr: float, max_per_img: int, debug_topk: bool = False, with_rois: bool = False):
+                  iou_thr: float, max_per_img: int, debug_topk: bool = False, with_rois: bool = False,
+                  with_info: bool = False):
     """-> proposals [B,max_per_img,5] (x1,y1,x2,y2,score), n_props [B] int32 (+ with_rois: the same boxes as
-    [B*max_per_img,5] RoIs (image index, box) = bbox2roi, fgn_roi_head.py:556)."""
+    [B*max_per_img,5] RoIs (image index, box) = bbox2roi, fgn_roi_head.py:556; + with_info, last: the [B,8] int32
+    info words of the multi-workgroup pre-selection - b1, count before b1, b2, candidate count, ok flag, finished by
+    rpn_matrix_nms_kernel - all zero when the pre-selection is not launched; like debug_topk it keeps the call off the
+    training-size route, which has no such words)."""
     _chk(scores, 'scores')
     _chk(deltas, 'deltas')
     _chk(anchors_base, 'anchors_base')
@@ -1494,7 +1498,7 @@ def rpn_proposals(scores: torch.Tensor, deltas: torch.Tensor, anchors_base: torc
     rois = torch.empty((batch * max_per_img, 5), device=scores.device, dtype=torch.float32)   # bbox2roi of the proposals
     n_props = zeros((batch,), scores.device, torch.int32)
     n_sel = nms_pre if 0 < nms_pre < n_total else n_total
-    if (n_sel > 8192 or max_per_img > 1024) and not debug_topk:
+    if (n_sel > 8192 or max_per_img > 1024) and not (debug_topk or with_info):
         # training sizes (train_cfg.rpn_proposal: 12000 -> 2000): the ranking runs as a global sort over many workgroups
         scratch = torch.empty(L.fgn_rpn_proposals_large_scratch_bytes(batch, n_total, nms_pre), device=scores.device,
                               dtype=torch.uint8)
@@ -1517,11 +1521,15 @@ def rpn_proposals(scores: torch.Tensor, deltas: torch.Tensor, anchors_base: torc
                                  float(img_w), _f4(means), _f4(stds), MAX_RATIO, nms_pre, float(min_bbox_size),
                                  float(iou_thr), max_per_img, _stream())
     _lib.check(rc, 'fgn_rpn_proposals_f32')
+    out = (props, n_props)
     if debug_topk:
-        return props, n_props, dbg
-    if with_rois:
-        return props, n_props, rois
-    return props, n_props
+        out += (dbg,)
+    elif with_rois:
+        out += (rois,)
+    if with_info:
+        # (fgn_rpn_proposals_f32 lays the workspace out as hist1 [B][4096] | hist2 [B][4096] | info [B][8] | counter [B])
+        out += (pre_zeroed[batch * 2 * 4096 * 4:batch * (2 * 4096 * 4 + 32)].view(torch.int32).view(batch, 8),)
+    return out
 
 
 def det_post(rois: torch.Tensor, cls_raw: torch.Tensor, reg_raw: torch.Tensor, n_ways: int, img_h: int, img_w: int,
