@@ -10,6 +10,7 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --source-size 200 --results-at-source     (... results in the 200^2 frame)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source     (supports cropped, resized and padded on the GPU)
     python examples/eval_loop.py --episodes 8 --match-on-device     (mask overlaps counted on the GPU: the evaluator decodes no RLE)
+    python examples/eval_loop.py --episodes 8 --eval-on-device --iou-thrs coco     (greedy matching on the GPU too; AP at COCO's ten thresholds)
 """
 import argparse
 import os
@@ -24,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fgn_amd.detector import FGN                          # noqa: E402
 from fgn_amd.episodes import collate                      # noqa: E402
 from fgn_amd.fewshot_ds import ClutteredCharsFewShotISEG, SyntheticFewShotISEG, write_chunked   # noqa: E402
+from fgn_amd.fsiseg_eval import COCO_IOU_THRS, evaluate_results_multi                # noqa: E402
 
 
 def main():
@@ -50,6 +52,13 @@ def main():
     ap.add_argument('--match-on-device', action='store_true',
                     help='count the overlaps of detections and ground truth on the GPU (FGN.match_on_device): the results '
                          'carry dt_gt_inter / dt_area / gt_area and the evaluator decodes no RLE')
+    ap.add_argument('--eval-on-device', action='store_true',
+                    help="match detections to ground truth on the GPU as well (FGN.evaluate_on_device; implies the counts): "
+                         'the results carry one matched bit per detection, IoU type and threshold, and the evaluator forms '
+                         'no IoU')
+    ap.add_argument('--iou-thrs', default=None, metavar='T',
+                    help="IoU thresholds to report besides the reference's 0.5: 'coco' (0.5:0.05:0.95) or a comma-separated "
+                         'list of at most 16 (evaluate_results_multi; with --eval-on-device they are matched on the GPU)')
     args = ap.parse_args()
     args.uint8 = args.uint8 or args.source_size is not None or args.spp_source
     if args.results_at_source and args.source_size is None:
@@ -67,14 +76,25 @@ def main():
     if args.uint8:
         model.set_input_norm(**ds.input_norm)
     model.match_on_device = args.match_on_device
+    iou_thrs = None
+    if args.iou_thrs is not None:
+        iou_thrs = COCO_IOU_THRS if args.iou_thrs == 'coco' else tuple(float(t) for t in args.iou_thrs.split(','))
+    model.evaluate_on_device = args.eval_on_device
+    if args.eval_on_device and iou_thrs is not None:
+        model.eval_iou_thrs = iou_thrs if 0.5 in iou_thrs else (0.5,) + tuple(iou_thrs)
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'))
     # (source-size queries of one size stack like any other; a real loader hands qry_img over as a list when they differ)
     loader = DataLoader(ds, batch_size=ds.batch, num_workers=2, collate_fn=collate)
 
+    kept = []
+
     def results():
         for data in loader:
-            yield model.simple_test(**data, rescale=True, results_at_source=args.results_at_source)
+            res = model.simple_test(**data, rescale=True, results_at_source=args.results_at_source)
+            if iou_thrs is not None:
+                kept.extend(res)
+            yield res
 
     with tempfile.TemporaryDirectory() as work_dir:
         out = os.path.join(work_dir, 'ResultsChunked')
@@ -87,6 +107,11 @@ def main():
     print(f'{len(ds)} episodes in {dt:.2f} s ({len(ds) / dt:.1f} img/s incl. data loading and H2D), '
           f'evaluation {de:.2f} s ({de / len(ds) * 1e3:.1f} ms per image)')
     print(metrics)
+    if iou_thrs is not None:
+        t0 = time.perf_counter()
+        multi = evaluate_results_multi(kept, args.n_ways, iou_thrs)
+        print(f'{len(iou_thrs)} thresholds in {time.perf_counter() - t0:.2f} s:',
+              {k: round(v, 4) for k, v in multi.items() if k.endswith(('mAP', 'mAR'))})
 
 
 if __name__ == '__main__':

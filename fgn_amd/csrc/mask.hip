@@ -853,3 +853,235 @@ extern "C" int fgn_mask_overlap_src_i32(const float* prob, const float* boxes, i
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }
+
+// ----------------------------------------------------------------------------------------------
+// Matching on the device, second half: the evaluator's greedy matching (fgn_amd/fsiseg_eval.py, match_flags /
+// FSISEGEval._evaluate_img) of one image's detections to its ground truth.  Per (IoU type, category): the detections of
+// the category in descending score order (ties in index order), cut at max_dets; each in turn takes the still
+// unmatched ground truth of the category with the largest IoU >= thr (among equal IoUs the largest index).  Output:
+// one int32 per detection and IoU type, bit t = matched at thr[t]; -1 = beyond max_dets of its category; 0 = label
+// outside 0..n_ways-1 or row at / beyond the device count.
+//
+// One workgroup per (IoU type, category) of T waves, ONE WAVE PER THRESHOLD.  The walk is sequential in the detections
+// (at most max_dets steps, each a wave reduction), so its latency is what the launch costs: waves of different
+// thresholds walk side by side instead of one wave walking T times.  They sit in one workgroup because they share the
+// score order (formed once, by all threads) and because a detection's T bits are then combined from LDS by one thread
+// and stored once - no two waves ever write the same word, so there is no atomic anywhere.
+//   rank   rank_i = #{j of the category: s_j > s_i or (s_j == s_i and j < i)}: the stable descending order, by counting,
+//          on scores and membership staged in LDS once; the detection of rank r leaves its operand (the box, divided to
+//          the source frame where asked, or |d|) in LDS at r, so the walk reads no detection from global memory.
+//   walk   lane = ground truth (passes of 64): its IoU in float64 with the expression of _bbox_iou / _count_iou (the
+//          translation unit is built with -ffp-contract=off; the f64 division is correctly rounded), then - only where
+//          more than one lane is at or above the threshold - a wave reduction to (max IoU, largest index among equals).
+//          The matched set lives in registers: bit p of a lane's
+//          word = its ground truth of pass p (the per-pass 64-bit masks, transposed).  The walk is a chain of dependent
+//          steps, so the one global load a step needs (segm: the row of inter) is issued two steps ahead for pass 0.
+// Scores are expected to be no NaN (a NaN has no rank); a rank left empty by one is skipped.
+// ----------------------------------------------------------------------------------------------
+constexpr int EVM_MAX_THRS = 16;
+constexpr int EVM_MAX_DET = 2048;        // detections of an image: scores and membership live in LDS
+constexpr int EVM_MAX_RANKS = 1024;      // min(D, max_dets) at most: the walk's order, operands and bits live in LDS
+constexpr int EVM_MAX_GT = 4096;         // 64 passes: one bit each in a lane's matched word
+constexpr int EVM_MIN_WAVES = 4;         // waves of a workgroup at least: the staging and ranking are shared work
+
+struct EvmGt {                           // one ground truth as a lane holds it
+    double x, y, w, h;                   // bbox: _xywh(qry_bboxes)
+    double area;                         // segm: |g|
+    bool ok;                             // of this workgroup's category
+};
+
+__device__ __forceinline__ EvmGt evm_load_gt(int g, int G, int k, int type, const double* __restrict__ gt_xywh,
+                                             const int32_t* __restrict__ gt_cat, const int32_t* __restrict__ gt_area) {
+    EvmGt v;
+    v.x = v.y = v.w = v.h = v.area = 0.0;
+    v.ok = g < G && gt_cat[g] == k;
+    if (v.ok) {
+        if (type == 0) {
+            v.x = gt_xywh[4 * (size_t)g]; v.y = gt_xywh[4 * (size_t)g + 1];
+            v.w = gt_xywh[4 * (size_t)g + 2]; v.h = gt_xywh[4 * (size_t)g + 3];
+        } else {
+            v.area = (double)gt_area[g];
+        }
+    }
+    return v;
+}
+
+// grid: (category, IoU type: 0 bbox, 1 segm), max(T, EVM_MIN_WAVES) * 64 threads: with few thresholds the extra waves
+// help to stage and rank, and walk nothing.  flags [2][D]; with has_segm == 0 the grid has one row
+// and its category-0 workgroup zeroes row 1.  D <= EVM_MAX_DET, min(D, max_dets) <= EVM_MAX_RANKS, G <= EVM_MAX_GT.
+__global__ __launch_bounds__(EVM_MAX_THRS * 64) void eval_match_kernel(
+    const float* __restrict__ boxes, int box_stride, const long long* __restrict__ labels,
+    const int32_t* __restrict__ n_dev, const int32_t* __restrict__ inter, const int32_t* __restrict__ det_area,
+    const int32_t* __restrict__ gt_area, const double* __restrict__ gt_xywh, const int32_t* __restrict__ gt_cat,
+    const double* __restrict__ thr, int32_t* __restrict__ flags, int D, int G, int T, int n_ways, int max_dets,
+    int src_h, int src_w, int net_h, int net_w, int has_segm) {
+    __shared__ float score[EVM_MAX_DET];
+    __shared__ uint8_t member[EVM_MAX_DET];
+    __shared__ int order[EVM_MAX_RANKS];
+    __shared__ float4 operand[EVM_MAX_RANKS];               // of the detection at a rank: bbox x1 y1 x2 y2; segm .x = |d| (bits)
+    __shared__ uint8_t hit[EVM_MAX_THRS][EVM_MAX_RANKS];
+    __shared__ int wave_cnt[EVM_MAX_THRS];
+    const int k = blockIdx.x, type = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, t = tid >> 6, nthreads = blockDim.x;
+    int n = D;
+    if (n_dev) n = max(0, min(D, *n_dev));
+    int32_t* __restrict__ out = flags + (size_t)type * D;
+    if (k == 0) {                                           // the words no category's workgroup owns
+        for (int d = tid; d < D; d += nthreads) {
+            bool outside = d >= n;
+            if (!outside) { const long long l = labels[d]; outside = l < 0 || l >= n_ways; }
+            if (outside) out[d] = 0;
+            if (!has_segm) flags[(size_t)D + d] = 0;
+        }
+    }
+    // ---- membership and scores into LDS; the category's detections are counted per wave (wave-uniform trip count)
+    const int r_cap = min(min(n, max_dets), EVM_MAX_RANKS);
+    for (int r = tid; r < r_cap; r += nthreads) order[r] = -1;
+    int cnt = 0;
+    for (int base = 0; base < n; base += nthreads) {
+        const int d = base + tid;
+        const bool m = d < n && labels[d] == k;
+        if (d < n) {
+            member[d] = m ? 1 : 0;
+            score[d] = m ? boxes[(size_t)d * box_stride + 4] : 0.f;
+        }
+        cnt += __popcll(__ballot(m));
+    }
+    if (lane == 0) wave_cnt[t] = cnt;
+    __syncthreads();
+    int nk = 0;
+    for (int w = 0; w < (nthreads >> 6); ++w) nk += wave_cnt[w];
+    // ---- rank by counting; the detection of rank r leaves its operand at r
+    const bool to_source = src_h > 0;
+    const SrcGeom geom = src_geom(to_source ? src_h : 1, to_source ? src_w : 1, net_h, net_w);
+    for (int d = tid; d < n; d += nthreads) {
+        if (!member[d]) continue;
+        const float s = score[d];
+        int rank = 0;
+        for (int j = 0; j < n; ++j) rank += (member[j] && (score[j] > s || (score[j] == s && j < d))) ? 1 : 0;
+        if (rank >= r_cap) {
+            out[d] = -1;                                    // beyond max_dets of its category: not evaluated
+            continue;
+        }
+        order[rank] = d;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (type == 0) {
+            float b[4];
+            const float* src = boxes + (size_t)d * box_stride;
+            if (to_source) box_to_source(src, geom, b);
+            else { b[0] = src[0]; b[1] = src[1]; b[2] = src[2]; b[3] = src[3]; }
+            o = make_float4(b[0], b[1], b[2], b[3]);
+        } else {
+            o.x = __int_as_float(det_area[d]);
+        }
+        operand[rank] = o;
+    }
+    __syncthreads();
+    const int n_ranked = min(nk, r_cap);
+
+    // ---- the walk of threshold t (wave-uniform control flow throughout); a wave beyond T (see EVM_MIN_WAVES) has none
+    const int nsel = t < T ? n_ranked : 0;
+    const double th = thr[min(t, T - 1)];
+    const int passes = (G + 63) >> 6;
+    const EvmGt g_first = evm_load_gt(lane, G, k, type, gt_xywh, gt_cat, gt_area);      // pass 0, kept in registers
+    // segm: inter[order[r]][lane], the one global load of a step, issued two steps ahead (0 where there is none)
+    auto row_first = [&](int r) -> int {
+        if (type != 1 || r >= nsel || !g_first.ok) return 0;
+        const int d = order[r];
+        return d >= 0 ? inter[(size_t)d * G + lane] : 0;
+    };
+    int ahead1 = row_first(0), ahead2 = row_first(1);
+    unsigned long long matched = 0;                         // bit p: ground truth p * 64 + lane is matched
+    for (int r = 0; r < nsel; ++r) {
+        const int in_first = ahead1;
+        ahead1 = ahead2;
+        ahead2 = row_first(r + 2);
+        const int d = order[r];
+        if (d < 0) {
+            if (lane == 0) hit[t][r] = 0;
+            continue;
+        }
+        const float4 o = operand[r];
+        double dx = 0, dy = 0, dx2 = 0, dy2 = 0, d_area;
+        if (type == 0) {
+            dx = (double)o.x; dy = (double)o.y;
+            const double dw = (double)fmaxf(o.z - o.x, 1.f);           // the differences in the boxes' own float32 (_xywh)
+            const double dh = (double)fmaxf(o.w - o.y, 1.f);
+            dx2 = dx + dw; dy2 = dy + dh;
+            d_area = dw * dh;
+        } else {
+            d_area = (double)__float_as_int(o.x);
+        }
+        double best = -1.0;                                 // (an IoU is never negative)
+        int best_g = -1;
+        for (int p = 0; p < passes; ++p) {
+            const int g = p * 64 + lane;
+            const EvmGt gt = p == 0 ? g_first : evm_load_gt(g, G, k, type, gt_xywh, gt_cat, gt_area);
+            if (!gt.ok || ((matched >> p) & 1ull)) continue;
+            double iou;
+            if (type == 0) {
+                const double w = fmax(fmin(dx2, gt.x + gt.w) - fmax(dx, gt.x), 0.0);
+                const double h = fmax(fmin(dy2, gt.y + gt.h) - fmax(dy, gt.y), 0.0);
+                const double in = w * h;
+                const double un = d_area + gt.w * gt.h - in;
+                iou = in / un;
+            } else {
+                const double in = (double)(p == 0 ? in_first : inter[(size_t)d * G + g]);
+                const double un = d_area + gt.area - in;
+                iou = un > 0.0 ? in / un : 0.0;
+            }
+            if (iou >= th && iou >= best) { best = iou; best_g = g; }     // a later pass holds the larger index
+        }
+        // most steps have no lane at or above the threshold, the others mostly one: the reduction runs for rivals only
+        const unsigned long long rivals = __ballot(best_g >= 0);
+        if (rivals == 0) {
+            if (lane == 0) hit[t][r] = 0;
+            continue;
+        }
+        if (rivals & (rivals - 1)) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const double ob = __shfl_xor(best, off);
+                const int og = __shfl_xor(best_g, off);
+                if (ob > best || (ob == best && og > best_g)) { best = ob; best_g = og; }
+            }
+        } else {
+            best_g = __shfl(best_g, __ffsll(rivals) - 1);
+        }
+        if (best_g >= 0 && (best_g & 63) == lane) matched |= 1ull << (best_g >> 6);
+        if (lane == 0) hit[t][r] = best_g >= 0 ? 1 : 0;
+    }
+    __syncthreads();
+    for (int r = tid; r < n_ranked; r += nthreads) {
+        const int d = order[r];
+        if (d < 0) continue;
+        int v = 0;
+        for (int tt = 0; tt < T; ++tt) v |= (int)hit[tt][r] << tt;
+        out[d] = v;
+    }
+}
+
+extern "C" int fgn_eval_match_i32(const float* boxes, int box_stride, const int64_t* labels, const int32_t* n_dev,
+                                  const int32_t* inter, const int32_t* det_area, const int32_t* gt_area,
+                                  const double* gt_xywh, const int32_t* gt_cat, const double* thr, int32_t* flags,
+                                  int n_det, int n_gt, int n_thr, int n_ways, int max_dets, int src_h, int src_w,
+                                  int net_h, int net_w, hipStream_t stream) {
+    if (n_thr < 1 || n_thr > EVM_MAX_THRS || n_det < 0 || n_gt < 0 || n_ways < 1 || max_dets < 1) return FGN_ERR_SHAPE;
+    if (n_det == 0) return FGN_OK;
+    const bool has_segm = det_area != nullptr;
+    if (!boxes || !labels || !thr || !flags || box_stride < 5) return FGN_ERR_ARG;
+    if (n_gt > 0 && (!gt_xywh || !gt_cat || (has_segm && (!inter || !gt_area)))) return FGN_ERR_ARG;
+    if (n_det > EVM_MAX_DET || std::min(n_det, max_dets) > EVM_MAX_RANKS || n_gt > EVM_MAX_GT || n_ways > 65535)
+        return FGN_ERR_SHAPE;
+    const bool to_source = src_h != 0 || src_w != 0;
+    if (to_source && (src_h < 1 || src_w < 1 || src_h > SRC_MAX_DIM || src_w > SRC_MAX_DIM || net_h < 1 || net_w < 1 ||
+                      net_h > SRC_MAX_DIM || net_w > SRC_MAX_DIM))
+        return FGN_ERR_SHAPE;
+    hipLaunchKernelGGL(eval_match_kernel, dim3(n_ways, has_segm ? 2 : 1), dim3(std::max(n_thr, EVM_MIN_WAVES) * 64), 0,
+                       stream, boxes, box_stride,
+                       reinterpret_cast<const long long*>(labels), n_dev, inter, det_area, gt_area, gt_xywh, gt_cat, thr,
+                       flags, n_det, n_gt, n_thr, n_ways, max_dets, to_source ? src_h : 0, to_source ? src_w : 0, net_h,
+                       net_w, has_segm ? 1 : 0);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}

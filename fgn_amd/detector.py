@@ -618,6 +618,13 @@ class FGN(torch.nn.Module):
         # on the device while the episode is in flight (result keys dt_gt_inter / dt_area / gt_area: the evaluator then
         # decodes no RLE); needs ``qry_isegmaps``.  False: nothing is launched, allocated or added
         self.match_on_device = False
+        # the evaluator's greedy matching on the device as well: implies the counts above for the call;
+        # ``detect_device`` runs ``ops.eval_match`` per image behind them and the result dicts gain ``dt_match_bbox``,
+        # ``dt_match_segm`` (bit t = matched at ``eval_iou_thrs[t]``, -1 = beyond the evaluator's 100 per category),
+        # ``eval_iou_thrs`` and ``gt_per_cat`` - all ``FSISEGEval`` needs besides scores and labels.  Off: nothing is
+        # launched, allocated or added.
+        self.evaluate_on_device = False
+        self.eval_iou_thrs = (0.5,)         # 1..16 thresholds; COCO's ten: ``fsiseg_eval.COCO_IOU_THRS``
         self._use_winograd = ops.WINOGRAD_M       # Winograd form of the 3x3 / stride 1 convs: 4 = F(4x4,3x3), 2 = F(2x2,3x3), 0 = direct
         self.use_roi_commute = True               # shared_head conv1 on the feature map, RoIAlign after (set before first use)
         # query + support maps through SHARED backbone launches (1x1 / stride 1 convolutions and the grouped Winograd GEMM
@@ -1437,16 +1444,17 @@ class FGN(torch.nn.Module):
                                        self._graphed())
         if qry_resize_to is None:
             dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
-                                      qry_isegmaps=qry_isegmaps, spp_crop_to=sp)
+                                      qry_isegmaps=qry_isegmaps, spp_crop_to=sp, qry_bboxes=qry_bboxes,
+                                      qry_cat_ids=qry_cat_ids)
             batch = qry_img.shape[0]
         else:
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps, self._graphed())
+            if not results_at_source:       # (host only: the boxes of the result dicts, which the device matches against)
+                qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
             dets = self.detect_device(qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code,
                                       qry_isegmaps=qry_isegmaps, qry_resize_to=rs, results_at_source=results_at_source,
-                                      spp_crop_to=sp)
+                                      spp_crop_to=sp, qry_bboxes=qry_bboxes, qry_cat_ids=qry_cat_ids)
             batch, img_shape = rs['B'], rs['img_shape']
-            if not results_at_source:
-                qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
         return self.pack_results(dets, batch, qry_bboxes=qry_bboxes, qry_cat_ids=qry_cat_ids,
                                  qry_isegmaps=qry_isegmaps, img_shape=img_shape, qry_child_idx=qry_child_idx,
                                  cats_ids_to_sample_real=cats_ids_to_sample_real, spp_insts_ids=spp_insts_ids,
@@ -1681,7 +1689,8 @@ class FGN(torch.nn.Module):
     def detect_device(self, qry_img, spp_imgs, spp_bboxes, spp_isegmaps, img_shape, support_code=None,
                       qry_isegmaps=None, phase_counter=None, qry_resize_to=None,
                       results_at_source: bool = False, spp_crop_to=None, spp_fill_ratio: float = 0.8,
-                      crop_square: bool = True, spp_augment=None, spp_photometric=None) -> list:
+                      crop_square: bool = True, spp_augment=None, spp_photometric=None, qry_bboxes=None,
+                      qry_cat_ids=None) -> list:
         """Everything up to the host wait: queues the host->device copies, the whole path and the device->host
         copies of the results.  Returns, per image, a dict of device tensors (det_bboxes [D,5], det_labels [D],
         n_dets [1], mask_prob, RLE bytes) plus the pinned host slot ``pack_results`` reads.
@@ -1703,7 +1712,9 @@ class FGN(torch.nn.Module):
         ``spp_imgs`` / ``spp_isegmaps``, the boxes are computed on the host, and a captured graph is keyed by the slot
         size and S, not by any source, window or crop size.  (``simple_test`` hands over the dict of
         ``_source_supports``.)  Ignored beside ``support_code``.  ``spp_augment`` / ``spp_photometric`` are refused: the
-        test path is without augmentation."""
+        test path is without augmentation.  ``qry_bboxes`` / ``qry_cat_ids`` (per image, as ``pack_results`` will be
+        given them: YXYX in the frame of the results) are read with ``evaluate_on_device`` only: the evaluator's greedy
+        matching runs on the device (``ops.eval_match``) and ``pack_results`` adds the matched bits."""
         self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric)
         graphed = self._graphed()
         source = spp_source = None
@@ -1742,7 +1753,8 @@ class FGN(torch.nn.Module):
             key = self._graph_key(ins, img_shape, support_code, phase_counter, main, dev, form)
             if self.use_packed_transfers and self._stream_for('upload', main) is main and key in self._graphs:
                 into = self._graphs[key].static
-        gt_bits = [] if (self.match_on_device and qry_isegmaps is not None) else None
+        evaluate = bool(self.evaluate_on_device)
+        gt_bits = [] if ((self.match_on_device or evaluate) and qry_isegmaps is not None) else None
         ins, gt_rle, uploaded = self._upload(ins, qry_isegmaps, dev, main, into=into, bits_out=gt_bits, form=form)
         if uploaded is not None:
             main.wait_event(uploaded)
@@ -1773,10 +1785,38 @@ class FGN(torch.nn.Module):
                     continue
                 d['overlap'] = ops.mask_overlap(d['mask_prob'], d['det_bboxes'], gb, *d['img_hw'], thr, d['n_dets'],
                                                 skip_empty=self._skip_empty(), packed=True)[3]
+        if evaluate and qry_bboxes is not None and qry_cat_ids is not None:
+            self._match_on_device(outs, qry_bboxes, qry_cat_ids, qry_isegmaps is not None, results_at_source)
         self._start_download(outs, main, uploaded if gt_rle is not None else None)
         if graphed:
             ge.last_download = outs[0]['host_ready']
         return outs
+
+    def _match_on_device(self, outs: list, qry_bboxes, qry_cat_ids, with_masks: bool, results_at_source: bool) -> None:
+        """``evaluate_on_device``: one ``ops.eval_match`` per image on the caller's stream, right behind its overlap
+        counts - eager also when the episode was a graph replay, for the reason the overlap launch gives (G is no part
+        of the captured geometry).  ``with_masks``: ground-truth masks came with the call, so segm bits are made (an
+        image without a ground-truth instance has no counts: every union is empty there)."""
+        from .fsiseg_eval import MATCH_MAX_DETS, _xywh, gt_per_cat
+        thrs = np.asarray(self.eval_iou_thrs, np.float64).reshape(-1)
+        for i, d in enumerate(outs):
+            if qry_bboxes[i] is None or qry_cat_ids[i] is None:
+                continue
+            xywh, cats = _xywh(_host(qry_bboxes[i])), _host(qry_cat_ids[i]).reshape(-1)
+            md, g = d['det_bboxes'].shape[0], len(cats)
+            ov = None
+            if 'overlap' in d:
+                o = d['overlap']
+                ov = (o[:md * g].view(md, g), o[md * g:md * g + md], o[md * g + md:])
+            elif with_masks and g == 0:
+                z = torch.zeros(md, device=d['det_bboxes'].device, dtype=torch.int32)
+                ov = (z[:0].view(md, 0), z, z[:0])
+            d['match'] = ops.eval_match(d['det_bboxes'], d['det_labels'], xywh, cats, thrs, self.n_ways, overlap=ov,
+                                        n_dev=d['n_dets'], max_dets=MATCH_MAX_DETS,
+                                        src_hw=d['src_hw'] if results_at_source else None,
+                                        net_hw=d['img_hw'] if results_at_source else None, packed=True)[2]
+            d['match_meta'] = (ov is not None, thrs.copy(), gt_per_cat(cats, self.n_ways))
+            d['gt_per_cat'] = torch.from_numpy(d['match_meta'][2])        # (host; ``dist.pack_matches`` sends it along)
 
     def _graphed(self) -> bool:
         return bool(self.use_graphs and self.debug_trace is None and ops.PROFILE is None)
@@ -2041,7 +2081,8 @@ class FGN(torch.nn.Module):
 
     MAX_SLOTS = 64
 
-    def _pinned_slot(self, batch: int, max_det: int, n_gt: int, mask_size: int = 14, n_ov: int = 0) -> dict:
+    def _pinned_slot(self, batch: int, max_det: int, n_gt: int, mask_size: int = 14, n_ov: int = 0,
+                     with_match: bool = False) -> dict:
         """A free pinned host slot for one batch's results (pinned allocation is slow, so slots are kept per
         (batch, max_det, mask size) and reused): the host mirror of a ``_ResultRecord`` plus a byte buffer for the
         packed ground-truth RLE.  A slot is busy from ``detect_device`` until ``pack_results`` has read it; when every
@@ -2068,6 +2109,9 @@ class FGN(torch.nn.Module):
             cap = max(64, 2 * n_ov)
             slot.update(ov_cap=cap, ov_buf=torch.empty(cap * (max_det + 1) + batch * max_det, dtype=torch.int32,
                                                        pin_memory=True))
+        if with_match and 'mt_buf' not in slot:
+            # matched bits (``evaluate_on_device``): [bbox | segm] rows of max_det int32 per image - a fixed size
+            slot['mt_buf'] = torch.empty(batch * 2 * max_det, dtype=torch.int32, pin_memory=True)
         slot['busy'] = True
         return slot
 
@@ -2086,7 +2130,8 @@ class FGN(torch.nn.Module):
         n_gt = sum(d['gt_rle'][1].shape[0] for d in outs if 'gt_rle' in d)
         rec = outs[0].get('record')
         n_ov = sum(d['gt_rle'][1].shape[0] for d in outs if 'overlap' in d)
-        slot = self._pinned_slot(len(outs), max_det, n_gt, outs[0]['mask_prob'].shape[-1], n_ov)
+        slot = self._pinned_slot(len(outs), max_det, n_gt, outs[0]['mask_prob'].shape[-1], n_ov,
+                                 any('match' in d for d in outs))
         cp.wait_stream(main)
         if also_wait is not None:
             cp.wait_event(also_wait)           # the ground-truth RLE kernels run on the upload stream
@@ -2128,6 +2173,12 @@ class FGN(torch.nn.Module):
                     d['overlap'].record_stream(cp)
                     d['ov_slice'] = (o0, n)
                     o0 += n
+            for i, d in enumerate(outs):
+                if 'match' in d:                   # the matched bits, in a slice of their own
+                    n = d['match'].numel()
+                    slot['mt_buf'][i * n:(i + 1) * n].copy_(d['match'].reshape(-1), non_blocking=True)
+                    d['match'].record_stream(cp)
+                    d['mt_slice'] = (i * n, n)
             ev = cp.record_event()
         for d in outs:
             d['host'] = slot
@@ -2217,6 +2268,15 @@ class FGN(torch.nn.Module):
                 one['dt_gt_inter'] = hb[:md * ng].reshape(md, ng)[:n].copy()
                 one['dt_area'] = hb[md * ng:md * ng + md][:n].copy()
                 one['gt_area'] = hb[md * ng + md:].copy()
+            if 'mt_slice' in di:                   # matched bits from the device: [bbox [D] | segm [D]]
+                m0, nm = di['mt_slice']
+                fl = host['mt_buf'][m0:m0 + nm].numpy().reshape(2, -1)
+                has_segm, thrs, per_cat = di['match_meta']
+                one['dt_match_bbox'] = fl[0, :n].copy()
+                if has_segm:
+                    one['dt_match_segm'] = fl[1, :n].copy()
+                one['eval_iou_thrs'] = thrs
+                one['gt_per_cat'] = per_cat
             results.append(one)
         host['busy'] = False
         return results

@@ -11,6 +11,9 @@ fgn_roi_head.py:668-671; 14 x 14 at the reference's settings), plus a per-episod
 The receiving rank turns any gathered episode into the reference's result dict
 (``results_from_gathered``: paste + threshold + COCO RLE of the gathered probabilities with the
 same fused kernel the producing rank runs, so the strings are byte-identical).
+Where only AP / AR is wanted, ``pack_matches`` / ``gather_matches`` / ``results_from_matches`` send the matched bits the
+producing rank formed on the device instead (``FGN.evaluate_on_device``): ~1.6 KB per episode and no mask work on the
+receiving side.
 """
 from __future__ import annotations
 
@@ -118,6 +121,78 @@ def _hip_rle(prob, boxes, h, w, thr, skip_empty=True):
         else:
             res.append({'size': [h, w], 'counts': by[j, :ln[j]].tobytes()})
     return res
+
+
+# ------------------------------------------------------------------------------------------
+# gather without masks (``FGN.evaluate_on_device``): the evaluator needs, per detection, its score, its
+# label and one matched bit per IoU threshold and IoU type, and per image the number of ground-truth instances of
+# every category.  The producing rank has all of that on the device; the record is 4 numbers per detection plus
+# 1 + n_ways per episode (~1.6 KB at 100 detections) and the receiving rank touches no mask.
+# ------------------------------------------------------------------------------------------
+REC_MATCH = 4        # score, label, bbox flags, segm flags (flags < 2^16 and -1 are exact in float32)
+
+
+def pack_matches(dets: list, max_det: int, n_ways: int, pad_to: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """List of per-image dicts of ``FGN.detect_device`` with ``evaluate_on_device`` (``det_bboxes`` [D,5],
+    ``det_labels`` [D], ``n_dets`` [1], ``match`` int32 [2,D] = bbox / segm flags, ``gt_per_cat`` int32 [n_ways]) ->
+    (records float32 [E, max_det, 4] = score, label, bbox flags, segm flags; head float32 [E, 1 + n_ways] = valid count,
+    ground-truth instances per category).  Pure torch on the tensors' device (``gt_per_cat`` is moved there).  An image
+    matched without masks sends its (zero) segm row as it is.  ``pad_to`` > len(dets) appends zero-count episodes."""
+    recs, heads = [], []
+    for d in dets:
+        if 'match' not in d or 'gt_per_cat' not in d:
+            raise ValueError('pack_matches: these detections carry no matched bits (FGN.evaluate_on_device with '
+                             'qry_bboxes and qry_cat_ids)')
+        box = d['det_bboxes'][:max_det]
+        fl = d['match'].reshape(2, -1)[:, :max_det].to(torch.float32)
+        recs.append(torch.stack([box[:, 4], d['det_labels'][:max_det].to(torch.float32), fl[0], fl[1]], 1))
+        per = d['gt_per_cat'].reshape(-1)
+        if per.numel() != n_ways:
+            raise ValueError(f'pack_matches: gt_per_cat has {per.numel()} categories, n_ways is {n_ways}')
+        heads.append(torch.cat([d['n_dets'].reshape(1).to(torch.float32),
+                                per.to(device=box.device, dtype=torch.float32)]))
+    recs, head = torch.stack(recs), torch.stack(heads)
+    if pad_to is not None and pad_to > len(dets):
+        extra = pad_to - len(dets)
+        recs = torch.cat([recs, recs.new_zeros((extra,) + tuple(recs.shape[1:]))])
+        head = torch.cat([head, head.new_zeros((extra, head.shape[1]))])
+    return recs.contiguous(), head.contiguous()
+
+
+def gather_matches(recs: torch.Tensor, head: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``gather_detections`` for the records of ``pack_matches``: ONE collective per step whose message is
+    ``max_det * 4 + 1 + n_ways`` float32 per episode.  -> ([world, E, max_det, 4], [world, E, 1 + n_ways])."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return recs[None], head[None]
+    world = dist.get_world_size()
+    e, m, f = recs.shape
+    msg = torch.cat([recs.reshape(e, m * f), head], 1).contiguous()
+    if dist.get_backend() == 'gloo' and msg.is_cuda:      # (as gather_detections: gloo has no CUDA all-gather)
+        out = torch.empty((world * e, msg.shape[1]), dtype=msg.dtype)
+        dist.all_gather_into_tensor(out, msg.cpu())
+        out = out.to(msg.device)
+    else:
+        out = torch.empty((world * e, msg.shape[1]), dtype=msg.dtype, device=msg.device)
+        dist.all_gather_into_tensor(out, msg)
+    out = out.view(world, e, -1)
+    return out[:, :, :m * f].reshape(world, e, m, f), out[:, :, m * f:]
+
+
+def results_from_matches(recs: torch.Tensor, head: torch.Tensor, iou_thrs) -> List[dict]:
+    """Gathered match records of E episodes ([E, max_det, 4], [E, 1 + n_ways]) -> minimal result dicts: ``dt_scores``,
+    ``dt_cat_ids``, ``dt_match_bbox``, ``dt_match_segm``, ``eval_iou_thrs`` (the thresholds the producing detectors
+    matched at, ``FGN.eval_iou_thrs``) and ``gt_per_cat``.  ``FSISEGEval(...).run()`` accepts them at those thresholds;
+    they hold no box and no mask, so ``annotations()`` / ``groups()`` refuse them."""
+    thrs = np.asarray(iou_thrs, np.float64).reshape(-1)
+    r, h = recs.cpu().numpy(), head.cpu().numpy()
+    out = []
+    for i in range(r.shape[0]):
+        n = int(round(float(h[i, 0])))
+        out.append({'dt_scores': r[i, :n, 0].copy(), 'dt_cat_ids': np.rint(r[i, :n, 1]).astype(np.int64),
+                    'dt_match_bbox': np.rint(r[i, :n, 2]).astype(np.int32),
+                    'dt_match_segm': np.rint(r[i, :n, 3]).astype(np.int32), 'eval_iou_thrs': thrs.copy(),
+                    'gt_per_cat': np.rint(h[i, 1:]).astype(np.int32)})
+    return out
 
 
 # ------------------------------------------------------------------------------------------

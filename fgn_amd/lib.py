@@ -93,6 +93,7 @@ SIGNATURES = {
     'fgn_mask_bits_u64': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'fgn_mask_overlap_i32': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
     'fgn_mask_overlap_src_i32': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
+    'fgn_eval_match_i32': (_i, [_p, _i] + [_p] * 9 + [_i] * 9 + [_p]),
     'fgn_rpn_proposals_large_scratch_bytes': (C.c_size_t, [_i, _i, _i]),
     'fgn_rpn_proposals_large_f32': (_i, [_p] * 7 + [_i, _i, _i, _i, _i, _f, _f, C.POINTER(_f), C.POINTER(_f),
                                                   _f, _i, _f, _f, _i, _p]),

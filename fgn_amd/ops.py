@@ -1822,6 +1822,66 @@ def mask_overlap_src(prob: torch.Tensor, boxes: torch.Tensor, gt_masks, src_hw, 
     return (inter, det_area, ga, buf) if packed else (inter, det_area, ga)
 
 
+EVAL_MAX_THRS = 16
+
+
+def eval_match(boxes: torch.Tensor, labels: torch.Tensor, gt_xywh, gt_cat, iou_thrs, n_ways: int, overlap=None,
+               n_dev: Optional[torch.Tensor] = None, max_dets: int = 100, src_hw=None, net_hw=None,
+               packed: bool = False):
+    """The evaluator's greedy matching of one image on the device (``fsiseg_eval.match_flags`` bit for bit):
+    ``boxes`` [D,>=5] (x1, y1, x2, y2, score) and ``labels`` [D] int64 as ``detect_device`` holds them, ``n_dev`` the
+    device-side count; ``gt_xywh`` [G,4] float64 = ``fsiseg_eval._xywh(qry_bboxes)`` and ``gt_cat`` [G] (host arrays are
+    uploaded: G is small); ``iou_thrs``: 1..16 thresholds as the evaluator is given them (the cap at 1 - 1e-10 is applied
+    here); ``overlap``: (inter [D,G], det_area [D], gt_area [G]) of ``mask_overlap`` / ``mask_overlap_src``, or None =
+    no segm flags.  ``src_hw`` / ``net_hw``: the boxes are network-frame boxes to be divided by the image's scale
+    (``results_at_source``), as ``mask_overlap_src`` divides them.  Returns (bbox flags [D], segm flags [D] or None),
+    int32 views of ONE allocation [2, D]; ``packed``: that allocation as a third value.  Bit t = matched at
+    ``iou_thrs[t]``, -1 = beyond ``max_dets`` of its category, 0 = label outside 0..n_ways-1 or row at / beyond the
+    device count."""
+    _chk(boxes, 'boxes')
+    _chk(labels, 'labels', torch.int64)
+    d = boxes.shape[0]
+    if boxes.dim() != 2 or boxes.shape[1] < 5 or labels.shape != (d,):
+        raise _lib.FgnHipError('eval_match: boxes must be [D,>=5] and labels [D]')
+    if n_dev is not None:
+        _chk(n_dev, 'n_dev', torch.int32)
+    dev = boxes.device
+    thrs = np.minimum(np.asarray(iou_thrs, np.float64).reshape(-1), 1 - 1e-10)
+    xywh = gt_xywh.detach().cpu().numpy() if isinstance(gt_xywh, torch.Tensor) else np.asarray(gt_xywh)
+    xywh = np.ascontiguousarray(xywh, np.float64).reshape(-1, 4)
+    cat = gt_cat.detach().cpu().numpy() if isinstance(gt_cat, torch.Tensor) else np.asarray(gt_cat)
+    cat = np.ascontiguousarray(cat.reshape(-1), np.int32)
+    g = xywh.shape[0]
+    if cat.shape[0] != g:
+        raise _lib.FgnHipError(f'eval_match: {g} ground-truth boxes, {cat.shape[0]} categories')
+    inter = det_area = gt_area = None
+    if overlap is not None:
+        inter, det_area, gt_area = overlap[:3]
+        for t, name, shape in ((inter, 'inter', (d, g)), (det_area, 'det_area', (d,)), (gt_area, 'gt_area', (g,))):
+            _chk(t, name, torch.int32)
+            if tuple(t.shape) != shape:
+                raise _lib.FgnHipError(f'eval_match: {name} is {tuple(t.shape)}, expected {shape}')
+    buf = torch.empty((2, d), device=dev, dtype=torch.int32)
+    out = (buf[0], buf[1] if overlap is not None else None)
+    if d == 0:
+        return out + (buf,) if packed else out
+    # ONE upload for the host operands: [thr float64 [T] | gt_xywh float64 [G,4] | gt_cat int32 [G]] as bytes
+    t_n = thrs.shape[0]
+    blob = torch.from_numpy(np.concatenate([thrs.view(np.uint8), xywh.reshape(-1).view(np.uint8),
+                                            cat.view(np.uint8)])).to(dev, non_blocking=True)
+    base = blob.data_ptr()
+    sh, sw = (int(src_hw[0]), int(src_hw[1])) if src_hw is not None else (0, 0)
+    nh, nw = (int(net_hw[0]), int(net_hw[1])) if net_hw is not None else (0, 0)
+    if src_hw is not None and net_hw is None:
+        raise _lib.FgnHipError('eval_match: src_hw needs net_hw')
+    rc = _lib.load().fgn_eval_match_i32(_ptr(boxes), boxes.shape[1], _ptr(labels), _ptr(n_dev), _ptr(inter),
+                                        _ptr(det_area), _ptr(gt_area), base + 8 * t_n if g else None,
+                                        base + 8 * t_n + 32 * g if g else None, base, _ptr(buf), d, g, t_n, int(n_ways),
+                                        int(max_dets), sh, sw, nh, nw, _stream())
+    _lib.check(rc, 'fgn_eval_match_i32')
+    return out + (buf,) if packed else out
+
+
 # --------------------------------------------------------------------------------------
 # forward_train pieces (csrc/train.hip)
 # --------------------------------------------------------------------------------------

@@ -503,6 +503,26 @@ int fgn_mask_overlap_src_i32(const float* prob, const float* boxes, int box_stri
                              int32_t* inter, int32_t* det_area, const int32_t* n_dev, int n_det, int n_gt, int src_h,
                              int src_w, int net_h, int net_w, int mask_size, float thr, int skip_empty, void* stream);
 
+/* Step 3: the evaluator's greedy matching of one image (fgn_amd/fsiseg_eval.py: match_flags, bit for bit).  Per IoU type
+ * and category 0..n_ways-1: the detections of the category in descending score order (ties in index order), cut at
+ * max_dets; each in turn takes the still unmatched ground truth of its category with the largest IoU >= thr (among equal
+ * IoUs the largest index).  boxes [n_det][box_stride >= 5] = x1, y1, x2, y2, score (no NaN scores); labels [n_det]
+ * int64; n_dev (optional) the device-side detection count.  inter [n_det][n_gt] / det_area [n_det] / gt_area [n_gt]: the
+ * counts of step 2 - segm IoU = inter / (|d| + |g| - inter) in float64, 0 where the union is 0; det_area == NULL = no
+ * segm row is computed (inter and gt_area are then not read).  gt_xywh [n_gt][4] float64 = x, y, max(w,1), max(h,1) of
+ * the ground-truth boxes, gt_cat [n_gt] int32 - bbox IoU as pycocotools' bbIou in float64, the detections' width and
+ * height being float32 differences clamped to >= 1.  thr [n_thr] float64 on the device, each already min(thr, 1 - 1e-10).
+ * src_h / src_w != 0: the boxes are network-frame boxes of a (net_h, net_w) network and are divided by the scale of the
+ * src_h x src_w image exactly as fgn_mask_rle_src divides them (sizes within 1..16384); both 0: as given.
+ * flags [2][n_det] int32, row 0 bbox, row 1 segm, fully written (row 1 is zero without det_area): bit t = matched at
+ * thr[t]; -1 = beyond max_dets of its category; 0 = label outside 0..n_ways-1, or row at / beyond the device count.
+ * n_thr in 1..16, n_ways >= 1, max_dets >= 1, counts >= 0, n_det <= 2048, min(n_det, max_dets) <= 1024, n_gt <= 4096, else
+ * FGN_ERR_SHAPE.  n_det == 0 launches nothing.  n_gt == 0: 0 for every evaluated detection. */
+int fgn_eval_match_i32(const float* boxes, int box_stride, const int64_t* labels, const int32_t* n_dev,
+                       const int32_t* inter, const int32_t* det_area, const int32_t* gt_area, const double* gt_xywh,
+                       const int32_t* gt_cat, const double* thr, int32_t* flags, int n_det, int n_gt, int n_thr,
+                       int n_ways, int max_dets, int src_h, int src_w, int net_h, int net_w, void* stream);
+
 /* ---- forward_train (fgn.py:125-185) ----------------------------------------------------- */
 
 /* The proposal stage at training sizes (train_cfg.rpn_proposal, fgn_r50_c4_densecl.py:153-157: nms_pre 12000,
