@@ -1497,7 +1497,7 @@ extern "C" int fgn_x3_row_tile(long long M, int Cout, int K, int grp_rows, int g
     return x3_pick_bm(M, Cout, K, grp_rows, grp_valid, 0);
 }
 
-#ifdef X3_PHASES        // tools/micro/build_x3_phases.sh: phase clocks of wave 0 of workgroups 0 / 1 (conv_pw_x3.h)
+#if defined(X3_PHASES) || defined(H2_PHASES)        // tools/micro/build_x3_phases.sh: phase clocks of wave 0 of workgroups 0 / 1 (conv_pw_x3.h, conv_pw_h2.h)
 static unsigned long long* g_x3_ph = nullptr;
 extern "C" int fgn_x3_phases(unsigned long long* host16) {
     if (!g_x3_ph) return FGN_ERR_ARG;
@@ -1803,6 +1803,10 @@ extern "C" int fgn_gemm_h2_f32(const float* x, const void* w_h2, float* y, const
     ConvParams p;
     const int rc = describe_gemm(p, MATH_H2, x, w_h2, y, shift, residual, rows, K, Cout, npad, relu, grp_rows, grp_valid, n_groups);
     if (rc != FGN_DESCRIBED) return rc;
+#ifdef H2_PHASES
+    if (!g_x3_ph && (hipMalloc(&g_x3_ph, 128) != hipSuccess || hipMemset(g_x3_ph, 0, 128) != hipSuccess)) return FGN_ERR_ARG;
+    p.ws = reinterpret_cast<float*>(g_x3_ph);
+#endif
     return launch_h2(p, rows, n_groups, bm, stream);
 }
 

@@ -60,6 +60,31 @@ __device__ __forceinline__ void h2_split4(const float x0, const float x1, const 
         : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "s"(s));
 }
 
+// h2_split4 in its four steps of two instructions, for issue one step at a time in the gaps between MFMAs (an MFMA holds
+// vector issue for half of its cycles): STEP 0 / 1 the low / high halves of the h pairs, 2 / 3 those of the l pairs.  The
+// same instructions in the same order, so the half-register rule above holds whatever lies between two steps; the caller
+// keeps two wait states between step 3 and the first MFMA that reads the planes.
+__device__ __forceinline__ void h2_split4_step(const int step, const float x0, const float x1, const float x2, const float x3,
+                                               const float s, unsigned& h01, unsigned& h23, unsigned& l01, unsigned& l23) {
+    // (`step` is a constant once the caller's loops are unrolled: one of the four statements remains)
+    if (step == 0)
+        asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
+            "v_fma_mixlo_f16 %1, %3, %4, 0"
+            : "=&v"(h01), "=&v"(h23) : "v"(x0), "v"(x2), "s"(s));
+    else if (step == 1)
+        asm("v_fma_mixhi_f16 %0, %2, %4, 0\n\t"
+            "v_fma_mixhi_f16 %1, %3, %4, 0"
+            : "+v"(h01), "+v"(h23) : "v"(x1), "v"(x3), "s"(s));
+    else if (step == 2)
+        asm("v_fma_mixlo_f16 %0, %2, %4, -%5 op_sel:[0,0,0] op_sel_hi:[0,0,1]\n\t"
+            "v_fma_mixlo_f16 %1, %3, %4, -%6 op_sel:[0,0,0] op_sel_hi:[0,0,1]"
+            : "=&v"(l01), "=&v"(l23) : "v"(x0), "v"(x2), "s"(s), "v"(h01), "v"(h23));
+    else
+        asm("v_fma_mixhi_f16 %0, %2, %4, -%5 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
+            "v_fma_mixhi_f16 %1, %3, %4, -%6 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
+            : "+v"(l01), "+v"(l23) : "v"(x1), "v"(x3), "s"(s), "v"(h01), "v"(h23));
+}
+
 // eight f32 -> two planes of eight f16
 __device__ __forceinline__ H2Frag h2_split(const float4& a, const float4& b, const float s) {
     unsigned h[4], l[4];
@@ -112,6 +137,15 @@ struct H2Im2col {
 // at the one workgroup barrier per step.  The chain is KT / KG steps long and each SIMD holds two waves that are out of
 // step in their phases.  In the epilogue group 0 writes its scaled accumulators to the C tile and group 1 adds its own
 // behind a barrier (a fixed order: the result is deterministic); all the threads store.  KG * NST stages of LDS.
+// phase clocks of one wave (tools/x3_probe.py --phases; -DH2_PHASES: the diagnostic build of tools/micro/build_x3_phases.sh
+// only, nothing in the product library executes a stamp): cycles in [wait + barrier | request issue | LDS reads landed |
+// watch + split of fragment 0 | MFMAs (with the split under them) | everything outside the K-tiles], written by wave 0 of
+// workgroups 0 and 1 to p.ws.  The build waits for every LDS read before the third mark, which the product does not.
+#ifdef H2_PHASES
+#define H2_T(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); ph_[i] += now_ - last_; last_ = now_; } while (0)
+#else
+#define H2_T(i) do { } while (0)
+#endif
 template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1>
 __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_h2_kernel(const ConvParams p, const H2Im2col q2, const int total_tiles) {
     // NW / NTHR_G: waves / threads of ONE K-group (the roles wm, wn and the DMA rows are those of the wave inside its group)
@@ -125,9 +159,12 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     constexpr int B_LD = 2 * BQ / NW;                       // weight wave-instructions per wave per K-tile
     static_assert(A_LD * 8 * NW == BM && B_LD * NW == 2 * BQ, "tile / wave split");
     constexpr int PER = A_LD + B_LD;                        // LDS-DMA wave-instructions per wave per K-tile
-    constexpr int D = NST - 1;                              // K-tiles in flight ahead of the one being multiplied
     constexpr int ROWS_PER_PASS = NTHR_G / 8;               // A rows one pass of a K-group's DMAs covers
-    static_assert(NST == 2 || NST == 3, "ring of 2 or 3 stages");      // (three: measured 5-12 % slower, DESIGN appendix A row 53)
+    // The two-K-group instance without the implicit-GEMM loader keeps the K loop and the issue cursor it had before the
+    // branch-free cursor below: with that cursor every 6504 x 1024 -> 256 launch of an episode measured 0.7 - 1 us slower in
+    // isolation (23.1 - 24.9 -> 23.8 - 25.6 us, whichever of its parts was taken out again)
+    constexpr bool OLD_CURSOR = KG == 2 && !IM2COL;
+    static_assert(NST == 2, "a ring of two stages: one K-tile in flight ahead of the one being multiplied");   // (three: measured 5-12 % slower, DESIGN appendix A row 53)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
 
     const int t = threadIdx.x, lane = t & 63;
@@ -147,7 +184,7 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     const i32x4 w_rs = make_rsrc(p.w3, p.w3_bytes);
     const bool dual = !IM2COL && p.x2 != nullptr;
     const i32x4 x2_rs = make_rsrc(dual ? p.x2 : p.x, dual ? p.x2_bytes : p.x_bytes);
-    const int KT = p.K / BK / KG;                // K-steps: the K-tiles of one group; >= D, K / BK a multiple of KG (launcher)
+    const int KT = p.K / BK / KG;                // K-steps: the K-tiles of one group; >= 2, K / BK a multiple of KG (launcher)
     const unsigned kt_bytes = (unsigned)(2 * p.npad3 * 64);          // one K-tile of the image, both planes, all rows
     const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<size_t>(smem_h2) + kg * (NST * STAGE));   // the group's ring
     const unsigned wave_row_bytes = __builtin_amdgcn_readfirstlane(wv) * 8 * 128;
@@ -238,26 +275,80 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
         }
         return o;
     };
-    auto issue = [&](const Offs& o, int step, int stage) {
+    // Issue cursor: the K-step the next request is for, as the byte offsets it takes (all wave-uniform).  seek() places
+    // it once per output tile; advance() moves it one K-step on by adds of loop-invariant values - no multiply, no division
+    // and no branch per K-tile.  IM2COL: the K-tiles of a filter row are contiguous in an NHWC row (Cin * 4 = 128 bytes
+    // x the slices of a tap), so the tap offset grows by 128 per K-tile and by the rest of the image row at a row's end.
+    const unsigned ko_step = (unsigned)(KG * BK * 4), kb_step = (unsigned)KG * kt_bytes;
+    const unsigned ko1 = dual ? (unsigned)(p.kt1 * BK * 4) : 0xffffffffu;      // the second operand's first K-tile, in bytes of a row (one operand: never reached)
+    unsigned c_ko = 0u, c_kb = 0u;                   // the K-tile's bytes in an activation row / in the weight image
+    int c_tap = 0, c_cs = 0, c_kx = 0;               // IM2COL: filter tap, channel slice of it, column of the tap
+    unsigned c_off0 = 0u, c_off1 = 0u;               //         the tap's byte offset in tensor 0 / 1
+    const int im_ct = 1 << q2.cin_shift;
+    const unsigned im_skip0 = (unsigned)((p.W - p.KW) * p.Cin * 4), im_skip1 = (unsigned)((q2.W1 - p.KW) * p.Cin * 4);
+    auto seek = [&](int step) {
         const int kt = step * KG + kg;           // the absolute K-tile
-        const unsigned st = lds_base + stage * STAGE;
+        c_ko = (unsigned)(kt * BK * 4);
+        c_kb = (unsigned)kt * kt_bytes;
+        if constexpr (IM2COL) {
+            c_tap = kt >> q2.cin_shift;
+            c_cs = kt - (c_tap << q2.cin_shift);
+            const int ky = p.KW == 3 ? (c_tap * 43) >> 7 : c_tap;         // tap / 3 for tap <= 8; KW == 1: one column
+            c_kx = c_tap - ky * p.KW;
+            c_off0 = (unsigned)(((ky * p.W + c_kx) * p.Cin + c_cs * BK) * 4);
+            c_off1 = (unsigned)(((ky * q2.W1 + c_kx) * p.Cin + c_cs * BK) * 4);
+        }
+    };
+    auto advance = [&]() {
+        c_ko += ko_step;
+        c_kb += kb_step;
+        if constexpr (IM2COL) {
+#pragma unroll
+            for (int g = 0; g < KG; ++g) {
+                const bool tw = ++c_cs == im_ct;             // the tap's last slice is behind
+                c_cs = tw ? 0 : c_cs;
+                c_tap += tw;
+                c_kx += tw;
+                const bool rw = c_kx == p.KW;                // ... and the filter row's last tap
+                c_kx = rw ? 0 : c_kx;
+                c_off0 += 128u + (rw ? im_skip0 : 0u);
+                c_off1 += 128u + (rw ? im_skip1 : 0u);
+            }
+        }
+    };
+    // LDS-DMA wave-instruction `idx` of the PER a wave issues per K-tile (A_LD activation ones, then B_LD weight ones) for
+    // the cursor's K-tile of the output tile `o`, into the stage at byte `wr` of the group's ring
+    auto piece = [&](const Offs& o, const unsigned wr, const int idx) {
+        const unsigned st = lds_base + wr;
+        if (idx >= A_LD) {
+            const int i = idx - A_LD;
+            lds_dma16_s(w_rs, st + b_lds[i], o.b[i], c_kb);
+            return;
+        }
+        const int i = idx;
+        const unsigned dst = st + wave_row_bytes + i * ROWS_PER_PASS * 128;
+        if constexpr (IM2COL) {
+            const bool ok = (o.a2[i] >> c_tap) & 1u;
+            const unsigned voff = ok ? o.a[i] + ((o.a2[i] >> 31) ? c_off1 : c_off0) : OOB;     // out-of-image taps: zeros
+            lds_dma16_s(x_rs, dst, voff, 0u);
+        } else {
+            // the K-tiles from p.kt1 on come from the second operand: a select of descriptor and offsets, not a branch
+            const bool second = c_ko >= ko1;
+            i32x4 rs;
+            rs[0] = second ? x2_rs[0] : x_rs[0]; rs[1] = second ? x2_rs[1] : x_rs[1];
+            rs[2] = second ? x2_rs[2] : x_rs[2]; rs[3] = x_rs[3];
+            lds_dma16_s(rs, dst, second ? o.a2[i] : o.a[i], second ? c_ko - ko1 : c_ko);
+        }
+    };
+
+    // (OLD_CURSOR) K-step `step` of the output tile `o` into the stage at byte `wr` of the group's ring, the offsets computed
+    // from the step
+    auto issue_step = [&](const Offs& o, const int step, const unsigned wr) {
+        const int kt = step * KG + kg;           // the absolute K-tile
+        const unsigned st = lds_base + wr;
         const unsigned sa = st + wave_row_bytes;
         const unsigned ko = (unsigned)(kt * BK * 4);
-        if constexpr (IM2COL) {
-            // K-tile -> (filter tap, channel slice), wave-uniform; the tap's byte offset differs with the tensor's width
-            const int tap = kt >> q2.cin_shift;
-            const int c0 = (kt - (tap << q2.cin_shift)) * BK;
-            const int ky = p.KW == 3 ? (tap * 43) >> 7 : tap;             // tap / 3 for tap <= 8; KW == 1: one column
-            const int kx = tap - ky * p.KW;
-            const unsigned off0 = (unsigned)(((ky * p.W + kx) * p.Cin + c0) * 4);
-            const unsigned off1 = (unsigned)(((ky * q2.W1 + kx) * p.Cin + c0) * 4);
-#pragma unroll
-            for (int i = 0; i < A_LD; ++i) {
-                const bool ok = (o.a2[i] >> tap) & 1u;
-                const unsigned voff = ok ? o.a[i] + ((o.a2[i] >> 31) ? off1 : off0) : OOB;     // out-of-image taps: zeros
-                lds_dma16_s(x_rs, sa + i * ROWS_PER_PASS * 128, voff, 0u);
-            }
-        } else if (dual && kt >= p.kt1) {
+        if (dual && kt >= p.kt1) {
             const unsigned ko2 = (unsigned)((kt - p.kt1) * BK * 4);
 #pragma unroll
             for (int i = 0; i < A_LD; ++i) lds_dma16_s(x2_rs, sa + i * ROWS_PER_PASS * 128, o.a2[i], ko2);
@@ -304,26 +395,36 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     if (tile < 0) { leave(); return; }
     Offs cur = offsets(m0, n0);
     int ntile = next_active(tile + gridDim.x, nm0, nn0);
-    Offs nxt = cur;
-    if (ntile >= 0) nxt = offsets(nm0, nn0);
-    // issue cursor: the next K-tile to be requested is K-tile ic_kt of the current (ic_next = false) or the next output tile
-    int ic_kt = 0, ic_stage = 0, ahead = 0;
+    auto following = [&]() -> Offs { return ntile >= 0 ? offsets(nm0, nn0) : cur; };
+    Offs nxt = following();
+    // One K-step is in flight ahead of the one being multiplied: iteration kt of an output tile requests K-step kt + 1 of
+    // it, the last one K-step 0 of the next output tile (when there is one) - into the stage the iteration before read
+    // (OLD_CURSOR) the next K-step to be requested is step ic_kt of the current (ic_next = false) or the next output tile
+    int ic_kt = 0;
     bool ic_next = false;
-    auto issue_one = [&]() {
+    auto issue_one = [&](const unsigned wr) {
         if (!ic_next) {
-            issue(cur, ic_kt, ic_stage);
+            issue_step(cur, ic_kt, wr);
             if (++ic_kt == KT) { ic_next = true; ic_kt = 0; }
         } else {
             if (ntile < 0 || ic_kt >= KT) return;
-            issue(nxt, ic_kt, ic_stage);
+            issue_step(nxt, ic_kt, wr);
             ++ic_kt;
         }
-        ic_stage = ic_stage + 1 == NST ? 0 : ic_stage + 1;
-        ++ahead;
     };
+    if constexpr (OLD_CURSOR) {
+        issue_one(0u);
+    } else {
+        seek(0);
 #pragma unroll
-    for (int i = 0; i < D; ++i) issue_one();
-    int stage = 0;                                  // stage of the K-tile being multiplied
+        for (int i = 0; i < PER; ++i) piece(cur, 0u, i);
+        advance();
+    }
+    unsigned rd = 0u;                               // byte offset in the ring of the stage being multiplied: 0 or STAGE
+#ifdef H2_PHASES
+    unsigned long long ph_[7] = {0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
+    const unsigned long long begin_ = last_;
+#endif
 
     while (true) {
         f32x4 acc[2 * RB][4];
@@ -335,16 +436,24 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
         float a_lim = 0.f;                          // |x| above this leaves the f16 range under the current scale (no scale yet:
                                                     // any non-zero element; an all-zero fragment - padded rows - passes as it is)
         a_s = 1.f; a_inv = 1.f;
-        for (int kt = 0; kt < KT; ++kt) {
-            // K-tile `kt` has landed: everything (first K-tile of an output tile: the previous epilogue's stores share
-            // the counter and return in no fixed order with the loads), or all but the K-tile requested after it
-            if (D == 2 && kt > 0 && ahead == 2) x3_wait_vm<PER>(); else x3_wait_vm<0>();
+        // One K-tile, a straight line but for the overflow watch: wait, barrier, the requests for the cursor's
+        // K-tile of the output tile `o` into the other stage (it was last read in the iteration before, and every wave has
+        // passed this one's barrier), LDS reads, watch, split and MFMAs.  `last`: the last K-tile of an output tile
+        auto k_tile = [&](auto&& requests) {
+            // the K-tile has landed: everything in flight is waited for (the first K-tile of an output tile: the previous
+            // epilogue's stores share the counter and return in no fixed order with the loads)
+            H2_T(5);
+            x3_wait_vm<0>();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();            // ... for every wave; and every wave is done with the stage before
-            --ahead;
-            issue_one();
+            asm volatile("" ::: "memory");           // (no LDS read moves above the barrier)
+            H2_T(0);
+            const unsigned wr = rd ^ (unsigned)STAGE;
+            // the requests for the cursor's K-tile of `o` (the last K-tile of the last output tile: none)
+            requests(wr);
             asm volatile("" ::: "memory");
-            const unsigned char* const S = smem_h2 + (KG == 1 ? 0 : kg * (NST * STAGE)) + stage * STAGE;
+            H2_T(1);
+            const unsigned char* const S = smem_h2 + (KG == 1 ? 0 : kg * (NST * STAGE)) + rd;
             float4 alo[2 * RB], ahi[2 * RB];
             f16x8_t bq[4][2];
 #pragma unroll
@@ -358,6 +467,10 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
                 for (int q = 0; q < 2; ++q)
                     bq[j][q] = *reinterpret_cast<const f16x8_t*>(S + b16_rd + j * (16 * 64) + q * (BN * 64));
             __builtin_amdgcn_sched_barrier(0);       // every read of the K-tile in flight before the first split
+#ifdef H2_PHASES
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            H2_T(2);
+#endif
             // a new scale from the maximum of this K-tile's fragment (wave-uniform); the accumulators follow it.  Only finite
             // elements count: a row holding Inf / NaN comes out non-finite whatever the scale, and must not take the scale of
             // the wave's other rows with it (Inf would leave them at the old scale - or at 1 - however large or small they are)
@@ -396,23 +509,80 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
                 // (a_lim = 0 until a scale is chosen: the first K-tile with a non-zero element chooses it)
                 if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(big <= a_lim)) != 0ull, 0)) adapt();
             }
+            if constexpr (RB == 2 || OLD_CURSOR) {
+                // every row fragment split, then multiplied, one after the other (the split of the next fragment in the gaps
+                // of this one's MFMAs, as below, measured 2 - 4 % slower on the 128-row instance: DESIGN appendix A row 58)
 #pragma unroll
-            for (int i = 0; i < 2 * RB; ++i) {
-                const H2Frag a = h2_split(alo[i], ahi[i], a_s);
+                for (int i = 0; i < 2 * RB; ++i) {
+                    const H2Frag a = h2_split(alo[i], ahi[i], a_s);
+#ifdef H2_PHASES
+                    if (i == 0) { asm volatile("s_nop 0" ::"v"(a.hi), "v"(a.lo)); H2_T(3); }
+#endif
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    f32x4 c = acc[i][j];
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, bq[j][0], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, bq[j][1], c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, bq[j][0], c, 0, 0, 0);
-                    acc[i][j] = c;
+                    for (int j = 0; j < 4; ++j) {
+                        f32x4 c = acc[i][j];
+                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.lo, bq[j][0], c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, bq[j][1], c, 0, 0, 0);
+                        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a.hi, bq[j][0], c, 0, 0, 0);
+                        acc[i][j] = c;
+                    }
+                }
+            } else {
+                // row fragment 0 is split ahead of the MFMAs, fragment 1 in the gaps of fragment 0's: one step (two
+                // instructions) behind each of its first eight MFMAs, pinned there by a scheduling barrier per MFMA
+                unsigned fh[2][4], fl[2][4];         // the planes of the fragment being multiplied / being split
+                h2_split4(alo[0].x, alo[0].y, alo[0].z, alo[0].w, a_s, fh[0][0], fh[0][1], fl[0][0], fl[0][1]);
+                h2_split4(ahi[0].x, ahi[0].y, ahi[0].z, ahi[0].w, a_s, fh[0][2], fh[0][3], fl[0][2], fl[0][3]);
+#ifdef H2_PHASES
+                asm volatile("s_nop 0" ::"v"(fh[0][0]), "v"(fl[0][3]));
+                H2_T(3);
+#endif
+#pragma unroll
+                for (int i = 0; i < 2 * RB; ++i) {
+                    const int u = i & 1, v = u ^ 1;
+                    const f16x8_t a_hi = __builtin_bit_cast(f16x8_t, make_uint4(fh[u][0], fh[u][1], fh[u][2], fh[u][3]));
+                    const f16x8_t a_lo = __builtin_bit_cast(f16x8_t, make_uint4(fl[u][0], fl[u][1], fl[u][2], fl[u][3]));
+                    const int n = i + 1 < 2 * RB ? i + 1 : i;        // (the last fragment: nothing left to split)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        f32x4 c = acc[i][j];
+#pragma unroll
+                        for (int m = 0; m < 3; ++m) {
+                            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(m == 0 ? a_lo : a_hi, bq[j][m == 1 ? 1 : 0], c, 0, 0, 0);
+                            if (m < 2 && i + 1 < 2 * RB) {
+                                const int sn = 2 * j + m, half = sn >> 2;      // step sn of the eight of a fragment: 4 per half
+                                const float4& x = half == 0 ? alo[n] : ahi[n];
+                                h2_split4_step(sn & 3, x.x, x.y, x.z, x.w, a_s, fh[v][2 * half], fh[v][2 * half + 1],
+                                               fl[v][2 * half], fl[v][2 * half + 1]);
+                            }
+                            __builtin_amdgcn_sched_barrier(0);       // (nothing moves out of its gap)
+                        }
+                        acc[i][j] = c;
+                    }
                 }
             }
-            stage = stage + 1 == NST ? 0 : stage + 1;
+#ifdef H2_PHASES
+            asm volatile("s_nop 0" ::"v"(acc[0][0][0]), "v"(acc[2 * RB - 1][3][3]));
+            H2_T(4);
+            ++ph_[6];
+#endif
+            if constexpr (!OLD_CURSOR) advance();
+            rd = wr;
+        };
+        auto request = [&](const Offs& o, const unsigned wr) {
+#pragma unroll
+            for (int k = 0; k < PER; ++k) piece(o, wr, k);
+        };
+        if constexpr (OLD_CURSOR) {
+            for (int kt = 0; kt < KT; ++kt) k_tile([&](const unsigned wr) { issue_one(wr); });
+        } else {
+            for (int kt = 0; kt < KT - 1; ++kt) k_tile([&](const unsigned wr) { request(cur, wr); });
+            seek(0);
+            k_tile([&](const unsigned wr) { if (ntile >= 0) request(nxt, wr); });
         }
-        // the stage of the last K-tile (the one before `stage` in the ring; group 0's ring) takes the C tile once every wave
+        // the stage of the last K-tile (the other one than `rd` now; group 0's ring) takes the C tile once every wave
         // has read it
-        float* const cbase = reinterpret_cast<float*>(smem_h2 + (stage == 0 ? NST - 1 : stage - 1) * STAGE);
+        float* const cbase = reinterpret_cast<float*>(smem_h2 + (rd ^ (unsigned)STAGE));
         const int em0 = m0, en0 = n0;
         const float* const winv = p.w_inv + (p.grp_rows ? (size_t)(em0 / p.grp_rows) * p.npad3 : 0);
         // one pass per wave row: PR = 32 RB rows x 128 floats (16 / 32 KB: fits the stage for either row tile)
@@ -481,14 +651,23 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
             }
         }
         if (ntile < 0) break;
-        // the next output tile becomes the current one (its first K-tiles are requested already: ic_kt of them)
+        // the next output tile becomes the current one (its first K-step is requested already: the cursor stands at its second)
         tile = ntile; m0 = nm0; n0 = nn0;
         cur = nxt;
-        ic_next = ic_kt >= KT;                       // (KT == D: the whole new current tile is requested already)
-        if (ic_next) ic_kt = 0;
+        if constexpr (OLD_CURSOR) {
+            ic_next = ic_kt >= KT;                   // (KT == 1: the whole new current tile is requested already)
+            if (ic_next) ic_kt = 0;
+        }
         ntile = next_active(tile + gridDim.x, nm0, nn0);
-        if (ntile >= 0) nxt = offsets(nm0, nn0);
+        nxt = following();
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef H2_PHASES
+    if (p.ws && lane == 0 && wv == 0 && kg == 0 && blockIdx.x < 2) {
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(p.ws) + 8 * blockIdx.x;
+        for (int i = 0; i < 7; ++i) o[i] = ph_[i];
+        o[7] = __builtin_amdgcn_s_memtime() - begin_;
+    }
+#endif
     leave();
 }

@@ -83,6 +83,25 @@ def timed_round_robin(fns: dict, reps: int, rounds: int = 5) -> dict:
     return {k: round(sorted(v)[len(v) // 2], 1) for k, v in res.items()}
 
 
+def h2_phases(fn):
+    """Phase clocks of wave 0 of workgroup 0 of one conv_pw_h2_kernel launch (a library built with -DH2_PHASES:
+    tools/micro/build_x3_phases.sh, FGN_HIP_LIB=tools/micro/libfgn_hip_h2ph.so), cycles per K-tile."""
+    import ctypes
+    raw = ctypes.CDLL(ops._lib.LIB_PATH)
+    if not hasattr(raw, 'fgn_x3_phases'):
+        return None
+    buf = (ctypes.c_ulonglong * 16)()
+    raw.fgn_x3_phases(buf)                      # clear
+    fn()
+    if raw.fgn_x3_phases(buf) != 0:
+        return None
+    v = list(buf[0:8])
+    steps = max(v[6], 1)
+    return dict(wait_barrier=round(v[0] / steps), issue=round(v[1] / steps), lds_landed=round(v[2] / steps),
+                watch_split0=round(v[3] / steps), mfma=round(v[4] / steps), outside_per_ktile=round(v[5] / steps),
+                ktiles=v[6], kernel_cycles=v[7])
+
+
 # default instances (16x16x32 MFMA): 64 / 128 rows, nine terms; + 2000: the 32x32x16 form (experiments build)
 VARIANTS = (('x6_bm64', 64, 6), ('x6_bm128', 128, 6), ('x9_bm64', 64, 9), ('x6_bm64_mfma32', 2064, 6), ('x6_bm128_mfma32', 2128, 6),
             ('x6_bm129_mfma32', 2129, 6))
@@ -93,7 +112,7 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--only', default='')
     ap.add_argument('--im2col', action='store_true', help="layer3.0's 3x3 / stride 2 implicit GEMM, one K-group against two")
-    ap.add_argument('--phases', action='store_true', help='phase clocks (FGN_HIP_LIB=tools/micro/libfgn_hip_x3ph.so)')
+    ap.add_argument('--phases', action='store_true', help='phase clocks (FGN_HIP_LIB=tools/micro/libfgn_hip_x3ph.so for conv_pw_x3_kernel, libfgn_hip_h2ph.so for conv_pw_h2_kernel)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     g = torch.Generator().manual_seed(1)
@@ -125,6 +144,10 @@ def main():
             d = (out[:, :valid].double() - ref).abs()
             outs[tag], fns[tag] = out, fn
             rec[tag] = dict(max_err=d.max().item() / scale, mean_err=d.mean().item() / scale)
+            if args.phases:
+                ph = h2_phases(fn)
+                if ph:
+                    rec[tag]['wg0_cycles_per_ktile'] = ph
         for tag, bm, nt in VARIANTS:
             if G > 1 and gr % (128 if bm % 1000 >= 128 else 64):
                 continue
