@@ -9,6 +9,7 @@ warm-up 100 iterations, 3 epochs) on the MI355X path: DataLoader(ds, collate_fn_
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --augment --photometric
     python examples/train_loop.py --dataset OMNIISEG --spp-source --augment-spp --photometric-spp
+    python examples/train_loop.py --dataset OMNIISEG --source-size 320 --augment --photometric --augs coco
 
 ``--source-size S``: the loader hands over decoded S x S pixels and the detector resizes them on the GPU
 (``qry_resize_to``); ``--spp-source``: the supports are cut from their source images on the GPU (``spp_crop_to``);
@@ -19,7 +20,10 @@ training configurations); ``--photometric`` (needs ``--augment``): the other six
 well (``qry_photometric``), and both rows come from one joint draw.  ``--augment-spp`` (needs ``--spp-source``): every
 support instance is augmented on the GPU behind its cut (``spp_augment``, one row per instance and epoch -
 ``augment_spp=True`` of the reference's training configurations); ``--photometric-spp`` (needs ``--augment-spp``): the
-photometric operators as well (``spp_photometric``).  The evaluation at the end is without augmentation.
+photometric operators as well (``spp_photometric``).  ``--augs coco``: the rows are drawn like COCO's ``augs_seq`` (flip,
+one of hue / saturation / brightness, then a blur) and the photometric half travels as a chain of two operators per image
+(``qry_photometric_chain`` / ``spp_photometric_chain``), which one kernel applies in one pass.  The evaluation at the
+end is without augmentation.
 
 The backbone is frozen as in fgn_r50_c4_densecl.py:31; with no pretrained checkpoint here it is randomly
 initialised, so this demonstrates the loop (losses fall on the training episodes), not a trained detector.
@@ -62,6 +66,8 @@ def main():
                     help='augment every support instance on the GPU behind its cut (needs --spp-source)')
     ap.add_argument('--photometric-spp', action='store_true',
                     help='the photometric operators on the supports as well (needs --augment-spp)')
+    ap.add_argument('--augs', default='natural', choices=['natural', 'coco'],
+                    help='the sequence the augmentation rows are drawn like: natural_fst\'s or COCO\'s (a chain)')
     args = ap.parse_args()
     if args.augment_spp and not args.spp_source:
         ap.error('--augment-spp needs --spp-source: the supports are augmented behind their cut from the source images')
@@ -81,7 +87,8 @@ def main():
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,
                                        raw_uint8=source, source_size=args.source_size, spp_source=args.spp_source,
                                        augment_qry=args.augment, photometric_qry=args.photometric,
-                                       augment_spp=args.augment_spp, photometric_spp=args.photometric_spp)
+                                       augment_spp=args.augment_spp, photometric_spp=args.photometric_spp,
+                                       augs=args.augs)
     model = FGN(args.n_ways, args.k_shots)
     if source:
         model.set_input_norm(**ds.input_norm)
@@ -114,7 +121,8 @@ def main():
         results = [r for data in loader
                    for r in model.simple_test(**{k: v for k, v in data.items()
                                                  if k not in ('qry_augment', 'qry_photometric', 'spp_augment',
-                                                              'spp_photometric')}, rescale=True)]
+                                                              'spp_photometric', 'qry_photometric_chain',
+                                                              'spp_photometric_chain')}, rescale=True)]
         print(ds.evaluate(results=results, model_dir=work_dir))
 
 

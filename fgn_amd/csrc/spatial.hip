@@ -590,10 +590,9 @@ __device__ __forceinline__ void photo_pixel(const int* __restrict__ rc, int p, i
 
 // A point operator on tiles of PHOTO_BLOCK * PHOTO_RUN pixels of the flat pixel array: a lane takes PHOTO_RUN
 // consecutive pixels, as three dwords each way where both slots are dword-aligned and the run is whole, bytewise
-// otherwise (odd slots, the image's last pixels).
-template <int OP>
-__device__ __forceinline__ void photo_point(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
-                                            const int* __restrict__ rc, int npix) {
+// otherwise (odd slots, the image's last pixels).  ``f(p, px)`` rewrites the three values of pixel p in registers.
+template <class F>
+__device__ __forceinline__ void photo_point(const uint8_t* __restrict__ in, uint8_t* __restrict__ out, int npix, F f) {
     const bool aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 3u) == 0;
     const int tiles = (npix + PHOTO_BLOCK * PHOTO_RUN - 1) / (PHOTO_BLOCK * PHOTO_RUN);
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -613,7 +612,7 @@ __device__ __forceinline__ void photo_point(const uint8_t* __restrict__ in, uint
         }
 #pragma unroll
         for (int j = 0; j < PHOTO_RUN; ++j)
-            if (j < n) photo_pixel<OP>(rc, p0 + j, v + 3 * j);
+            if (j < n) f(p0 + j, v + 3 * j);
         if (wide) {
             unsigned wd[3] = {0u, 0u, 0u};
 #pragma unroll
@@ -636,41 +635,27 @@ __device__ __forceinline__ int photo_reflect101(int k, int n) {
     return r < n ? r : p - r;
 }
 
-// src [n_img][stride] bytes, image b as [h_b, w_b, 3] at the start of its slot (any byte alignment), records from the
-// DEVICE array recs[b] (no launch argument depends on a source size or on an operator) -> dst in the same layout: bytes
-// [0, 3 h w) of the slot are written, the rest of it is left alone.  A record out of range, or an image that does not fit
-// its slot, gets its WHOLE slot written as zeros and none of its source bytes are read.
-// Blur: the 32 x 32 tile's input with a halo of the record's radii goes to LDS as bytes (reflected indices, so every
-// read is inside the image), a horizontal pass leaves int32 sums (<= 255 * 2^11) of its 32 + 2 ry rows in LDS, a vertical
-// pass makes the bytes.  No rounding between the passes: the separable form is the 2D rule bit for bit.  36 KB of LDS.
-__global__ __launch_bounds__(PHOTO_BLOCK) void photometric_u8hwc3_kernel(const uint8_t* __restrict__ src,
-                                                                         uint8_t* __restrict__ dst, long long stride,
-                                                                         const int* __restrict__ recs) {
+// The whole slot of a refused image as zeros, by all workgroups of the image.
+__device__ __forceinline__ void photo_zero_slot(uint8_t* __restrict__ out, long long stride) {
+    for (long long o = ((long long)blockIdx.x * PHOTO_BLOCK + (int)threadIdx.x) * 16; o < stride;
+         o += (long long)gridDim.x * PHOTO_BLOCK * 16)
+        for (int k = 0; k < 16; ++k)
+            if (o + k < stride) out[o + k] = 0;
+}
+
+// The blur of record rc over the image, a 32 x 32 tile per workgroup at a time: the tile's input with a halo of the
+// record's radii goes to LDS as bytes (reflected indices, so every read is inside the image), a horizontal pass leaves
+// int32 sums (<= 255 * 2^11) of its 32 + 2 ry rows in LDS, a vertical pass makes the bytes.  No rounding between the
+// passes: the separable form is the 2D rule bit for bit.  36 KB of LDS.  ``f(p, px)`` rewrites a staged pixel in
+// registers on its way to LDS, p = sy * w + sx being the SOURCE pixel's own flat index, halo and reflected pixels
+// included: the tile then holds what an intermediate image after f would have held.  UNROLL: staged pixels in flight.
+template <int UNROLL, class F>
+__device__ __forceinline__ void photo_blur(const uint8_t* __restrict__ in, uint8_t* __restrict__ out,
+                                           const int* __restrict__ rc, int h, int w, F f) {
     __shared__ uint8_t tin[PHOTO_IN][PHOTO_IN * 3];
     __shared__ int hsum[PHOTO_IN][PHOTO_TILE * 3];
     __shared__ int wgt[2][PHOTO_R_MAX + 1];
-    const int b = blockIdx.y;
     const int tid = threadIdx.x;
-    const int* rc = recs + (size_t)b * PHOTO_REC_INTS;
-    const uint8_t* in = src + (long long)b * stride;
-    uint8_t* out = dst + (long long)b * stride;
-    if (!photo_record_ok(rc, stride)) {
-        for (long long o = ((long long)blockIdx.x * PHOTO_BLOCK + tid) * 16; o < stride;
-             o += (long long)gridDim.x * PHOTO_BLOCK * 16)
-            for (int k = 0; k < 16; ++k)
-                if (o + k < stride) out[o + k] = 0;
-        return;
-    }
-    const int h = rc[0], w = rc[1], op = rc[2];
-    switch (op) {
-        case 0: photo_point<0>(in, out, rc, h * w); return;
-        case 1: photo_point<1>(in, out, rc, h * w); return;
-        case 2: photo_point<2>(in, out, rc, h * w); return;
-        case 4: photo_point<4>(in, out, rc, h * w); return;
-        case 5: photo_point<5>(in, out, rc, h * w); return;
-        case 6: photo_point<6>(in, out, rc, h * w); return;
-        default: break;
-    }
     const int rx = rc[6], ry = rc[7];
     if (tid <= rx) wgt[0][tid] = rc[PHOTO_PAYLOAD + tid];
     if (tid <= ry) wgt[1][tid] = rc[PHOTO_PAYLOAD + PHOTO_R_MAX + 1 + tid];
@@ -681,14 +666,17 @@ __global__ __launch_bounds__(PHOTO_BLOCK) void photometric_u8hwc3_kernel(const u
         const int ty = t / tiles_x;
         const int y0 = ty * PHOTO_TILE, x0 = (t - ty * tiles_x) * PHOTO_TILE;
         __syncthreads();                                    // (the weights; the last tile's reads of tin and hsum)
-#pragma unroll 4
+#pragma unroll UNROLL
         for (int i = tid; i < ih * iw; i += PHOTO_BLOCK) {             // (unrolled: several pixels' loads in flight)
             const int ly = i / iw, lx = i - ly * iw;
             const int sy = photo_reflect101(y0 - ry + ly, h), sx = photo_reflect101(x0 - rx + lx, w);
-            const uint8_t* p = in + (unsigned)((sy * w + sx) * 3);              // (< 3 * 16384^2: a 32-bit offset)
-            tin[ly][3 * lx] = p[0];
-            tin[ly][3 * lx + 1] = p[1];
-            tin[ly][3 * lx + 2] = p[2];
+            const int q = sy * w + sx;
+            const uint8_t* p = in + (unsigned)(q * 3);                          // (< 3 * 16384^2: a 32-bit offset)
+            int px[3] = {(int)p[0], (int)p[1], (int)p[2]};
+            f(q, px);
+            tin[ly][3 * lx] = (uint8_t)px[0];
+            tin[ly][3 * lx + 1] = (uint8_t)px[1];
+            tin[ly][3 * lx + 2] = (uint8_t)px[2];
         }
         __syncthreads();
         for (int i = tid; i < ih * ROW; i += PHOTO_BLOCK) {
@@ -710,6 +698,35 @@ __global__ __launch_bounds__(PHOTO_BLOCK) void photometric_u8hwc3_kernel(const u
     }
 }
 
+// src [n_img][stride] bytes, image b as [h_b, w_b, 3] at the start of its slot (any byte alignment), records from the
+// DEVICE array recs[b] (no launch argument depends on a source size or on an operator) -> dst in the same layout: bytes
+// [0, 3 h w) of the slot are written, the rest of it is left alone.  A record out of range, or an image that does not fit
+// its slot, gets its WHOLE slot written as zeros and none of its source bytes are read.
+// The blur is photo_blur above, with nothing done to a staged pixel.
+__global__ __launch_bounds__(PHOTO_BLOCK) void photometric_u8hwc3_kernel(const uint8_t* __restrict__ src,
+                                                                         uint8_t* __restrict__ dst, long long stride,
+                                                                         const int* __restrict__ recs) {
+    const int b = blockIdx.y;
+    const int* rc = recs + (size_t)b * PHOTO_REC_INTS;
+    const uint8_t* in = src + (long long)b * stride;
+    uint8_t* out = dst + (long long)b * stride;
+    if (!photo_record_ok(rc, stride)) {
+        photo_zero_slot(out, stride);
+        return;
+    }
+    const int h = rc[0], w = rc[1], op = rc[2];
+    switch (op) {
+        case 0: photo_point(in, out, h * w, [=](int p, int* px) { photo_pixel<0>(rc, p, px); }); return;
+        case 1: photo_point(in, out, h * w, [=](int p, int* px) { photo_pixel<1>(rc, p, px); }); return;
+        case 2: photo_point(in, out, h * w, [=](int p, int* px) { photo_pixel<2>(rc, p, px); }); return;
+        case 4: photo_point(in, out, h * w, [=](int p, int* px) { photo_pixel<4>(rc, p, px); }); return;
+        case 5: photo_point(in, out, h * w, [=](int p, int* px) { photo_pixel<5>(rc, p, px); }); return;
+        case 6: photo_point(in, out, h * w, [=](int p, int* px) { photo_pixel<6>(rc, p, px); }); return;
+        default: break;
+    }
+    photo_blur<4>(in, out, rc, h, w, [](int, int*) {});
+}
+
 extern "C" int fgn_photometric_u8hwc3(const unsigned char* src, unsigned char* dst, long long stride_bytes,
                                       const int* recs, int n_img, hipStream_t stream) {
     if (!src || !dst || !recs) return FGN_ERR_ARG;
@@ -722,6 +739,89 @@ extern "C" int fgn_photometric_u8hwc3(const unsigned char* src, unsigned char* d
     const int grid = (int)std::min<long long>((stride_bytes + tile_bytes - 1) / tile_bytes, PHOTO_GRID_CAP);
     hipLaunchKernelGGL(photometric_u8hwc3_kernel, dim3(grid, n_img), dim3(PHOTO_BLOCK), 0, stream, src, dst,
                        stride_bytes, recs);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------
+// A chain of photometric operators in one pass (COCODS.augs_seq, coco_ds.py:45-59: one of AddToHue / AddToSaturation /
+// AddToBrightness, then GaussianBlur): image b has n_ops records at recs[b][0..n_ops), applied in order, of the form
+// "point operators, then at most one blur".  The rule is the left fold of photometric_image_u8 over the records
+// (fgn_amd/fewshot_ds.py photometric_chain_u8) and the kernel agrees with it bit for bit.  Every
+// operator but the blur is a function of (pixel index, the pixel's three bytes, record), so the point stages run on a
+// pixel in registers one after the other - in the run of four pixels of photo_point where the chain has no blur, in the
+// staging loop of photo_blur where it ends in one: one read and one write of the image either way.
+// ----------------------------------------------------------------------------------
+constexpr int PHOTO_CHAIN_MAX = 3;
+
+// Every record inside its sets (photo_record_ok), one (h, w) for the image, and only operator-0 records behind a blur.
+__device__ __forceinline__ bool photo_chain_ok(const int* __restrict__ rcs, int n_ops, long long stride) {
+    bool ok = true, blurred = false;
+    for (int s = 0; s < n_ops; ++s) {
+        const int* rc = rcs + s * PHOTO_REC_INTS;
+        ok = ok && photo_record_ok(rc, stride) && rc[0] == rcs[0] && rc[1] == rcs[1] && !(blurred && rc[2] != 0);
+        blurred = blurred || rc[2] == 3;
+    }
+    return ok;
+}
+
+// One stage of a chain on a pixel in registers; the operator is workgroup-uniform.  Operator 0 and the blur (which the
+// caller runs behind the point stages) leave the pixel as it is, and rc is then not read.
+__device__ __forceinline__ void photo_stage(const int* __restrict__ rc, int op, int p, int px[3]) {
+    switch (op) {
+        case 1: photo_pixel<1>(rc, p, px); break;
+        case 2: photo_pixel<2>(rc, p, px); break;
+        case 4: photo_pixel<4>(rc, p, px); break;
+        case 5: photo_pixel<5>(rc, p, px); break;
+        case 6: photo_pixel<6>(rc, p, px); break;
+        default: break;
+    }
+}
+
+// Slots and zeroing as photometric_u8hwc3_kernel; recs [n_img][n_ops][64].  An image whose chain fails photo_chain_ok
+// gets its WHOLE slot written as zeros and none of its source bytes are read.
+__global__ __launch_bounds__(PHOTO_BLOCK) void photometric_chain_u8hwc3_kernel(const uint8_t* __restrict__ src,
+                                                                               uint8_t* __restrict__ dst,
+                                                                               long long stride,
+                                                                               const int* __restrict__ recs, int n_ops) {
+    const int b = blockIdx.y;
+    const int* rcs = recs + (size_t)b * n_ops * PHOTO_REC_INTS;
+    const uint8_t* in = src + (long long)b * stride;
+    uint8_t* out = dst + (long long)b * stride;
+    if (!photo_chain_ok(rcs, n_ops, stride)) {
+        photo_zero_slot(out, stride);
+        return;
+    }
+    const int h = rcs[0], w = rcs[1];
+    const int* rc1 = rcs + PHOTO_REC_INTS;
+    const int* rc2 = rcs + 2 * PHOTO_REC_INTS;
+    const int op0 = rcs[2], op1 = n_ops > 1 ? rc1[2] : 0, op2 = n_ops > 2 ? rc2[2] : 0;
+    auto stages = [=](int p, int* px) {
+        photo_stage(rcs, op0, p, px);
+        photo_stage(rc1, op1, p, px);
+        photo_stage(rc2, op2, p, px);
+    };
+    const int* blur = op0 == 3 ? rcs : (op1 == 3 ? rc1 : (op2 == 3 ? rc2 : nullptr));
+    if (!blur) {
+        photo_point(in, out, h * w, stages);
+        return;
+    }
+    photo_blur<1>(in, out, blur, h, w, stages);     // (one staged pixel at a time: an unrolled copy of the stages spills SGPRs)
+}
+
+extern "C" int fgn_photometric_chain_u8hwc3(const unsigned char* src, unsigned char* dst, long long stride_bytes,
+                                            const int* recs, int n_ops, int n_img, hipStream_t stream) {
+    if (!src || !dst || !recs) return FGN_ERR_ARG;
+    if (n_img < 0 || n_img > 65535 || stride_bytes < 0 || stride_bytes > (1ll << 40)) return FGN_ERR_SHAPE;
+    if (n_ops < 1 || n_ops > PHOTO_CHAIN_MAX) return FGN_ERR_SHAPE;
+    if (n_img == 0 || stride_bytes == 0) return FGN_OK;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src), d = reinterpret_cast<uintptr_t>(dst);
+    const uintptr_t span = (uintptr_t)n_img * (uintptr_t)stride_bytes;
+    if (a < d + span && d < a + span) return FGN_ERR_ARG;     // (the blur reads neighbours: never in place)
+    const long long tile_bytes = 3ll * PHOTO_BLOCK * PHOTO_RUN;
+    const int grid = (int)std::min<long long>((stride_bytes + tile_bytes - 1) / tile_bytes, PHOTO_GRID_CAP);
+    hipLaunchKernelGGL(photometric_chain_u8hwc3_kernel, dim3(grid, n_img), dim3(PHOTO_BLOCK), 0, stream, src, dst,
+                       stride_bytes, recs, n_ops);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }

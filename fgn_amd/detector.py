@@ -481,7 +481,9 @@ class _SupportWindows(NamedTuple):
     where the ``spp_imgs`` tensor stands; ``spp_isegmaps`` is None beside it (the kernel makes the masks).  With an
     augmentation (``spp_augment`` / ``spp_photometric``): ``aug`` int32 [n,16], the records of
     ``fewshot_ds.query_augment_record`` at S -> S, and ``photo`` int32 [n,64], the records of
-    ``fewshot_ds.query_photometric_record`` - or None where every instance's is neutral (no photometric launch)."""
+    ``fewshot_ds.query_photometric_record`` - or None where every instance's is neutral (no photometric launch); with
+    ``spp_photometric_chain`` and an instance of two active operators, int32 [n,P,64], the records of
+    ``fewshot_ds.photometric_chain_records``, for the chain kernel."""
     src: torch.Tensor
     msk: torch.Tensor
     rec: torch.Tensor
@@ -503,8 +505,9 @@ class _SupportWindows(NamedTuple):
         if self.aug is None:
             return ops.support_from_source(self.src, self.msk, self.rec, lut, self.S)
         crop, msk = ops.support_from_source_u8(self.src, self.msk, self.rec, self.S)
-        if self.photo is not None:
-            crop = ops.photometric_u8(crop.view(crop.shape[0], -1), self.photo).view(crop.shape)
+        if self.photo is not None:                  # ([n,64]: one operator per instance; [n,P,64]: a chain of them)
+            run = ops.photometric_u8 if self.photo.dim() == 2 else ops.photometric_chain_u8
+            crop = run(crop.view(crop.shape[0], -1), self.photo).view(crop.shape)
         return ops.support_augment(crop, msk, self.aug, lut, self.S)
 
 
@@ -1105,6 +1108,36 @@ class FGN(torch.nn.Module):
         return torch.from_numpy(recs) if recs[:, 2].any() else None
 
     @staticmethod
+    def _chain_launch(recs: np.ndarray):
+        """Compacted chain records int32 [n,3,64] (``fewshot_ds.photometric_chain_records``) -> what is launched: None
+        where no image has an active operator; int32 [n,64], the records of the single-operator launch
+        (``ops.photometric_u8``), where every image has at most one; else int32 [n,P,64], P the longest chain, for
+        ``ops.photometric_chain_u8``."""
+        depth = int((recs[:, :, 2] != 0).sum(1).max()) if len(recs) else 0
+        if depth == 0:
+            return None
+        return torch.from_numpy(np.ascontiguousarray(recs[:, 0] if depth == 1 else recs[:, :depth]))
+
+    @staticmethod
+    def _photometric_chain_records(qry_photometric_chain, rs: dict, qry_augment=None, aug_recs=None):
+        """The contract of ``qry_photometric_chain`` (host only, nothing is queued): [B,P,3] finite rows of
+        ``fewshot_ds.PHOTO_PARAMS``, P in 1..3, each inside the sets of ``qry_photometric`` and of the form "point
+        operators, then at most one blur" (``fewshot_ds.check_photometric_chain``).  -> ``_chain_launch`` of the compacted
+        records; an image whose geometric row fell back gets the neutral chain, as in ``_photometric_records``."""
+        from . import fewshot_ds as fd
+        a = _host(qry_photometric_chain)
+        if a.dtype.kind not in 'iuf' or a.ndim != 3 or a.shape[0] != rs['B'] or \
+                not 1 <= a.shape[1] <= fd.PHOTO_CHAIN_MAX or a.shape[2] != len(fd.PHOTO_PARAMS):
+            raise ValueError(f'qry_photometric_chain must be [B,P,{len(fd.PHOTO_PARAMS)}] numbers {fd.PHOTO_PARAMS} with P '
+                             f'in 1..{fd.PHOTO_CHAIN_MAX} for {rs["B"]} images, got {a.dtype} {list(a.shape)}')
+        recs = np.stack([fd.photometric_chain_records(c, hw, rs['hw']) for c, hw in zip(a, rs['sizes'])])
+        if qry_augment is not None:
+            for i, (g, hw) in enumerate(zip(_host(qry_augment), rs['sizes'])):
+                if not fd.augment_is_neutral(fd.check_augment_params(g)) and not aug_recs[i, 2:6].any():
+                    recs[i] = fd.photometric_chain_records(None, hw, rs['hw'])
+        return FGN._chain_launch(recs)
+
+    @staticmethod
     def _refuse_augment(**given) -> None:
         """The test path takes none of the augmentation arguments (by keyword, refused in the order given)."""
         for name, v in given.items():
@@ -1112,15 +1145,29 @@ class FGN(torch.nn.Module):
                 raise ValueError(f'{name} is for forward_train: the test is without augmentation')
 
     @staticmethod
-    def _support_plans(spp_augment, spp_photometric, sp: dict) -> dict:
+    def _support_plans(spp_augment, spp_photometric, sp: dict, spp_photometric_chain=None) -> dict:
         """The contract of ``spp_augment`` / ``spp_photometric`` (host only, nothing is queued): [B,N*K,8] / [B,N*K,3]
         finite rows ([N*K,.] for a single support set) inside the sets and bounds of the queries' rows, at S -> S.  ``sp``:
         the dict of ``_source_supports``, whose boxes the plan starts from.  -> ``sp`` with ``boxes`` replaced by
         ``fewshot_ds.support_augment_plan``'s and, unless every instance is neutral after the per-instance fallback,
-        ``aug`` int32 [n,16] and ``photo`` int32 [n,64] (None where every photometric record is neutral)."""
+        ``aug`` int32 [n,16] and ``photo`` int32 [n,64] (None where every photometric record is neutral).
+        ``spp_photometric_chain`` (in place of ``spp_photometric``): [B,N*K,P,3] ([N*K,P,3] for a single set), a chain per
+        instance through ``fewshot_ds.support_augment_chain_plan``; ``photo`` is then ``_chain_launch`` of its records."""
         from . import fewshot_ds as fd
         B, n, S = sp['B'], sp['n'], sp['S']
         rows = {}
+        chains = None
+        if spp_photometric_chain is not None:
+            chains = _host(spp_photometric_chain)
+            width = len(fd.PHOTO_PARAMS)
+            lead = tuple(chains.shape[:-2])
+            if chains.dtype.kind not in 'iuf' or chains.ndim < 3 or chains.shape[-1] != width or \
+                    not 1 <= chains.shape[-2] <= fd.PHOTO_CHAIN_MAX or \
+                    not (lead == (B, n // B) or (B == 1 and lead == (n,))):
+                raise ValueError(f'spp_photometric_chain must be [B,N*K,P,{width}] numbers {fd.PHOTO_PARAMS} with P in 1..'
+                                 f'{fd.PHOTO_CHAIN_MAX} for {B} support set(s) of {n // B} instances ([N*K,P,{width}] for '
+                                 f'a single set), got {chains.dtype} {list(chains.shape)}')
+            chains = chains.reshape(n, chains.shape[-2], width)
         for name, v, width, fields in (('spp_augment', spp_augment, len(fd.AUG_PARAMS), fd.AUG_PARAMS),
                                        ('spp_photometric', spp_photometric, len(fd.PHOTO_PARAMS), fd.PHOTO_PARAMS)):
             if v is None:
@@ -1131,25 +1178,40 @@ class FGN(torch.nn.Module):
                 f'{name} must be [B,N*K,{width}] numbers {fields} for {B} support set(s) of {n // B} instances '
                 f'([N*K,{width}] for a single set)').reshape(n, width)
         try:
-            recs, precs, boxes, _ = fd.support_augment_plan(rows['spp_augment'], rows['spp_photometric'],
-                                                            sp['boxes'].numpy().reshape(n, 4), S)
+            if chains is not None:
+                recs, precs, boxes, _ = fd.support_augment_chain_plan(rows['spp_augment'], chains,
+                                                                      sp['boxes'].numpy().reshape(n, 4), S)
+            else:
+                recs, precs, boxes, _ = fd.support_augment_plan(rows['spp_augment'], rows['spp_photometric'],
+                                                                sp['boxes'].numpy().reshape(n, 4), S)
         except ValueError as e:             # (the rows' sets and bounds are the queries': name the supports' arguments)
             raise ValueError(str(e).replace('qry_augment', 'spp_augment').replace('qry_photometric', 'spp_photometric')
                              ) from None
         sp = dict(sp, boxes=torch.from_numpy(boxes.reshape(B, n // B, 4)))
-        if recs[:, 2:6].any() or precs[:, 2].any():
+        if chains is not None:
+            photo = FGN._chain_launch(precs)
+            if recs[:, 2:6].any() or photo is not None:
+                sp.update(aug=torch.from_numpy(recs), photo=photo)
+        elif recs[:, 2:6].any() or precs[:, 2].any():
             sp.update(aug=torch.from_numpy(recs), photo=torch.from_numpy(precs) if precs[:, 2].any() else None)
         return sp
 
     def _train_front(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                      spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
                      spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
-                     qry_photometric=None, spp_augment=None, spp_photometric=None, **kwargs) -> dict:
+                     qry_photometric=None, spp_augment=None, spp_photometric=None, qry_photometric_chain=None,
+                     spp_photometric_chain=None, **kwargs) -> dict:
         """The front of a training batch, shared by ``forward_train`` and ``train.Trainer``: the contracts of
-        ``qry_resize_to``, ``spp_crop_to``, ``qry_augment``, ``qry_photometric``, ``spp_augment`` and ``spp_photometric``
-        (every error before anything is queued), then the uploads and the kernels behind them.  -> the keyword arguments
-        of ``train.forward_train``."""
-        for name, v in (('spp_augment', spp_augment), ('spp_photometric', spp_photometric)):
+        ``qry_resize_to``, ``spp_crop_to``, ``qry_augment``, ``qry_photometric``, ``spp_augment``, ``spp_photometric``,
+        ``qry_photometric_chain`` and ``spp_photometric_chain`` (every error before anything is queued), then the uploads
+        and the kernels behind them.  -> the keyword arguments of ``train.forward_train``."""
+        for single, chain, s, c in (('qry_photometric', 'qry_photometric_chain', qry_photometric, qry_photometric_chain),
+                                    ('spp_photometric', 'spp_photometric_chain', spp_photometric, spp_photometric_chain)):
+            if s is not None and c is not None:
+                raise ValueError(f'{single} and {chain} are two forms of one argument: give one operator per image '
+                                 f'({single}) or a chain of them ({chain}), not both')
+        for name, v in (('spp_augment', spp_augment), ('spp_photometric', spp_photometric),
+                        ('spp_photometric_chain', spp_photometric_chain)):
             if v is not None and spp_crop_to is None:
                 raise ValueError(f'{name} needs spp_crop_to: the supports are augmented on the device behind their cut '
                                  f'from the source images')
@@ -1159,11 +1221,14 @@ class FGN(torch.nn.Module):
         if qry_photometric is not None and qry_resize_to is None:
             raise ValueError('qry_photometric needs qry_resize_to: the photometric operators run on the source pixels, '
                              'ahead of their resize')
+        if qry_photometric_chain is not None and qry_resize_to is None:
+            raise ValueError('qry_photometric_chain needs qry_resize_to: the photometric operators run on the source '
+                             'pixels, ahead of their resize')
         sp = None
         if spp_crop_to is not None:                       # (every contract error before anything is queued)
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
-            if spp_augment is not None or spp_photometric is not None:
-                sp = self._support_plans(spp_augment, spp_photometric, sp)
+            if spp_augment is not None or spp_photometric is not None or spp_photometric_chain is not None:
+                sp = self._support_plans(spp_augment, spp_photometric, sp, spp_photometric_chain)
         rs = recs = precs = None
         if qry_resize_to is not None:
             rs = self._source_query(qry_img, qry_resize_to, img_shape, qry_isegmaps)
@@ -1172,12 +1237,16 @@ class FGN(torch.nn.Module):
             if qry_photometric is not None:
                 precs = self._photometric_records(qry_photometric, rs, qry_augment,
                                                   None if recs is None else recs.numpy())
+            if qry_photometric_chain is not None:
+                precs = self._photometric_chain_records(qry_photometric_chain, rs, qry_augment,
+                                                        None if recs is None else recs.numpy())
         if rs is not None or sp is not None:
             dev = self._gpu('forward_train')
         if rs is not None:
             qry_img = _InputForm(source=rs).query(self._upload_source(rs, dev))
             if precs is not None:                          # (all rows neutral after the fallback: no launch)
-                qry_img = qry_img._replace(src=ops.photometric_u8(qry_img.src, precs.to(dev, non_blocking=True)))
+                run = ops.photometric_u8 if precs.dim() == 2 else ops.photometric_chain_u8      # ([B,64] or [B,P,64])
+                qry_img = qry_img._replace(src=run(qry_img.src, precs.to(dev, non_blocking=True)))
             if recs is None:
                 qry_bboxes = self._scaled_boxes(qry_bboxes, rs['sizes'], rs['hw'])
                 qry_isegmaps = [self._resized_masks(g, rs['hw'], dev) for g in qry_isegmaps]
@@ -1383,7 +1452,8 @@ class FGN(torch.nn.Module):
     def forward_train(self, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                       spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, qry_resize_to=None,
                       spp_crop_to=None, spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None,
-                      qry_photometric=None, spp_augment=None, spp_photometric=None, **kwargs) -> Dict:
+                      qry_photometric=None, spp_augment=None, spp_photometric=None, qry_photometric_chain=None,
+                      spp_photometric_chain=None, **kwargs) -> Dict:
         """The loss dict of one training step (fgn.py:125-185) as forward values - see ``fgn_amd.train``.  Keys and
         container types are the reference's: ``loss_rpn_cls`` / ``loss_rpn_bbox`` (lists of one tensor),
         ``loss_cls``, ``ACC-Unbalanced``, ``ACC-Balanced``, ``loss_bbox``, ``loss_mask``.  ``qry_resize_to``: source-size
@@ -1401,14 +1471,20 @@ class FGN(torch.nn.Module):
         the device to the S x S crop behind its cut - after resize and pad, the reference's own order
         (``fewshot_ds.augment_support`` bit for bit; ``get_support`` with ``augment_spp``, base_fst.py:1151-1153;
         DESIGN 4.4.7) - and to ``spp_bboxes`` on the host; an instance whose box leaves its crop is used un-augmented,
-        that instance alone.  At most three launches make the supports, whatever N*K."""
+        that instance alone.  At most three launches make the supports, whatever N*K.  ``qry_photometric_chain`` [B,P,3]
+        / ``spp_photometric_chain`` [B,N*K,P,3] (P in 1..3; each in place of its single-operator sibling, never beside
+        it): a chain of rows per image or instance, applied in order - point operators, then at most one blur, COCO's
+        ``augs_seq`` (coco_ds.py:45-59) - in the same place and in one launch that reads and writes every image once
+        (``fewshot_ds.photometric_chain_u8`` bit for bit).  A batch whose chains hold at most one active
+        operator each makes exactly the single-operator launch, an all-neutral one none."""
         from . import train
         return train.forward_train(self, **self._train_front(
             qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=qry_bboxes_ignore, proposals=proposals,
             spp_imgs=spp_imgs, spp_bboxes=spp_bboxes, spp_isegmaps=spp_isegmaps, img_shape=img_shape,
             qry_resize_to=qry_resize_to, spp_crop_to=spp_crop_to, spp_fill_ratio=spp_fill_ratio, crop_square=crop_square,
             qry_augment=qry_augment, qry_photometric=qry_photometric, spp_augment=spp_augment,
-            spp_photometric=spp_photometric, **kwargs))
+            spp_photometric=spp_photometric, qry_photometric_chain=qry_photometric_chain,
+            spp_photometric_chain=spp_photometric_chain, **kwargs))
 
     @torch.no_grad()
     def simple_test(self, qry_img, qry_bboxes=None, qry_cat_ids=None, qry_isegmaps=None, qry_bboxes_ignore=None,
@@ -1416,9 +1492,10 @@ class FGN(torch.nn.Module):
                     rescale=False, cats_ids_to_sample_real=None, spp_insts_ids=None, idx=None,
                     support_code=None, qry_resize_to=None, results_at_source: bool = False, spp_crop_to=None,
                     spp_fill_ratio: float = 0.8, crop_square: bool = True, qry_augment=None, qry_photometric=None,
-                    spp_augment=None, spp_photometric=None, **kwargs) -> List[Dict]:
-        """Test without augmentation (fgn.py:187-303; ``qry_augment``, ``qry_photometric``, ``spp_augment`` and
-        ``spp_photometric`` are refused).  ``support_code`` (optional, from
+                    spp_augment=None, spp_photometric=None, qry_photometric_chain=None, spp_photometric_chain=None,
+                    **kwargs) -> List[Dict]:
+        """Test without augmentation (fgn.py:187-303; ``qry_augment``, ``qry_photometric``, ``spp_augment``,
+        ``spp_photometric`` and the two ``*_photometric_chain`` are refused).  ``support_code`` (optional, from
         ``encode_supports``) replaces the three ``spp_*`` inputs.  ``qry_resize_to`` = (H, W) (or a [B,2] tensor of
         equal rows): ``qry_img`` holds decoded images at their SOURCE size - a uint8 tensor [B,h,w,3] or a list of B
         uint8 tensors [h_i,w_i,3] - and ``qry_isegmaps`` / ``qry_bboxes`` are at source size too; image and masks are
@@ -1435,7 +1512,8 @@ class FGN(torch.nn.Module):
         run on the device in one launch (``fewshot_ds.support_from_source`` bit for bit); only the window
         of each image that its crop reads is uploaded; needs ``set_input_norm``."""
         self._refuse_augment(qry_augment=qry_augment, qry_photometric=qry_photometric, spp_augment=spp_augment,
-                             spp_photometric=spp_photometric)
+                             spp_photometric=spp_photometric, qry_photometric_chain=qry_photometric_chain,
+                             spp_photometric_chain=spp_photometric_chain)
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
         sp = None
@@ -1526,15 +1604,18 @@ class FGN(torch.nn.Module):
 
     @torch.no_grad()
     def encode_supports(self, spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to=None, spp_fill_ratio: float = 0.8,
-                        crop_square: bool = True, spp_augment=None, spp_photometric=None) -> dict:
+                        crop_square: bool = True, spp_augment=None, spp_photometric=None,
+                        spp_photometric_chain=None) -> dict:
         """Support-feature caching across queries: everything the path derives
         from the support set alone - backbone pass, AG-RPN class vectors, count_spp, the support
         half of the relation conv - computed once on the current stream.  The returned code is
         passed as ``support_code=`` to ``simple_test`` / ``detect_device`` for every query that
         shares the support set (the reference recomputes it per query, fgn.py:212-215; results
         are identical).  ``spp_crop_to``: the supports come as their source images, as for ``simple_test``.
-        ``spp_augment`` / ``spp_photometric`` are refused: the test path is without augmentation."""
-        self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric)
+        ``spp_augment`` / ``spp_photometric`` / ``spp_photometric_chain`` are refused: the test path is without
+        augmentation."""
+        self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric,
+                             spp_photometric_chain=spp_photometric_chain)
         sp = None
         if spp_crop_to is not None:
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
@@ -1690,7 +1771,7 @@ class FGN(torch.nn.Module):
                       qry_isegmaps=None, phase_counter=None, qry_resize_to=None,
                       results_at_source: bool = False, spp_crop_to=None, spp_fill_ratio: float = 0.8,
                       crop_square: bool = True, spp_augment=None, spp_photometric=None, qry_bboxes=None,
-                      qry_cat_ids=None) -> list:
+                      qry_cat_ids=None, spp_photometric_chain=None) -> list:
         """Everything up to the host wait: queues the host->device copies, the whole path and the device->host
         copies of the results.  Returns, per image, a dict of device tensors (det_bboxes [D,5], det_labels [D],
         n_dets [1], mask_prob, RLE bytes) plus the pinned host slot ``pack_results`` reads.
@@ -1715,7 +1796,8 @@ class FGN(torch.nn.Module):
         test path is without augmentation.  ``qry_bboxes`` / ``qry_cat_ids`` (per image, as ``pack_results`` will be
         given them: YXYX in the frame of the results) are read with ``evaluate_on_device`` only: the evaluator's greedy
         matching runs on the device (``ops.eval_match``) and ``pack_results`` adds the matched bits."""
-        self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric)
+        self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric,
+                             spp_photometric_chain=spp_photometric_chain)
         graphed = self._graphed()
         source = spp_source = None
         if spp_crop_to is not None and support_code is None:

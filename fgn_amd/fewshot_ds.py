@@ -784,6 +784,114 @@ def draw_query_augment_full(rng):
     return p, q
 
 
+# ---- chains of photometric operators (COCODS.augs_seq, coco_ds.py:45-59) --------------------------------------------
+# ``COCOFewShotISEG`` assigns ``augs_qry = augs_spp = COCODS.augs_seq`` (coco_fst.py:16-17): HorizontalFlip(0.5), then
+# one of AddToHue / AddToSaturation / AddToBrightness, then GaussianBlur - two photometric operators per image, one
+# behind the other.  A chain is up to ``PHOTO_CHAIN_MAX`` rows of ``PHOTO_PARAMS`` applied in order, of the form "point
+# operators, then at most one blur".  No arithmetic is restated: the rule is the left fold of ``photometric_image_u8``
+# over the chain's records, and photometric_chain_u8hwc3_kernel of csrc/spatial.hip agrees with that fold bit for bit in
+# one read and one write of the image.
+PHOTO_CHAIN_MAX = 3
+PHOTO_BLUR_OP = PHOTO_OPS.index('gaussian_blur')
+
+
+def check_photometric_chain(rows, name: str = 'qry_photometric_chain') -> np.ndarray:
+    """One image's chain as float64 [P,3], P in 1..``PHOTO_CHAIN_MAX``: every row through ``check_photometric_params``,
+    and the one structural rule - the blur (operator 3) appears at most once and every row behind it is neutral (point
+    operators, then at most one blur).  ValueError otherwise; ``name`` is the argument the message speaks of."""
+    c = np.asarray(rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else rows)
+    if c.dtype.kind not in 'iuf' or c.ndim != 2 or c.shape[1] != len(PHOTO_PARAMS) or \
+            not 1 <= c.shape[0] <= PHOTO_CHAIN_MAX:
+        raise ValueError(f'{name}: one image\'s chain is [P,{len(PHOTO_PARAMS)}] numbers {PHOTO_PARAMS} with P in 1..'
+                         f'{PHOTO_CHAIN_MAX}, got {c.dtype} {list(c.shape)}')
+    try:
+        c = np.stack([check_photometric_params(r) for r in c])
+    except ValueError as e:
+        raise ValueError(str(e).replace('qry_photometric', name)) from None
+    blurs = [i for i, r in enumerate(c) if r[0] == PHOTO_BLUR_OP]           # (a blur row of sigma 0 counts: it is a blur)
+    if len(blurs) > 1 or (blurs and not all(photometric_is_neutral(r) for r in c[blurs[0] + 1:])):
+        raise ValueError(f'{name}: a chain is point operators, then at most one blur - the blur (operator '
+                         f'{PHOTO_BLUR_OP}) appears at most once and every row behind it is neutral, got operators '
+                         f'{[int(r[0]) for r in c]}')
+    return c
+
+
+def photometric_chain_records(rows, src_hw, net_hw, name: str = 'qry_photometric_chain') -> np.ndarray:
+    """What photometric_chain_u8hwc3_kernel reads for one image, int32 [``PHOTO_CHAIN_MAX``, 64]: the non-neutral rows of
+    the chain compacted to the front, each as its ``query_photometric_record``, the rest the neutral record of the same
+    (h, w).  ``rows`` None: all neutral."""
+    neutral = query_photometric_record(None, src_hw, net_hw)
+    recs = np.tile(neutral, (PHOTO_CHAIN_MAX, 1))
+    if rows is None:
+        return recs
+    try:
+        active = [query_photometric_record(r, src_hw, net_hw) for r in check_photometric_chain(rows, name)
+                  if not photometric_is_neutral(r)]
+    except ValueError as e:
+        raise ValueError(str(e).replace('qry_photometric:', f'{name}:')) from None
+    for i, rec in enumerate(active):
+        recs[i] = rec
+    return recs
+
+
+def _check_chain_records(recs) -> np.ndarray:
+    """Records int32 [P,64], P in 1..3, checked as the kernel checks a chain: one (h, w), a blur only with operator-0
+    records behind it (each record's own fields are checked by ``photometric_image_u8``)."""
+    recs = np.asarray(recs)
+    if recs.dtype != np.int32 or recs.ndim != 2 or recs.shape[1] != PHOTO_REC_INTS or \
+            not 1 <= recs.shape[0] <= PHOTO_CHAIN_MAX:
+        raise ValueError(f'a photometric chain is int32 [P,{PHOTO_REC_INTS}] records with P in 1..{PHOTO_CHAIN_MAX}, got '
+                         f'{recs.dtype} {list(recs.shape)}')
+    if (recs[:, :2] != recs[0, :2]).any():
+        raise ValueError(f'the records of a chain carry one (h, w), got {recs[:, :2].tolist()}')
+    ops_ = recs[:, 2].tolist()
+    if PHOTO_BLUR_OP in ops_ and any(ops_[ops_.index(PHOTO_BLUR_OP) + 1:]):
+        raise ValueError(f'a blur record has only operator-0 records behind it, got operators {ops_}')
+    return recs
+
+
+def photometric_chain_u8(img: np.ndarray, recs: np.ndarray) -> np.ndarray:
+    """uint8 [h,w,3] -> uint8 [h,w,3]: the left fold of ``photometric_image_u8`` over the records int32 [P,64]
+    (``photometric_chain_records``).  The rule of photometric_chain_u8hwc3_kernel; the image is not changed."""
+    recs = _check_chain_records(recs)
+    for g in recs:
+        _photo_fields(g)                                # (every record before any pixel, as the kernel does)
+    out = np.asarray(img)
+    for rec in recs:
+        out = photometric_image_u8(out, rec)
+    return out
+
+
+def augment_query_chain(img: np.ndarray, bboxes_yxyx: np.ndarray, isegmaps: np.ndarray, H: int, W: int, params=None,
+                        chain=None):
+    """``augment_query_full`` with a chain of photometric rows [P,3] in place of the single row: the fold
+    ``photometric_chain_u8`` on the SOURCE image (a blur's sigma is given in network pixels), then resize and geometry as
+    one gather.  A sample whose boxes leave the image is used un-augmented in BOTH halves."""
+    h, w = img.shape[:2]
+    rec, _ = augment_plan(params, bboxes_yxyx, (h, w), (H, W))
+    fell_back = params is not None and not augment_is_neutral(check_augment_params(params)) and not rec[2:6].any()
+    precs = photometric_chain_records(chain, (h, w), (H, W))                # (its contract errors, fallback or not)
+    if not fell_back and precs[:, 2].any():
+        img = photometric_chain_u8(img, precs)
+    return augment_query(img, bboxes_yxyx, isegmaps, H, W, params)
+
+
+def draw_coco_augment(rng):
+    """(row of ``AUG_PARAMS`` [8], chain of ``PHOTO_PARAMS`` [2,3]) drawn like ``COCODS.augs_seq`` (coco_ds.py:45-59):
+    HorizontalFlip with p = 1/2 and no other geometric operator; one of hue uniform in [-10, 10], saturation uniform in
+    [-25, 25], brightness uniform in [-30, 30] with equal weights; then a blur with sigma uniform in [0, 1.5].  Never a
+    noise operator, so the seeds stay 0.  ``rng``: a numpy Generator or RandomState (``random`` and ``uniform``)."""
+    p = np.array(AUG_NEUTRAL, np.float64)
+    if rng.random() < 0.5:
+        p[0] = 1
+    chain = np.zeros((2, len(PHOTO_PARAMS)), np.float64)
+    op = min(int(rng.random() * 3), 2)
+    lo, hi = ((-10., 10.), (-25., 25.), (-30., 30.))[op]
+    chain[0, :2] = (PHOTO_OPS.index('hue') + op, rng.uniform(lo, hi))
+    chain[1, :2] = (PHOTO_BLUR_OP, rng.uniform(0., 1.5))
+    return p, chain
+
+
 # ---- supports from the source image (BaseFewShotISEG.get_support, base_fst.py:1043-1167) ---------------------------
 # ``support_from_instance`` as ONE gather from the source image: crop (reflect context), bicubic resize of the longer
 # side to S and centre pad, with no padded copy of the image and no float.  The crop geometry is the golden-pinned
@@ -967,12 +1075,14 @@ def support_window(img: np.ndarray, isegmap: np.ndarray, rec: np.ndarray):
 # crop AFTER resize and pad, with one mask and one box.  The few-shot dataset classes assign ``augs_spp = augs_seq``, the
 # queries' sequence, so the rule is the queries' by composition, at equal size: nothing new is restated here
 # (DESIGN.md 4.4.7).  Unlike the queries the supports see the operators in the reference's own place, after the resize.
-def augment_support(crop: np.ndarray, box, mask: np.ndarray, params=None, photometric=None):
+def augment_support(crop: np.ndarray, box, mask: np.ndarray, params=None, photometric=None, photometric_chain=None):
     """One support instance of ``support_from_source`` (crop uint8 [S,S,3], box float32 YXYX in the S x S frame, mask
     [S,S]) through one row pair (``AUG_PARAMS``, ``PHOTO_PARAMS``): ``augment_query_full`` at equal size with one box
     and one mask - ``photometric_image_u8`` (the blur's sigma in crop pixels), the gather of ``query_augment_record``
     whose symmetric border reflects the S x S frame, pad bands included, and the box through ``augment_boxes_yxyx``.  A
     box that leaves the open S x S rectangle: the instance is used un-augmented in both halves.
+    ``photometric_chain`` (in place of ``photometric``, never beside it): a chain [P,3] of rows, folded by
+    ``augment_query_chain`` in the same place.
     -> (crop', box' [4], mask' [S,S])."""
     crop, mask = np.asarray(crop), np.asarray(mask)
     if crop.ndim != 3 or crop.shape[0] != crop.shape[1] or mask.shape != crop.shape[:2]:
@@ -980,6 +1090,11 @@ def augment_support(crop: np.ndarray, box, mask: np.ndarray, params=None, photom
                          f'{list(mask.shape)}')
     S = crop.shape[0]
     box = np.asarray(box).reshape(1, 4)
+    if photometric_chain is not None:
+        if photometric is not None:
+            raise ValueError('augment_support: give photometric or photometric_chain, not both')
+        img, boxes, masks = augment_query_chain(crop, box, mask[None], S, S, params, photometric_chain)
+        return img, boxes[0], masks[0]
     img, boxes, masks = augment_query_full(crop, box, mask[None], S, S, params, photometric)
     return img, boxes[0], masks[0]
 
@@ -1018,6 +1133,23 @@ def support_augment_plan(rows, photo_rows, boxes, S: int):
             fell_back[i] = True
             recs[i] = query_augment_record(None, (S, S), (S, S))
             precs[i] = query_photometric_record(None, (S, S), (S, S))
+    return recs, precs, out, fell_back
+
+
+def support_augment_chain_plan(rows, chains, boxes, S: int):
+    """``support_augment_plan`` with a chain per instance in place of the single photometric row: ``chains`` [n,P,3] (or
+    None: neutral) -> (geometric records int32 [n,16], chain records int32 [n,``PHOTO_CHAIN_MAX``,64] of
+    ``photometric_chain_records`` at S -> S, boxes, fallback flags).  A fallen-back instance gets the neutral chain;
+    every contract error of a chain is raised, fallback or not."""
+    S = int(S)
+    recs, _, out, fell_back = support_augment_plan(rows, None, boxes, S)
+    n = len(recs)
+    chains = [None] * n if chains is None else chains
+    if len(chains) != n:
+        raise ValueError(f'support_augment_chain_plan: {n} boxes and {len(chains)} photometric chains')
+    precs = np.stack([photometric_chain_records(c, (S, S), (S, S), 'spp_photometric_chain') for c in chains]) if n else \
+        np.zeros((0, PHOTO_CHAIN_MAX, PHOTO_REC_INTS), np.int32)
+    precs[fell_back] = query_photometric_record(None, (S, S), (S, S))
     return recs, precs, out, fell_back
 
 
@@ -1109,7 +1241,11 @@ class ClutteredCharsFewShotISEG(Dataset):
     by ``draw_query_augment``; the pixels, masks and boxes of the sample are NOT augmented.  ``photometric_spp`` (needs
     ``augment_spp``): the sample also carries ``spp_photometric`` [N*K,3] and both rows of an instance come from the
     joint draw ``draw_support_augment``, seeded the same way.  Off by default: the samples are then key for key what
-    they are without them, and ``qry_augment`` / ``qry_photometric`` are the same with or without them."""
+    they are without them, and ``qry_augment`` / ``qry_photometric`` are the same with or without them.
+    ``augs`` = 'natural' (default: everything above) or 'coco': the rows come from ``draw_coco_augment`` (COCO's
+    ``augs_seq``, coco_ds.py:45-59: flip, one HSV operator, blur), seeded the same way, and with ``photometric_qry`` /
+    ``photometric_spp`` the sample carries ``qry_photometric_chain`` [2,3] / ``spp_photometric_chain`` [N*K,2,3] in place
+    of the single rows, for ``FGN.forward_train(qry_photometric_chain=..., spp_photometric_chain=...)``."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
@@ -1117,8 +1253,12 @@ class ClutteredCharsFewShotISEG(Dataset):
 
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
                  spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None,
-                 spp_source=False, augment_qry=False, photometric_qry=False, augment_spp=False, photometric_spp=False):
+                 spp_source=False, augment_qry=False, photometric_qry=False, augment_spp=False, photometric_spp=False,
+                 augs='natural'):
         par = self.PARAMS[dataset]
+        if augs not in ('natural', 'coco'):
+            raise ValueError(f'augs is \'natural\' (natural_fst.py:18-35) or \'coco\' (coco_ds.py:45-59), got {augs!r}')
+        self.augs = augs
         self.raw_uint8 = bool(raw_uint8)
         self.spp_source = bool(spp_source)
         if self.spp_source and not self.raw_uint8:
@@ -1235,7 +1375,13 @@ class ClutteredCharsFewShotISEG(Dataset):
         }
         if self.source_size is not None:
             sample['qry_resize_to'] = np.array([self.img_size, self.img_size], dtype=np.int32)
-        if self.photometric_qry:
+        coco = self.augs == 'coco'               # (one joint draw per image either way; the chain only with photometric_*)
+        if coco and self.augment_qry:
+            row, chain = draw_coco_augment(np.random.default_rng([int(self.seed), child, self.epoch]))
+            sample['qry_augment'] = row
+            if self.photometric_qry:
+                sample['qry_photometric_chain'] = chain
+        elif self.photometric_qry:
             sample['qry_augment'], sample['qry_photometric'] = \
                 draw_query_augment_full(np.random.default_rng([int(self.seed), child, self.epoch]))
         elif self.augment_qry:
@@ -1244,7 +1390,12 @@ class ClutteredCharsFewShotISEG(Dataset):
             sample.update(spp_crop_to=int(self.spp_img_size), spp_fill_ratio=float(self.spp_fill_ratio), crop_square=True)
         if self.augment_spp:                     # instance i: its own stream, disjoint from the query's three-word seed
             rngs = [np.random.default_rng([int(self.seed), child, self.epoch, 1 + i]) for i in range(len(spp_ids))]
-            if self.photometric_spp:
+            if coco:
+                pairs = [draw_coco_augment(r) for r in rngs]
+                sample['spp_augment'] = np.stack([p for p, _ in pairs])
+                if self.photometric_spp:
+                    sample['spp_photometric_chain'] = np.stack([q for _, q in pairs])
+            elif self.photometric_spp:
                 pairs = [draw_support_augment(r) for r in rngs]
                 sample['spp_augment'] = np.stack([p for p, _ in pairs])
                 sample['spp_photometric'] = np.stack([q for _, q in pairs])

@@ -43,6 +43,7 @@ SIGNATURES = {
     'fgn_augment_u8hwc3_to_nhwc4_f32': (_i, [_p, C.c_longlong, _p, _p, _p, _i, _i, _i, _p]),
     'fgn_augment_mask_u8': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
     'fgn_photometric_u8hwc3': (_i, [_p, _p, C.c_longlong, _p, _i, _p]),
+    'fgn_photometric_chain_u8hwc3': (_i, [_p, _p, C.c_longlong, _p, _i, _i, _p]),
     'fgn_support_from_source_f32': (_i, [_p, C.c_longlong, _p, C.c_longlong, _p, _p, _p, _p, _i, _i, _p]),
     'fgn_support_from_source_u8': (_i, [_p, C.c_longlong, _p, C.c_longlong, _p, _p, _p, _i, _i, _p]),
     'fgn_support_augment_f32': (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),

@@ -1237,6 +1237,31 @@ def photometric_u8(src: torch.Tensor, recs: torch.Tensor) -> torch.Tensor:
     return dst
 
 
+PHOTO_CHAIN_MAX = 3          # csrc/spatial.hip; fewshot_ds.PHOTO_CHAIN_MAX: records per image of a chain
+
+
+def photometric_chain_u8(src: torch.Tensor, recs: torch.Tensor) -> torch.Tensor:
+    """``photometric_u8`` for a chain of operators per image: ``fewshot_ds.photometric_chain_u8`` (the left fold of
+    ``photometric_image_u8`` over the image's records) of every image, bit for bit, in ONE launch that reads and writes
+    every image once.  ``recs`` int32 [n,P,64] ON THE DEVICE, P in 1..3: the records of
+    ``fewshot_ds.photometric_chain_records`` - point operators, then at most one blur.  -> a new uint8 [n,capacity].  An
+    image with a record out of range, records of differing (h, w) or an active record behind a blur has its slot written
+    as zeros."""
+    _chk(src, 'src', torch.uint8)
+    _chk(recs, 'recs', torch.int32)
+    if src.dim() != 2 or recs.dim() != 3 or not 1 <= recs.shape[1] <= PHOTO_CHAIN_MAX or \
+            (recs.shape[0], recs.shape[2]) != (src.shape[0], PHOTO_REC_INTS) or recs.device != src.device:
+        raise _lib.FgnHipError(f'photometric_chain_u8: expects src [n,capacity] and recs [n,P,64] with P in 1..'
+                               f'{PHOTO_CHAIN_MAX} on one device')
+    dst = torch.empty_like(src)
+    if src.numel() == 0:                # (an empty tensor has no address to hand over)
+        return dst
+    _lib.check(_lib.load().fgn_photometric_chain_u8hwc3(_ptr(src), _ptr(dst), int(src.shape[1]), _ptr(recs),
+                                                        int(recs.shape[1]), int(src.shape[0]), _stream()),
+               'fgn_photometric_chain_u8hwc3')
+    return dst
+
+
 def maxpool3x3s2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _chk(x, 'x')
     n, h, w, c = x.shape

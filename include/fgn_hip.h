@@ -288,6 +288,19 @@ int fgn_augment_mask_u8(const unsigned char* src, unsigned char* dst, const int*
 int fgn_photometric_u8hwc3(const unsigned char* src, unsigned char* dst, long long stride_bytes, const int* recs,
                            int n_img, void* stream);
 
+/* A chain of the operators above in ONE pass over the same slots (COCODS.augs_seq, coco_ds.py:45-59: one of AddToHue /
+ * AddToSaturation / AddToBrightness, then GaussianBlur): image b has n_ops records, recs int32 [n_img][n_ops][64] read ON
+ * THE DEVICE, applied in order.  The rule is the left fold of photometric_image_u8 over the records
+ * (fgn_amd.fewshot_ds.photometric_chain_u8) and the kernel agrees with it bit for bit; the point operators run on a pixel
+ * in registers, where the chain ends in a blur while its tile and halo are staged (each staged pixel with its own flat
+ * index y * w + x as the noise counter), so the image is read once and written once.
+ *   A chain is point operators, then at most one blur: every record must pass the checks above, all records of an image
+ *   carry the same (h, w), and a blur record has only operator-0 records behind it (operator-0 records may stand
+ *   anywhere).  An image that fails gets its whole slot written as zeros and none of its source bytes are read.
+ *   n_ops outside 1..3: FGN_ERR_SHAPE.  src and dst must not overlap (FGN_ERR_ARG).  Other return codes as above. */
+int fgn_photometric_chain_u8hwc3(const unsigned char* src, unsigned char* dst, long long stride_bytes, const int* recs,
+                                 int n_ops, int n_img, void* stream);
+
 /* Supports from the source image behind the upload (BaseFewShotISEG.get_support, base_fst.py:1043-1167: get_crop with
  * reflected context, bicubic resize of the longer side to S, centre pad): one launch for all n = B * N * K instances of
  * a batch.  The arithmetic is the integer rule of fgn_amd.fewshot_ds (cubic_taps: cubic convolution A = -3/4, half-pixel
