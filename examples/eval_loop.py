@@ -9,6 +9,7 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --source-size 200     (200^2 sources, resized to 128^2 on the GPU)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --source-size 200 --results-at-source     (... results in the 200^2 frame)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source     (supports cropped, resized and padded on the GPU)
+    python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source --rle-masks     (masks travel as COCO RLE, decoded on the GPU)
     python examples/eval_loop.py --episodes 8 --match-on-device     (mask overlaps counted on the GPU: the evaluator decodes no RLE)
     python examples/eval_loop.py --episodes 8 --eval-on-device --iou-thrs coco     (greedy matching on the GPU too; AP at COCO's ten thresholds)
 """
@@ -49,6 +50,10 @@ def main():
     ap.add_argument('--spp-source', action='store_true',
                     help='character datasets: the loader hands over the supports\' source images, masks and boxes; the '
                          'detector crops, resizes and pads them on the GPU (spp_crop_to; implies --uint8)')
+    ap.add_argument('--rle-masks', action='store_true',
+                    help='character datasets: the loader yields the ground-truth masks as COCO RLE dicts (the form the '
+                         'reference\'s COCO dataset holds them in), with --spp-source the support masks too; the detector '
+                         'decodes them on the GPU and only their runs are uploaded')
     ap.add_argument('--match-on-device', action='store_true',
                     help='count the overlaps of detections and ground truth on the GPU (FGN.match_on_device): the results '
                          'carry dt_gt_inter / dt_area / gt_area and the evaluator decodes no RLE')
@@ -63,6 +68,8 @@ def main():
     args.uint8 = args.uint8 or args.source_size is not None or args.spp_source
     if args.results_at_source and args.source_size is None:
         ap.error('--results-at-source needs --source-size')
+    if args.rle_masks and args.dataset == 'SYNTH':
+        ap.error('--rle-masks needs --dataset MNISTISEG or OMNIISEG')
     if args.uint8 and args.dataset == 'SYNTH':
         ap.error('--uint8 / --source-size / --spp-source need --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
 
@@ -71,7 +78,8 @@ def main():
     else:       # cluttered characters: 128^2 (MNISTISEG, cfg1) / 256^2 (OMNIISEG, cfg2) queries, 128^2 supports
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,
-                                       raw_uint8=args.uint8, source_size=args.source_size, spp_source=args.spp_source)
+                                       raw_uint8=args.uint8, source_size=args.source_size, spp_source=args.spp_source,
+                                       rle_masks=args.rle_masks)
     model = FGN(args.n_ways, args.k_shots)
     if args.uint8:
         model.set_input_norm(**ds.input_norm)

@@ -657,6 +657,86 @@ extern "C" int fgn_dense_mask_rle(const uint8_t* masks, void* scratch, size_t sc
 }
 
 // ----------------------------------------------------------------------------------------------
+// COCO RLE as an INPUT: ground-truth and support masks that arrive as runs (the reference's COCO dataset holds nothing
+// else, coco_ds.py:195-207, and decodes on the host per sample, get_isegmap coco_ds.py:265-278) become, on the device,
+// exactly the bytes a dense upload would have put there.  The host sends the cumulative run ENDS of each mask
+// (fgn_amd/rle.py: RleMasks) and one record per mask; pixel (y, x) sits at column-major position p = x * h + y and is
+// set where an odd number of its mask's ends are <= p - zero-length runs (repeated ends) need no special case.
+//   Mapping: one lane per window column, RLED_THREADS columns per workgroup, RLED_ROWS rows per blockIdx.y, masks and
+//   column blocks flattened into blockIdx.x.  A lane finds r for its first p by one binary search, then walks down its
+//   column: p grows by 1 per row, r advances while ends[r] <= p (one load per run crossed, the current end stays in a
+//   register).  A row's store is 64 consecutive bytes per wave - one coalesced segment - and no pointer is cast, so the
+//   output needs no alignment (the rows of a [rows, capacity] slot start at any byte).
+//   Safety: r never leaves [0, n_runs], ends is read at run0 + r with r < n_runs only, and a record that fails a check
+//   reads no run at all: whatever ends holds, no index leaves its slice.
+// ----------------------------------------------------------------------------------------------
+constexpr int RLED_THREADS = 256;   // window columns per workgroup
+constexpr int RLED_ROWS = 32;       // window rows per blockIdx.y
+constexpr int RLED_REC_INTS = 8;    // {h, w, wy, wx, wh, ww, run0, n_runs}
+
+__global__ __launch_bounds__(RLED_THREADS) void rle_decode_kernel(const uint32_t* __restrict__ ends, long long n_ends,
+                                                                  const int32_t* __restrict__ recs,
+                                                                  uint8_t* __restrict__ out, long long out_stride,
+                                                                  int col_blocks, int max_wh, int max_ww) {
+    const int i = blockIdx.x / col_blocks, cb = blockIdx.x - i * col_blocks;      // (workgroup-uniform)
+    const int32_t* rec = recs + (size_t)i * RLED_REC_INTS;
+    const int h = rec[0], w = rec[1], wy = rec[2], wx = rec[3], wh = rec[4], ww = rec[5], run0 = rec[6], n_runs = rec[7];
+    uint8_t* dst = out + (size_t)i * (size_t)out_stride;
+    const bool window = wh >= 1 && ww >= 1;
+    const bool fits = window && (long long)wh * ww <= out_stride;
+    const bool ok = fits && h >= 1 && h <= SRC_MAX_DIM && w >= 1 && w <= SRC_MAX_DIM && wy >= 0 && wx >= 0 &&
+                    wh <= h - wy && ww <= w - wx && wh <= max_wh && ww <= max_ww && n_runs >= 1 && run0 >= 0 &&
+                    (long long)run0 + n_runs <= n_ends;
+    if (!ok) {
+        // an out-of-range record reads none of its runs; its window is zeros where it fits the slot (the workgroups of
+        // this mask share the bytes), and nothing is written otherwise
+        if (!fits) return;
+        const long long total = (long long)wh * ww;
+        const long long step = (long long)col_blocks * gridDim.y * RLED_THREADS;
+        for (long long b = ((long long)blockIdx.y * col_blocks + cb) * RLED_THREADS + threadIdx.x; b < total; b += step)
+            dst[b] = 0;
+        return;
+    }
+    const int c = cb * RLED_THREADS + threadIdx.x;                                // window column of this lane
+    const int y0 = blockIdx.y * RLED_ROWS;
+    if (c >= ww || y0 >= wh) return;
+    const int rows = min(RLED_ROWS, wh - y0);
+    const uint32_t* e = ends + run0;
+    uint32_t p = (uint32_t)(wx + c) * (uint32_t)h + (uint32_t)(wy + y0);          // < 2^28
+    int lo = 0, hi = n_runs;                                                      // r = #{j : e[j] <= p}, in [0, n_runs]
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (e[mid] <= p) lo = mid + 1;
+        else hi = mid;
+    }
+    int r = lo;
+    uint32_t cur = r < n_runs ? e[r] : 0xffffffffu;                               // the first end beyond p
+    uint8_t* o = dst + (size_t)y0 * ww + c;
+    for (int y = 0; y < rows; ++y, ++p, o += ww) {
+        while (cur <= p) {                                                        // (a repeated end = a zero-length run)
+            ++r;
+            cur = r < n_runs ? e[r] : 0xffffffffu;
+        }
+        *o = (uint8_t)(r & 1);
+    }
+}
+
+extern "C" int fgn_rle_decode_u8(const uint32_t* ends, long long n_ends, const int32_t* recs, uint8_t* out,
+                                 long long out_stride_bytes, int n, int max_wh, int max_ww, hipStream_t stream) {
+    if (n < 0 || out_stride_bytes < 0 || n_ends < 0 || max_wh < 0 || max_ww < 0 || max_wh > SRC_MAX_DIM ||
+        max_ww > SRC_MAX_DIM)
+        return FGN_ERR_SHAPE;
+    if (n == 0 || max_wh == 0 || max_ww == 0) return FGN_OK;
+    if (!ends || !recs || !out) return FGN_ERR_ARG;
+    const int col_blocks = cdiv(max_ww, RLED_THREADS);
+    if ((long long)n * col_blocks >= (1ll << 24)) return FGN_ERR_SHAPE;     // (grid.x * RLED_THREADS stays below 2^32)
+    hipLaunchKernelGGL(rle_decode_kernel, dim3((unsigned)(n * col_blocks), cdiv(max_wh, RLED_ROWS)), dim3(RLED_THREADS), 0,
+                       stream, ends, n_ends, recs, out, out_stride_bytes, col_blocks, max_wh, max_ww);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
 // Matching on the device: exact pixel counts |d & g|, |d|, |g| of every (detection, ground truth) pair.
 // The evaluator (fgn_amd/fsiseg_eval.py) needs nothing else from the masks, and both operands are on the device while
 // the episode is in flight: the ground-truth masks (uploaded for the RLE above) and the mask probabilities + boxes the

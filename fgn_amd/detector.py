@@ -430,6 +430,27 @@ def _host(v) -> np.ndarray:
     return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
 
+def _gt_entries(qry_isegmaps, sizes):
+    """``qry_isegmaps`` normalised once at the front (host only, nothing is queued): an entry given as COCO RLE
+    (``rle.as_masks``: a list of dicts or ``[size, counts]`` pairs, an ``RleMasks``, the empty list) becomes a checked
+    ``RleMasks`` at ``sizes[i]`` = (h, w) - a size that disagrees is a ValueError -, a dense entry stays as it is.
+    Without an RLE entry the argument itself comes back."""
+    if qry_isegmaps is None or not any(rle.is_rle(g) for g in qry_isegmaps):
+        return qry_isegmaps
+    if sizes is not None and len(sizes) != len(qry_isegmaps):
+        raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {len(sizes)} images')
+    return [rle.as_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]') if rle.is_rle(g) else g
+            for i, g in enumerate(qry_isegmaps)]
+
+
+def _dense_supports_only(spp_isegmaps) -> None:
+    """The plain support path takes the dense [B,N*K,S,S] tensor only: the supports are already cut, resized and
+    padded there, and no dataset holds such masks as runs."""
+    if isinstance(spp_isegmaps, (list, tuple, dict, rle.RleMasks)):
+        raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; RLE masks '
+                         'are taken at source size, with spp_crop_to')
+
+
 def _number_rows(v, shapes: tuple, must: str) -> np.ndarray:
     """The rows of an augmentation argument as a host array: numbers, in one of ``shapes``."""
     a = _host(v)
@@ -1055,7 +1076,9 @@ class FGN(torch.nn.Module):
         if qry_isegmaps is not None:
             if len(qry_isegmaps) != B:
                 raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {B} images')
-            for g, hw in zip(qry_isegmaps, sizes):
+            for i, (g, hw) in enumerate(zip(qry_isegmaps, sizes)):
+                if rle.is_rle(g):                          # (an ``RleMasks`` of ``_gt_entries`` passes by its shape)
+                    g = rle.as_masks(g, hw, f'qry_isegmaps[{i}]')
                 if len(g.shape) != 3 or (int(g.shape[1]), int(g.shape[2])) != hw:
                     raise ValueError(f'qry_isegmaps: with qry_resize_to the masks are at source size {hw}, got '
                                      f'{list(g.shape)}')
@@ -1068,6 +1091,27 @@ class FGN(torch.nn.Module):
                                  f'the attribute (the static source slot of the captured graph)')
         return dict(B=B, hw=(H, W), flats=[im.contiguous().reshape(-1) for im in imgs], sizes=sizes, need=need,
                     capacity=capacity, img_shape=img_shape)
+
+    def _gt_sizes(self, qry_img, img_shape, qry_resize_to):
+        """The (h, w) the ground truth of every image is given at - its image's source size with ``qry_resize_to`` (the
+        setting, or the dict of ``_source_query``), else the network size: ``img_shape``, or without it the size of the
+        ``qry_img`` tensor itself - or None where the images do not say (they are refused next)."""
+        if isinstance(qry_resize_to, dict):
+            return qry_resize_to['sizes']
+        if qry_resize_to is None:
+            if img_shape is not None:
+                return [(int(s[0]), int(s[1])) for s in img_shape]
+            if not isinstance(qry_img, torch.Tensor) or qry_img.dim() != 4:
+                return None
+            try:
+                (b,), h, w = self._image_dims(qry_img, 'qry_img')
+            except ValueError:
+                return None
+            return [(h, w)] * b
+        imgs = list(qry_img) if isinstance(qry_img, (list, tuple, torch.Tensor)) else []
+        if not imgs or any(not isinstance(im, torch.Tensor) or im.dim() != 3 for im in imgs):
+            return None
+        return [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
 
     @staticmethod
     def _augment_plans(qry_augment, qry_bboxes, rs: dict) -> tuple:
@@ -1224,8 +1268,11 @@ class FGN(torch.nn.Module):
         if qry_photometric_chain is not None and qry_resize_to is None:
             raise ValueError('qry_photometric_chain needs qry_resize_to: the photometric operators run on the source '
                              'pixels, ahead of their resize')
+        qry_isegmaps = _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to))
         sp = None
-        if spp_crop_to is not None:                       # (every contract error before anything is queued)
+        if spp_crop_to is None:
+            _dense_supports_only(spp_isegmaps)
+        else:                                             # (every contract error before anything is queued)
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
             if spp_augment is not None or spp_photometric is not None or spp_photometric_chain is not None:
                 sp = self._support_plans(spp_augment, spp_photometric, sp, spp_photometric_chain)
@@ -1294,7 +1341,10 @@ class FGN(torch.nn.Module):
         at its image's size, ``spp_bboxes`` holds one YXYX box per instance, inside its image and not empty
         (``fewshot_ds.support_geometry``), and every window fits the slot.  -> B, n = B*N*K, S, the records int32 [n,16],
         the boxes in the S x S supports float32 (``support_from_instance``'s, computed here on the host) [B,N*K,4], the
-        image and mask windows as flat byte tensors, the largest of each and the slot sizes in bytes per instance."""
+        image and mask windows as flat byte tensors, the largest of each and the slot sizes in bytes per instance.  A mask
+        may be ONE COCO RLE item (``rle.as_masks``: dict or ``[size, counts]`` pair) at its image's size: the geometry is
+        the same, its entry of ``mflats`` is empty - no mask byte is uploaded - and ``mrle`` lists (row, ``RleMasks``,
+        window) for ``_upload_supports``; ``window_bytes`` counts the bytes of its run ends instead."""
         from . import fewshot_ds as fd
         if isinstance(spp_crop_to, bool) or not isinstance(spp_crop_to, (int, np.integer)) or \
                 not 1 <= int(spp_crop_to) <= ops.RESIZE_MAX_DIM:
@@ -1304,7 +1354,8 @@ class FGN(torch.nn.Module):
         if self.input_lut is None:
             raise ValueError('spp_crop_to needs the normalisation table: call set_input_norm first')
         NK = self.n_ways * self.k_shots
-        nested = lambda v: isinstance(v, (list, tuple)) and len(v) > 0 and isinstance(v[0], (list, tuple))
+        nested = lambda v: isinstance(v, (list, tuple)) and len(v) > 0 and isinstance(v[0], (list, tuple)) and \
+            not rle.is_item(v[0])                          # (a ``[size, counts]`` pair is one mask, not a support set)
         if not isinstance(spp_imgs, (list, tuple)) or not isinstance(spp_isegmaps, (list, tuple)):
             raise ValueError('spp_imgs / spp_isegmaps: with spp_crop_to, lists of N*K source images [h,w,3] and masks '
                              '[h,w] (or B such lists)')
@@ -1319,19 +1370,30 @@ class FGN(torch.nn.Module):
             raise ValueError(f'spp_bboxes: with spp_crop_to, [..,{NK},4] YXYX in the source frame for {B} support '
                              f'set(s), got {list(bb.shape)}')
         bb = bb.reshape(B * NK, 4)
-        recs, boxes, wins = [], [], []
+        recs, boxes, wins, mrle = [], [], [], []
         for i, (im, mk) in enumerate((im, mk) for g in groups for im, mk in zip(*g)):
-            im, mk = _host(im), _host(mk)
+            im = _host(im)
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise ValueError(f'spp_imgs: with spp_crop_to every image is channels-last uint8 pixels [h,w,3], got '
                                  f'{im.dtype} {list(im.shape)}')
-            if mk.shape != im.shape[:2]:
-                raise ValueError(f'spp_isegmaps: with spp_crop_to every mask is at its image\'s size '
-                                 f'{list(im.shape[:2])}, got {list(mk.shape)}')
+            runs = None
+            if rle.is_item(mk) or isinstance(mk, rle.RleMasks):     # ONE mask as COCO RLE, at its image's size
+                runs = rle.as_masks(mk if isinstance(mk, rle.RleMasks) else [mk], im.shape[:2], f'spp_isegmaps[{i}]')
+                if len(runs) != 1:
+                    raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(runs)}')
+                mk = np.zeros((0, 0), np.uint8)
+            else:
+                mk = _host(mk)
+                if mk.shape != im.shape[:2]:
+                    raise ValueError(f'spp_isegmaps: with spp_crop_to every mask is at its image\'s size '
+                                     f'{list(im.shape[:2])}, got {list(mk.shape)}')
             rec, box = fd.support_geometry(im.shape[0], im.shape[1], bb[i], S, spp_fill_ratio, crop_square)
             recs.append(rec); boxes.append(box); wins.append(fd.support_window(im, mk, rec))
+            if runs is not None:        # no mask byte is uploaded: the window is decoded into its row (_upload_supports)
+                g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
+                mrle.append((i, runs, (g['wy'], g['wx'], g['wh'], g['ww'])))
         need = max(w[0].size for w in wins)
-        mneed = max(w[1].size for w in wins)
+        mneed = need // 3                                  # (wh * ww of the largest window, dense or not)
         capacity, mcapacity = need, mneed
         if graphed:
             capacity = int(self.support_source_capacity)
@@ -1343,7 +1405,8 @@ class FGN(torch.nn.Module):
                     boxes=torch.from_numpy(np.stack(boxes).reshape(B, NK, 4)),
                     flats=[torch.from_numpy(w.reshape(-1)) for w, _ in wins],
                     mflats=[torch.from_numpy(m.reshape(-1)) for _, m in wins], need=need, mneed=mneed,
-                    capacity=capacity, mcapacity=mcapacity, window_bytes=int(sum(w.size + m.size for w, m in wins)))
+                    capacity=capacity, mcapacity=mcapacity, mrle=mrle,
+                    window_bytes=int(sum(w.size + m.size for w, m in wins) + sum(r.ends.nbytes for _, r, _ in mrle)))
 
     @staticmethod
     def _slot_rows(flats: list, width: int, capacity: int, dev, slot: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1359,10 +1422,15 @@ class FGN(torch.nn.Module):
         """The windows of ``_source_supports`` on the device, on the current stream: wh_i * ww_i * 3 image bytes and
         wh_i * ww_i mask bytes of instance i into row i of ``into['spp_src']`` / ``into['spp_msk']`` (the static slots of
         a captured graph) when those are given, else of fresh buffers as wide as the largest window of the batch - only
-        the window bytes cross the bus, and what lies behind a window in its row is never read.  -> the two by name."""
+        the window bytes cross the bus, and what lies behind a window in its row is never read.  The window of an
+        instance whose mask came as RLE (``sp['mrle']``) is decoded on the device into its row, right where the copy would
+        have stood (``ops.rle_decode_rows``: one launch for all of them).  -> the two by name."""
         into = into or {}
+        msk = self._slot_rows(sp['mflats'], sp['mneed'], sp['mcapacity'], dev, into.get('spp_msk'))
+        # an instance whose mask came as RLE uploaded no mask byte: its window is decoded straight into its row
+        ops.rle_decode_rows(msk, sp.get('mrle') or [])
         return {'spp_src': self._slot_rows(sp['flats'], sp['need'], sp['capacity'], dev, into.get('spp_src')),
-                'spp_msk': self._slot_rows(sp['mflats'], sp['mneed'], sp['mcapacity'], dev, into.get('spp_msk'))}
+                'spp_msk': msk}
 
     def _supports_on_device(self, sp: dict, dev) -> tuple:
         """``_source_supports`` uploaded on the current stream, in the form ``_support_front`` takes:
@@ -1510,12 +1578,18 @@ class FGN(torch.nn.Module):
         such lists), ``spp_isegmaps`` the instances' masks [h_i,w_i] nested alike, ``spp_bboxes`` [..,N*K,4] YXYX in the
         source frame - and crop, bicubic resize and centre pad of ``BaseFewShotISEG.get_support`` (base_fst.py:1043-1167)
         run on the device in one launch (``fewshot_ds.support_from_source`` bit for bit); only the window
-        of each image that its crop reads is uploaded; needs ``set_input_norm``."""
+        of each image that its crop reads is uploaded; needs ``set_input_norm``.  Masks as COCO RLE: every
+        entry of ``qry_isegmaps`` may be a list of RLE items (``rle.as_masks``: pycocotools dicts or ``[size, counts]``
+        pairs; at the image's source size with ``qry_resize_to``, else at the network size; dense and RLE entries may be
+        mixed in a batch), and with ``spp_crop_to`` every instance of ``spp_isegmaps`` may be one RLE item at its source
+        image's size; they are checked on the host, only their runs are uploaded and the device decodes them into the
+        bytes of the dense form - every result is that of the dense call."""
         self._refuse_augment(qry_augment=qry_augment, qry_photometric=qry_photometric, spp_augment=spp_augment,
                              spp_photometric=spp_photometric, qry_photometric_chain=qry_photometric_chain,
                              spp_photometric_chain=spp_photometric_chain)
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
+        qry_isegmaps = _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to))
         sp = None
         if spp_crop_to is not None and support_code is None:
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square,
@@ -1617,7 +1691,9 @@ class FGN(torch.nn.Module):
         self._refuse_augment(spp_augment=spp_augment, spp_photometric=spp_photometric,
                              spp_photometric_chain=spp_photometric_chain)
         sp = None
-        if spp_crop_to is not None:
+        if spp_crop_to is None:
+            _dense_supports_only(spp_isegmaps)
+        else:
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square)
         dev = self._gpu('encode_supports')
         if self._packed_device != dev:
@@ -1691,7 +1767,11 @@ class FGN(torch.nn.Module):
 
     @staticmethod
     def _device_masks(g, dev) -> torch.Tensor:
-        """Ground-truth masks of one image (array or tensor) on the device as contiguous bool / uint8 [n,h,w]."""
+        """Ground-truth masks of one image (array or tensor) on the device as contiguous bool / uint8 [n,h,w].  Masks
+        given as COCO RLE (``_gt_entries``) are decoded there (``ops.rle_decode_masks``): the same bytes, uint8 0/1, and
+        only their runs cross the bus."""
+        if rle.is_rle(g):
+            return ops.rle_decode_masks(rle.as_masks(g, what='qry_isegmaps'), device=dev)
         g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
         g = g.to(dev, non_blocking=True)
         g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
@@ -1731,10 +1811,11 @@ class FGN(torch.nn.Module):
         source, spp_source = form.source, form.spp_source
         gts = None
         if gt_masks is not None:
-            gts = [g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
+            gts = [g if isinstance(g, torch.Tensor) or rle.is_rle(g) else torch.from_numpy(np.ascontiguousarray(g))
+                   for g in gt_masks]
         on_host = [t for t in list(tensors.values()) + (gts or []) + (source['flats'] if source else []) +
                    (spp_source['flats'] + spp_source['mflats'] if spp_source else [])
-                   if t is not None and not t.is_cuda]
+                   if t is not None and (rle.is_rle(t) or not t.is_cuda)]     # (runs are host data)
         if not on_host and gts is None and source is None:
             return tensors, None, None
         up = self._stream_for('upload', main)
@@ -1800,6 +1881,9 @@ class FGN(torch.nn.Module):
                              spp_photometric_chain=spp_photometric_chain)
         graphed = self._graphed()
         source = spp_source = None
+        qry_isegmaps = _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to))
+        if spp_crop_to is None and support_code is None:
+            _dense_supports_only(spp_isegmaps)
         if spp_crop_to is not None and support_code is None:
             spp_source = spp_crop_to if isinstance(spp_crop_to, dict) else \
                 self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square,
@@ -2281,6 +2365,8 @@ class FGN(torch.nn.Module):
             raise ValueError('results_at_source: these detections were not made with detect_device(results_at_source=True)')
 
         def host_mask(m):
+            if rle.is_rle(m):                   # masks given as COCO RLE: decoded on the host, here only
+                m = rle.as_masks(m, what='qry_isegmaps').dense()
             m = np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m)
             if results_at_source:               # as given
                 return m
@@ -2336,12 +2422,13 @@ class FGN(torch.nn.Module):
                 hb = host['gt_buf'][g0 * row:(g0 + ng) * row]
                 glen, govf = hb[:ng * 4].view(torch.int32).numpy(), hb[ng * 4:ng * 8].view(torch.int32).numpy()
                 gstr = hb[ng * 8:].view(ng, ops.RLE_BYTE_CAP).numpy()
+                on_host = host_mask(gt) if govf.any() else None     # (once, for the masks whose device RLE overflowed)
                 one['qry_isegmaps_rle'] = [
                     {'size': [oh, ow], 'counts': gstr[j, :glen[j]].tobytes()} if not govf[j] else
-                    rle.encode(host_mask(gt[j]))
+                    rle.encode(on_host[j])
                     for j in range(ng)]
             elif gt is not None:
-                one['qry_isegmaps_rle'] = rle.encode_many(host_mask(gt))
+                one['qry_isegmaps_rle'] = rle.encode_many(host_mask(gt)) if len(gt) else []
             if 'ov_slice' in di:                   # overlap counts from the device: [inter [D,G] | det_area [D] | gt_area [G]]
                 o0, nov = di['ov_slice']
                 md = host['det'].shape[1]

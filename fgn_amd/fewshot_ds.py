@@ -20,7 +20,7 @@ import torch
 from torch.utils.data import Dataset
 
 from . import cluttered_chars as cc
-from . import episodes
+from . import episodes, rle
 from .fsiseg_eval import FSISEGEval
 
 
@@ -1245,7 +1245,11 @@ class ClutteredCharsFewShotISEG(Dataset):
     ``augs`` = 'natural' (default: everything above) or 'coco': the rows come from ``draw_coco_augment`` (COCO's
     ``augs_seq``, coco_ds.py:45-59: flip, one HSV operator, blur), seeded the same way, and with ``photometric_qry`` /
     ``photometric_spp`` the sample carries ``qry_photometric_chain`` [2,3] / ``spp_photometric_chain`` [N*K,2,3] in place
-    of the single rows, for ``FGN.forward_train(qry_photometric_chain=..., spp_photometric_chain=...)``."""
+    of the single rows, for ``FGN.forward_train(qry_photometric_chain=..., spp_photometric_chain=...)``.
+    ``rle_masks``: ``qry_isegmaps`` is the list of the instances' ``rle.encode`` dicts - the form the reference's COCO
+    dataset holds its masks in (coco_ds.py:195-207) - for a detector that decodes on the device, and
+    with ``spp_source`` every entry of ``spp_isegmaps`` is such a dict too.  Off by default; nothing else of a sample
+    changes."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
@@ -1254,8 +1258,9 @@ class ClutteredCharsFewShotISEG(Dataset):
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
                  spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None,
                  spp_source=False, augment_qry=False, photometric_qry=False, augment_spp=False, photometric_spp=False,
-                 augs='natural'):
+                 augs='natural', rle_masks=False):
         par = self.PARAMS[dataset]
+        self.rle_masks = bool(rle_masks)
         if augs not in ('natural', 'coco'):
             raise ValueError(f'augs is \'natural\' (natural_fst.py:18-35) or \'coco\' (coco_ds.py:45-59), got {augs!r}')
         self.augs = augs
@@ -1351,7 +1356,8 @@ class ClutteredCharsFewShotISEG(Dataset):
                 if self.spp_source:                      # the instance as it is: image, box and mask at source size
                     spp_imgs.append(torch.from_numpy(src['img'].copy()))
                     spp_boxes.append(np.asarray(src['bboxes'][o], np.float32))
-                    spp_masks.append(src['isegmaps'][o].astype(bool))
+                    m = src['isegmaps'][o].astype(bool)
+                    spp_masks.append(rle.encode(m) if self.rle_masks else m)
                     spp_ids.append(p)
                     continue
                 crop, nb, m = support_from_instance(src['img'], src['bboxes'][o], src['isegmaps'][o],
@@ -1364,7 +1370,8 @@ class ClutteredCharsFewShotISEG(Dataset):
             'qry_cat_ids_real': im['cat_ids'][keep].astype(np.int64),
             'qry_cat_ids': mapping[im['cat_ids'][keep]].astype(np.int64),
             'qry_bboxes': im['bboxes'][keep].astype(np.float32),
-            'qry_isegmaps': im['isegmaps'][keep].astype(bool),
+            'qry_isegmaps': rle.encode_many(im['isegmaps'][keep]) if self.rle_masks else
+            im['isegmaps'][keep].astype(bool),
             'spp_imgs': spp_imgs if self.spp_source else torch.stack(spp_imgs),
             'spp_bboxes': np.stack(spp_boxes).astype(np.float32),
             'spp_isegmaps': spp_masks if self.spp_source else np.stack(spp_masks).astype(bool),

@@ -1761,6 +1761,88 @@ def dense_mask_rle(masks: torch.Tensor, packed: bool = False):
     return (out, lens, ovf, buf) if packed else (out, lens, ovf)
 
 
+RLE_REC_INTS = 8             # csrc/mask.hip: {h, w, wy, wx, wh, ww, run0, n_runs} per mask
+
+
+def _rle_window(m, window) -> tuple:
+    _, h, w = m.shape
+    wy, wx, wh, ww = (0, 0, h, w) if window is None else (int(v) for v in window)
+    if not (1 <= h <= RESIZE_MAX_DIM and 1 <= w <= RESIZE_MAX_DIM):
+        raise _lib.FgnHipError(f'rle_decode: mask sizes must be within 1..{RESIZE_MAX_DIM}, got {(h, w)}')
+    if not (wy >= 0 and wx >= 0 and wh >= 1 and ww >= 1 and wy + wh <= h and wx + ww <= w):
+        raise _lib.FgnHipError(f'rle_decode: window {(wy, wx, wh, ww)} is empty or outside its {h}x{w} mask')
+    return wy, wx, wh, ww
+
+
+def _rle_decode(parts: list, recs: np.ndarray, out: torch.Tensor, stride: int, max_wh: int, max_ww: int) -> None:
+    """ONE upload - [recs int32 [n,8] | the run ends uint32 of ``parts`` concatenated] as bytes - and ONE launch of
+    ``fgn_rle_decode_u8`` into ``out`` (output i at byte i * stride), on the current stream."""
+    ends = np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+    n = recs.shape[0]
+    blob = torch.from_numpy(np.concatenate([np.ascontiguousarray(recs, np.int32).reshape(-1).view(np.uint8),
+                                            np.ascontiguousarray(ends, np.uint32).view(np.uint8)]))
+    blob = blob.to(out.device, non_blocking=True)
+    base = blob.data_ptr()
+    # (no run at all: every record is refused by the kernel; it needs an address only)
+    _lib.check(_lib.load().fgn_rle_decode_u8(base + 4 * RLE_REC_INTS * n if ends.size else base, int(ends.size), base,
+                                             _ptr(out), int(stride), n, int(max_wh), int(max_ww), _stream()),
+               'fgn_rle_decode_u8')
+
+
+def rle_decode_masks(m, window=None, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
+    """The n masks of an ``rle.RleMasks`` (what ``rle.as_masks`` makes of COCO RLE items) -> dense uint8 0/1 [n,h,w] on
+    the device, or [n,wh,ww] for one ``window`` = (wy, wx, wh, ww) of every mask: ``rle.decode`` bit for bit, i.e. the
+    bytes a dense upload would have put there (maskUtils.decode in get_isegmap, coco_ds.py:265-278, moved behind the
+    bus).  One upload of the run ends and records, one launch; only the runs cross the bus.  ``out``: a contiguous uint8
+    tensor of that shape to write; else a fresh one on ``device`` (default: the current GPU).  An entry without masks
+    launches nothing."""
+    n = int(m.shape[0])
+    wy, wx, wh, ww = _rle_window(m, window)
+    if out is None:
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        out = torch.empty((n, wh, ww), device=dev, dtype=torch.uint8)
+    else:
+        _chk(out, 'out', torch.uint8)
+        if tuple(out.shape) != (n, wh, ww):
+            raise _lib.FgnHipError(f'rle_decode_masks: out is {tuple(out.shape)}, expected {(n, wh, ww)}')
+    if n == 0:
+        return out
+    first = np.asarray(m.first, np.int64)
+    recs = np.empty((n, RLE_REC_INTS), np.int32)
+    recs[:, :6] = (m.shape[1], m.shape[2], wy, wx, wh, ww)
+    recs[:, 6] = first[:-1]
+    recs[:, 7] = np.diff(first)
+    _rle_decode([m.ends], recs, out, wh * ww, wh, ww)
+    return out
+
+
+def rle_decode_rows(slot: torch.Tensor, items: list) -> torch.Tensor:
+    """``rle_decode_masks`` into rows of an existing slot (the support path: ``spp_msk``, the static slot of a captured
+    graph included): ``slot`` uint8 [rows, capacity], contiguous; ``items`` = (row, RleMasks of ONE mask, window) each:
+    the window's wh * ww bytes go to the front of that row, what lies behind them and every other row stays as it is.
+    One upload, one launch for all items; none, no launch."""
+    _chk(slot, 'slot', torch.uint8)
+    if slot.dim() != 2:
+        raise _lib.FgnHipError('rle_decode_rows: slot must be [rows, capacity]')
+    rows, cap = slot.shape
+    if not items:
+        return slot
+    recs = np.zeros((rows, RLE_REC_INTS), np.int32)          # (an all-zero record has an empty window: nothing is written)
+    parts, run0, max_wh, max_ww = [], 0, 0, 0
+    for row, m, window in items:
+        if not 0 <= int(row) < rows or int(m.shape[0]) != 1 or recs[int(row), 4]:
+            raise _lib.FgnHipError(f'rle_decode_rows: row {row} of {rows}: one mask per item, one item per row')
+        wy, wx, wh, ww = _rle_window(m, window)
+        if wh * ww > cap:
+            raise _lib.FgnHipError(f'rle_decode_rows: a window of {wh * ww} bytes exceeds the slot capacity {cap}')
+        recs[int(row)] = (m.shape[1], m.shape[2], wy, wx, wh, ww, run0, m.ends.size)
+        parts.append(m.ends)
+        run0 += int(m.ends.size)
+        max_wh, max_ww = max(max_wh, wh), max(max_ww, ww)
+    _rle_decode(parts, recs, slot, cap, max_wh, max_ww)
+    return slot
+
+
 def mask_bits(masks: torch.Tensor):
     """Bit planes of dense binary masks [G,H,W] (bool / uint8, non-zero = set), the ground-truth operand of
     ``mask_overlap``: returns (bits int64 [H, ceil(W/64), G] - bit b of word xw of a row = pixel 64 xw + b - ,

@@ -492,8 +492,7 @@ def forward_train(model, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bbo
         # mask_target_single + BitmapMasks.crop_and_resize: RoIAlign(aligned, adaptive grid) of the GT bitmaps
         gt_masks = []
         for m_ in qry_isegmaps:
-            m_ = torch.as_tensor(m_).to(dev, non_blocking=True)
-            gt_masks.append((m_ if m_.dtype in (torch.bool, torch.uint8) else (m_ != 0)).to(torch.uint8))
+            gt_masks.append(model._device_masks(m_, dev).to(torch.uint8))       # (dense, or decoded from COCO RLE)
         first = np.cumsum([0] + [m_.shape[0] for m_ in gt_masks[:-1]])
         masks_all = torch.cat(gt_masks).contiguous()
         mh_, mw_ = masks_all.shape[-2:]

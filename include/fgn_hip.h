@@ -492,6 +492,27 @@ int fgn_dense_mask_rle(const uint8_t* masks, void* scratch, size_t scratch_bytes
                        int32_t* out_len, int32_t* overflow, int n_masks, int img_h, int img_w, int trans_cap,
                        int byte_cap, void* stream);
 
+/* COCO RLE as an INPUT, decoded on the device: the masks the reference's COCO dataset keeps as [size, counts]
+ * (coco_ds.py:195-207) and decodes on the host for every sample (maskUtils.decode in get_isegmap, coco_ds.py:265-278).
+ * n masks, or windows of them, in ONE launch; output i is exactly the bytes a dense upload of that window would hold.
+ *   ends uint32 [n_ends]: the cumulative run ends of all masks concatenated, each mask counted from its own 0
+ *        (fgn_amd.rle.RleMasks; a repeated end is a zero-length run)
+ *   recs int32 [n][8], read ON THE DEVICE: {h, w, wy, wx, wh, ww, run0, n_runs} = the mask size, the window of it to
+ *        produce (rows [wy, wy + wh), columns [wx, wx + ww)) and its slice ends[run0, run0 + n_runs)
+ *   out  output i is [wh][ww] bytes, each 0 or 1, row-major, at out + i * out_stride_bytes; no alignment is assumed, and
+ *        the bytes behind the window in its row of the slot are not written
+ * Pixel (y, x) of a mask sits at column-major position p = x * h + y (< 2^28) and its value is r & 1, r = the number
+ * of entries of the slice that are <= p.  The kernel is safe for ANY contents of ends: every index it forms lies in
+ * [run0, run0 + n_runs); a slice that is not monotone gives garbage bits, never a read outside it.
+ * A record is out of range when a size is outside 1..16384, the window is empty or leaves the mask, wh > max_wh or
+ * ww > max_ww, wh * ww > out_stride_bytes, n_runs < 1, or the slice leaves [0, n_ends): none of its runs is read, and
+ * its window is written as zeros where wh >= 1, ww >= 1 and wh * ww <= out_stride_bytes, and not at all otherwise.
+ * A null pointer is FGN_ERR_ARG; negative n, stride or n_ends, max_wh / max_ww above 16384, or
+ * n * ceil(max_ww / 256) >= 2^24 (the grid), FGN_ERR_SHAPE; n == 0 or
+ * an empty maximum window FGN_OK with no launch (pointers are not looked at). */
+int fgn_rle_decode_u8(const uint32_t* ends, long long n_ends, const int32_t* recs, unsigned char* out,
+                      long long out_stride_bytes, int n, int max_wh, int max_ww, void* stream);
+
 /* Matching on the device: the exact pixel counts the evaluator needs from the masks, so that no RLE is decoded on the
  * host.  Step 1, bit planes of the ground-truth masks: masks [n][H][W] bytes (non-zero = set) -> bits, one 64-bit word
  * per 64 consecutive x of a row (bit b of word xw = pixel x = 64 xw + b; bits of x >= W are zero), laid out
