@@ -10,6 +10,7 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --source-size 200 --results-at-source     (... results in the 200^2 frame)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source     (supports cropped, resized and padded on the GPU)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source --rle-masks     (masks travel as COCO RLE, decoded on the GPU)
+    python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source --color-masks     (masks travel as box + colour, made on the GPU from the image bytes)
     python examples/eval_loop.py --episodes 8 --match-on-device     (mask overlaps counted on the GPU: the evaluator decodes no RLE)
     python examples/eval_loop.py --episodes 8 --eval-on-device --iou-thrs coco     (greedy matching on the GPU too; AP at COCO's ten thresholds)
 """
@@ -54,6 +55,10 @@ def main():
                     help='character datasets: the loader yields the ground-truth masks as COCO RLE dicts (the form the '
                          'reference\'s COCO dataset holds them in), with --spp-source the support masks too; the detector '
                          'decodes them on the GPU and only their runs are uploaded')
+    ap.add_argument('--color-masks', action='store_true',
+                    help='character datasets: the loader yields the ground-truth masks as box + colour, all that MNISTISEG / '
+                         'OMNIISEG store per instance, with --spp-source the support masks too; the detector makes the '
+                         'masks on the GPU from the image bytes (implies --uint8; not beside --rle-masks)')
     ap.add_argument('--match-on-device', action='store_true',
                     help='count the overlaps of detections and ground truth on the GPU (FGN.match_on_device): the results '
                          'carry dt_gt_inter / dt_area / gt_area and the evaluator decodes no RLE')
@@ -65,11 +70,13 @@ def main():
                     help="IoU thresholds to report besides the reference's 0.5: 'coco' (0.5:0.05:0.95) or a comma-separated "
                          'list of at most 16 (evaluate_results_multi; with --eval-on-device they are matched on the GPU)')
     args = ap.parse_args()
-    args.uint8 = args.uint8 or args.source_size is not None or args.spp_source
+    args.uint8 = args.uint8 or args.source_size is not None or args.spp_source or args.color_masks
     if args.results_at_source and args.source_size is None:
         ap.error('--results-at-source needs --source-size')
     if args.rle_masks and args.dataset == 'SYNTH':
         ap.error('--rle-masks needs --dataset MNISTISEG or OMNIISEG')
+    if args.color_masks and args.rle_masks:
+        ap.error('--color-masks and --rle-masks are two forms of one argument: choose one')
     if args.uint8 and args.dataset == 'SYNTH':
         ap.error('--uint8 / --source-size / --spp-source need --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
 
@@ -79,7 +86,7 @@ def main():
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,
                                        raw_uint8=args.uint8, source_size=args.source_size, spp_source=args.spp_source,
-                                       rle_masks=args.rle_masks)
+                                       rle_masks=args.rle_masks, color_masks=args.color_masks)
     model = FGN(args.n_ways, args.k_shots)
     if args.uint8:
         model.set_input_norm(**ds.input_norm)

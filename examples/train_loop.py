@@ -11,6 +11,7 @@ warm-up 100 iterations, 3 epochs) on the MI355X path: DataLoader(ds, collate_fn_
     python examples/train_loop.py --dataset OMNIISEG --spp-source --augment-spp --photometric-spp
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --augment --photometric --augs coco
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment --rle-masks
+    python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment --photometric --color-masks
 
 ``--source-size S``: the loader hands over decoded S x S pixels and the detector resizes them on the GPU
 (``qry_resize_to``); ``--spp-source``: the supports are cut from their source images on the GPU (``spp_crop_to``);
@@ -25,7 +26,9 @@ photometric operators as well (``spp_photometric``).  ``--augs coco``: the rows 
 one of hue / saturation / brightness, then a blur) and the photometric half travels as a chain of two operators per image
 (``qry_photometric_chain`` / ``spp_photometric_chain``), which one kernel applies in one pass.  ``--rle-masks``: the
 ground-truth masks (with ``--spp-source`` the support masks too) travel as COCO RLE, the form the reference's COCO
-dataset holds them in, and are decoded on the GPU.  The evaluation at the end is without augmentation.
+dataset holds them in, and are decoded on the GPU.  ``--color-masks`` (needs ``--source-size`` or ``--spp-source``: the
+images travel as bytes): the masks travel as box + colour, all the character datasets store, and are made on the GPU
+from the image bytes as uploaded, ahead of any augmentation.  The evaluation at the end is without augmentation.
 
 The backbone is frozen as in fgn_r50_c4_densecl.py:31; with no pretrained checkpoint here it is randomly
 initialised, so this demonstrates the loop (losses fall on the training episodes), not a trained detector.
@@ -72,9 +75,16 @@ def main():
                     help='the sequence the augmentation rows are drawn like: natural_fst\'s or COCO\'s (a chain)')
     ap.add_argument('--rle-masks', action='store_true',
                     help='masks travel as COCO RLE and are decoded on the GPU (character datasets)')
+    ap.add_argument('--color-masks', action='store_true',
+                    help='masks travel as box + colour and are made on the GPU from the image bytes (character datasets; '
+                         'needs --source-size or --spp-source)')
     args = ap.parse_args()
     if args.rle_masks and args.dataset == 'SYNTH':
         ap.error('--rle-masks needs a character dataset (MNISTISEG, OMNIISEG)')
+    if args.color_masks and args.rle_masks:
+        ap.error('--color-masks and --rle-masks are two forms of one argument: choose one')
+    if args.color_masks and args.source_size is None and not args.spp_source:
+        ap.error('--color-masks needs --source-size or --spp-source: the detector makes the masks from the image bytes')
     if args.augment_spp and not args.spp_source:
         ap.error('--augment-spp needs --spp-source: the supports are augmented behind their cut from the source images')
     if args.photometric_spp and not args.augment_spp:
@@ -94,7 +104,7 @@ def main():
                                        raw_uint8=source, source_size=args.source_size, spp_source=args.spp_source,
                                        augment_qry=args.augment, photometric_qry=args.photometric,
                                        augment_spp=args.augment_spp, photometric_spp=args.photometric_spp,
-                                       augs=args.augs, rle_masks=args.rle_masks)
+                                       augs=args.augs, rle_masks=args.rle_masks, color_masks=args.color_masks)
     model = FGN(args.n_ways, args.k_shots)
     if source:
         model.set_input_norm(**ds.input_norm)

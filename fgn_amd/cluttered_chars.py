@@ -129,8 +129,10 @@ def make_image(seed: int, size: int, cats) -> dict:
         if len(bboxes) >= 2:
             break
     masks = np.stack([char_mask_by_color(img, b, c) for b, c in zip(bboxes, colors)])
+    # (``colors``: what the reference keeps per instance in ``*_colors.pkl``, mnistiseg_ds.py:103 - with the box, all
+    # a mask is derived from)
     return dict(img=img, bboxes=np.asarray(bboxes, np.float32), cat_ids=np.asarray(cat_ids, np.int64),
-                isegmaps=masks)
+                isegmaps=masks, colors=np.asarray(colors, np.uint8).reshape(-1, 3))
 
 
 def crop_support(img, box, mask, out_size: int, fill_ratio: float = 0.8):

@@ -737,6 +737,111 @@ extern "C" int fgn_rle_decode_u8(const uint32_t* ends, long long n_ends, const i
 }
 
 // ----------------------------------------------------------------------------------------------
+// Box + colour as an INPUT: the character datasets of the reference (cfg1 MNISTISEG, cfg2 OMNIISEG) store no mask, only
+// a box and the RGB colour of every instance, and derive the mask from the image on the host for every sample
+// (get_char_mask_by_color, create_img_from_chars.py:136-158; base_fst.py:836 for the query, :1107 per support
+// instance): the pixels of the box inside the colour window, dilated 3x3 inside the box.  The image bytes are on the
+// device already (qry_src / spp_src / the uint8 qry_img), so the mask is made here, right where a dense upload would
+// have put its bytes, from 16 ints per mask.
+//   p(y, x) = all_c(lo_c <= img[y][x][c] <= hi_c) inside the box, 0 outside; mask(y, x) = OR of p over the 3x3
+//   neighbourhood for (y, x) inside the box, 0 outside.  No pixel outside the box (or the image) ever contributes.
+//   Mapping: one workgroup of 4 waves per (mask, 64 x 32 tile of the IMAGE) - the output is written in full, zeros
+//   outside the box included, so tiles that miss the box store zeros and read nothing.  A tile that meets it evaluates p
+//   on its 34 rows (one halo row above and below): a wave takes a row, a lane a column, and the wave's ballot IS the
+//   row's 64-bit word, kept in LDS; the two halo columns of the 34 rows are 68 single predicates.  Each image byte is
+//   read once per tile (plus halo).  The dilation of a row is w | w << 1 | w >> 1 with the halo bits carried in at bit 0
+//   and bit 63, ORed over three rows; a lane stores its bit as one byte: 64 consecutive bytes per wave and row, no
+//   pointer cast, so neither the image row nor the output needs any alignment.  No atomics, no scratch.
+//   Safety: every record field is checked against the capacities passed in before an address is formed; inside a valid
+//   record a pixel is read only where it lies inside the box, and the box lies inside h x w, 3 * h * w <= src_cap.
+// ----------------------------------------------------------------------------------------------
+constexpr int CM_THREADS = 256;
+constexpr int CM_TW = 64;           // tile columns: one ballot word
+constexpr int CM_TH = 32;           // tile rows
+constexpr int CM_REC_INTS = 16;     // {row, h, w, y0, x0, y1, x1, lo_r, lo_g, lo_b, hi_r, hi_g, hi_b, out, 0, 0}
+
+__global__ __launch_bounds__(CM_THREADS) void color_mask_kernel(const uint8_t* __restrict__ src, long long src_stride,
+                                                                long long src_cap, int src_rows,
+                                                                const int32_t* __restrict__ recs,
+                                                                uint8_t* __restrict__ out, long long out_stride,
+                                                                int n_out, int tiles_x, int max_h, int max_w) {
+    __shared__ unsigned long long words[CM_TH + 2];
+    __shared__ uint8_t side[2][CM_TH + 2];
+    const int i = blockIdx.x / tiles_x, tx = blockIdx.x - i * tiles_x;            // (workgroup-uniform)
+    const int32_t* rec = recs + (size_t)i * CM_REC_INTS;
+    const int row = rec[0], h = rec[1], w = rec[2], y0 = rec[3], x0 = rec[4], y1 = rec[5], x1 = rec[6], oi = rec[13];
+    // the output must exist before anything is written: index inside the slot array, h * w bytes inside its stride
+    if (!(oi >= 0 && oi < n_out && h >= 1 && w >= 1 && (long long)h * w <= out_stride)) return;
+    uint8_t* dst = out + (size_t)oi * (size_t)out_stride;
+    const bool ok = h <= max_h && w <= max_w && h <= SRC_MAX_DIM && w <= SRC_MAX_DIM && row >= 0 && row < src_rows &&
+                    3ll * h * w <= src_cap && y0 >= 0 && y0 <= y1 && y1 <= h && x0 >= 0 && x0 <= x1 && x1 <= w;
+    if (!ok) {
+        // an out-of-range record reads no pixel; its output is zeros (the workgroups of this mask share the bytes)
+        const long long total = (long long)h * w;
+        const long long step = (long long)tiles_x * gridDim.y * CM_THREADS;
+        for (long long b = ((long long)blockIdx.y * tiles_x + tx) * CM_THREADS + threadIdx.x; b < total; b += step)
+            dst[b] = 0;
+        return;
+    }
+    const int X0 = tx * CM_TW, Y0 = blockIdx.y * CM_TH;
+    if (X0 >= w || Y0 >= h) return;
+    const int rows = min(CM_TH, h - Y0), cols = min(CM_TW, w - X0);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int x = X0 + lane;
+    if (!(y0 < y1 && x0 < x1 && Y0 < y1 && Y0 + CM_TH > y0 && X0 < x1 && X0 + CM_TW > x0)) {
+        if (lane < cols)                                                          // the tile misses the box: zeros
+            for (int r = wave; r < rows; r += CM_THREADS / 64) dst[(size_t)(Y0 + r) * w + x] = 0;
+        return;
+    }
+    const uint8_t* img = src + (size_t)row * (size_t)src_stride;
+    const int lo0 = rec[7], lo1 = rec[8], lo2 = rec[9], hi0 = rec[10], hi1 = rec[11], hi2 = rec[12];
+    auto pred = [&](int py, int px) -> bool {                                     // (inside the box => inside the image)
+        if (py < y0 || py >= y1 || px < x0 || px >= x1) return false;
+        const uint8_t* p = img + ((size_t)py * w + px) * 3;
+        const int r = p[0], g = p[1], b = p[2];
+        return r >= lo0 && r <= hi0 && g >= lo1 && g <= hi1 && b >= lo2 && b <= hi2;
+    };
+    for (int rr = wave; rr < CM_TH + 2; rr += CM_THREADS / 64) {                  // row Y0 - 1 + rr of the image
+        const unsigned long long word = __ballot(pred(Y0 - 1 + rr, x));
+        if (lane == 0) words[rr] = word;
+    }
+    if (threadIdx.x < 2 * (CM_TH + 2)) {                                          // the halo columns X0 - 1 and X0 + 64
+        const int s = threadIdx.x / (CM_TH + 2), rr = threadIdx.x - s * (CM_TH + 2);
+        side[s][rr] = pred(Y0 - 1 + rr, s ? X0 + CM_TW : X0 - 1) ? 1 : 0;
+    }
+    __syncthreads();
+    for (int r = wave; r < rows; r += CM_THREADS / 64) {
+        const int y = Y0 + r;
+        unsigned long long acc = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const unsigned long long c = words[r + k];
+            acc |= c | (c << 1) | (c >> 1) | (unsigned long long)side[0][r + k] |
+                   ((unsigned long long)side[1][r + k] << 63);
+        }
+        const bool in = y >= y0 && y < y1 && x >= x0 && x < x1;
+        if (lane < cols) dst[(size_t)y * w + x] = (uint8_t)(in ? (acc >> lane) & 1ull : 0ull);
+    }
+}
+
+extern "C" int fgn_color_mask_u8(const uint8_t* src, long long src_stride_bytes, long long src_cap_bytes, int src_rows,
+                                 const int32_t* recs, int n, uint8_t* out, long long out_stride_bytes, int n_out,
+                                 int max_h, int max_w, hipStream_t stream) {
+    if (n < 0 || src_rows < 0 || n_out < 0 || src_stride_bytes < 0 || src_cap_bytes < 0 || out_stride_bytes < 0 ||
+        max_h < 0 || max_w < 0 || max_h > SRC_MAX_DIM || max_w > SRC_MAX_DIM)
+        return FGN_ERR_SHAPE;
+    if (n == 0 || max_h == 0 || max_w == 0) return FGN_OK;
+    if (!src || !recs || !out) return FGN_ERR_ARG;
+    const int tiles_x = cdiv(max_w, CM_TW);
+    if ((long long)n * tiles_x >= (1ll << 24)) return FGN_ERR_SHAPE;        // (grid.x * CM_THREADS stays below 2^32)
+    hipLaunchKernelGGL(color_mask_kernel, dim3((unsigned)(n * tiles_x), cdiv(max_h, CM_TH)), dim3(CM_THREADS), 0, stream,
+                       src, src_stride_bytes, src_cap_bytes, src_rows, recs, out, out_stride_bytes, n_out, tiles_x, max_h,
+                       max_w);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
 // Matching on the device: exact pixel counts |d & g|, |d|, |g| of every (detection, ground truth) pair.
 // The evaluator (fgn_amd/fsiseg_eval.py) needs nothing else from the masks, and both operands are on the device while
 // the episode is in flight: the ground-truth masks (uploaded for the RLE above) and the mask probabilities + boxes the

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import config as _config
-from . import ops, rle
+from . import colormask, ops, rle
 from .weights import backbone_state_from_pretrained, init_state_dict
 
 
@@ -430,22 +430,45 @@ def _host(v) -> np.ndarray:
     return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
 
 
-def _gt_entries(qry_isegmaps, sizes):
+def _gt_entries(qry_isegmaps, sizes, imgs=None):
     """``qry_isegmaps`` normalised once at the front (host only, nothing is queued): an entry given as COCO RLE
     (``rle.as_masks``: a list of dicts or ``[size, counts]`` pairs, an ``RleMasks``, the empty list) becomes a checked
     ``RleMasks`` at ``sizes[i]`` = (h, w) - a size that disagrees is a ValueError -, a dense entry stays as it is.
-    Without an RLE entry the argument itself comes back."""
-    if qry_isegmaps is None or not any(rle.is_rle(g) for g in qry_isegmaps):
+    An entry given as box + colour (``colormask.as_color_masks``: a ``ColorMasks`` or a dict of ``bboxes`` and
+    ``colors``) becomes a checked ``ColorMasks`` at ``sizes[i]``, bound to ``imgs[i]`` - the image's bytes [h,w,3] as
+    they were handed over, which is what its mask is made from; ``imgs`` is None where the images are not bytes (float
+    input), and a colour entry is refused then.  Without an RLE or colour entry the argument itself comes back."""
+    if qry_isegmaps is None or not isinstance(qry_isegmaps, (list, tuple)) or \
+            not any(rle.is_rle(g) or colormask.is_color(g) for g in qry_isegmaps):
         return qry_isegmaps
     if sizes is not None and len(sizes) != len(qry_isegmaps):
         raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {len(sizes)} images')
-    return [rle.as_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]') if rle.is_rle(g) else g
-            for i, g in enumerate(qry_isegmaps)]
+    out = []
+    for i, g in enumerate(qry_isegmaps):
+        if colormask.is_color(g):
+            if imgs is None:
+                raise ValueError(f'qry_isegmaps[{i}]: a box + colour entry is made into a mask from the image\'s bytes on '
+                                 f'the device: give qry_img as uint8 pixels (set_input_norm, with or without '
+                                 f'qry_resize_to), not as a normalised float tensor')
+            g = colormask.as_color_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]', img=imgs[i])
+        elif rle.is_rle(g):
+            g = rle.as_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]')
+        out.append(g)
+    return out
+
+
+def _has_color(entries) -> bool:
+    return isinstance(entries, (list, tuple)) and any(isinstance(g, colormask.ColorMasks) for g in entries)
 
 
 def _dense_supports_only(spp_isegmaps) -> None:
     """The plain support path takes the dense [B,N*K,S,S] tensor only: the supports are already cut, resized and
-    padded there, and no dataset holds such masks as runs."""
+    padded there, and no dataset holds such masks as runs - nor is there a source image to derive a box + colour mask
+    from."""
+    flat = spp_isegmaps if isinstance(spp_isegmaps, (list, tuple)) else [spp_isegmaps]
+    if any(colormask.is_color(m) or (isinstance(m, (list, tuple)) and any(colormask.is_color(v) for v in m)) for m in flat):
+        raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; box + colour '
+                         'masks are made from the instances\' source images, with spp_crop_to')
     if isinstance(spp_isegmaps, (list, tuple, dict, rle.RleMasks)):
         raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; RLE masks '
                          'are taken at source size, with spp_crop_to')
@@ -1077,7 +1100,9 @@ class FGN(torch.nn.Module):
             if len(qry_isegmaps) != B:
                 raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {B} images')
             for i, (g, hw) in enumerate(zip(qry_isegmaps, sizes)):
-                if rle.is_rle(g):                          # (an ``RleMasks`` of ``_gt_entries`` passes by its shape)
+                if colormask.is_color(g):                  # (a ``ColorMasks`` of ``_gt_entries`` passes by its shape)
+                    g = colormask.as_color_masks(g, hw, f'qry_isegmaps[{i}]')
+                elif rle.is_rle(g):                        # (an ``RleMasks`` of ``_gt_entries`` passes by its shape)
                     g = rle.as_masks(g, hw, f'qry_isegmaps[{i}]')
                 if len(g.shape) != 3 or (int(g.shape[1]), int(g.shape[2])) != hw:
                     raise ValueError(f'qry_isegmaps: with qry_resize_to the masks are at source size {hw}, got '
@@ -1112,6 +1137,41 @@ class FGN(torch.nn.Module):
         if not imgs or any(not isinstance(im, torch.Tensor) or im.dim() != 3 for im in imgs):
             return None
         return [(int(im.shape[0]), int(im.shape[1])) for im in imgs]
+
+    def _gt_images(self, qry_img, qry_resize_to):
+        """The images a box + colour entry is derived from, one [h,w,3] uint8 tensor per image, in the frame
+        ``_gt_sizes`` names - the source images with ``qry_resize_to``, else the uint8 ``qry_img`` under a table - or None
+        where the query is not bytes."""
+        if isinstance(qry_resize_to, dict):
+            return [f.view(h, w, 3) for f, (h, w) in zip(qry_resize_to['flats'], qry_resize_to['sizes'])]
+        imgs = qry_img
+        if qry_resize_to is None and (not isinstance(imgs, torch.Tensor) or imgs.dim() != 4 or self.input_lut is None):
+            return None
+        imgs = list(imgs) if isinstance(imgs, (list, tuple, torch.Tensor)) else []
+        if not imgs or any(not isinstance(im, torch.Tensor) or im.dtype != torch.uint8 or im.dim() != 3 or
+                           im.shape[2] != 3 for im in imgs):
+            return None
+        return imgs
+
+    def _gt_front(self, qry_isegmaps, qry_img, img_shape, qry_resize_to):
+        """``_gt_entries`` with the sizes and images of this call."""
+        if qry_isegmaps is None or not isinstance(qry_isegmaps, (list, tuple)) or \
+                not any(rle.is_rle(g) or colormask.is_color(g) for g in qry_isegmaps):
+            return qry_isegmaps
+        return _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to),
+                           self._gt_images(qry_img, qry_resize_to))
+
+    @staticmethod
+    def _color_on_device(entries: list, slot: torch.Tensor) -> list:
+        """The box + colour entries of ``entries`` (``ColorMasks``, entry b reading image b) made into dense uint8 masks
+        [n_b,h_b,w_b] on the device from ``slot`` - uint8 [B, bytes], image b as [h_b,w_b,3] at the front of row b, AS
+        UPLOADED - in ONE launch on the current stream, which is the stream that carried those bytes up (DESIGN
+        4.4.11); every other entry stays as it is.  Without a colour entry nothing is called."""
+        items = [(b, g) for b, g in enumerate(entries or ()) if isinstance(g, colormask.ColorMasks)]
+        if not items:
+            return entries
+        made = iter(ops.color_masks(slot, items))
+        return [next(made) if isinstance(g, colormask.ColorMasks) else g for g in entries]
 
     @staticmethod
     def _augment_plans(qry_augment, qry_bboxes, rs: dict) -> tuple:
@@ -1268,7 +1328,7 @@ class FGN(torch.nn.Module):
         if qry_photometric_chain is not None and qry_resize_to is None:
             raise ValueError('qry_photometric_chain needs qry_resize_to: the photometric operators run on the source '
                              'pixels, ahead of their resize')
-        qry_isegmaps = _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to))
+        qry_isegmaps = self._gt_front(qry_isegmaps, qry_img, img_shape, qry_resize_to)
         sp = None
         if spp_crop_to is None:
             _dense_supports_only(spp_isegmaps)
@@ -1289,8 +1349,16 @@ class FGN(torch.nn.Module):
                                                         None if recs is None else recs.numpy())
         if rs is not None or sp is not None:
             dev = self._gpu('forward_train')
+        if rs is None and _has_color(qry_isegmaps):
+            # uint8 pixels at the network size: up on this stream, the masks made right behind the copy
+            dev = self._gpu('forward_train')
+            qry_img = qry_img.to(dev, non_blocking=True).contiguous()
+            qry_isegmaps = self._color_on_device(qry_isegmaps, qry_img.view(qry_img.shape[0], -1))
         if rs is not None:
             qry_img = _InputForm(source=rs).query(self._upload_source(rs, dev))
+            # box + colour entries: from the bytes AS UPLOADED, ahead of the photometric pass (which writes a new tensor;
+            # the reference derives its masks before it augments, mnistiseg_ds.py:124-132)
+            qry_isegmaps = self._color_on_device(qry_isegmaps, qry_img.src)
             if precs is not None:                          # (all rows neutral after the fallback: no launch)
                 run = ops.photometric_u8 if precs.dim() == 2 else ops.photometric_chain_u8      # ([B,64] or [B,P,64])
                 qry_img = qry_img._replace(src=run(qry_img.src, precs.to(dev, non_blocking=True)))
@@ -1344,7 +1412,10 @@ class FGN(torch.nn.Module):
         image and mask windows as flat byte tensors, the largest of each and the slot sizes in bytes per instance.  A mask
         may be ONE COCO RLE item (``rle.as_masks``: dict or ``[size, counts]`` pair) at its image's size: the geometry is
         the same, its entry of ``mflats`` is empty - no mask byte is uploaded - and ``mrle`` lists (row, ``RleMasks``,
-        window) for ``_upload_supports``; ``window_bytes`` counts the bytes of its run ends instead."""
+        window) for ``_upload_supports``; ``window_bytes`` counts the bytes of its run ends instead.  Or ONE box + colour
+        item (``colormask.as_color_masks``) in its image's frame: likewise no mask byte, ``mcol`` lists (row, the item
+        moved into the window's frame) - the window holds the item's whole box, which is checked here - and
+        ``window_bytes`` counts its record."""
         from . import fewshot_ds as fd
         if isinstance(spp_crop_to, bool) or not isinstance(spp_crop_to, (int, np.integer)) or \
                 not 1 <= int(spp_crop_to) <= ops.RESIZE_MAX_DIM:
@@ -1370,14 +1441,19 @@ class FGN(torch.nn.Module):
             raise ValueError(f'spp_bboxes: with spp_crop_to, [..,{NK},4] YXYX in the source frame for {B} support '
                              f'set(s), got {list(bb.shape)}')
         bb = bb.reshape(B * NK, 4)
-        recs, boxes, wins, mrle = [], [], [], []
+        recs, boxes, wins, mrle, mcol = [], [], [], [], []
         for i, (im, mk) in enumerate((im, mk) for g in groups for im, mk in zip(*g)):
             im = _host(im)
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise ValueError(f'spp_imgs: with spp_crop_to every image is channels-last uint8 pixels [h,w,3], got '
                                  f'{im.dtype} {list(im.shape)}')
-            runs = None
-            if rle.is_item(mk) or isinstance(mk, rle.RleMasks):     # ONE mask as COCO RLE, at its image's size
+            runs = col = None
+            if colormask.is_color(mk):                              # ONE mask as box + colour, in its image's frame
+                col = colormask.as_color_masks(mk, im.shape[:2], f'spp_isegmaps[{i}]')
+                if len(col) != 1:
+                    raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(col)}')
+                mk = np.zeros((0, 0), np.uint8)
+            elif rle.is_item(mk) or isinstance(mk, rle.RleMasks):   # ONE mask as COCO RLE, at its image's size
                 runs = rle.as_masks(mk if isinstance(mk, rle.RleMasks) else [mk], im.shape[:2], f'spp_isegmaps[{i}]')
                 if len(runs) != 1:
                     raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(runs)}')
@@ -1392,6 +1468,17 @@ class FGN(torch.nn.Module):
             if runs is not None:        # no mask byte is uploaded: the window is decoded into its row (_upload_supports)
                 g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
                 mrle.append((i, runs, (g['wy'], g['wx'], g['wh'], g['ww'])))
+            if col is not None:         # no mask byte is uploaded: the mask is made from the image window in row i
+                g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
+                y0, x0, y1, x1 = (int(v) for v in col.boxes[0])
+                # (``support_geometry``: the crop reads the rows and columns of the instance's box unreflected, so the
+                # window holds the whole box - and with it every pixel the mask is made from)
+                if not (g['wy'] <= y0 and y1 <= g['wy'] + g['wh'] and g['wx'] <= x0 and x1 <= g['wx'] + g['ww']):
+                    raise ValueError(f'spp_isegmaps[{i}]: the box {[y0, x0, y1, x1]} of the colour item leaves the window '
+                                     f'{[g["wy"], g["wx"], g["wy"] + g["wh"], g["wx"] + g["ww"]]} that the crop of '
+                                     f'spp_bboxes[{i}] reads: give the instance\'s own box')
+                mcol.append((i, colormask.ColorMasks(col.boxes - np.array([g['wy'], g['wx']] * 2, np.int32), col.colors,
+                                                     (g['wh'], g['ww']), col.shift)))
         need = max(w[0].size for w in wins)
         mneed = need // 3                                  # (wh * ww of the largest window, dense or not)
         capacity, mcapacity = need, mneed
@@ -1405,8 +1492,9 @@ class FGN(torch.nn.Module):
                     boxes=torch.from_numpy(np.stack(boxes).reshape(B, NK, 4)),
                     flats=[torch.from_numpy(w.reshape(-1)) for w, _ in wins],
                     mflats=[torch.from_numpy(m.reshape(-1)) for _, m in wins], need=need, mneed=mneed,
-                    capacity=capacity, mcapacity=mcapacity, mrle=mrle,
-                    window_bytes=int(sum(w.size + m.size for w, m in wins) + sum(r.ends.nbytes for _, r, _ in mrle)))
+                    capacity=capacity, mcapacity=mcapacity, mrle=mrle, mcol=mcol,
+                    window_bytes=int(sum(w.size + m.size for w, m in wins) + sum(r.ends.nbytes for _, r, _ in mrle) +
+                                     4 * ops.CM_REC_INTS * len(mcol)))
 
     @staticmethod
     def _slot_rows(flats: list, width: int, capacity: int, dev, slot: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1429,8 +1517,12 @@ class FGN(torch.nn.Module):
         msk = self._slot_rows(sp['mflats'], sp['mneed'], sp['mcapacity'], dev, into.get('spp_msk'))
         # an instance whose mask came as RLE uploaded no mask byte: its window is decoded straight into its row
         ops.rle_decode_rows(msk, sp.get('mrle') or [])
-        return {'spp_src': self._slot_rows(sp['flats'], sp['need'], sp['capacity'], dev, into.get('spp_src')),
-                'spp_msk': msk}
+        src = self._slot_rows(sp['flats'], sp['need'], sp['capacity'], dev, into.get('spp_src'))
+        if sp.get('mcol'):
+            # ... and one that came as box + colour has its mask made from its image window, on this stream BEHIND the
+            # copy of that window and ahead of the cut that reads both
+            ops.color_mask_rows(src, msk, sp['mcol'])
+        return {'spp_src': src, 'spp_msk': msk}
 
     def _supports_on_device(self, sp: dict, dev) -> tuple:
         """``_source_supports`` uploaded on the current stream, in the form ``_support_front`` takes:
@@ -1583,13 +1675,19 @@ class FGN(torch.nn.Module):
         pairs; at the image's source size with ``qry_resize_to``, else at the network size; dense and RLE entries may be
         mixed in a batch), and with ``spp_crop_to`` every instance of ``spp_isegmaps`` may be one RLE item at its source
         image's size; they are checked on the host, only their runs are uploaded and the device decodes them into the
-        bytes of the dense form - every result is that of the dense call."""
+        bytes of the dense form - every result is that of the dense call.  Masks as box + colour, the
+        form the character datasets store: an entry of ``qry_isegmaps`` may be a ``colormask.ColorMasks`` or a dict
+        ``{'bboxes': [n,4] YXYX, 'colors': [n,3] RGB[, 'shift']}`` in the frame of the image as handed over (source size
+        with ``qry_resize_to``, else the network size), mixed freely with the other two forms; it needs the image as
+        uint8 pixels (``set_input_norm``; a float image is refused), and with ``spp_crop_to`` every instance of
+        ``spp_isegmaps`` may be one such item in its source image's frame.  The device makes the masks from the image
+        bytes it was sent anyway, on the stream that carried them and behind their copy; 16 ints per mask are uploaded."""
         self._refuse_augment(qry_augment=qry_augment, qry_photometric=qry_photometric, spp_augment=spp_augment,
                              spp_photometric=spp_photometric, qry_photometric_chain=qry_photometric_chain,
                              spp_photometric_chain=spp_photometric_chain)
         if results_at_source and qry_resize_to is None:
             raise ValueError('results_at_source needs qry_resize_to: results at source size exist for source-size queries')
-        qry_isegmaps = _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to))
+        qry_isegmaps = self._gt_front(qry_isegmaps, qry_img, img_shape, qry_resize_to)
         sp = None
         if spp_crop_to is not None and support_code is None:
             sp = self._source_supports(spp_imgs, spp_bboxes, spp_isegmaps, spp_crop_to, spp_fill_ratio, crop_square,
@@ -1772,6 +1870,9 @@ class FGN(torch.nn.Module):
         only their runs cross the bus."""
         if rle.is_rle(g):
             return ops.rle_decode_masks(rle.as_masks(g, what='qry_isegmaps'), device=dev)
+        if colormask.is_color(g):              # (made beside the upload of its image: ``_color_on_device``)
+            raise ValueError('qry_isegmaps: a box + colour entry is made into a mask from its image\'s bytes, where those '
+                             'are uploaded; it cannot be moved to the device on its own')
         g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
         g = g.to(dev, non_blocking=True)
         g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
@@ -1811,16 +1912,19 @@ class FGN(torch.nn.Module):
         source, spp_source = form.source, form.spp_source
         gts = None
         if gt_masks is not None:
-            gts = [g if isinstance(g, torch.Tensor) or rle.is_rle(g) else torch.from_numpy(np.ascontiguousarray(g))
-                   for g in gt_masks]
+            gts = [g if isinstance(g, (torch.Tensor, colormask.ColorMasks)) or rle.is_rle(g) else
+                   torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
+        colour = _has_color(gts)
         on_host = [t for t in list(tensors.values()) + (gts or []) + (source['flats'] if source else []) +
                    (spp_source['flats'] + spp_source['mflats'] if spp_source else [])
-                   if t is not None and (rle.is_rle(t) or not t.is_cuda)]     # (runs are host data)
+                   if t is not None and (rle.is_rle(t) or isinstance(t, colormask.ColorMasks) or not t.is_cuda)]
+        # (runs, boxes and colours are host data)
         if not on_host and gts is None and source is None:
             return tensors, None, None
         up = self._stream_for('upload', main)
-        if not on_host:
-            up.wait_stream(main)               # device-resident inputs may still be being produced on the caller's stream
+        if not on_host or (colour and source is None and tensors['qry_img'].is_cuda):
+            # device-resident inputs may still be being produced on the caller's stream - the image a colour mask reads too
+            up.wait_stream(main)
         out, gt_out = {}, None
         with torch.cuda.stream(up):
             for k, t in tensors.items():
@@ -1834,6 +1938,12 @@ class FGN(torch.nn.Module):
                 out.update(self._upload_source(source, dev, into))
             if spp_source is not None:
                 out.update(self._upload_supports(spp_source, dev, into))
+            if colour:
+                # box + colour entries: made from the image bytes on THIS stream, behind their copy (into a fresh buffer
+                # or into the static slot of a captured graph alike) and ahead of everything that reads the masks
+                slot = out['qry_src'] if source is not None else \
+                    out['qry_img'].reshape(out['qry_img'].shape[0], -1)
+                gts = self._color_on_device(gts, slot)
             if gts is not None:
                 gt_out = []
                 for g in gts:
@@ -1881,7 +1991,7 @@ class FGN(torch.nn.Module):
                              spp_photometric_chain=spp_photometric_chain)
         graphed = self._graphed()
         source = spp_source = None
-        qry_isegmaps = _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to))
+        qry_isegmaps = self._gt_front(qry_isegmaps, qry_img, img_shape, qry_resize_to)
         if spp_crop_to is None and support_code is None:
             _dense_supports_only(spp_isegmaps)
         if spp_crop_to is not None and support_code is None:
@@ -2365,7 +2475,9 @@ class FGN(torch.nn.Module):
             raise ValueError('results_at_source: these detections were not made with detect_device(results_at_source=True)')
 
         def host_mask(m):
-            if rle.is_rle(m):                   # masks given as COCO RLE: decoded on the host, here only
+            if colormask.is_color(m):           # box + colour: derived on the host from the image it is bound to, here only
+                m = colormask.as_color_masks(m, None, 'qry_isegmaps').dense()
+            elif rle.is_rle(m):                 # masks given as COCO RLE: decoded on the host, here only
                 m = rle.as_masks(m, what='qry_isegmaps').dense()
             m = np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m)
             if results_at_source:               # as given

@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import rle
+from . import colormask, rle
 
 
 def _ellipse_mask(h, w, y0, x0, y1, x1):
@@ -103,7 +103,8 @@ def collate(samples: list) -> dict:
             batch[key] = vals[0]
             continue
         if isinstance(vals[0], list):
-            batch[key] = [[v if rle.is_item(v) else torch.as_tensor(v) for v in lst] for lst in vals]    # (RLE: as it is)
+            batch[key] = [[v if rle.is_item(v) or colormask.is_color(v) else torch.as_tensor(v) for v in lst]
+                          for lst in vals]                 # (RLE, box + colour: as it is)
             continue
         if isinstance(vals[0], torch.Tensor):
             batch[key] = torch.stack(vals)
@@ -111,8 +112,9 @@ def collate(samples: list) -> dict:
             batch[key] = torch.as_tensor(np.stack([np.asarray(v) for v in vals]))
     for key in _LIST_KEYS:                       # ... then the ragged keys as lists of tensors, in the reference's order
         if key in samples[0]:
-            batch[key] = [s[key] if key == 'qry_isegmaps' and rle.is_rle(s[key]) else torch.as_tensor(s[key])
-                          for s in samples]             # (masks given as COCO RLE stay the lists they are)
+            batch[key] = [s[key] if key == 'qry_isegmaps' and (rle.is_rle(s[key]) or colormask.is_color(s[key])) else
+                          torch.as_tensor(s[key]) for s in samples]
+            # (masks given as COCO RLE or as box + colour stay what they are)
     return batch
 
 

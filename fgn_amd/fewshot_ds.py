@@ -20,7 +20,7 @@ import torch
 from torch.utils.data import Dataset
 
 from . import cluttered_chars as cc
-from . import episodes, rle
+from . import colormask, episodes, rle
 from .fsiseg_eval import FSISEGEval
 
 
@@ -1249,7 +1249,11 @@ class ClutteredCharsFewShotISEG(Dataset):
     ``rle_masks``: ``qry_isegmaps`` is the list of the instances' ``rle.encode`` dicts - the form the reference's COCO
     dataset holds its masks in (coco_ds.py:195-207) - for a detector that decodes on the device, and
     with ``spp_source`` every entry of ``spp_isegmaps`` is such a dict too.  Off by default; nothing else of a sample
-    changes."""
+    changes.  ``color_masks`` (needs ``raw_uint8``; not beside ``rle_masks``): ``qry_isegmaps`` is a
+    ``colormask.ColorMasks`` of the kept instances - box and colour, all that MNISTISEG / OMNIISEG store per instance
+    (``*_colors.pkl``, mnistiseg_ds.py:103) - for a detector that makes the masks on the device from the image bytes
+    (DESIGN.md 4.4.11), and with ``spp_source`` every entry of ``spp_isegmaps`` is one such item.  Off by default;
+    nothing else of a sample changes."""
     PARAMS = {'MNISTISEG': dict(mean=(0.9531239867210388, 0.9524800777435303, 0.9531603455543518),
                                 std=(0.16827817261219025, 0.16883736848831177, 0.16667258739471436), n_cats=10),
               'OMNIISEG': dict(mean=(0.9628916382789612, 0.9640044569969177, 0.9626953601837158),
@@ -1258,9 +1262,15 @@ class ClutteredCharsFewShotISEG(Dataset):
     def __init__(self, dataset='MNISTISEG', n_ways=1, k_shots=1, n_imgs=32, img_size=128, spp_img_size=128,
                  spp_fill_ratio=0.8, batch=1, shuffle=False, seed=1234, raw_uint8=False, source_size=None,
                  spp_source=False, augment_qry=False, photometric_qry=False, augment_spp=False, photometric_spp=False,
-                 augs='natural', rle_masks=False):
+                 augs='natural', rle_masks=False, color_masks=False):
         par = self.PARAMS[dataset]
         self.rle_masks = bool(rle_masks)
+        self.color_masks = bool(color_masks)
+        if self.color_masks and self.rle_masks:
+            raise ValueError('color_masks and rle_masks are two forms of one argument: a sample carries its masks as '
+                             'box + colour or as COCO RLE, not both')
+        if self.color_masks and not raw_uint8:
+            raise ValueError('color_masks needs raw_uint8=True: the detector makes the masks from the image\'s bytes')
         if augs not in ('natural', 'coco'):
             raise ValueError(f'augs is \'natural\' (natural_fst.py:18-35) or \'coco\' (coco_ds.py:45-59), got {augs!r}')
         self.augs = augs
@@ -1356,8 +1366,12 @@ class ClutteredCharsFewShotISEG(Dataset):
                 if self.spp_source:                      # the instance as it is: image, box and mask at source size
                     spp_imgs.append(torch.from_numpy(src['img'].copy()))
                     spp_boxes.append(np.asarray(src['bboxes'][o], np.float32))
-                    m = src['isegmaps'][o].astype(bool)
-                    spp_masks.append(rle.encode(m) if self.rle_masks else m)
+                    if self.color_masks:                 # box + colour: what the dataset stores, nothing dense
+                        spp_masks.append(colormask.as_color_masks(
+                            {'bboxes': src['bboxes'][o], 'colors': src['colors'][o]}, src['img'].shape[:2], 'support'))
+                    else:
+                        m = src['isegmaps'][o].astype(bool)
+                        spp_masks.append(rle.encode(m) if self.rle_masks else m)
                     spp_ids.append(p)
                     continue
                 crop, nb, m = support_from_instance(src['img'], src['bboxes'][o], src['isegmaps'][o],
@@ -1371,7 +1385,8 @@ class ClutteredCharsFewShotISEG(Dataset):
             'qry_cat_ids': mapping[im['cat_ids'][keep]].astype(np.int64),
             'qry_bboxes': im['bboxes'][keep].astype(np.float32),
             'qry_isegmaps': rle.encode_many(im['isegmaps'][keep]) if self.rle_masks else
-            im['isegmaps'][keep].astype(bool),
+            colormask.as_color_masks({'bboxes': im['bboxes'][keep], 'colors': im['colors'][keep]}, im['img'].shape[:2],
+                                     'query') if self.color_masks else im['isegmaps'][keep].astype(bool),
             'spp_imgs': spp_imgs if self.spp_source else torch.stack(spp_imgs),
             'spp_bboxes': np.stack(spp_boxes).astype(np.float32),
             'spp_isegmaps': spp_masks if self.spp_source else np.stack(spp_masks).astype(bool),

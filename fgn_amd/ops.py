@@ -1843,6 +1843,110 @@ def rle_decode_rows(slot: torch.Tensor, items: list) -> torch.Tensor:
     return slot
 
 
+CM_REC_INTS = 16             # csrc/mask.hip: {row, h, w, y0, x0, y1, x1, lo[3], hi[3], out, 0, 0} per mask
+
+
+def _color_records(items: list, rows: int, cap: int, fn: str) -> list:
+    """``items`` = (row, ``colormask.ColorMasks``) each, checked against a [rows, cap] image slot -> per item the
+    int32 records [n_i, 16] with the output index still 0."""
+    recs = []
+    for row, m in items:
+        n, h, w = m.shape
+        if not 0 <= int(row) < rows:
+            raise _lib.FgnHipError(f'{fn}: row {row} is outside the {rows} rows of the image slot')
+        if not (1 <= h <= RESIZE_MAX_DIM and 1 <= w <= RESIZE_MAX_DIM) or 3 * h * w > cap:
+            raise _lib.FgnHipError(f'{fn}: an image of {h}x{w} pixels does not fit a slot row of {cap} bytes')
+        r = np.zeros((n, CM_REC_INTS), np.int32)
+        r[:, 0], r[:, 1], r[:, 2] = int(row), h, w
+        r[:, 3:7] = m.boxes
+        r[:, 7:10], r[:, 10:13] = m.bounds()
+        recs.append(r)
+    return recs
+
+
+def _color_launch(src_slot: torch.Tensor, recs: np.ndarray, out: torch.Tensor, out_stride: int, n_out: int, max_h: int,
+                  max_w: int) -> None:
+    """ONE upload of the records and ONE launch of ``fgn_color_mask_u8``, on the current stream - behind whatever that
+    stream has queued, the copy of the image bytes into ``src_slot`` included."""
+    rows, cap = src_slot.shape
+    dev_recs = torch.from_numpy(np.ascontiguousarray(recs, np.int32)).to(out.device, non_blocking=True)
+    _lib.check(_lib.load().fgn_color_mask_u8(_ptr(src_slot), int(src_slot.stride(0)) if rows > 1 else int(cap), int(cap),
+                                             int(rows), _ptr(dev_recs), int(recs.shape[0]), _ptr(out), int(out_stride),
+                                             int(n_out), int(max_h), int(max_w), _stream()), 'fgn_color_mask_u8')
+
+
+def _image_slot(src_slot: torch.Tensor, fn: str) -> None:
+    if not src_slot.is_cuda or src_slot.dtype != torch.uint8 or src_slot.dim() != 2:
+        raise _lib.FgnHipError(f'{fn}: src_slot must be a uint8 device tensor [rows, capacity]')
+    if (src_slot.shape[1] > 1 and src_slot.stride(1) != 1) or (src_slot.shape[0] > 1 and
+                                                               src_slot.stride(0) < src_slot.shape[1]):
+        raise _lib.FgnHipError(f'{fn}: the rows of src_slot must be dense and must not overlap (a view of rows at any '
+                               f'byte offset and pitch is fine)')
+
+
+def color_masks(src_slot: torch.Tensor, items: list, out: Optional[torch.Tensor] = None) -> list:
+    """Masks from box + colour (``colormask.ColorMasks``; get_char_mask_by_color, create_img_from_chars.py:136-158,
+    moved behind the bus): ``src_slot`` uint8 [rows, capacity] on the device, row r holding an image [h,w,3] at its
+    front (``qry_src``, or a [B,H,W,3] batch viewed as [B, H*W*3]; rows may start at any byte); ``items`` = (row,
+    ColorMasks at that image's size) each.  -> per item the dense masks uint8 0/1 [n_i,h_i,w_i]:
+    ``ColorMasks.dense`` bit for bit, written in full.  One upload of the records (16 ints per mask), one launch for all
+    items, on the current stream - which must be the one that carries the copy of the image bytes, or wait for it.
+    ``out``: a contiguous uint8 [total masks, max h*w] to write; else a fresh one.  The items' masks are views of it
+    (copies for an image smaller than the largest).  No mask at all: no launch."""
+    _image_slot(src_slot, 'color_masks')
+    rows, cap = src_slot.shape
+    recs = _color_records(items, rows, cap, 'color_masks')
+    total = int(sum(r.shape[0] for r in recs))
+    stride = max((m.shape[1] * m.shape[2] for _, m in items if m.shape[0]), default=0)
+    if out is None:
+        out = torch.empty((total, stride), device=src_slot.device, dtype=torch.uint8)
+    else:
+        _chk(out, 'out', torch.uint8)
+        if tuple(out.shape) != (total, stride):
+            raise _lib.FgnHipError(f'color_masks: out is {tuple(out.shape)}, expected {(total, stride)}')
+    if total:
+        allr = np.concatenate(recs)
+        allr[:, 13] = np.arange(total)
+        _color_launch(src_slot, allr, out, stride, total, max(m.shape[1] for _, m in items if m.shape[0]),
+                      max(m.shape[2] for _, m in items if m.shape[0]))
+    res, first = [], 0
+    for _, m in items:
+        n, h, w = m.shape
+        res.append(out[first:first + n, :h * w].reshape(n, h, w) if n else
+                   torch.zeros((0, h, w), device=src_slot.device, dtype=torch.uint8))
+        first += n
+    return res
+
+
+def color_mask_rows(src_slot: torch.Tensor, msk_slot: torch.Tensor, items: list) -> torch.Tensor:
+    """``color_masks`` for the support path: ``src_slot`` uint8 [rows, capacity] holds instance i's image window
+    [wh,ww,3] at the front of row i (``spp_src``), ``msk_slot`` uint8 [rows, mask capacity], contiguous (``spp_msk``, the
+    static slot of a captured graph included); ``items`` = (row, ColorMasks of ONE mask at the window's size, its box in
+    the window's frame) each: the mask's wh * ww bytes go to the front of that row of ``msk_slot`` - the layout
+    ``rle_decode_rows`` writes -, what lies behind them and every other row stays as it is.  One upload, one launch for
+    all items, on the current stream; none, no launch."""
+    _image_slot(src_slot, 'color_mask_rows')
+    _chk(msk_slot, 'msk_slot', torch.uint8)
+    if msk_slot.dim() != 2 or msk_slot.shape[0] != src_slot.shape[0]:
+        raise _lib.FgnHipError('color_mask_rows: msk_slot must be [rows, capacity] with the rows of src_slot')
+    if not items:
+        return msk_slot
+    rows, mcap = msk_slot.shape
+    seen = set()
+    for row, m in items:
+        if m.shape[0] != 1 or int(row) in seen:
+            raise _lib.FgnHipError(f'color_mask_rows: row {row}: one mask per item, one item per row')
+        seen.add(int(row))
+        if m.shape[1] * m.shape[2] > mcap:
+            raise _lib.FgnHipError(f'color_mask_rows: a window of {m.shape[1] * m.shape[2]} bytes exceeds the slot '
+                                   f'capacity {mcap}')
+    recs = np.concatenate(_color_records(items, rows, src_slot.shape[1], 'color_mask_rows'))
+    recs[:, 13] = recs[:, 0]
+    _color_launch(src_slot, recs, msk_slot, mcap, rows, max(m.shape[1] for _, m in items),
+                  max(m.shape[2] for _, m in items))
+    return msk_slot
+
+
 def mask_bits(masks: torch.Tensor):
     """Bit planes of dense binary masks [G,H,W] (bool / uint8, non-zero = set), the ground-truth operand of
     ``mask_overlap``: returns (bits int64 [H, ceil(W/64), G] - bit b of word xw of a row = pixel 64 xw + b - ,

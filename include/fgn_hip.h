@@ -513,6 +513,37 @@ int fgn_dense_mask_rle(const uint8_t* masks, void* scratch, size_t scratch_bytes
 int fgn_rle_decode_u8(const uint32_t* ends, long long n_ends, const int32_t* recs, unsigned char* out,
                       long long out_stride_bytes, int n, int max_wh, int max_ww, void* stream);
 
+/* Box + colour as an INPUT, made into masks on the device: the reference's character datasets (MNISTISEG, OMNIISEG)
+ * store a box and an RGB colour per instance and derive the mask from the image on the host for every sample
+ * (get_char_mask_by_color, create_img_from_chars.py:136-158).  n masks in ONE launch, from image bytes that are on the
+ * device already; output i is exactly the bytes a dense upload of that mask would hold.
+ *   src  uint8, the image slot: row r starts at src + r * src_stride_bytes and holds an image [h][w][3] (RGB bytes,
+ *        packed, no padding) at its front; src_cap_bytes of every row may be read; src_rows rows.  No alignment is
+ *        assumed: src and the stride may be any byte count.
+ *   recs int32 [n][16], read ON THE DEVICE: {row, h, w, y0, x0, y1, x1, lo_r, lo_g, lo_b, hi_r, hi_g, hi_b, out, 0, 0}
+ *        = the slot row the mask reads and the size of the image in it, the box (rows [y0, y1), columns [x0, x1)) in
+ *        that frame, the inclusive colour window (the host forms lo = max(c - shift, 0), hi = min(c + shift, 255)) and
+ *        the index of the output
+ *   out  output `out` of a record is [h][w] bytes, each 0 or 1, row-major, at out + out * out_stride_bytes; n_out
+ *        outputs exist.  It is written IN FULL, zeros outside the box included (no memset is needed); the bytes behind
+ *        h * w in its stride are not written.  No alignment is assumed.
+ * p(y, x) = all_c(lo_c <= img[y][x][c] <= hi_c) for (y, x) inside the box and 0 outside it; the mask is the OR of p
+ * over the 3x3 neighbourhood for (y, x) inside the box and 0 outside: a pixel outside the box never dilates in, even
+ * where it matches the colour, and no pixel outside the image is read (OpenCV's dilate on the ROI array: the border
+ * does not contribute).  An empty box gives a mask of zeros.
+ * The kernel is safe for ANY contents of recs: every address it reads lies inside 3 * h * w <= src_cap_bytes of a row
+ * below src_rows, every address it writes inside h * w <= out_stride_bytes of an output below n_out.  A record is out
+ * of range when a size is outside 1..16384, h > max_h or w > max_w, row is outside [0, src_rows), 3 * h * w >
+ * src_cap_bytes, or the box is not 0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= w: none of its pixels is read and its output
+ * is written as zeros where 0 <= out < n_out, h >= 1, w >= 1 and h * w <= out_stride_bytes, and not at all otherwise.
+ * Two records naming the same output race (whole bytes, 0 or 1): the caller gives every record its own.
+ * Negative n, src_rows, n_out, strides or capacity, max_h / max_w outside 0..16384, or n * ceil(max_w / 64) >= 2^24
+ * (the grid) is FGN_ERR_SHAPE; n == 0 or an empty maximum size FGN_OK with no launch (pointers are not looked at);
+ * a null pointer otherwise FGN_ERR_ARG. */
+int fgn_color_mask_u8(const unsigned char* src, long long src_stride_bytes, long long src_cap_bytes, int src_rows,
+                      const int32_t* recs, int n, unsigned char* out, long long out_stride_bytes, int n_out, int max_h,
+                      int max_w, void* stream);
+
 /* Matching on the device: the exact pixel counts the evaluator needs from the masks, so that no RLE is decoded on the
  * host.  Step 1, bit planes of the ground-truth masks: masks [n][H][W] bytes (non-zero = set) -> bits, one 64-bit word
  * per 64 consecutive x of a row (bit b of word xw = pixel x = 64 xw + b; bits of x >= W are zero), laid out
