@@ -138,7 +138,23 @@ int fgn_winograd_gemm_x3_f32(const float* V, const void* U_x3, float* Mo, const 
  * Shapes: as the x3 entry points, and Cout 48..64 on a 64-column tile (fgn_h2_row_tile decides).  fgn_gemm_h2_f32: the direct entry (tests, tools);
  * bm 0 (= fgn_h2_row_tile, fgn_h2_k_groups) / 64 / 128 / 264 force the tile on one K-group; 1064 = 64 rows on two K-groups
  * (K / 32 even and >= 4).  fgn_h2_k_groups: 2 = the launch runs its 64-row tiles on two sets of four waves, each on every
- * other K-tile (ungrouped launches of at most 256 tiles, one per CU, with an even and long enough K-tile count); 1 = one set. */
+ * other K-tile (ungrouped launches of at most 256 tiles, one per CU, with an even and long enough K-tile count); 1 = one set.
+ * ACCURACY CONTRACT of every entry point on conv_pw_h2_kernel (fgn_gemm_h2_f32, fgn_conv1x1_h2_nhwc_f32,
+ * fgn_conv1x1_dual_h2_nhwc_f32, fgn_conv2d_pair_h2[_bm]_nhwc_f32, fgn_winograd_gemm_h2_f32).  It is PER WAVE: the 32 rows
+ * (64 on the 128-row x 128-column tile) of an output tile that one wave holds share one activation scale S, chosen for the largest
+ * finite |x| of those rows in the K-tile that set it.
+ *   (1) Exactly summable operands give the exact result, whatever the tile, the K-groups or the order of the sum: when
+ *       the activations have at most 22 and the weights at most 11 significant bits (or the other way round: the dropped
+ *       l_a l_b is then zero), every element lies within 2^15 of its wave's maximum, and for every output element
+ *       sum |a||w| + |shift| + |residual| is at most 2^22 times a power of two that divides each of its terms, y is the
+ *       exact sum - bit for bit, with shift, residual and ReLU.  (f32 holds 2^24; the two spare bits are a margin for the
+ *       matrix pipe's alignment inside a 32-deep dot product.)
+ *   (2) An element within 2^15 of the maximum S was chosen for keeps both planes at full precision (22 bits).
+ *   (3) A smaller element loses low bits of its l plane to the f16 subnormals: an absolute error of at most 2^-38 of that
+ *       maximum per element, i.e. at most 2^-38 max|x| sum_k |w[n, k]| per output - a row far below its wave's largest
+ *       row is right to that absolute bound only, not relative to itself; outputs stay finite.
+ * tests/test_hip_conv_exact.py pins all three ((1), (2) by equality against integer arithmetic; (3) as a bound with rows
+ * 2^30 and 2^40 below their wave's maximum); the operand classes are in tests/_exact_ref.py, DESIGN 7.6. */
 size_t fgn_h2_image_bytes(int K, int npad, int n_groups);
 int fgn_h2_k_groups(long long M, int Cout, int K, int grp_rows, int grp_valid);
 int fgn_h2_row_tile(long long M, int Cout, int K, int grp_rows, int grp_valid);   /* 64 / 128: rows of a 128-column tile; 264: 128 rows x 64 columns (Cout 48..64); 0: use the f32 entry point */

@@ -243,8 +243,12 @@ def test_two_tensor_launch_equals_one_launch_per_tensor(cin, cout, k, stride, ma
         layer = ops.pack_conv(wt, bn=bn, stride=stride, pad=k // 2, relu=True, **({'pad_cin_to': 4} if cin == 4 else {})).to('cuda')
     h2 = math == 'h2' and cin != 4
     assert (layer.wh is not None) == h2
-    xq = torch.randn(1, 201, 335, cin, generator=g).cuda()
-    xs = torch.randn(9, 32, 32, cin, generator=g).cuda()
+    xq = torch.randn(1, 201, 335, cin, generator=g)
+    xs = torch.randn(9, 32, 32, cin, generator=g)
+    # both inputs in ONE allocation: the implicit-GEMM form takes inputs within 2 GiB of each other only, and where two
+    # separate allocations land is the caching allocator's business (the route asserted below fell to f32 when they lay apart)
+    xb = torch.cat((xq.reshape(-1), xs.reshape(-1))).cuda()
+    xq, xs = xb[:xq.numel()].view(xq.shape), xb[xq.numel():].view(xs.shape)
     if cin == 4:
         xq[..., 3] = 0
         xs[..., 3] = 0
