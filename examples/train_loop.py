@@ -12,6 +12,8 @@ warm-up 100 iterations, 3 epochs) on the MI355X path: DataLoader(ds, collate_fn_
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --augment --photometric --augs coco
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment --rle-masks
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment --photometric --color-masks
+    python examples/train_loop.py --dataset MNISTISEG --optimizer Adam --lr 0.01 --lr-policy CosineAnnealing
+    python examples/train_loop.py --dataset OMNIISEG --optimizer SGD --grad-clip 35 --cumulative-iters 4
 
 ``--source-size S``: the loader hands over decoded S x S pixels and the detector resizes them on the GPU
 (``qry_resize_to``); ``--spp-source``: the supports are cut from their source images on the GPU (``spp_crop_to``);
@@ -30,6 +32,12 @@ dataset holds them in, and are decoded on the GPU.  ``--color-masks`` (needs ``-
 images travel as bytes): the masks travel as box + colour, all the character datasets store, and are made on the GPU
 from the image bytes as uploaded, ahead of any augmentation.  The evaluation at the end is without augmentation.
 
+``--optimizer`` chooses among the three optimizers the schedule files list (Adagrad; Adam; SGD with momentum 0.9 and
+Nesterov), ``--grad-clip MAX_NORM`` is mmcv's ``optimizer_config.grad_clip`` (global L2 norm, logged as ``grad_norm``),
+``--cumulative-iters N`` its GradientCumulativeOptimizerHook (an update every N iterations; what is pending at the end
+of the run is applied by ``Trainer.flush()``), ``--lr-policy`` one of the three learning-rate policies of ``lr_config``
+(Step [3] x0.1; Fixed; CosineAnnealing to 0.01 of the base), each with the linear warm-up of 100 iterations.
+
 The backbone is frozen as in fgn_r50_c4_densecl.py:31; with no pretrained checkpoint here it is randomly
 initialised, so this demonstrates the loop (losses fall on the training episodes), not a trained detector.
 """
@@ -46,7 +54,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fgn_amd.detector import FGN                          # noqa: E402
 from fgn_amd.episodes import collate                      # noqa: E402
 from fgn_amd.fewshot_ds import ClutteredCharsFewShotISEG, SyntheticFewShotISEG   # noqa: E402
-from fgn_amd.train import Trainer, step_lr               # noqa: E402
+from fgn_amd.train import Trainer, scheduled_lr          # noqa: E402
 
 
 def main():
@@ -78,6 +86,10 @@ def main():
     ap.add_argument('--color-masks', action='store_true',
                     help='masks travel as box + colour and are made on the GPU from the image bytes (character datasets; '
                          'needs --source-size or --spp-source)')
+    ap.add_argument('--optimizer', default='Adagrad', choices=['Adagrad', 'Adam', 'SGD'])
+    ap.add_argument('--grad-clip', type=float, default=None, metavar='MAX_NORM', help='clip the global gradient L2 norm')
+    ap.add_argument('--cumulative-iters', type=int, default=1, help='accumulate the gradients of N iterations per update')
+    ap.add_argument('--lr-policy', default='Step', choices=['Step', 'Fixed', 'CosineAnnealing'])
     args = ap.parse_args()
     if args.rle_masks and args.dataset == 'SYNTH':
         ap.error('--rle-masks needs a character dataset (MNISTISEG, OMNIISEG)')
@@ -110,7 +122,11 @@ def main():
         model.set_input_norm(**ds.input_norm)
     if args.checkpoint:
         model.load_state_dict(torch.load(args.checkpoint, map_location='cpu'))
-    trainer = Trainer(model, lr=args.lr)
+    trainer = Trainer(model, lr=args.lr, optimizer=args.optimizer, cumulative_iters=args.cumulative_iters,
+                      grad_clip=None if args.grad_clip is None else dict(max_norm=args.grad_clip, norm_type=2))
+    lr_config = dict({'Step': dict(policy='Step', step=[3], gamma=0.1, min_lr=0.000001), 'Fixed': dict(policy='Fixed'),
+                      'CosineAnnealing': dict(policy='CosineAnnealing', min_lr_ratio=0.01)}[args.lr_policy],
+                     warmup='linear', warmup_iters=100, warmup_ratio=0.01)
     it = 0
     for epoch in range(args.epochs):
         if args.augment or args.augment_spp:
@@ -120,7 +136,7 @@ def main():
         loader = DataLoader(ds, batch_size=ds.batch, num_workers=2, collate_fn=collate)
         t0, tot, n = time.perf_counter(), {}, 0
         for data in loader:
-            trainer.lr = step_lr(args.lr, it, epoch)
+            trainer.set_lr(scheduled_lr(lr_config, args.lr, it, epoch, args.epochs))
             losses = trainer.step(data)
             for k, v in losses.items():
                 tot[k] = tot.get(k, 0.0) + float(v[0] if isinstance(v, list) else v)
@@ -128,6 +144,7 @@ def main():
         dt = time.perf_counter() - t0
         print(f'epoch {epoch}: {n} iterations in {dt:.2f} s, lr {trainer.lr:.2e}, ' +
               ', '.join(f'{k} {v / n:.4f}' for k, v in tot.items()))
+    trainer.flush()                                           # a pending partial accumulation (mmcv: remainder_iters)
     sd = trainer.state_dict()
     if args.save:
         torch.save(trainer.checkpoint(meta={'iter': it, 'epoch': args.epochs}), args.save)   # resumable: Trainer.resume

@@ -26,6 +26,7 @@ SOURCES = [
     ('mask.hip', ['-ffp-contract=off']),
     ('train.hip', ['-ffp-contract=off']),
     ('train_bwd.hip', []),
+    ('optim.hip', ['-ffp-contract=off']),
 ]
 COMMON = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 

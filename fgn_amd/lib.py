@@ -123,6 +123,9 @@ SIGNATURES = {
     'fgn_gemm_tn_f32': (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     'fgn_adagrad_step_f32': (_i, [_p, _p, _p, C.c_longlong, _f, _f, _f, _p]),
     'fgn_adagrad_multi_f32': (_i, [_p, _p, _p, _p, _p, _i, _f, _f, _p]),
+    'fgn_optim_multi_f32': (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _f, _f, _f, _f, C.c_double, C.c_double, _i, _p, _f, _p]),
+    'fgn_grad_sqnorm_multi_f32': (_i, [_p, _p, _i, _f, _f, _p, C.c_longlong, _p, _p]),
+    'fgn_grad_accumulate_multi_f32': (_i, [_p, _p, _p, _i, _f, _i, _p]),
 }
 
 ABI_VERSION = 33

@@ -2413,3 +2413,142 @@ def adagrad_step(param: torch.Tensor, grad: torch.Tensor, state: torch.Tensor, l
     rc = _lib.load().fgn_adagrad_step_f32(_ptr(param), _ptr(grad), _ptr(state), param.numel(), float(lr),
                                           float(weight_decay), float(eps), _stream())
     _lib.check(rc, 'fgn_adagrad_step_f32')
+
+
+# --------------------------------------------------------------------------------------
+# optimiser rules, gradient norm and accumulation over tensor lists (csrc/optim.hip)
+OPTIM_RULES = {'Adagrad': 0, 'Adam': 1, 'SGD': 2}
+OPTIM_CHUNK = 4096
+
+
+def _list_ptrs(tensors, name: str, numel=None):
+    """-> ctypes pointer array of a list of contiguous fp32 device tensors (checked; ``numel``: the sizes they must have)."""
+    import ctypes as C
+    arr = (C.c_void_p * max(len(tensors), 1))()
+    for i, t in enumerate(tensors):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() \
+                or (numel is not None and t.numel() != numel[i]):
+            raise _lib.FgnHipError(f'{name}: entry {i} must be a contiguous fp32 device tensor of its parameter\'s size')
+        arr[i] = t.data_ptr()
+    return arr
+
+
+def optim_multi(rule: str, params, grads, states, lrs, weight_decay: float = 0.0, eps: Optional[float] = None,
+                betas=(0.9, 0.999), step: int = 1, momentum: float = 0.0, nesterov: bool = False, dampening: float = 0.0,
+                coef: Optional[torch.Tensor] = None, grad_scale: float = 1.0, table: Optional[dict] = None) -> None:
+    """One optimiser step of ``rule`` ('Adagrad' | 'Adam' | 'SGD': torch.optim's single-tensor forms) on a list of tensors
+    in one launch per 64 non-empty tensors, each tensor with its own learning rate.
+
+    ``states``: per tensor the Adagrad ``sum``, the Adam pair ``(exp_avg, exp_avg_sq)`` or the SGD ``momentum_buffer``
+    (``None`` for the whole list when ``momentum`` is 0).  ``step``: the number of optimiser steps taken including this
+    one (Adam's bias corrections, formed here in double from the fp32 betas).  The gradient enters as
+    ``g * coef * grad_scale``: ``coef`` is the device record of ``grad_norm_multi`` (its second element is read by the
+    kernel, no host synchronisation), ``grad_scale`` a host scalar; with ``coef=None`` and ``grad_scale=1`` the gradient
+    is used bit for bit.  ``table``: a dict the caller keeps between steps - the checked parameter / state pointer arrays
+    are built once per (tensors, lrs) and only the gradient pointers are refreshed."""
+    import ctypes as C
+    if rule not in OPTIM_RULES:
+        raise _lib.FgnHipError(f'optim_multi: unknown rule {rule!r} (one of {sorted(OPTIM_RULES)})')
+    if float(dampening) != 0.0:
+        raise _lib.FgnHipError('optim_multi: SGD dampening other than 0 is not supported')
+    k = len(params)
+    no_state = rule == 'SGD' and float(momentum) == 0.0
+    if states is None:
+        if not no_state:
+            raise _lib.FgnHipError(f'optim_multi: {rule} needs its state tensors')
+        states = [None] * k
+    if not (len(grads) == len(states) == len(lrs) == k):
+        raise _lib.FgnHipError('optim_multi: list lengths differ')
+    if not k:
+        return
+    if rule == 'Adam':
+        s1 = [s[0] for s in states]
+        s2 = [s[1] for s in states]
+    else:
+        s1, s2 = (None if no_state else list(states)), None
+    key = (rule, tuple(p.data_ptr() for p in params), tuple(s.data_ptr() for s in s1) if s1 else None,
+           tuple(s.data_ptr() for s in s2) if s2 else None, tuple(float(v) for v in lrs))
+    if table is None or table.get('key') != key:
+        numel = [p.numel() for p in params] if all(torch.is_tensor(p) for p in params) else None
+        built = dict(key=key, pa=_list_ptrs(params, 'optim_multi: params'),
+                     s1=_list_ptrs(s1, 'optim_multi: states', numel) if s1 else None,
+                     s2=_list_ptrs(s2, 'optim_multi: states', numel) if s2 else None,
+                     na=(C.c_longlong * k)(*numel), la=(C.c_float * k)(*key[4]), ga=(C.c_void_p * k)(), numel=numel)
+        if table is None:
+            table = built
+        else:
+            table.clear(); table.update(built)
+    ga = table['ga']
+    for i, g in enumerate(grads):
+        if not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float32 or not g.is_contiguous() \
+                or g.numel() != table['numel'][i]:
+            raise _lib.FgnHipError('optim_multi: gradients must be contiguous fp32 device tensors of the parameters\' sizes')
+        ga[i] = g.data_ptr()
+    if coef is not None:
+        _chk(coef, 'coef')
+        if coef.numel() != 2:
+            raise _lib.FgnHipError('optim_multi: coef is the {norm, coef} record of grad_norm_multi')
+    if eps is None:
+        eps = 1e-8 if rule == 'Adam' else 1e-10
+    h0 = h1 = 0.0
+    bc1 = bc2 = 1.0
+    if rule == 'Adam':
+        if int(step) < 1:
+            raise _lib.FgnHipError('optim_multi: Adam step counts from 1')
+        h0, h1 = (float(C.c_float(b).value) for b in betas)
+        bc1, bc2 = 1.0 - h0 ** int(step), 1.0 - h1 ** int(step)
+    elif rule == 'SGD':
+        h0 = float(momentum)
+    rc = _lib.load().fgn_optim_multi_f32(OPTIM_RULES[rule], table['pa'], ga, table['s1'], table['s2'], table['na'],
+                                         table['la'], k, float(weight_decay), float(eps), h0, h1, bc1, bc2,
+                                         int(bool(nesterov)), None if coef is None else coef.data_ptr() + 4,
+                                         float(grad_scale), _stream())
+    _lib.check(rc, 'fgn_optim_multi_f32')
+
+
+def grad_norm_multi(grads, max_norm: float, norm_type: float = 2, out: Optional[torch.Tensor] = None,
+                    grad_scale: float = 1.0) -> torch.Tensor:
+    """The global L2 norm of a list of gradients and the coefficient of ``torch.nn.utils.clip_grad_norm_(max_norm,
+    norm_type=2)`` -> device record ``out`` = [norm, coef], norm that of ``grad_scale * g`` (the host scalar
+    ``optim_multi`` multiplies the gradients by), coef = min(1, max_norm / (norm + 1e-6)); nothing is scaled
+    here - ``optim_multi(coef=out)`` applies the coefficient.  Squares are summed in fp64 in a fixed order without
+    atomics (the same input gives the same bits); no host synchronisation.  Non-finite gradients behave as in torch with
+    ``error_if_nonfinite=False``: the norm and the coefficient become NaN, and so do the gradients they multiply."""
+    import ctypes as C
+    if float(norm_type) != 2.0:
+        raise _lib.FgnHipError(f'grad_norm_multi: norm_type {norm_type} is not supported (2 only)')
+    if not float(max_norm) >= 0.0:
+        raise _lib.FgnHipError('grad_norm_multi: max_norm must be >= 0')
+    k = len(grads)
+    ga = _list_ptrs(grads, 'grad_norm_multi: grads')
+    dev = grads[0].device if k else torch.device('cuda', torch.cuda.current_device())
+    if out is None:
+        out = torch.empty(2, device=dev, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        if out.numel() != 2:
+            raise _lib.FgnHipError('grad_norm_multi: out holds {norm, coef}')
+    na = (C.c_longlong * max(k, 1))(*[g.numel() for g in grads])
+    chunks = sum((g.numel() + OPTIM_CHUNK - 1) // OPTIM_CHUNK for g in grads)
+    part = torch.empty(max(chunks, 1), device=dev, dtype=torch.float64)
+    rc = _lib.load().fgn_grad_sqnorm_multi_f32(ga, na, k, float(max_norm), float(grad_scale), part.data_ptr(), part.numel(), out.data_ptr(),
+                                               _stream())
+    _lib.check(rc, 'fgn_grad_sqnorm_multi_f32')
+    return out
+
+
+def grad_accumulate_multi(accs, grads, a: float, first: bool) -> None:
+    """``acc = (0 if first else acc) + a * g`` over a list of tensors in one launch per 64 non-empty tensors; ``first``
+    overwrites whatever the accumulators held (no zero fill needed)."""
+    import ctypes as C
+    k = len(accs)
+    if len(grads) != k:
+        raise _lib.FgnHipError('grad_accumulate_multi: list lengths differ')
+    if not k:
+        return
+    aa = _list_ptrs(accs, 'grad_accumulate_multi: accs')
+    numel = [t.numel() for t in accs]
+    ga = _list_ptrs(grads, 'grad_accumulate_multi: grads', numel)
+    rc = _lib.load().fgn_grad_accumulate_multi_f32(aa, ga, (C.c_longlong * k)(*numel), k, float(a), int(bool(first)),
+                                                   _stream())
+    _lib.check(rc, 'fgn_grad_accumulate_multi_f32')

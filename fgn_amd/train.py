@@ -17,7 +17,8 @@ trainable heads, the Adagrad update and the re-pack of the kernel layouts itself
     permutation mmdet draws (``torch.randperm(n)`` on the CPU generator, my_random_sampler.py:58) and the label /
     target gathers run there in numpy, the selected indices go back as small index tensors
   * backward: loss gradients, BatchNorm(train) / relation-GroupNorm / mask-logit backward, im2col, column sums, the
-    weight-gradient GEMM (``fgn_gemm_tn_f32``, fp32 MFMA), Adagrad: ``csrc/train_bwd.hip``; data gradients: the forward
+    weight-gradient GEMM (``fgn_gemm_tn_f32``, fp32 MFMA), Adagrad: ``csrc/train_bwd.hip``; Adam, SGD, gradient clipping
+    and accumulation: ``csrc/optim.hip``; data gradients: the forward
     convolution kernel with transposed (1x1) / flipped (3x3) weights; the 6-row fc products and the 75-channel
     AG-RPN head (shapes the MFMA kernels do not take) on ``fgn_gemm_small_f32`` - no rocBLAS call in the step
 """
@@ -868,15 +869,236 @@ def step_lr(base_lr: float, it: int, epoch: int, steps=(3,), gamma: float = 0.1,
     return lr
 
 
+def scheduled_lr(lr_config: dict, base_lr: float, it: int, epoch: int, max_epochs: int) -> float:
+    """The learning rate mmcv's LrUpdaterHook of ``lr_config`` (fgn_train_schedule.py:28-37) sets at iteration ``it`` of
+    epoch ``epoch`` (by_epoch=True) for a parameter group whose base is ``base_lr``:
+      * ``Step``: ``step_lr`` (step, gamma, min_lr)
+      * ``Fixed``: the base
+      * ``CosineAnnealing``: target = base * min_lr_ratio (or ``min_lr``), lr = target + 0.5 (base - target)
+        (1 + cos(pi epoch / max_epochs))
+    with linear warm-up as in ``step_lr`` (warmup='linear' or None; other kinds are refused)."""
+    cfg = dict(lr_config)
+    policy = cfg.pop('policy')
+    warmup = cfg.pop('warmup', None)
+    w_iters, w_ratio = int(cfg.pop('warmup_iters', 0)), float(cfg.pop('warmup_ratio', 0.1))
+    if warmup not in (None, 'linear'):
+        raise NotImplementedError(f'warmup={warmup!r}: only linear warm-up (or none) is supported')
+    if not cfg.pop('by_epoch', True):
+        raise NotImplementedError('lr_config by_epoch=False is not supported')
+    if warmup is None:
+        w_iters = 0
+    if policy == 'Step':
+        steps = cfg.pop('step', (3,))
+        steps = (steps,) if isinstance(steps, int) else tuple(steps)
+        lr = step_lr(base_lr, it, epoch, steps=steps, gamma=cfg.pop('gamma', 0.1), min_lr=cfg.pop('min_lr', 0.0) or 0.0,
+                     warmup_iters=w_iters, warmup_ratio=w_ratio)
+        if cfg:
+            raise ValueError(f'lr_config: unknown keys {sorted(cfg)} for policy Step')
+        return lr
+    if policy == 'Fixed':
+        lr = float(base_lr)
+    elif policy == 'CosineAnnealing':
+        ratio, min_lr = cfg.pop('min_lr_ratio', None), cfg.pop('min_lr', None)
+        if (ratio is None) == (min_lr is None):
+            raise ValueError('CosineAnnealing takes exactly one of min_lr and min_lr_ratio')
+        target = base_lr * ratio if ratio is not None else min_lr
+        lr = target + 0.5 * (base_lr - target) * (1.0 + np.cos(np.pi * epoch / float(max_epochs)))
+        lr = float(lr)
+    else:
+        raise NotImplementedError(f'lr_config policy {policy!r} (Step, Fixed and CosineAnnealing are supported)')
+    if cfg:
+        raise ValueError(f'lr_config: unknown keys {sorted(cfg)} for policy {policy}')
+    if it < w_iters:
+        lr *= 1.0 - (1.0 - it / float(w_iters)) * (1.0 - w_ratio)
+    return lr
+
+
+# ------------------------------------------------------------------------------------------
+# optimiser configuration and torch.optim state-dict layouts: pure host code (no GPU), so the CPU tests drive it
+# against real torch.optim objects
+# ------------------------------------------------------------------------------------------
+OPTIMIZERS = ('Adagrad', 'Adam', 'SGD')
+_STATE_KEYS = {'Adagrad': ('sum',), 'Adam': ('exp_avg', 'exp_avg_sq'), 'SGD': ('momentum_buffer',)}
+
+
+def optimizer_config(optimizer='Adagrad', lr: float = 0.005, weight_decay: float = 1e-5, roi_head_lr_mult: float = 0.1,
+                     eps: Optional[float] = None) -> dict:
+    """``optimizer``: a name of ``OPTIMIZERS`` or the reference's ``optimizer`` dict as the schedule files write it
+    (fgn_train_schedule.py:5-17: type, lr, weight_decay, betas, eps, momentum, nesterov,
+    paramwise_cfg.custom_keys['roi_head'].lr_mult) -> dict(type, lr, weight_decay, lr_mult, eps, betas, momentum,
+    nesterov).  A name alone takes torch's defaults for Adam (betas (0.9, 0.999), eps 1e-8) and the schedule files' SGD
+    line (momentum 0.9, nesterov=True); a dict takes torch's defaults for what it leaves out."""
+    out = dict(lr=float(lr), weight_decay=float(weight_decay), lr_mult=float(roi_head_lr_mult), eps=eps,
+               betas=(0.9, 0.999), momentum=0.0, nesterov=False)
+    if isinstance(optimizer, str):
+        out['type'] = optimizer
+        if optimizer == 'SGD':
+            out.update(momentum=0.9, nesterov=True)
+    else:
+        cfg = dict(optimizer)
+        out['type'] = cfg.pop('type')
+        for k in ('lr', 'weight_decay', 'momentum'):
+            if k in cfg:
+                out[k] = float(cfg.pop(k))
+        if 'eps' in cfg:
+            out['eps'] = float(cfg.pop('eps'))
+        if 'betas' in cfg:
+            out['betas'] = tuple(float(b) for b in cfg.pop('betas'))
+        out['nesterov'] = bool(cfg.pop('nesterov', False))
+        if float(cfg.pop('dampening', 0.0)) != 0.0:
+            raise ValueError('SGD dampening other than 0 is not supported')
+        for k in ('amsgrad', 'maximize', 'decoupled_weight_decay'):
+            if cfg.pop(k, False):
+                raise NotImplementedError(f'optimizer option {k}=True is not supported')
+        if float(cfg.pop('lr_decay', 0.0)) != 0.0 or float(cfg.pop('initial_accumulator_value', 0.0)) != 0.0:
+            raise NotImplementedError('Adagrad lr_decay / initial_accumulator_value other than 0 are not supported')
+        pw = dict(cfg.pop('paramwise_cfg', None) or {})
+        keys = dict(pw.pop('custom_keys', None) or {})
+        roi = dict(keys.pop('roi_head', None) or {})
+        if pw or keys:
+            raise NotImplementedError(f"paramwise_cfg: only custom_keys['roi_head'] is supported, got {sorted(pw) + sorted(keys)}")
+        if float(roi.pop('decay_mult', 1.0)) != 1.0:
+            raise NotImplementedError('paramwise_cfg decay_mult other than 1 is not supported')
+        if 'lr_mult' in roi:
+            out['lr_mult'] = float(roi.pop('lr_mult'))
+        else:
+            out['lr_mult'] = 1.0                      # an optimizer dict without the key trains every head at `lr`
+        if cfg or roi:
+            raise ValueError(f'optimizer: unknown keys {sorted(cfg) + sorted(roi)}')
+    if out['type'] not in OPTIMIZERS:
+        raise ValueError(f"optimizer type {out['type']!r}: one of {OPTIMIZERS}")
+    if out['type'] != 'SGD' and (out['momentum'] != 0.0 or out['nesterov']):
+        raise ValueError(f"momentum / nesterov belong to SGD, not to {out['type']}")
+    if out['nesterov'] and out['momentum'] <= 0.0:
+        raise ValueError('Nesterov momentum requires a momentum')                 # torch.optim.SGD's own rule
+    if out['eps'] is None:
+        out['eps'] = 1e-8 if out['type'] == 'Adam' else 1e-10
+    return out
+
+
+def optimizer_kind(opt: dict) -> str:
+    """Which torch optimizer wrote the ``state_dict()`` ``opt``: from the keys of a state entry, or - no step taken yet,
+    or every parameter frozen - from the keys of a param group."""
+    for st in opt.get('state', {}).values():
+        if 'exp_avg' in st:
+            return 'Adam'
+        if 'momentum_buffer' in st:
+            return 'SGD'
+        if 'sum' in st:
+            return 'Adagrad'
+        if st:
+            break
+    for g in opt.get('param_groups', []):
+        if 'betas' in g:
+            return 'Adam'
+        if 'momentum' in g:
+            return 'SGD'
+        if 'lr_decay' in g:
+            return 'Adagrad'
+    raise ValueError("unknown 'optimizer' entry: expected the state_dict() layout of torch.optim.Adagrad, Adam or SGD")
+
+
+def build_optimizer_state_dict(cfg: dict, order: list, trained: dict, lr: float, base_lr: float, n_steps: int) -> dict:
+    """The ``state_dict()`` of the reference's torch optimizer as mmcv saves it: one param group per parameter of
+    ``order`` ([(name, shape)], ``reference_param_order``: frozen parameters included), mmcv's ``initial_lr`` next to the
+    current ``lr``, and the extra key ``param_names``.  ``trained``: name -> {state key: CPU tensor} of the trained
+    parameters.  Adagrad creates ``step`` / ``sum`` for every parameter in its constructor; Adam and SGD create state at a
+    parameter's first gradient, so frozen parameters - and everything before the first step - have NO state entry
+    (SGD without momentum keeps ``momentum_buffer: None``)."""
+    kind = cfg['type']
+    state, groups = {}, []
+    for i, (k, shape) in enumerate(order):
+        mult = cfg['lr_mult'] if k in trained and k.startswith('roi_head') else 1.0
+        if kind == 'Adagrad':
+            if k in trained:
+                state[i] = {'step': torch.tensor(float(n_steps)), 'sum': trained[k]['sum']}
+            else:
+                state[i] = {'step': torch.tensor(0.0), 'sum': torch.zeros(shape)}
+            g = {'lr_decay': 0, 'eps': cfg['eps'], 'weight_decay': cfg['weight_decay'], 'initial_accumulator_value': 0,
+                 'foreach': None, 'maximize': False, 'differentiable': False, 'fused': None}
+        elif kind == 'Adam':
+            if k in trained and n_steps > 0:
+                state[i] = {'step': torch.tensor(float(n_steps)), 'exp_avg': trained[k]['exp_avg'],
+                            'exp_avg_sq': trained[k]['exp_avg_sq']}
+            g = {'betas': tuple(cfg['betas']), 'eps': cfg['eps'], 'weight_decay': cfg['weight_decay'], 'amsgrad': False,
+                 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
+                 'decoupled_weight_decay': False}
+        else:
+            if k in trained and n_steps > 0:
+                state[i] = {'momentum_buffer': trained[k].get('momentum_buffer')}
+            g = {'momentum': cfg['momentum'], 'dampening': 0, 'nesterov': cfg['nesterov'],
+                 'weight_decay': cfg['weight_decay'], 'maximize': False, 'foreach': None, 'differentiable': False,
+                 'fused': None}
+        groups.append(dict({'lr': lr * mult, 'initial_lr': base_lr * mult}, **g, params=[i]))
+    return {'state': state, 'param_groups': groups, 'param_names': [k for k, _ in order]}
+
+
+def parse_optimizer_state_dict(opt: dict, full_names: list, trainable: list, expect: Optional[str] = None) -> dict:
+    """The inverse: -> dict(type, states {name: {state key: tensor}} of the trainable parameters that HAVE state, step
+    (the largest ``step`` entry, None without one), group (the param group of the first trainable parameter outside
+    ``roi_head``: lr, initial_lr, weight_decay and the rule's hyper-parameters), by_name).  Index -> name: the dict's own
+    ``param_names``, else ``full_names`` (a checkpoint mmcv / torch wrote over every parameter), else ``trainable`` (an
+    optimizer built over the heads alone).  ``expect``: the trainer's optimizer - another kind raises a ValueError that
+    names both."""
+    kind = optimizer_kind(opt)
+    if expect is not None and kind != expect:
+        raise ValueError(f"the checkpoint's optimizer state is torch.optim.{kind}'s, this trainer runs {expect}: "
+                         f"construct Trainer(optimizer='{kind}') to continue that run")
+    n_idx = sum(len(g['params']) for g in opt['param_groups'])
+    if 'param_names' in opt:
+        names = list(opt['param_names'])
+    elif n_idx == len(full_names):
+        names = list(full_names)
+    elif n_idx == len(trainable):
+        names = list(trainable)
+    else:
+        names = []
+    if n_idx != len(names) or not set(trainable) <= set(names):
+        raise ValueError(f'optimizer state covers {n_idx} parameters; the reference model has {len(full_names)} '
+                         f'({len(trainable)} of them trainable): cannot map indices to parameters (pass param_names)')
+    flat = [i for g in opt['param_groups'] for i in g['params']]
+    name_of = {int(i): names[pos] for pos, i in enumerate(flat)}
+    tset = set(trainable)
+    states, steps = {}, []
+    for i, st in opt['state'].items():
+        k = name_of[int(i)]
+        if k not in tset:
+            continue
+        states[k] = {key: st[key] for key in _STATE_KEYS[kind] if st.get(key) is not None}
+        if 'step' in st:
+            steps.append(float(st['step']))
+    by_name = {name_of[int(i)]: g for g in opt['param_groups'] for i in g['params']}
+    group = next((g for k, g in by_name.items() if k in tset and not k.startswith('roi_head')), None)
+    return dict(type=kind, states=states, step=int(max(steps)) if steps else None, group=group, by_name=by_name)
+
+
 class Trainer:
-    """Training of the heads on the HIP path: ``step(batch)`` = forward_train (losses) + backward + Adagrad update,
+    """Training of the heads on the HIP path: ``step(batch)`` = forward_train (losses) + backward + optimizer update,
     the loop body the reference gets from mmcv's runner + torch.optim (main.py training branch with
-    fgn_train_schedule.py:3-13: Adagrad, lr 0.005, weight decay 1e-5, lr_mult 0.1 under ``roi_head``).  The backbone
-    is frozen (fgn_r50_c4_densecl.py:31).  Master weights live on the device in torch layout; the packed kernel
-    layouts are re-derived from them after every update."""
+    fgn_train_schedule.py:3-13: Adagrad, lr 0.005, weight decay 1e-5, lr_mult 0.1 under ``roi_head`` - the default;
+    the file's other optimizers, ``grad_clip`` and the cumulative hook through ``optimizer`` / ``grad_clip`` /
+    ``cumulative_iters``).  The backbone is frozen (fgn_r50_c4_densecl.py:31).  Master weights live on the device in
+    torch layout; the packed kernel layouts are re-derived from them after every update."""
 
     def __init__(self, model, lr: float = 0.005, weight_decay: float = 1e-5, roi_head_lr_mult: float = 0.1,
-                 eps: float = 1e-10, bn_momentum: float = 0.1, freeze_backbone: bool = False):
+                 eps: Optional[float] = None, bn_momentum: float = 0.1, freeze_backbone: bool = False,
+                 optimizer='Adagrad', grad_clip: Optional[dict] = None, cumulative_iters: int = 1):
+        """``optimizer``: 'Adagrad' (default, eps 1e-10) | 'Adam' | 'SGD', or the reference's ``optimizer`` dict
+        (``optimizer_config``; its lr / weight_decay / lr_mult win over the keyword arguments).  ``grad_clip``: mmcv's
+        ``optimizer_config.grad_clip`` - ``dict(max_norm=..., norm_type=2)`` clips the global gradient norm before every
+        update (``torch.nn.utils.clip_grad_norm_``) and ``step`` returns the norm as ``grad_norm``.  ``cumulative_iters``:
+        mmcv's GradientCumulativeOptimizerHook - ``step`` accumulates ``g / cumulative_iters`` and updates on every
+        ``cumulative_iters``-th call; ``flush()`` applies what is pending at the end of a run."""
+        cfg = optimizer_config(optimizer, lr, weight_decay, roi_head_lr_mult, eps)
+        lr, weight_decay, roi_head_lr_mult, eps = cfg['lr'], cfg['weight_decay'], cfg['lr_mult'], cfg['eps']
+        if grad_clip is not None:
+            grad_clip = dict(grad_clip)
+            if float(grad_clip.get('norm_type', 2)) != 2.0:
+                raise NotImplementedError(f"grad_clip norm_type {grad_clip['norm_type']}: only the L2 norm is supported")
+            if set(grad_clip) - {'max_norm', 'norm_type'} or not float(grad_clip.get('max_norm', -1.0)) > 0.0:
+                raise ValueError('grad_clip: dict(max_norm=<positive>, norm_type=2)')
+        if int(cumulative_iters) < 1:
+            raise ValueError('cumulative_iters counts from 1')
         if model.cfg['backbone'].get('norm', 'BN') != 'BN' and not freeze_backbone:
             raise NotImplementedError('the from-scratch configuration (fgn_r50_c4_scratch.py: frozen_stages=-1, GroupNorm) '
                                       'trains its backbone; only the heads have backward kernels - pass '
@@ -895,8 +1117,17 @@ class Trainer:
         self.device = dev
         sd = model._sd
         self.W = {k: sd[k].to(dev).float().contiguous().clone() for k in trainable_names(sd)}
-        self.state = {k: torch.zeros_like(v) for k, v in self.W.items()}
-        self.buffers = {k: v.to(dev).float().contiguous().clone() for k, v in sd.items()
+        # per-parameter optimizer state: Adagrad's `sum`, Adam's `exp_avg` (+ `exp_avg_sq` in state2), SGD's
+        # `momentum_buffer` (none without momentum).  Zero-initialised state gives torch's lazily created one exactly.
+        self.opt = cfg
+        self.optimizer = cfg['type']
+        self.grad_clip, self.cumulative_iters = grad_clip, int(cumulative_iters)
+        stateless = self.optimizer == 'SGD' and cfg['momentum'] == 0.0
+        self.state = {} if stateless else {k: torch.zeros_like(v) for k, v in self.W.items()}
+        self.state2 = {k: torch.zeros_like(v) for k, v in self.W.items()} if self.optimizer == 'Adam' else {}
+        self.acc = {k: torch.empty_like(v) for k, v in self.W.items()} if self.cumulative_iters > 1 else {}
+        self._pending = 0                    # micro-steps accumulated since the last update
+        self.buffers ={k: v.to(dev).float().contiguous().clone() for k, v in sd.items()
                         if k.startswith('roi_head.shared_head') and 'running_' in k}
         self.grads: dict = {}
         self.n_steps = 0
@@ -968,18 +1199,90 @@ class Trainer:
         bucket - so every rank applies the same update (data-parallel training; BatchNorm statistics stay per rank,
         like torch DDP without SyncBN)."""
         losses = self.forward_backward(batch, perm_fn)
-        from .dist import allreduce_mean
-        self.grads = allreduce_mean(self.grads, keys=sorted(self.W))
+        if self.cumulative_iters == 1:
+            losses.update(self.apply_gradients())
+            return losses
+        # GradientCumulativeOptimizerHook: loss / cumulative_iters backwards into the same .grad for cumulative_iters
+        # iterations, then clip + optimizer.step().  BatchNorm statistics move with every forward pass; the weights,
+        # n_steps and the packed layers only at the boundary.  One all-reduce there replaces one per micro-step.
         keys = list(self.W)
-        if not hasattr(self, '_adagrad_table'):
-            self._adagrad_table = {}
-        ops.adagrad_multi([self.W[k] for k in keys], [self.grads[k].contiguous() for k in keys],
-                          [self.state[k] for k in keys],
-                          [self.lr * (self.mult if k.startswith('roi_head') else 1.0) for k in keys], self.wd, self.eps,
-                          table=self._adagrad_table)
+        ops.grad_accumulate_multi([self.acc[k] for k in keys], [self.grads[k].contiguous() for k in keys],
+                                  1.0 / self.cumulative_iters, first=self._pending == 0)
+        self._pending += 1
+        if self._pending == self.cumulative_iters:
+            losses.update(self._update(self.acc, 1.0))
+        else:
+            self.model._shared_dirty = {**self.W, **self.buffers}      # the running statistics moved
+            self.model._graphs = {}
+        return losses
+
+    def flush(self) -> dict:
+        """Apply a pending partial accumulation of k < cumulative_iters micro-steps: the accumulated sum of g / cumulative_iters
+        rescaled by cumulative_iters / k, i.e. the mean of the k gradients at full weight (mmcv divides the last
+        ``remainder_iters`` losses of a run by their own count); the clip norm is that of the rescaled gradient.  Nothing
+        pending: nothing happens.  -> {} or {'grad_norm': ...}."""
+        if self._pending == 0:
+            return {}
+        return self._update(self.acc, float(self.cumulative_iters) / float(self._pending))
+
+    def apply_gradients(self) -> dict:
+        """All-reduce (under a process group), clip norm, optimizer update from ``self.grads``; then ``n_steps`` += 1 and
+        the packed layers follow.  The norm is taken AFTER the average over the ranks, as DDP followed by
+        ``clip_grad_norm_`` does.  -> {} or, with clipping, {'grad_norm': 0-d device tensor} (mmcv's log variable; no
+        host synchronisation here)."""
+        if self.optimizer == 'Adagrad' and self.grad_clip is None:
+            # the default recipe: the launches and bits of every earlier version of this step
+            from .dist import allreduce_mean
+            self.grads = allreduce_mean(self.grads, keys=sorted(self.W))
+            keys = list(self.W)
+            if not hasattr(self, '_adagrad_table'):
+                self._adagrad_table = {}
+            ops.adagrad_multi([self.W[k] for k in keys], [self.grads[k].contiguous() for k in keys],
+                              [self.state[k] for k in keys],
+                              [self.lr * (self.mult if k.startswith('roi_head') else 1.0) for k in keys], self.wd, self.eps,
+                              table=self._adagrad_table)
+            self.n_steps += 1
+            self.refresh()
+            return {}
+        return self._update(self.grads, 1.0)
+
+    def _update(self, grads: dict, scale: float) -> dict:
+        """One optimizer step from ``grads`` x ``scale`` through ``ops.optim_multi`` (and ``ops.grad_norm_multi`` when
+        clipping): at most three launches for the ~40 tensors of the heads."""
+        from .dist import allreduce_mean
+        reduced = allreduce_mean(grads, keys=sorted(self.W))
+        if grads is self.grads:
+            self.grads = reduced
+        keys = list(self.W)
+        glist = [reduced[k].contiguous() for k in keys]
+        out, rec = {}, None
+        if self.grad_clip is not None:
+            rec = ops.grad_norm_multi(glist, self.grad_clip['max_norm'], grad_scale=scale)   # a fresh record per step
+            out['grad_norm'] = rec[0]
+        if not hasattr(self, '_optim_table'):
+            self._optim_table = {}
+        kind, o = self.optimizer, self.opt
+        if kind == 'Adam':
+            states = [(self.state[k], self.state2[k]) for k in keys]
+        else:
+            states = [self.state[k] for k in keys] if self.state else None
+        ops.optim_multi(kind, [self.W[k] for k in keys], glist, states,
+                        [self.lr * (self.mult if k.startswith('roi_head') else 1.0) for k in keys], self.wd, eps=self.eps,
+                        betas=o['betas'], step=self.n_steps + 1, momentum=o['momentum'], nesterov=o['nesterov'],
+                        coef=rec, grad_scale=scale, table=self._optim_table)
+        self._pending = 0
         self.n_steps += 1
         self.refresh()
-        return losses
+        return out
+
+    def _trained_state(self) -> dict:
+        """name -> {torch state key: CPU tensor} of the trained parameters."""
+        if self.optimizer == 'Adagrad':
+            return {k: {'sum': v.detach().cpu()} for k, v in self.state.items()}
+        if self.optimizer == 'Adam':
+            return {k: {'exp_avg': v.detach().cpu(), 'exp_avg_sq': self.state2[k].detach().cpu()}
+                    for k, v in self.state.items()}
+        return {k: ({'momentum_buffer': self.state[k].detach().cpu()} if self.state else {}) for k in self.W}
 
     def optimizer_state_dict(self) -> dict:
         """``torch.optim.Adagrad.state_dict()`` of the REFERENCE's optimizer, as mmcv saves it (checkpoint_config
@@ -991,6 +1294,11 @@ class Trainer:
         next to the current ``lr``.  The reference's ``optimizer.load_state_dict`` accepts this dict as it is (same group
         count, one parameter per group); ``param_names`` (extra key, ignored by torch) spells the index space out."""
         order = reference_param_order(self.model._sd, self.model.cfg['backbone'])
+        if self.optimizer != 'Adagrad':
+            # torch.optim.Adam / SGD: the same groups over the same index space; state (Adam: step, exp_avg, exp_avg_sq;
+            # SGD: momentum_buffer) for the trained parameters only, and none before the first step - both optimizers
+            # create it at a parameter's first gradient (``build_optimizer_state_dict``)
+            return build_optimizer_state_dict(self.opt, order, self._trained_state(), self.lr, self.base_lr, self.n_steps)
         state, groups = {}, []
         for i, (k, shape) in enumerate(order):
             if k in self.W:
@@ -1009,14 +1317,24 @@ class Trainer:
         return {'state': state, 'param_groups': groups, 'param_names': [k for k, _ in order]}
 
     def checkpoint(self, meta: Optional[dict] = None) -> dict:
-        """mmcv checkpoint layout: {'state_dict', 'optimizer' (torch Adagrad layout, see ``optimizer_state_dict``),
-        'meta'}."""
+        """mmcv checkpoint layout: {'state_dict', 'optimizer' (the layout of the trainer's torch optimizer, see
+        ``optimizer_state_dict``), 'meta'}.  A pending partial accumulation is not part of it, as in mmcv: checkpoint at
+        an update boundary (or after ``flush()``)."""
         return {'state_dict': self.state_dict(), 'meta': dict(meta or {}, iter=self.n_steps),
                 'optimizer': self.optimizer_state_dict()}
 
     def resume(self, ckpt: dict) -> None:
         """Continue from ``checkpoint()``, from a torch / mmcv checkpoint whose 'optimizer' is a
-        ``torch.optim.Adagrad.state_dict()`` over the same parameter order, or from a plain state dict."""
+        ``state_dict()`` of the trainer's torch optimizer (Adagrad, Adam or SGD) over the same parameter order, or from a
+        plain state dict.  A checkpoint of another optimizer than the trainer's raises a ValueError naming both, before
+        anything is loaded."""
+        opt = ckpt.get('optimizer')
+        parsed = None
+        if opt is not None and 'state_sum' in opt and self.optimizer != 'Adagrad':
+            raise ValueError(f"the checkpoint's optimizer state is Adagrad's, this trainer runs {self.optimizer}")
+        if opt is not None and 'state' in opt and 'param_groups' in opt:
+            full = [k for k, _ in reference_param_order(self.model._sd, self.model.cfg['backbone'])]
+            parsed = parse_optimizer_state_dict(opt, full, list(self.W), expect=self.optimizer)
         sd = ckpt.get('state_dict', ckpt)
         for k in self.W:
             self.W[k].copy_(sd[k].to(self.device, torch.float32))
@@ -1029,8 +1347,9 @@ class Trainer:
         self._bn_calls = 0
         if 'iter' in ckpt.get('meta', {}):
             self.n_steps = int(ckpt['meta']['iter'])                  # mmcv's runner resumes its iteration from here
-        opt = ckpt.get('optimizer')
-        if opt is not None:
+        if opt is not None and parsed is not None and self.optimizer != 'Adagrad':
+            self._load_parsed(parsed)
+        elif opt is not None:
             if 'state_sum' in opt:                                    # this package's round-2 layout
                 sums = opt['state_sum']
                 self.lr, self.wd = opt.get('lr', self.lr), opt.get('weight_decay', self.wd)
@@ -1071,6 +1390,25 @@ class Trainer:
             for k, v in sums.items():
                 self.state[k].copy_(v.to(self.device, torch.float32).view_as(self.state[k]))
         self.refresh()
+
+    def _load_parsed(self, parsed: dict) -> None:
+        """Adam / SGD state of ``parse_optimizer_state_dict``: parameters without an entry (no step taken yet) start from
+        zeros, which is what torch creates at their first gradient."""
+        keys = {'Adam': ('exp_avg', 'exp_avg_sq'), 'SGD': ('momentum_buffer', None)}[self.optimizer]
+        for store, key in ((self.state, keys[0]), (self.state2, keys[1])):
+            for k, t in store.items():
+                src = parsed['states'].get(k, {}).get(key) if key else None
+                if src is None:
+                    t.zero_()
+                else:
+                    t.copy_(src.to(self.device, torch.float32).view_as(t))
+        if parsed['step'] is not None:
+            self.n_steps = parsed['step']                             # Adam's own step count wins over meta
+        g = parsed['group']
+        if g is not None:
+            self.lr, self.wd = float(g['lr']), float(g['weight_decay'])
+            self.base_lr = float(g.get('initial_lr', g['lr']))
+        self._pending = 0
 
     def state_dict(self) -> dict:
         """The model's state dict with the trained heads and the updated running statistics (CPU tensors)."""

@@ -707,6 +707,29 @@ int fgn_adagrad_multi_f32(float* const* params, const float* const* grads, float
 int fgn_adagrad_step_f32(float* param, const float* grad, float* state_sum, long long n, float lr, float weight_decay,
                          float eps, void* stream);
 
+/* Optimiser step for `count` parameter tensors in one launch per 64 non-empty tensors (csrc/optim.hip, compiled with
+ * contraction off).  rule 0: Adagrad (state1 = sum); 1: Adam, L2 decay, no amsgrad (state1 = exp_avg, state2 = exp_avg_sq,
+ * h0 / h1 = beta1 / beta2, bc1 / bc2 = 1 - beta^t formed by the caller in double); 2: SGD, dampening 0 (h0 = momentum,
+ * state1 = momentum_buffer, may be null when h0 == 0; flags bit 0 = Nesterov).  g' = g * mul + weight_decay * p with
+ * mul = (coef ? *coef * grad_scale : grad_scale); coef (device, nullable) is the clip coefficient of
+ * fgn_grad_sqnorm_multi_f32; with coef null and grad_scale == 1 the gradient is used bit for bit. */
+int fgn_optim_multi_f32(int rule, float* const* params, const float* const* grads, float* const* state1,
+                        float* const* state2, const long long* n, const float* lr, int count, float weight_decay, float eps,
+                        float h0, float h1, double bc1, double bc2, int flags, const float* coef, float grad_scale,
+                        void* stream);
+
+/* torch.nn.utils.clip_grad_norm_(max_norm, norm_type=2) without the host: out[0] = grad_scale x the L2 norm of all
+ * gradients (the norm of the gradients scaled by the host scalar fgn_optim_multi_f32 takes),
+ * out[1] = min(1, max_norm / (out[0] + 1e-6)).  Squares summed in fp64, one partial per 4096-element chunk in a fixed
+ * order, the partials in a fixed second stage: no atomics, the same bits on every run.  partials: fp64 scratch of
+ * partials_capacity >= sum ceil(n_i / 4096) entries.  Non-finite gradients give a NaN coefficient. */
+int fgn_grad_sqnorm_multi_f32(const float* const* grads, const long long* n, int count, float max_norm, float grad_scale,
+                              double* partials, long long partials_capacity, float* out, void* stream);
+
+/* accs[i] = (first ? 0 : accs[i]) + a * grads[i] (gradient accumulation; `first` saves the zero fill) */
+int fgn_grad_accumulate_multi_f32(float* const* accs, const float* const* grads, const long long* n, int count, float a,
+                                  int first, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
