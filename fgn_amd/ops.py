@@ -896,8 +896,10 @@ def _winograd_records(prof, ev, L, layer: WinogradLayer, route: str, t_pad: int,
 
 
 def conv3x3_winograd(x: torch.Tensor, layer: WinogradLayer, in_scale: Optional[torch.Tensor] = None,
-                     a_img_div: int = 1, n_img_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x [n_in,H,W,Cin] -> relu?(conv3x3(x[i // a_img_div] * in_scale[i]) + shift) [n_in*a_img_div,H,W,Cout]."""
+                     a_img_div: int = 1, n_img_dev: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [n_in,H,W,Cin] -> relu?(conv3x3(x[i // a_img_div] * in_scale[i]) + shift) [n_in*a_img_div,H,W,Cout].
+    ``out``: a caller-owned result tensor (images past a device count keep their bytes)."""
     _chk(x, 'x')
     n_in, H, W, cin = x.shape
     if cin != layer.cin:
@@ -917,7 +919,13 @@ def conv3x3_winograd(x: torch.Tensor, layer: WinogradLayer, in_scale: Optional[t
     t_pad = L.fgn_winograd_t_pad(n_img * tiles)
     V = torch.empty((G, t_pad, cin), device=x.device, dtype=torch.float32)
     Mo = torch.empty((G, t_pad, layer.cout), device=x.device, dtype=torch.float32)
-    y = torch.empty((n_img, H, W, layer.cout), device=x.device, dtype=torch.float32)
+    if out is None:
+        y = torch.empty((n_img, H, W, layer.cout), device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != (n_img, H, W, layer.cout):
+            raise _lib.FgnHipError('conv3x3_winograd: bad out shape')
+        y = out
     prof = PROFILE
     st = _stream()
     ev = [] if prof is not None else None

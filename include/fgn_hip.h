@@ -123,6 +123,8 @@ int fgn_conv1x1_x3_nhwc_f32(const float* x, const void* w_x3, float* y, const fl
 int fgn_conv1x1_dual_x3_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
                                  const void* w_x3, float* y, const float* shift, int rows, int Cin1, int Cin2, int Cout,
                                  int cout_pad, int relu, void* stream);
+/* rows written, device count, untouched rows: as stated at fgn_winograd_gemm_f32, with the row tile of fgn_x3_row_tile(
+ * n_groups * t_pad, Cout, Cin, t_pad, n_img * tiles_per_img); where that is 0 the call returns FGN_ERR_SHAPE and writes nothing */
 int fgn_winograd_gemm_x3_f32(const float* V, const void* U_x3, float* Mo, const int32_t* n_img_dev, int n_img,
                              int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups, void* stream);
 /* The same GEMMs with THREE f16 MFMA products per f32 product (conv_pw_h2_kernel, csrc/conv_pw_h2.h; the default of the
@@ -178,6 +180,9 @@ int fgn_conv1x1_h2_nhwc_f32(const float* x, const void* w_h2, float* y, const fl
 int fgn_conv1x1_dual_h2_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
                                  const void* w_h2, float* y, const float* shift, int rows, int Cin1, int Cin2, int Cout,
                                  int cout_pad, int relu, void* stream);
+/* rows written, device count, untouched rows: as stated at fgn_winograd_gemm_f32, with the row tile of fgn_h2_row_tile(
+ * n_groups * t_pad, Cout, Cin, t_pad, n_img * tiles_per_img) (64 / 128, 264 = 128 rows; rows of V past the valid ones reach neither a
+ * wave's scale nor a valid row); where that is 0 the call returns FGN_ERR_SHAPE and writes nothing */
 int fgn_winograd_gemm_h2_f32(const float* V, const void* U_h2, float* Mo, const int32_t* n_img_dev, int n_img,
                              int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups, void* stream);
 
@@ -204,6 +209,12 @@ int fgn_conv2d_pair_nhwc_f32(const float* x0, float* y0, int n_img0, int H0, int
 int fgn_winograd_input_f32(const float* x, const float* in_scale, float* V, const int32_t* n_img_dev, int n_img,
                            int a_img_div, int H, int W, int C, int t_pad, void* stream);
 int fgn_winograd_t_pad(int tiles_total);
+/* WHAT A LAUNCH WRITES (all three fgn_winograd_gemm_* entries; tests/test_hip_wg_exact.py holds them to it): per group the
+ * first min(n_img, *n_img_dev) * tiles_per_img rows of Mo (n_img_dev NULL: n_img * tiles_per_img) are the products; a launch
+ * writes whole row tiles, so the rows from there up to the next multiple of the row tile (64 here; 64 / 128 on the image
+ * entries: fgn_x3_row_tile / fgn_h2_row_tile) are unspecified, and every row behind that up to t_pad keeps its bytes.  A
+ * count above n_img is clamped to n_img; a count of 0 writes nothing.  Columns [0, Cout) only: Mo is [n_groups][t_pad][Cout].
+ * Group g reads U[g] alone.  On exactly summable operands (fgn_gemm_h2_f32's contract (1)) the products are exact. */
 int fgn_winograd_gemm_f32(const float* V, const float* U, float* Mo, const int32_t* n_img_dev, int n_img,
                           int tiles_per_img, int t_pad, int Cin, int Cout, int cout_pad, int n_groups, void* stream);
 int fgn_winograd_output_f32(const float* Mo, float* y, const float* shift, const int32_t* n_img_dev, int n_img,

@@ -466,3 +466,201 @@ def dual_case(rows, cin1, cin2, cout, arith, cls, scaled):
         out[f'w{j + 1}'] = (wf[:, lo:hi] / sc[:, None]).float().view(cout, hi - lo, 1, 1)
         out[f'bn{j + 1}'] = bn
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the Winograd path: the grouped-GEMM entry points alone, and whole convolutions exact through all four stages
+# (tests/test_hip_wg_exact.py runs them, tests/test_wg_exact_cpu.py pins them)
+# ----------------------------------------------------------------------------------------------------------------------
+WG_LIMIT = float(2 ** 24)          # the transform stages: plain f32 adds and fmaf, no matrix pipe - all of f32's 24 bits
+# groups, t_pad, valid rows, K, N, n_img, tiles_per_img (n_img * tiles_per_img == valid), the row tile fgn_h2_row_tile /
+# fgn_x3_row_tile must return for it (0: the f32 entry only - the image entries refuse the launch)
+WG_GEMM = [
+    (36, 128, 100, 64, 384, 25, 4, 64),        # 64-row tile, two K-tiles, 72 x 3 = 216 tiles
+    (16, 256, 201, 128, 384, 67, 3, 64),       # 64 x 3 = 192 tiles: exactly the threshold; valid ends inside the fourth tile
+    (36, 128, 100, 64, 132, 25, 4, 0),         # 132 of 256 columns: below 70 % - refused; the f32 entry's column guard
+    (36, 256, 250, 256, 768, 125, 2, 128),     # K >= 256, rows128 == rows64, 36 x 2 x 6 = 432 >= 400: 128 rows
+    (16, 640, 640, 256, 640, 40, 16, 128),     # F(2x2)'s group count: 16 x 5 x 5 = 400, exactly the threshold
+    (36, 128, 100, 64, 128, 25, 4, 0),         # 72 tiles: too few
+    (16, 128, 37, 32, 8, 37, 1, 0),            # K < 64, Cout < a tile
+]
+WG_GEMM_CLASSES = {'h2': CLASSES, 'x3': X3_CLASSES, 'f32': F32_CLASSES}
+_wg_gemm_cache = {}
+
+
+def wg_gemm_case(i, cls, arith, scaled):
+    """``gemm_case`` of the valid rows of WG_GEMM[i] with per-group operands, once per (shape, class, arithmetic) and never
+    written.  ``scaled`` is derived from the unscaled case: the same draws times 2^-9 (products times 2^-18) - exactly
+    what ``gemm_case(scaled=True)`` computes, every factor being a power of two - so that the two 128-row shapes (1.8 GMAC
+    of float64 each, and as much again for ``mag``) are multiplied once.  -> x [groups, valid, K], w [groups, N, K] f32,
+    prod [groups, valid, N] float64."""
+    key = (i, cls, arith)
+    if key not in _wg_gemm_cache:
+        groups, _, valid, K, N = WG_GEMM[i][:5]
+        c = gemm_case(valid, K, N, cls, arith, False, groups=groups, seed=300 + i)
+        assert not torch.equal(c['w'][0], c['w'][1])                    # per-group weights differ
+        _wg_gemm_cache[key] = dict(x=c['x'], w=c['w'], prod=c['prod'])
+    c = _wg_gemm_cache[key]
+    if not scaled:
+        return c
+    s = 2.0 ** -9
+    out = dict(x=c['x'] * s, w=c['w'] * s, prod=c['prod'] * (s * s))
+    assert torch.equal(out['x'].double() @ out['w'].double()[..., :8, :].transpose(1, 2), out['prod'][..., :8])
+    return out
+
+
+def wg_counts(n_img, tiles_per_img, tile):
+    """The device counts of a grouped launch: none, n_img, one whose last row lies inside a row tile, one whose last row
+    ends a row tile (None where no count below n_img does), 0, n_img + 2 (clamped to n_img)."""
+    inside = next(c for c in range(1, n_img) if (c * tiles_per_img) % tile)
+    edge = next((c for c in range(1, n_img) if (c * tiles_per_img) % tile == 0), None)
+    return [None, n_img, inside] + ([] if edge is None else [edge]) + [0, n_img + 2]
+
+
+def wg_scaled_g(m):
+    """(s, s G) with s G an integer matrix: s = 2 for F(2x2), 15 for F(4x4) (tests/_wg_ref.py's rationals)"""
+    import _wg_ref
+    s = 2 if m == 2 else 15
+    sg = torch.tensor([[float(v * s) for v in row] for row in _wg_ref.G[m]], dtype=torch.float64)
+    assert torch.equal(sg, sg.round())
+    return s, sg
+
+
+# whole convolutions: name -> m, shapes [(n, H, W), ...], cin, cout, operand kind, a_img_div, device counts (None: no
+# count), the route of the grouped GEMM under gemm_math('h2') and its row tile (under 'x3': the same tile on
+# conv_pw_x3_kernel; under 'f32' always the f32 entry)
+WG_CONV = {
+    'f4_ragged': (4, [(2, 13, 21)], 64, 384, 'sparse', 1, (None,), 'h2', 64),
+    'f4_counts': (4, [(5, 29, 29)], 64, 128, 'sparse', 1, (None, 5, 3, 0), 'h2', 64),
+    'f4_guided': (4, [(1, 13, 21)], 128, 384, 'sparse', 3, (None,), 'h2', 64),
+    'f4_rois': (4, [(37, 7, 7)], 64, 64, 'sparse', 1, (None, 23), 'f32', 0),
+    'f4_small0': (4, [(1, 7, 9)], 32, 8, 'sparse', 1, (None,), 'f32', 0),
+    'f4_small1': (4, [(3, 5, 3)], 32, 32, 'sparse', 1, (None,), 'f32', 0),
+    'f4_small2': (4, [(1, 1, 1)], 32, 4, 'sparse', 1, (None,), 'f32', 0),
+    'f2_dense': (2, [(1, 29, 31)], 64, 384, 'dense', 1, (None,), 'h2', 64),
+    'f2_wide': (2, [(1, 29, 31)], 256, 384, 'wide', 1, (None,), 'h2', 64),
+    'f2_counts': (2, [(6, 7, 9)], 32, 32, 'dense', 1, (None, 0, 1, 5, 6, 9), 'f32', 0),
+    'f4_pair': (4, [(2, 13, 10), (3, 7, 9)], 64, 384, 'sparse', 1, (None,), 'h2', 64),
+    'f2_pair': (2, [(2, 13, 10), (3, 7, 9)], 64, 384, 'dense', 1, (None,), 'h2', 64),
+}
+# F(4x4): density of the non-zero activations / weights by input channels (module docstring of the GPU file: the chain
+# needs about 27 bits plus log2 of the term count, so each output element can afford about one term)
+_WG_DENSITY = {32: (0.06, 0.06), 64: (0.04, 0.04), 128: (0.04, 0.03)}
+_WG_DENSITY_GUIDED = (0.02, 0.01)     # under input scales that differ by 2^2 within an image
+_wg_conv_cache = {}
+
+
+def wg_tiles(H, W, m):
+    return -(-H // m) * -(-W // m)
+
+
+def wg_conv_case(name):
+    """A 3x3 / pad 1 convolution whose Winograd form is exact in f32 at EVERY stage - the weight transform, the input
+    transform, the grouped GEMM and the output transform - and whose direct form is exact too.  Built once per name, never
+    written.  -> dict: m, shapes, cin, cout, div, xs (f32 NHWC per tensor), wt [cout, cin, 3, 3] f32, in_scale [n div, cin]
+    f32 or None, u [groups, cout, cin] float64 = G w G^T over the rationals (integers here), shift [cout] f32, and per
+    tensor: refs = {(shifted?, relu?): float64 NHWC}, the stage tensors v, mo (float64) of the unshifted chain, and
+    worst = {stage: the largest mag / unit} (the conditions below are asserted here, per element).
+
+     F(2x2) 'dense'  x integers of [-7, 7] none zero, w = 4 k with k in [-7, 7]: U = (2 G) k (2 G)^T are integers.
+     F(2x2) 'wide'   ceil(cin / 20) channels hold activations of 12 - 13 significant bits, 2048 p + q, against weights
+                     whose only non-zero tap is the centre, 4 * +-1 (U = +-1 at the four inner positions); everywhere else
+                     |x| <= 7 with half of them zero and w = 4 k.
+     F(4x4) 'sparse' x in {-1, 0, 1} and w = 225 k, k in {-1, 0, 1}, non-zero with the densities of _WG_DENSITY: U = (15 G) k
+                     (15 G)^T are integers, V multiples of 1/4, Mo multiples of 1/4, y multiples of 1/256.
+     ``div`` > 1     every input image read by ``div`` output images under a per-(image, channel) input scale, a power of
+                     two or exactly 0.  The scales span 2^-3 .. 2^3 over the images, but within one image at most 2^2 (image 0:
+                     2^-3, 2^-2; image 1: 2^-1 .. 2^1; image 2: 2^2, 2^3; div = 3): an element that mixed a 2^3 term with the unit of a 2^-3 one would need six
+                     bits more than F(4x4) leaves.  The unit of image i follows its smallest scale.
+
+    THE CONDITIONS (mag = the stage's sum of absolute terms, unit = the power of two every term is a multiple of):
+        input transform   mag / unit <= 2^24,  mag = |B^T| |x s| |B|
+        grouped GEMM      mag / unit <= 2^22,  mag = sum_c |V| |U|              (LIMIT: two spare bits for the matrix pipe)
+        output transform  mag / unit <= 2^24,  mag = |A^T| (sum_c |V| |U|) |A| + |shift|
+        direct form       mag / unit <= 2^22,  mag = sum |x s| |w| + |shift|
+    Where a shape does not meet them the density shrinks, never the condition."""
+    if name in _wg_conv_cache:
+        return _wg_conv_cache[name]
+    import _wg_ref
+    m, shapes, cin, cout, kind, div, counts, route, tile = WG_CONV[name]
+    g = torch.Generator().manual_seed(7001 + sorted(WG_CONV).index(name))
+    s, sg = wg_scaled_g(m)
+    if kind == 'sparse':
+        dx, dw = _WG_DENSITY[cin]
+        if div > 1:
+            dx, dw = _WG_DENSITY_GUIDED
+        k = _ints(g, (cout, cin, 3, 3), 1) * (torch.rand(cout, cin, 3, 3, generator=g) < dw).double()
+        k[0, 0, 1, 1] = 1.0
+    else:
+        k = _ints(g, (cout, cin, 3, 3), 7)
+    ka = None
+    if kind == 'wide':
+        ka = torch.randperm(cin, generator=g)[:-(-cin // 20)]
+        k[:, ka] = 0.0
+        k[:, ka, 1, 1] = _ints(g, (cout, len(ka)), 1)
+    wt = k * float(s * s)
+    u = torch.einsum('ai,ocij,bj->aboc', sg, k, sg).reshape((m + 2) ** 2, cout, cin)
+    unit_v, unit_y = (0.25, 1.0 / 256) if m == 4 else (1.0, 1.0)
+    # integers of up to 17 bits in y's unit; under ``div`` the images' units differ by up to 2^6: multiples of the largest
+    # (2^3 unit_y) that are at most 2^17 of the smallest (2^-3 unit_y)
+    shift = _ints(g, (cout,), 2 ** 11) * 8.0 * unit_y if div > 1 else _ints(g, (cout,), 2 ** 17) * unit_y
+    out = dict(m=m, shapes=shapes, cin=cin, cout=cout, div=div, counts=counts, route=route, tile=tile, wt=wt.float(), u=u,
+               shift=shift.float(), xs=[], in_scale=[], refs=[], v=[], mo=[], worst=dict(v=0.0, mo=0.0, y=0.0, direct=0.0))
+    assert torch.equal(out['wt'].double(), wt) and torch.equal(out['shift'].double(), shift)
+    for n, H, W in shapes:
+        if kind == 'sparse':
+            x = _ints(g, (n, H, W, cin), 1) * (torch.rand(n, H, W, cin, generator=g) < dx).double()
+            x[0, 0, 0, 0] = 1.0
+        elif kind == 'dense':
+            x = _ints(g, (n, H, W, cin), 7)
+        else:
+            x = _ints(g, (n, H, W, cin), 7, zeros=True)
+            x[..., ka] = (2048.0 * torch.randint(1, 4, (n, H, W, len(ka)), generator=g).double() +
+                          torch.randint(1, 2048, (n, H, W, len(ka)), generator=g).double()) * \
+                (torch.randint(0, 2, (n, H, W, len(ka)), generator=g).double() * 2 - 1)
+        vec, unit_x = None, torch.ones(n * div, dtype=torch.float64)
+        if div > 1:
+            assert div == 3
+            img = torch.arange(n * div) % div
+            lo = torch.tensor([-3.0, -1.0, 2.0], dtype=torch.float64)[img]          # image 0: 2^-3, 2^-2; 1: 2^-1 .. 2^1; 2: 2^2, 2^3
+            e = lo[:, None] + torch.randint(0, 6, (n * div, cin), generator=g).double() % (2.0 + (img == 1).double())[:, None]
+            vec = 2.0 ** e * (torch.rand(n * div, cin, generator=g) >= 0.1).double()
+            unit_x = 2.0 ** lo
+            assert (vec == 0).any() and vec.max().item() == 8.0 and vec[vec > 0].min().item() == 0.125
+        n_img = n * div
+        v, vmag = _wg_ref.input_transform(x, vec, div, m)
+        mo = torch.einsum('gtc,goc->gto', v, u)
+        momag = torch.einsum('gtc,goc->gto', v.abs(), u.abs())         # the GEMM's terms: products of its operands
+        xe = x.repeat_interleave(div, 0) * (1.0 if vec is None else vec[:, None, None, :])
+        xn = xe.permute(0, 3, 1, 2)
+        dmag = F.conv2d(xn.abs(), wt.abs(), padding=1).permute(0, 2, 3, 1)
+        tiles = wg_tiles(H, W, m)
+        ut = unit_x.repeat_interleave(tiles)[None, :, None]                     # per tile row of V / Mo
+        ui = unit_x[:, None, None, None]
+        refs = {}
+        for sh in (False, True):
+            sv = shift if sh else None
+            want = F.conv2d(xn, wt, sv, padding=1).permute(0, 2, 3, 1).contiguous()
+            y, _ = _wg_ref.output_transform(mo, sv, False, n_img, H, W, m)
+            _, ymag = _wg_ref.output_transform(momag, sv, False, n_img, H, W, m)
+            assert torch.equal(y, want), name                                   # the float64 chain IS the convolution
+            ud = ui * unit_y if sh else ui                                      # the direct form: integer weights, the shift's unit
+            for t, unit, tag in ((v, ut * unit_v, 'v'), (mo, ut * unit_v, 'mo'), (y, ui * unit_y, 'y'), (want, ud, 'direct')):
+                q = t / unit
+                assert torch.equal(q, q.round()), (name, tag)                   # every value a multiple of its unit
+            for mag, unit, lim, tag in ((vmag, ut * unit_v, WG_LIMIT, 'v'), (momag, ut * unit_v, LIMIT, 'mo'),
+                                        (ymag, ui * unit_y, WG_LIMIT, 'y'),
+                                        (dmag + (shift.abs() if sh else 0.0), ud, LIMIT, 'direct')):
+                worst = (mag / unit).max().item()
+                out['worst'][tag] = max(out['worst'][tag], worst)
+                assert worst <= lim, f'{name} {tag}: mag / unit = 2^{torch.log2(torch.tensor(worst)).item():.2f}'
+            assert torch.equal(want.float().double(), want)
+            for relu in (False, True):
+                refs[(sh, relu)] = torch.relu(want) if relu else want
+        out['xs'].append(x.float().contiguous())
+        out['in_scale'].append(None if vec is None else vec.float())
+        out['refs'].append(refs)
+        out['v'].append(v)
+        out['mo'].append(mo)
+    _wg_conv_cache[name] = out
+    return out

@@ -586,7 +586,12 @@ def test_winograd_h2_is_as_close_to_fp64_as_x3():
     conv64 = lambda t: torch.nn.functional.conv2d(t.permute(0, 3, 1, 2).double(), w.cuda().double(), b.cuda().double(),
                                                   padding=1).relu_().permute(0, 2, 3, 1)
     for kw in (dict(), dict(in_scale=sc), dict(n_img_dev=n_dev)):
-        yh, y3 = ops.conv3x3_winograd(x, lh, **kw), ops.conv3x3_winograd(x, l3, **kw)
+        # 36 groups of 640 rows (576 valid) -> 192 channels, K 256: the 64-row tile of both plane kernels (K >= 256, but 360 of
+        # the 400 tiles the 128-row tile asks for)
+        (yh, y3), maths = _route(lambda: (ops.conv3x3_winograd(x, lh, **kw), ops.conv3x3_winograd(x, l3, **kw)))
+        assert maths == ['h2', 'x3'], maths
+        assert ops.h2_kernel(36 * 640, cout, cin, 640, 576) == ops.H2_KERNELS[64] % 'false'
+        assert ops.x3_kernel(36 * 640, cout, cin, 640, 576) == ops.X3_KERNELS[64]
         n = 5 if 'n_img_dev' in kw else 6
         ref = conv64(x[:n] * sc[:n, None, None, :] if 'in_scale' in kw else x[:n])
         rng = ref.abs().max().item()

@@ -6,12 +6,49 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 
+def _wg_gemm_records(fn):
+    """(result of ``fn``, the records of the grouped GEMMs it launched: route in 'math', kernel name in 'kernel')"""
+    from fgn_amd import ops
+    prev, ops.PROFILE = ops.PROFILE, ops.ConvProfile()
+    try:
+        out = fn()
+        recs = [r for r in ops.PROFILE if r['kind'] == 'wg_gemm']
+    finally:
+        ops.PROFILE = prev
+    return out, recs
+
+
+def _assert_route(recs, tile):
+    """The grouped GEMM ran on conv_pw_h2_kernel's ``tile``-row instance (layers packed under the default arithmetic,
+    'h2'), or - ``tile`` 0 - on the f32 kernel behind ``fgn_winograd_gemm_f32``"""
+    from fgn_amd import ops
+    assert len(recs) == 1, recs
+    if ops.GEMM_MATH != 'h2':
+        return
+    if tile:
+        assert recs[0]['math'] == 'h2' and recs[0]['kernel'] == ops.H2_KERNELS[tile] % 'false', recs[0]
+    else:
+        assert recs[0]['math'] == 'f32' and 'conv_pw_h2' not in recs[0]['kernel'], recs[0]
+
+
 def _ref(x, w, b, scale_in=None, div=1, relu=True):
     xi = x.repeat_interleave(div, 0) if div > 1 else x
     if scale_in is not None:
         xi = xi * scale_in[:, None, None, :]
     y = F.conv2d(xi.permute(0, 3, 1, 2).double(), w.double(), b.double(), padding=1)
     return (F.relu(y) if relu else y).float()
+
+
+# the row tile of conv_pw_h2_kernel the grouped GEMM of each shape below runs on under (F(4x4), F(2x2)); 0 = the f32 kernel
+# behind fgn_winograd_gemm_f32 (fewer than 192 tiles of 64 rows x 128 columns, or too few of 128 columns real)
+_H2_TILE = {
+    (2, 8, 10, 64, 128, 1): (0, 0),
+    (1, 7, 9, 32, 8, 1): (0, 0),
+    (1, 13, 21, 128, 256, 3): (0, 0),
+    (37, 7, 7, 64, 64, 1): (0, 0),
+    (1, 50, 84, 256, 128, 3): (64, 128),   # the one shape with enough tiles for the f16-plane kernel
+    (3, 5, 3, 32, 32, 1): (0, 0),
+}
 
 
 @pytest.mark.parametrize('m', [4, 2])
@@ -32,7 +69,9 @@ def test_winograd_matches_direct(n, h, w, cin, cout, div, scaled, m):
     s = (torch.rand(n * div, cin, generator=g) + 0.5) if scaled else None
     layer = ops.pack_winograd(wt, bias=b, relu=True, m=m).to('cuda')
     assert layer.groups == (m + 2) ** 2
-    got = ops.conv3x3_winograd(x.cuda(), layer, in_scale=None if s is None else s.cuda(), a_img_div=div)
+    got, recs = _wg_gemm_records(lambda: ops.conv3x3_winograd(x.cuda(), layer, in_scale=None if s is None else s.cuda(),
+                                                              a_img_div=div))
+    _assert_route(recs, _H2_TILE[(n, h, w, cin, cout, div)][0 if m == 4 else 1])
     ref = _ref(x, wt, b, s, div)
     assert got.shape == (n * div, h, w, cout)
     d = (got.cpu().permute(0, 3, 1, 2) - ref).abs().max().item()
@@ -61,7 +100,11 @@ def test_winograd_bn_fold_and_device_count(m):
               running_mean=torch.randn(cout, generator=g) * 0.1, running_var=torch.rand(cout, generator=g) + 0.5)
     layer = ops.pack_winograd(wt, bn=bn, relu=True, m=m).to('cuda')
     cnt = torch.tensor([23], dtype=torch.int32, device='cuda')
-    got = ops.conv3x3_winograd(x.cuda(), layer, n_img_dev=cnt)
+    out = torch.full((n, 7, 7, cout), 0x7B5A5A5A, dtype=torch.int32, device='cuda').view(torch.float32)
+    got, recs = _wg_gemm_records(lambda: ops.conv3x3_winograd(x.cuda(), layer, n_img_dev=cnt, out=out))
+    _assert_route(recs, 0)                 # Cout <= 64 and fewer than 256 row tiles: the f32 kernel
+    # images past the device count keep their bytes (include/fgn_hip.h: the transforms and the grouped GEMM stop at the count)
+    assert got is out and bool((out[23:].view(torch.int32) == 0x7B5A5A5A).all())
     y = F.conv2d(x.permute(0, 3, 1, 2), wt, padding=1)
     ref = F.relu(F.batch_norm(y, bn['running_mean'], bn['running_var'], bn['weight'], bn['bias'], False, 0.0, 1e-5))
     d = (got[:23].cpu().permute(0, 3, 1, 2) - ref[:23]).abs().max().item()
