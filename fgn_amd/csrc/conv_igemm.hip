@@ -1505,6 +1505,14 @@ extern "C" int fgn_x3_phases(unsigned long long* host16) {
     if (hipMemcpy(host16, g_x3_ph, 128, hipMemcpyDeviceToHost) != hipSuccess) return FGN_ERR_ARG;
     return hipMemset(g_x3_ph, 0, 128) == hipSuccess ? FGN_OK : FGN_ERR_ARG;
 }
+// the parts of conv_pw_h2_kernel's time outside the K-tiles (conv_pw_h2.h, ph_[7 .. 13]) of the same two workgroups: the
+// second 128 bytes of the record.  Call it BEFORE fgn_x3_phases, which ends the launch's record.
+extern "C" int fgn_h2_epilogue_phases(unsigned long long* host16) {
+    if (!g_x3_ph) return FGN_ERR_ARG;
+    if (hipDeviceSynchronize() != hipSuccess) return FGN_ERR_ARG;
+    if (hipMemcpy(host16, g_x3_ph + 16, 128, hipMemcpyDeviceToHost) != hipSuccess) return FGN_ERR_ARG;
+    return hipMemset(g_x3_ph + 16, 0, 128) == hipSuccess ? FGN_OK : FGN_ERR_ARG;
+}
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -1791,7 +1799,7 @@ extern "C" int fgn_gemm_x3_f32(const float* x, const void* w3, float* y, const f
     const int rc = describe_gemm(p, MATH_X3, x, w3, y, shift, residual, rows, K, Cout, npad, relu, grp_rows, grp_valid, n_groups);
     if (rc != FGN_DESCRIBED) return rc;
 #ifdef X3_PHASES
-    if (!g_x3_ph && (hipMalloc(&g_x3_ph, 128) != hipSuccess || hipMemset(g_x3_ph, 0, 128) != hipSuccess)) return FGN_ERR_ARG;
+    if (!g_x3_ph && (hipMalloc(&g_x3_ph, 256) != hipSuccess || hipMemset(g_x3_ph, 0, 256) != hipSuccess)) return FGN_ERR_ARG;
     p.ws = reinterpret_cast<float*>(g_x3_ph);
 #endif
     return launch_x3(p, rows, bm, nterms, stream);
@@ -1804,7 +1812,7 @@ extern "C" int fgn_gemm_h2_f32(const float* x, const void* w_h2, float* y, const
     const int rc = describe_gemm(p, MATH_H2, x, w_h2, y, shift, residual, rows, K, Cout, npad, relu, grp_rows, grp_valid, n_groups);
     if (rc != FGN_DESCRIBED) return rc;
 #ifdef H2_PHASES
-    if (!g_x3_ph && (hipMalloc(&g_x3_ph, 128) != hipSuccess || hipMemset(g_x3_ph, 0, 128) != hipSuccess)) return FGN_ERR_ARG;
+    if (!g_x3_ph && (hipMalloc(&g_x3_ph, 256) != hipSuccess || hipMemset(g_x3_ph, 0, 256) != hipSuccess)) return FGN_ERR_ARG;
     p.ws = reinterpret_cast<float*>(g_x3_ph);
 #endif
     return launch_h2(p, rows, n_groups, bm, stream);

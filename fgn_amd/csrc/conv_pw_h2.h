@@ -29,8 +29,10 @@
 //    the transform 3x slower (profiles/r05_ab_h2_100steps.jsonl, r05_h2_probe_record_vs_own_scale.jsonl; DESIGN appendix A).
 //
 // Structure: conv_pw_x3_kernel's (16x16x32 form): BM = 32 RB WMW rows x 128 columns, WMW x 2 waves, wave tile 32 RB x 64,
-// a ring of NST LDS stages of (BM * 128 + 16384) bytes running across output tiles (the C tile goes through the last
-// stage one wave row at a time: 32 RB rows x 512 bytes fit it for either row tile), the f32 activations split in
+// a ring of NST LDS stages of (BM * 128 + 16384) bytes running across output tiles (the C tile goes through the stage the
+// last K-tile was read from: every wave takes its own accumulators through a 16-row region of its own, behind one
+// workgroup barrier per output tile - "the epilogue" in the kernel; two K-groups: one wave row at a time, the second
+// group's sum added in place: 32 RB rows x 512 bytes fit the stage for either row tile), the f32 activations split in
 // registers after the ds_read (2 vector instructions per element: v_fma_mixlo / mixhi_f16), the weight image
 // [group][K-tile][plane][npad][32] f16 with the k order and chunk swizzle of ops.pack_x3's 16x16x32 form.  64 rows: 48 KB
 // of LDS, three workgroups per CU; 128 rows: 64 KB, two; 64 rows on two K-groups (KG = 2, below): 96 KB, one.
@@ -146,6 +148,8 @@ struct H2Im2col {
 #else
 #define H2_T(i) do { } while (0)
 #endif
+struct H2Yes { static constexpr bool value = true; };
+struct H2No { static constexpr bool value = false; };
 template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1>
 __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_h2_kernel(const ConvParams p, const H2Im2col q2, const int total_tiles) {
     // NW / NTHR_G: waves / threads of ONE K-group (the roles wm, wn and the DMA rows are those of the wave inside its group)
@@ -164,6 +168,22 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     // branch-free cursor below: with that cursor every 6504 x 1024 -> 256 launch of an episode measured 0.7 - 1 us slower in
     // isolation (23.1 - 24.9 -> 23.8 - 25.6 us, whichever of its parts was taken out again)
     constexpr bool OLD_CURSOR = KG == 2 && !IM2COL;
+    // The wave-private epilogue (below, "the epilogue") of the one-K-group instances; two K-groups add their sums in the C
+    // tile in a fixed order and keep the pass per wave row.  (-DH2_EPILOGUE_PASSES: that form on every instance, for the
+    // phase clocks of tools/micro/build_x3_phases.sh to measure both with the same stamps.)
+#ifdef H2_EPILOGUE_PASSES
+    constexpr bool WPE = false;
+#else
+    constexpr bool WPE = KG == 1;
+#endif
+#ifdef H2_PHASES
+    constexpr bool PEEL = true;                             // (the phase clocks tell a tile's first K-tile by its call site)
+#else
+    constexpr bool PEEL = WPE;
+#endif
+    constexpr int C_LD = 68;                                // floats of a staged C row: 64 + 4, so that the four row groups
+                                                            // of a 16x16 block write to different banks
+    static_assert(!WPE || NW * 16 * C_LD * 4 <= STAGE, "a 16-row block per wave fits the free stage");
     static_assert(NST == 2, "a ring of two stages: one K-tile in flight ahead of the one being multiplied");   // (three: measured 5-12 % slower, DESIGN appendix A row 53)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_h2[];
 
@@ -420,9 +440,19 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
         for (int i = 0; i < PER; ++i) piece(cur, 0u, i);
         advance();
     }
+    // (WPE) the first K-tile of an output tile finds its pieces waited for: here for the workgroup's first tile - its first
+    // K-tile would wait at once anyway - and in the epilogue of the tile before for every other (k_tile, `first`)
+    if constexpr (WPE) x3_wait_vm<0>();
     unsigned rd = 0u;                               // byte offset in the ring of the stage being multiplied: 0 or STAGE
 #ifdef H2_PHASES
-    unsigned long long ph_[7] = {0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
+    bool walked = false;                            // the workgroup has an output tile behind it
+    // [7 .. 12]: the time outside the K-tiles by its parts, summed over the output tiles ([13] counts them): [8] last MFMA ->
+    // past the first epilogue barrier, [9] C-tile LDS writes and their barriers / waits, [10] the wait for the residual
+    // rows (and whatever else is in flight), [11] LDS reads, arithmetic and store issue, [12] the tile walk (next_active,
+    // offsets, accumulator clear; before the workgroup's first tile: nothing); [5] keeps what lies between the MFMA mark
+    // of a K-tile and the top of the next one; [7] of [0]: the vmcnt wait at the top of the first K-tile of a tile that is
+    // not the workgroup's first
+    unsigned long long ph_[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
     const unsigned long long begin_ = last_;
 #endif
 
@@ -436,14 +466,36 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
         float a_lim = 0.f;                          // |x| above this leaves the f16 range under the current scale (no scale yet:
                                                     // any non-zero element; an all-zero fragment - padded rows - passes as it is)
         a_s = 1.f; a_inv = 1.f;
+        // (WPE) the residual values of the rows and the column quad this thread stores in the epilogue: rows g4 + 4 k of
+        // the wave's 16-row block i, columns 4 r16 .. + 3 of the wave's 64.  Zeros without a residual and past M / Cout.
+        // Block 0 is requested ahead of the epilogue's barrier, block i + 1 ahead of block i's stores.  (Requested behind the
+        // last K-tile's requests, to land under its MFMAs, they are live beside the K-tile's fragments: all 2 RB blocks
+        // cost 44 - 48 registers, block 0 alone 28 - 34, and the implicit-GEMM instances of the 64-row and 128 x 64 tiles
+        // pass the 168 registers that three workgroups per CU leave a wave: DESIGN appendix A.)
+        float4 res_e[4];
+        auto residual_rows = [&](const int i) {
+            const int n = n0 + wn * 64 + r16 * 4;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int m = m0 + wm * (32 * RB) + 16 * i + g4 + 4 * k;
+                res_e[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (p.residual && m < M && n < p.Cout) res_e[k] = *reinterpret_cast<const float4*>(p.residual + (size_t)m * p.Cout + n);
+            }
+        };
         // One K-tile, a straight line but for the overflow watch: wait, barrier, the requests for the cursor's
         // K-tile of the output tile `o` into the other stage (it was last read in the iteration before, and every wave has
         // passed this one's barrier), LDS reads, watch, split and MFMAs.  `last`: the last K-tile of an output tile
-        auto k_tile = [&](auto&& requests) {
-            // the K-tile has landed: everything in flight is waited for (the first K-tile of an output tile: the previous
-            // epilogue's stores share the counter and return in no fixed order with the loads)
-            H2_T(5);
-            x3_wait_vm<0>();
+        auto k_tile = [&](auto&& requests, auto first) {
+            // the K-tile has landed: everything in flight is waited for.  `first` (WPE: the first K-tile of an output
+            // tile): every wave has waited for its pieces of this K-tile already - in the epilogue of the tile before,
+            // ahead of its first store - so only that epilogue's stores are in flight: they are left to the next K-tile's
+            // wait, one K-tile of work later, and the barrier alone says that all the pieces have landed.  (The stores
+            // share the counter with the loads: waited for here, their acknowledgements stood in front of this K-tile.)
+            if constexpr (decltype(first)::value) H2_T(12); else H2_T(5);     // since the epilogue's last store: the tile walk | since the last MFMA
+            if constexpr (!(WPE && decltype(first)::value)) x3_wait_vm<0>();
+#ifdef H2_PHASES
+            if (decltype(first)::value && walked) H2_T(7);
+#endif
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();            // ... for every wave; and every wave is done with the stage before
             asm volatile("" ::: "memory");           // (no LDS read moves above the barrier)
@@ -574,22 +626,89 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
             for (int k = 0; k < PER; ++k) piece(o, wr, k);
         };
         if constexpr (OLD_CURSOR) {
-            for (int kt = 0; kt < KT; ++kt) k_tile([&](const unsigned wr) { issue_one(wr); });
+            for (int kt = 0; kt < KT; ++kt) k_tile([&](const unsigned wr) { issue_one(wr); }, H2No{});
         } else {
-            for (int kt = 0; kt < KT - 1; ++kt) k_tile([&](const unsigned wr) { request(cur, wr); });
+            // (WPE: the first K-tile is a call of its own - it does not wait; two K-groups keep the one loop they had)
+            if constexpr (PEEL) k_tile([&](const unsigned wr) { request(cur, wr); }, H2Yes{});
+            for (int kt = PEEL ? 1 : 0; kt < KT - 1; ++kt) k_tile([&](const unsigned wr) { request(cur, wr); }, H2No{});
             seek(0);
-            k_tile([&](const unsigned wr) { if (ntile >= 0) request(nxt, wr); });
+            k_tile([&](const unsigned wr) { if (ntile >= 0) request(nxt, wr); }, H2No{});
         }
         // the stage of the last K-tile (the other one than `rd` now; group 0's ring) takes the C tile once every wave
         // has read it
         float* const cbase = reinterpret_cast<float*>(smem_h2 + (rd ^ (unsigned)STAGE));
         const int em0 = m0, en0 = n0;
         const float* const winv = p.w_inv + (p.grp_rows ? (size_t)(em0 / p.grp_rows) * p.npad3 : 0);
-        // one pass per wave row: PR = 32 RB rows x 128 floats (16 / 32 KB: fits the stage for either row tile)
+        if constexpr (WPE) {
+            // The wave-private epilogue.  ONE workgroup barrier: every wave has read the last K-tile's stage before any
+            // wave writes to it.  Then each wave is on its own: it takes its accumulators through a region of that stage
+            // no other wave touches (16 rows x C_LD floats), one 16-row block at a time - 16 ds_write_b32 per lane in the
+            // 16x16 C/D layout (col = lane & 15, row = 4 * (lane >> 4) + reg), its own lgkmcnt wait, and the block back as
+            // float4: lane (r16, g4) reads columns 4 r16 .. + 3 of rows g4 + 4 k, so a wave instruction stores 4 rows x
+            // 256 bytes.  LDS operations of one wave execute in order: the next block's writes need no wait for these reads.
+            // The barrier at the top of the next output tile's first K-tile keeps the stage from being refilled before
+            // every wave is through.  The arithmetic per element and its order are those of the pass form below.
+            residual_rows(0);                        // ahead of the barrier: in flight while the waves gather
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            H2_T(8);
+            float* const cw0 = cbase + wv * (16 * C_LD);
+            const int n = en0 + wn * 64 + r16 * 4;
+            const bool n_in = n < p.Cout;
+            float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f), iv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (n_in) {
+                if (p.scale) sc = *reinterpret_cast<const float4*>(p.scale + n);
+                if (p.shift) sh = *reinterpret_cast<const float4*>(p.shift + n);
+                iv = *reinterpret_cast<const float4*>(winv + n);                  // the column scales out again (exact)
+            }
+#pragma unroll
+            for (int i = 0; i < 2 * RB; ++i) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) cw0[(4 * g4 + r) * C_LD + 16 * j + r16] = acc[i][j][r] * a_inv;      // the wave's scale out again
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                H2_T(9);
+                if (i == 0) {
+                    // Everything this wave has in flight - its pieces of the next output tile's first K-tile, the residual
+                    // rows, the vectors above: all requested a K-tile ago or needed now - BEFORE its first store, so that
+                    // the next tile's first K-tile need not wait for the stores (k_tile, `first`).  Not a counted wait:
+                    // the threads of a ragged tile issue fewer stores.
+                    x3_wait_vm<0>();
+                    H2_T(10);
+                }
+                float4 res[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) res[k] = res_e[k];
+                if (i + 1 < 2 * RB) residual_rows(i + 1);       // (m0, n0 are still this tile's)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int row = g4 + 4 * k;
+                    const int m = em0 + wm * (32 * RB) + 16 * i + row;
+                    if (m >= M || !n_in) continue;
+                    float4 v = *reinterpret_cast<const float4*>(cw0 + row * C_LD + r16 * 4);
+                    v.x *= iv.x; v.y *= iv.y; v.z *= iv.z; v.w *= iv.w;
+                    v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
+                    v.x += res[k].x; v.y += res[k].y; v.z += res[k].z; v.w += res[k].w;
+                    if (p.relu) {
+                        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+                    }
+                    float* const yrow = (IM2COL && m >= q2.M0) ? q2.y1 + (size_t)(m - q2.M0) * p.Cout : p.y + (size_t)m * p.Cout;
+                    *reinterpret_cast<float4*>(yrow + n) = v;
+                }
+                asm volatile("" ::: "memory");
+                H2_T(11);
+            }
+        }
+        // (two K-groups) one pass per wave row: PR = 32 RB rows x 128 floats (16 / 32 KB: fits the stage for either row tile)
         constexpr int PR = 32 * RB;
 #pragma unroll
-        for (int pass = 0; pass < WMW; ++pass) {
+        for (int pass = 0; pass < (WPE ? 0 : WMW); ++pass) {
             __syncthreads();
+#ifdef H2_PHASES
+            if (pass == 0) H2_T(8);
+#endif
             if (wm == pass && kg == 0) {             // 16x16 C/D layout: col = lane & 15, row = 4 * (lane >> 4) + reg
 #pragma unroll
                 for (int i = 0; i < 2 * RB; ++i)
@@ -614,6 +733,7 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
                 }
                 __syncthreads();
             }
+            H2_T(9);
             constexpr int C4 = BN / 4, RPP = NTHR / C4, NPASS = PR / RPP, SW = NPASS < 4 ? NPASS : 4;
             static_assert(NPASS % SW == 0, "row sweeps in groups of SW");
             const int c4 = t % C4, rr = t / C4;
@@ -632,6 +752,10 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
                         res[k] = make_float4(0.f, 0.f, 0.f, 0.f);
                         if (p.residual && m < M) res[k] = *reinterpret_cast<const float4*>(p.residual + (size_t)m * p.Cout + n);
                     }
+#ifdef H2_PHASES
+                    x3_wait_vm<0>();                 // (the product waits where the compiler puts it: before the first use)
+                    H2_T(10);
+#endif
 #pragma unroll
                     for (int k = 0; k < SW; ++k) {
                         const int row = rr + RPP * (k0 + k);
@@ -647,9 +771,17 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
                         float* const yrow = (IM2COL && m >= q2.M0) ? q2.y1 + (size_t)(m - q2.M0) * p.Cout : p.y + (size_t)m * p.Cout;
                         *reinterpret_cast<float4*>(yrow + n) = v;
                     }
+#ifdef H2_PHASES
+                    asm volatile("" ::: "memory");
+                    H2_T(11);
+#endif
                 }
             }
         }
+#ifdef H2_PHASES
+        ++ph_[13];
+        walked = true;
+#endif
         if (ntile < 0) break;
         // the next output tile becomes the current one (its first K-step is requested already: the cursor stands at its second)
         tile = ntile; m0 = nm0; n0 = nn0;
@@ -667,6 +799,7 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
         unsigned long long* o = reinterpret_cast<unsigned long long*>(p.ws) + 8 * blockIdx.x;
         for (int i = 0; i < 7; ++i) o[i] = ph_[i];
         o[7] = __builtin_amdgcn_s_memtime() - begin_;
+        for (int i = 7; i < 14; ++i) o[16 + i - 7] = ph_[i];          // the epilogue's parts: behind the two workgroups' [0 .. 7]
     }
 #endif
     leave();

@@ -63,6 +63,41 @@ def probe_im2col(dev, reps):
     print(json.dumps(rec), flush=True)
 
 
+# --epilogue: the shapes whose time outside the K-tiles profiles/h2_epilogue_phases.jsonl splits, on the instance the
+# launcher picks (tile code 0) unless one is named: name, groups, rows per group, valid rows, K, N, residual, tile code
+EPILOGUE_SHAPES = [
+    ('relq 14700x1024>1024', 1, 14700, 14700, 1024, 1024, False, 64),
+    ('relq 14700x1024>1024', 1, 14700, 14700, 1024, 1024, False, 128),
+    ('wino agrpn 36x819 1024>1024', 36, 896, 819, 1024, 1024, False, 0),
+    ('layer3 conv1 6504x1024>256', 1, 6504, 6504, 1024, 256, False, 0),
+    ('layer3 conv3 6504x256>1024 +residual', 1, 6504, 6504, 256, 1024, True, 0),
+    ('layer1 conv1 103664x256>64', 1, 103664, 103664, 256, 64, False, 0),
+]
+
+
+def probe_epilogue(dev, reps, build):
+    """One record per shape of EPILOGUE_SHAPES: the phase clocks with the epilogue's split (a library built with
+    -DH2_PHASES) and the time per launch, shift + ReLU (+ residual) in the epilogue."""
+    L = ops._lib.load()
+    g = torch.Generator().manual_seed(3)
+    for name, G, gr, valid, K, N, with_res, bm in EPILOGUE_SHAPES:
+        x = torch.randn(G, gr, K, generator=g).relu_().to(dev)
+        w = (torch.randn(G, N, K, generator=g) * (1.0 / K ** 0.5)).to(dev)
+        shift = torch.randn(N, generator=g).to(dev)
+        res = torch.randn(G, gr, N, generator=g).to(dev) if with_res else None
+        img = ops.pack_h2(w)
+        out = torch.zeros(G, gr, N, device=dev)
+        fn = (lambda: ops.gemm_h2(x, img, N, shift=shift, residual=res, relu=True, groups=G, grp_valid=valid, bm=bm, out=out))
+        fn()
+        torch.cuda.synchronize()
+        tile = bm or L.fgn_h2_row_tile(G * gr, N, K, gr if G > 1 else 0, valid if G > 1 else 0)
+        kg = L.fgn_h2_k_groups(G * gr, N, K, gr if G > 1 else 0, valid if G > 1 else 0) if bm == 0 else 1
+        rec = dict(build=build, shape=name, tile=tile, k_groups=kg, wg0_cycles_per_ktile=h2_phases(fn))
+        rec['us'] = timed_round_robin({'h2': fn}, reps)['h2']
+        print(json.dumps(rec), flush=True)
+        del x, w, res, out, img
+
+
 def timed_round_robin(fns: dict, reps: int, rounds: int = 5) -> dict:
     """Median over `rounds` of the time per launch of every variant, the variants taking turns (the clock the chip holds
     depends on what ran just before: one variant after the other ranks them by their place in the queue)."""
@@ -91,15 +126,32 @@ def h2_phases(fn):
     if not hasattr(raw, 'fgn_x3_phases'):
         return None
     buf = (ctypes.c_ulonglong * 16)()
+    ep = (ctypes.c_ulonglong * 16)() if hasattr(raw, 'fgn_h2_epilogue_phases') else None
     raw.fgn_x3_phases(buf)                      # clear
+    if ep is not None:
+        raw.fgn_h2_epilogue_phases(ep)
     fn()
+    if ep is not None and raw.fgn_h2_epilogue_phases(ep) != 0:
+        return None
     if raw.fgn_x3_phases(buf) != 0:
         return None
     v = list(buf[0:8])
     steps = max(v[6], 1)
-    return dict(wait_barrier=round(v[0] / steps), issue=round(v[1] / steps), lds_landed=round(v[2] / steps),
-                watch_split0=round(v[3] / steps), mfma=round(v[4] / steps), outside_per_ktile=round(v[5] / steps),
-                ktiles=v[6], kernel_cycles=v[7])
+    rec = dict(wait_barrier=round(v[0] / steps), issue=round(v[1] / steps), lds_landed=round(v[2] / steps),
+               watch_split0=round(v[3] / steps), mfma=round(v[4] / steps), outside_per_ktile=round(v[5] / steps),
+               ktiles=v[6], kernel_cycles=v[7])
+    if ep is not None:
+        # the time outside the K-tiles by its parts (conv_pw_h2.h, ph_[7 .. 13]), cycles per OUTPUT TILE of the wave: what
+        # the kernel books under "outside" and under "wait + barrier" is put back so that both keep their meaning
+        e = list(ep[0:8])
+        tiles = max(e[6], 1)
+        rec['wait_barrier'] = round((v[0] + e[0]) / steps)
+        rec['outside_per_ktile'] = round((v[5] + e[1] + e[2] + e[3] + e[4] + e[5]) / steps)
+        rec['outside_per_tile'] = dict(a_skew_to_first_barrier=round(e[1] / tiles), b_lds_writes_and_barriers=round(e[2] / tiles),
+                                       c_wait_in_flight_residual=round(e[3] / tiles), d_lds_reads_math_stores=round(e[4] / tiles),
+                                       e_tile_walk=round(e[5] / tiles), between_ktiles_per_ktile=round(v[5] / steps), f_vmcnt_first_ktile_of_later_tiles=round(e[0] / max(tiles - 1, 1)),
+                                       tiles=e[6])
+    return rec
 
 
 # default instances (16x16x32 MFMA): 64 / 128 rows, nine terms; + 2000: the 32x32x16 form (experiments build)
@@ -112,12 +164,18 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--only', default='')
     ap.add_argument('--im2col', action='store_true', help="layer3.0's 3x3 / stride 2 implicit GEMM, one K-group against two")
+    ap.add_argument('--epilogue', default='', metavar='BUILD',
+                    help="the epilogue's phase split on EPILOGUE_SHAPES, the records labelled BUILD (FGN_HIP_LIB=tools/micro/"
+                         'libfgn_hip_h2ph.so, or libfgn_hip_h2ph_passes.so for the pass-per-wave-row form)')
     ap.add_argument('--phases', action='store_true', help='phase clocks (FGN_HIP_LIB=tools/micro/libfgn_hip_x3ph.so for conv_pw_x3_kernel, libfgn_hip_h2ph.so for conv_pw_h2_kernel)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     g = torch.Generator().manual_seed(1)
     if args.im2col:
         probe_im2col(dev, args.reps)
+    if args.epilogue:
+        probe_epilogue(dev, args.reps, args.epilogue)
+        return
     for name, G, gr, valid, K, N in SHAPES:
         if args.only and args.only not in name:
             continue
