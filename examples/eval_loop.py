@@ -11,6 +11,8 @@ DataLoader(ds, batch_size=ds.batch, collate_fn=collate_fn_new) -> model.simple_t
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source     (supports cropped, resized and padded on the GPU)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source --rle-masks     (masks travel as COCO RLE, decoded on the GPU)
     python examples/eval_loop.py --dataset MNISTISEG --episodes 16 --spp-source --color-masks     (masks travel as box + colour, made on the GPU from the image bytes)
+    python examples/eval_loop.py --episodes 8 --poly-masks     (polygonal instances; masks travel as COCO polygons, rasterised on the GPU)
+    python examples/eval_loop.py --episodes 8 --poly-dense     (the same episodes and the same truth, masks handed over dense)
     python examples/eval_loop.py --episodes 8 --match-on-device     (mask overlaps counted on the GPU: the evaluator decodes no RLE)
     python examples/eval_loop.py --episodes 8 --eval-on-device --iou-thrs coco     (greedy matching on the GPU too; AP at COCO's ten thresholds)
 """
@@ -59,6 +61,13 @@ def main():
                     help='character datasets: the loader yields the ground-truth masks as box + colour, all that MNISTISEG / '
                          'OMNIISEG store per instance, with --spp-source the support masks too; the detector makes the '
                          'masks on the GPU from the image bytes (implies --uint8; not beside --rle-masks)')
+    ap.add_argument('--poly-masks', action='store_true',
+                    help='synthetic episodes: the instances are polygons and the loader yields the ground-truth masks as '
+                         'COCO polygons ({\'polygons\': [...], \'size\': [h, w]}); the detector rasterises them on the GPU and '
+                         'only their vertices are uploaded')
+    ap.add_argument('--poly-dense', action='store_true',
+                    help='synthetic episodes: the same polygonal instances with their masks handed over dense '
+                         '(polygon.dense of the same vertices): the other arm of --poly-masks, same results')
     ap.add_argument('--match-on-device', action='store_true',
                     help='count the overlaps of detections and ground truth on the GPU (FGN.match_on_device): the results '
                          'carry dt_gt_inter / dt_area / gt_area and the evaluator decodes no RLE')
@@ -77,11 +86,16 @@ def main():
         ap.error('--rle-masks needs --dataset MNISTISEG or OMNIISEG')
     if args.color_masks and args.rle_masks:
         ap.error('--color-masks and --rle-masks are two forms of one argument: choose one')
+    if (args.poly_masks or args.poly_dense) and args.dataset != 'SYNTH':
+        ap.error('--poly-masks / --poly-dense need --dataset SYNTH (the character datasets hold no polygons)')
+    if args.poly_masks and args.poly_dense:
+        ap.error('--poly-masks and --poly-dense are the two arms of one comparison: choose one')
     if args.uint8 and args.dataset == 'SYNTH':
         ap.error('--uint8 / --source-size / --spp-source need --dataset MNISTISEG or OMNIISEG (the synthetic images are Gaussian floats, not pixels)')
 
     if args.dataset == 'SYNTH':
-        ds = SyntheticFewShotISEG(args.n_ways, args.k_shots, args.episodes, args.height, args.width, batch=args.batch)
+        ds = SyntheticFewShotISEG(args.n_ways, args.k_shots, args.episodes, args.height, args.width, batch=args.batch,
+                                  polygons='poly' if args.poly_masks else 'dense' if args.poly_dense else None)
     else:       # cluttered characters: 128^2 (MNISTISEG, cfg1) / 256^2 (OMNIISEG, cfg2) queries, 128^2 supports
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,

@@ -6,6 +6,7 @@ warm-up 100 iterations, 3 epochs) on the MI355X path: DataLoader(ds, collate_fn_
 
     python examples/train_loop.py --dataset OMNIISEG --episodes 32 --epochs 3
     python examples/train_loop.py --dataset SYNTH --height 320 --width 480 --episodes 16
+    python examples/train_loop.py --dataset SYNTH --height 320 --width 480 --episodes 16 --poly-masks
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --spp-source --augment
     python examples/train_loop.py --dataset OMNIISEG --source-size 320 --augment --photometric
     python examples/train_loop.py --dataset OMNIISEG --spp-source --augment-spp --photometric-spp
@@ -30,7 +31,9 @@ one of hue / saturation / brightness, then a blur) and the photometric half trav
 ground-truth masks (with ``--spp-source`` the support masks too) travel as COCO RLE, the form the reference's COCO
 dataset holds them in, and are decoded on the GPU.  ``--color-masks`` (needs ``--source-size`` or ``--spp-source``: the
 images travel as bytes): the masks travel as box + colour, all the character datasets store, and are made on the GPU
-from the image bytes as uploaded, ahead of any augmentation.  The evaluation at the end is without augmentation.
+from the image bytes as uploaded, ahead of any augmentation.  ``--poly-masks`` (``--dataset SYNTH``): the synthetic
+instances are polygons and their masks travel as COCO polygons, rasterised on the GPU; ``--poly-dense``: the same
+episodes with ``polygon.dense`` of the same vertices handed over dense - the same losses and weights.  The evaluation at the end is without augmentation.
 
 ``--optimizer`` chooses among the three optimizers the schedule files list (Adagrad; Adam; SGD with momentum 0.9 and
 Nesterov), ``--grad-clip MAX_NORM`` is mmcv's ``optimizer_config.grad_clip`` (global L2 norm, logged as ``grad_norm``),
@@ -86,6 +89,10 @@ def main():
     ap.add_argument('--color-masks', action='store_true',
                     help='masks travel as box + colour and are made on the GPU from the image bytes (character datasets; '
                          'needs --source-size or --spp-source)')
+    ap.add_argument('--poly-masks', action='store_true',
+                    help='synthetic episodes of polygonal instances; masks travel as COCO polygons, rasterised on the GPU')
+    ap.add_argument('--poly-dense', action='store_true',
+                    help='the same polygonal episodes, masks handed over dense: the other arm of --poly-masks')
     ap.add_argument('--optimizer', default='Adagrad', choices=['Adagrad', 'Adam', 'SGD'])
     ap.add_argument('--grad-clip', type=float, default=None, metavar='MAX_NORM', help='clip the global gradient L2 norm')
     ap.add_argument('--cumulative-iters', type=int, default=1, help='accumulate the gradients of N iterations per update')
@@ -93,6 +100,10 @@ def main():
     args = ap.parse_args()
     if args.rle_masks and args.dataset == 'SYNTH':
         ap.error('--rle-masks needs a character dataset (MNISTISEG, OMNIISEG)')
+    if (args.poly_masks or args.poly_dense) and args.dataset != 'SYNTH':
+        ap.error('--poly-masks / --poly-dense need --dataset SYNTH (the character datasets hold no polygons)')
+    if args.poly_masks and args.poly_dense:
+        ap.error('--poly-masks and --poly-dense are the two arms of one comparison: choose one')
     if args.color_masks and args.rle_masks:
         ap.error('--color-masks and --rle-masks are two forms of one argument: choose one')
     if args.color_masks and args.source_size is None and not args.spp_source:
@@ -109,7 +120,8 @@ def main():
     if args.augment and args.source_size is None:
         ap.error('--augment needs --source-size: the query is augmented together with its resize')
     if args.dataset == 'SYNTH':
-        ds = SyntheticFewShotISEG(args.n_ways, args.k_shots, args.episodes, args.height, args.width, batch=args.batch)
+        ds = SyntheticFewShotISEG(args.n_ways, args.k_shots, args.episodes, args.height, args.width, batch=args.batch,
+                                  polygons='poly' if args.poly_masks else 'dense' if args.poly_dense else None)
     else:
         ds = ClutteredCharsFewShotISEG(args.dataset, args.n_ways, args.k_shots, n_imgs=args.episodes,
                                        img_size=128 if args.dataset == 'MNISTISEG' else 256, batch=args.batch,

@@ -24,6 +24,7 @@ SOURCES = [
     ('rpn_post.hip', ['-ffp-contract=off']),
     ('det_post.hip', ['-ffp-contract=off']),
     ('mask.hip', ['-ffp-contract=off']),
+    ('poly.hip', ['-ffp-contract=off']),    # (polygon points: product, sum, sum - never an fma)
     ('train.hip', ['-ffp-contract=off']),
     ('train_bwd.hip', []),
     ('optim.hip', ['-ffp-contract=off']),

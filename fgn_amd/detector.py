@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import config as _config
-from . import colormask, ops, rle
+from . import colormask, ops, polygon, rle
 from .weights import backbone_state_from_pretrained, init_state_dict
 
 
@@ -437,9 +437,16 @@ def _gt_entries(qry_isegmaps, sizes, imgs=None):
     An entry given as box + colour (``colormask.as_color_masks``: a ``ColorMasks`` or a dict of ``bboxes`` and
     ``colors``) becomes a checked ``ColorMasks`` at ``sizes[i]``, bound to ``imgs[i]`` - the image's bytes [h,w,3] as
     they were handed over, which is what its mask is made from; ``imgs`` is None where the images are not bytes (float
-    input), and a colour entry is refused then.  Without an RLE or colour entry the argument itself comes back."""
-    if qry_isegmaps is None or not isinstance(qry_isegmaps, (list, tuple)) or \
-            not any(rle.is_rle(g) or colormask.is_color(g) for g in qry_isegmaps):
+    input), and a colour entry is refused then.  An entry given as COCO polygons (``polygon.as_polys``: a ``PolyMasks``
+    or a dict ``{'polygons': [...][, 'size']}``) becomes a checked ``PolyMasks`` at ``sizes[i]``; a bare nested list is
+    never polygons - it reads as a dense mask, and one that is no [n,h,w] array of numbers is refused here.  Without an
+    RLE, colour or polygon entry the argument itself comes back."""
+    if qry_isegmaps is None or not isinstance(qry_isegmaps, (list, tuple)):
+        return qry_isegmaps
+    for i, g in enumerate(qry_isegmaps):
+        if isinstance(g, (list, tuple)) and not rle.is_rle(g):
+            _dense_lists(g, f'qry_isegmaps[{i}]', sizes[i] if sizes is not None and i < len(sizes) else None)
+    if not any(rle.is_rle(g) or colormask.is_color(g) or polygon.is_poly(g) for g in qry_isegmaps):
         return qry_isegmaps
     if sizes is not None and len(sizes) != len(qry_isegmaps):
         raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {len(sizes)} images')
@@ -451,10 +458,27 @@ def _gt_entries(qry_isegmaps, sizes, imgs=None):
                                  f'the device: give qry_img as uint8 pixels (set_input_norm, with or without '
                                  f'qry_resize_to), not as a normalised float tensor')
             g = colormask.as_color_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]', img=imgs[i])
+        elif polygon.is_poly(g):
+            g = polygon.as_polys(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]')
         elif rle.is_rle(g):
             g = rle.as_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]')
         out.append(g)
     return out
+
+
+def _dense_lists(g, what: str, hw=None) -> None:
+    """A mask entry given as nested lists that is no RLE reads as a dense mask: it must be an [n,h,w] array of numbers,
+    at ``hw`` where that is known.  COCO's ``segmentation`` lists have the same nesting, which is why polygons never come
+    bare."""
+    try:
+        a = np.asarray(g)
+    except (ValueError, TypeError):
+        a = None
+    if a is None or a.ndim != 3 or a.dtype.kind not in 'biuf' or \
+            (hw is not None and a.shape[0] and tuple(a.shape[1:]) != tuple(int(v) for v in hw)):
+        raise ValueError(f"{what}: a nested list reads as a dense mask and must be an [n,h,w] array of numbers at its image's "
+                         f"size{'' if hw is None else ' ' + str([int(v) for v in hw])}; polygons "
+                         f"come as {{'polygons': [instance, ...]}} or a PolyMasks (fgn_amd.polygon), never as bare lists")
 
 
 def _has_color(entries) -> bool:
@@ -466,6 +490,9 @@ def _dense_supports_only(spp_isegmaps) -> None:
     padded there, and no dataset holds such masks as runs - nor is there a source image to derive a box + colour mask
     from."""
     flat = spp_isegmaps if isinstance(spp_isegmaps, (list, tuple)) else [spp_isegmaps]
+    if any(polygon.is_poly(m) or (isinstance(m, (list, tuple)) and any(polygon.is_poly(v) for v in m)) for m in flat):
+        raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; polygon masks '
+                         'are taken in their source images\' frame, with spp_crop_to')
     if any(colormask.is_color(m) or (isinstance(m, (list, tuple)) and any(colormask.is_color(v) for v in m)) for m in flat):
         raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; box + colour '
                          'masks are made from the instances\' source images, with spp_crop_to')
@@ -1102,6 +1129,8 @@ class FGN(torch.nn.Module):
             for i, (g, hw) in enumerate(zip(qry_isegmaps, sizes)):
                 if colormask.is_color(g):                  # (a ``ColorMasks`` of ``_gt_entries`` passes by its shape)
                     g = colormask.as_color_masks(g, hw, f'qry_isegmaps[{i}]')
+                elif polygon.is_poly(g):                   # (a ``PolyMasks`` of ``_gt_entries`` passes by its shape)
+                    g = polygon.as_polys(g, hw, f'qry_isegmaps[{i}]')
                 elif rle.is_rle(g):                        # (an ``RleMasks`` of ``_gt_entries`` passes by its shape)
                     g = rle.as_masks(g, hw, f'qry_isegmaps[{i}]')
                 if len(g.shape) != 3 or (int(g.shape[1]), int(g.shape[2])) != hw:
@@ -1156,7 +1185,8 @@ class FGN(torch.nn.Module):
     def _gt_front(self, qry_isegmaps, qry_img, img_shape, qry_resize_to):
         """``_gt_entries`` with the sizes and images of this call."""
         if qry_isegmaps is None or not isinstance(qry_isegmaps, (list, tuple)) or \
-                not any(rle.is_rle(g) or colormask.is_color(g) for g in qry_isegmaps):
+                not any(rle.is_rle(g) or colormask.is_color(g) or polygon.is_poly(g) or isinstance(g, (list, tuple))
+                        for g in qry_isegmaps):
             return qry_isegmaps
         return _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to),
                            self._gt_images(qry_img, qry_resize_to))
@@ -1441,14 +1471,19 @@ class FGN(torch.nn.Module):
             raise ValueError(f'spp_bboxes: with spp_crop_to, [..,{NK},4] YXYX in the source frame for {B} support '
                              f'set(s), got {list(bb.shape)}')
         bb = bb.reshape(B * NK, 4)
-        recs, boxes, wins, mrle, mcol = [], [], [], [], []
+        recs, boxes, wins, mrle, mcol, mpoly = [], [], [], [], [], []
         for i, (im, mk) in enumerate((im, mk) for g in groups for im, mk in zip(*g)):
             im = _host(im)
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise ValueError(f'spp_imgs: with spp_crop_to every image is channels-last uint8 pixels [h,w,3], got '
                                  f'{im.dtype} {list(im.shape)}')
-            runs = col = None
-            if colormask.is_color(mk):                              # ONE mask as box + colour, in its image's frame
+            runs = col = poly = None
+            if polygon.is_poly(mk):                                 # ONE mask as COCO polygons, in its image's frame
+                poly = polygon.as_polys(mk, im.shape[:2], f'spp_isegmaps[{i}]', single=True)
+                if len(poly) != 1:
+                    raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(poly)}')
+                mk = np.zeros((0, 0), np.uint8)
+            elif colormask.is_color(mk):                              # ONE mask as box + colour, in its image's frame
                 col = colormask.as_color_masks(mk, im.shape[:2], f'spp_isegmaps[{i}]')
                 if len(col) != 1:
                     raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(col)}')
@@ -1468,6 +1503,9 @@ class FGN(torch.nn.Module):
             if runs is not None:        # no mask byte is uploaded: the window is decoded into its row (_upload_supports)
                 g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
                 mrle.append((i, runs, (g['wy'], g['wx'], g['wh'], g['ww'])))
+            if poly is not None:        # no mask byte is uploaded: the window is rasterised into its row (_upload_supports)
+                g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
+                mpoly.append((i, poly, (g['wy'], g['wx'], g['wh'], g['ww'])))
             if col is not None:         # no mask byte is uploaded: the mask is made from the image window in row i
                 g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
                 y0, x0, y1, x1 = (int(v) for v in col.boxes[0])
@@ -1492,9 +1530,9 @@ class FGN(torch.nn.Module):
                     boxes=torch.from_numpy(np.stack(boxes).reshape(B, NK, 4)),
                     flats=[torch.from_numpy(w.reshape(-1)) for w, _ in wins],
                     mflats=[torch.from_numpy(m.reshape(-1)) for _, m in wins], need=need, mneed=mneed,
-                    capacity=capacity, mcapacity=mcapacity, mrle=mrle, mcol=mcol,
+                    capacity=capacity, mcapacity=mcapacity, mrle=mrle, mcol=mcol, mpoly=mpoly,
                     window_bytes=int(sum(w.size + m.size for w, m in wins) + sum(r.ends.nbytes for _, r, _ in mrle) +
-                                     4 * ops.CM_REC_INTS * len(mcol)))
+                                     4 * ops.CM_REC_INTS * len(mcol) + sum(p.xy.nbytes for _, p, _ in mpoly)))
 
     @staticmethod
     def _slot_rows(flats: list, width: int, capacity: int, dev, slot: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1517,6 +1555,8 @@ class FGN(torch.nn.Module):
         msk = self._slot_rows(sp['mflats'], sp['mneed'], sp['mcapacity'], dev, into.get('spp_msk'))
         # an instance whose mask came as RLE uploaded no mask byte: its window is decoded straight into its row
         ops.rle_decode_rows(msk, sp.get('mrle') or [])
+        # ... and one that came as polygons is rasterised into its row (one upload, two launches for all)
+        ops.poly_mask_rows(msk, sp.get('mpoly') or [])
         src = self._slot_rows(sp['flats'], sp['need'], sp['capacity'], dev, into.get('spp_src'))
         if sp.get('mcol'):
             # ... and one that came as box + colour has its mask made from its image window, on this stream BEHIND the
@@ -1681,7 +1721,12 @@ class FGN(torch.nn.Module):
         with ``qry_resize_to``, else the network size), mixed freely with the other two forms; it needs the image as
         uint8 pixels (``set_input_norm``; a float image is refused), and with ``spp_crop_to`` every instance of
         ``spp_isegmaps`` may be one such item in its source image's frame.  The device makes the masks from the image
-        bytes it was sent anyway, on the stream that carried them and behind their copy; 16 ints per mask are uploaded."""
+        bytes it was sent anyway, on the stream that carried them and behind their copy; 16 ints per mask are uploaded.
+        Masks as COCO polygons: an entry of ``qry_isegmaps`` may be a ``polygon.PolyMasks`` or a dict
+        ``{'polygons': [instance, ...][, 'size': [h, w]]}``, every instance a list of parts ``[x0, y0, x1, y1, ...]`` as
+        COCO's ``segmentation`` holds them, in the same frame, mixed freely with the other forms - never a bare nested
+        list - and with ``spp_crop_to`` every instance of ``spp_isegmaps`` may be ``{'polygons': parts}``; the vertices
+        are checked on the host, uploaded as records and rasterised on the device into the bytes ``polygon.dense`` gives."""
         self._refuse_augment(qry_augment=qry_augment, qry_photometric=qry_photometric, spp_augment=spp_augment,
                              spp_photometric=spp_photometric, qry_photometric_chain=qry_photometric_chain,
                              spp_photometric_chain=spp_photometric_chain)
@@ -1870,6 +1915,8 @@ class FGN(torch.nn.Module):
         only their runs cross the bus."""
         if rle.is_rle(g):
             return ops.rle_decode_masks(rle.as_masks(g, what='qry_isegmaps'), device=dev)
+        if polygon.is_poly(g):                 # COCO polygons: rasterised there, only the vertices cross the bus
+            return ops.poly_masks(polygon.as_polys(g, None, 'qry_isegmaps'), device=dev)
         if colormask.is_color(g):              # (made beside the upload of its image: ``_color_on_device``)
             raise ValueError('qry_isegmaps: a box + colour entry is made into a mask from its image\'s bytes, where those '
                              'are uploaded; it cannot be moved to the device on its own')
@@ -1912,13 +1959,14 @@ class FGN(torch.nn.Module):
         source, spp_source = form.source, form.spp_source
         gts = None
         if gt_masks is not None:
-            gts = [g if isinstance(g, (torch.Tensor, colormask.ColorMasks)) or rle.is_rle(g) else
+            gts = [g if isinstance(g, (torch.Tensor, colormask.ColorMasks)) or rle.is_rle(g) or polygon.is_poly(g) else
                    torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
         colour = _has_color(gts)
         on_host = [t for t in list(tensors.values()) + (gts or []) + (source['flats'] if source else []) +
                    (spp_source['flats'] + spp_source['mflats'] if spp_source else [])
-                   if t is not None and (rle.is_rle(t) or isinstance(t, colormask.ColorMasks) or not t.is_cuda)]
-        # (runs, boxes and colours are host data)
+                   if t is not None and (rle.is_rle(t) or isinstance(t, colormask.ColorMasks) or polygon.is_poly(t) or
+                                         not t.is_cuda)]
+        # (runs, boxes, colours and vertices are host data)
         if not on_host and gts is None and source is None:
             return tensors, None, None
         up = self._stream_for('upload', main)
@@ -2477,6 +2525,8 @@ class FGN(torch.nn.Module):
         def host_mask(m):
             if colormask.is_color(m):           # box + colour: derived on the host from the image it is bound to, here only
                 m = colormask.as_color_masks(m, None, 'qry_isegmaps').dense()
+            elif polygon.is_poly(m):            # COCO polygons: rasterised on the host, here only
+                m = polygon.as_polys(m, None, 'qry_isegmaps').dense()
             elif rle.is_rle(m):                 # masks given as COCO RLE: decoded on the host, here only
                 m = rle.as_masks(m, what='qry_isegmaps').dense()
             m = np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m)

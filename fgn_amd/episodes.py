@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import colormask, rle
+from . import colormask, polygon, rle
 
 
 def _ellipse_mask(h, w, y0, x0, y1, x1):
@@ -24,11 +24,31 @@ def _ellipse_mask(h, w, y0, x0, y1, x1):
     return (((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2) <= 1.0
 
 
+def star_polygon(rng, y0, x0, y1, x1, k=None) -> list:
+    """One star-shaped polygon inside the box, as COCO holds a part: flat [x0, y0, x1, y1, ...] of k (default 5..12)
+    vertices at sorted angles, radii 0.45..1 of the box's half sides, coordinates rounded to 0.01 as in the annotation
+    files."""
+    k = int(rng.randint(5, 13)) if k is None else int(k)
+    ang = np.sort(rng.uniform(0.0, 2.0 * np.pi, k))
+    rad = rng.uniform(0.45, 1.0, k)
+    cy, cx = (y0 + y1) / 2.0, (x0 + x1) / 2.0
+    x = cx + rad * (x1 - x0) / 2.0 * np.cos(ang)
+    y = cy + rad * (y1 - y0) / 2.0 * np.sin(ang)
+    return np.round(np.stack([x, y], 1), 2).reshape(-1).tolist()
+
+
 def make_episode(idx: int, n_ways: int, k_shots: int, height: int, width: int,
                  spp_size: int, n_qry_objs: int = 4, seed: int = 1234,
-                 spp_fill_ratio: float = 0.8) -> dict:
-    """One sample dict (un-collated) for episode ``idx``."""
+                 spp_fill_ratio: float = 0.8, polygons=None) -> dict:
+    """One sample dict (un-collated) for episode ``idx``.  ``polygons``: the query instances are star polygons in their
+    boxes instead of ellipses (``star_polygon``, from a generator of its own: boxes, classes and supports are those of the
+    default episode) and their ground truth is ``polygon.dense`` of those vertices - handed over dense (``'dense'``) or
+    as the polygons themselves, ``{'polygons': [...], 'size': [h, w]}`` (``'poly'``), so both forms state one truth."""
+    if polygons not in (None, 'dense', 'poly'):
+        raise ValueError(f"polygons must be None, 'dense' or 'poly', got {polygons!r}")
     rng = np.random.RandomState(seed + idx)
+    prng = np.random.RandomState(seed + idx + 7919)
+    polys = []
     g = torch.Generator().manual_seed(seed + idx)
     qry = torch.randn(3, height, width, generator=g)
     class_tint = rng.randn(n_ways, 3).astype(np.float32)
@@ -40,7 +60,11 @@ def make_episode(idx: int, n_ways: int, k_shots: int, height: int, width: int,
         y0 = rng.randint(0, height - bh)
         x0 = rng.randint(0, width - bw)
         c = int(rng.randint(0, n_ways))
-        m = _ellipse_mask(height, width, y0, x0, y0 + bh, x0 + bw)
+        if polygons is None:
+            m = _ellipse_mask(height, width, y0, x0, y0 + bh, x0 + bw)
+        else:
+            polys.append([star_polygon(prng, y0, x0, y0 + bh, x0 + bw)])
+            m = polygon.dense(polys[-1], height, width).astype(bool)
         qry += torch.from_numpy(m.astype(np.float32))[None] * \
             torch.from_numpy(class_tint[c])[:, None, None] * 1.5
         bboxes.append([y0, x0, y0 + bh, x0 + bw])
@@ -70,8 +94,8 @@ def make_episode(idx: int, n_ways: int, k_shots: int, height: int, width: int,
         'qry_img': qry,
         'qry_cat_ids': np.asarray(cat_ids, np.int64),
         'qry_bboxes': np.asarray(bboxes, np.float32).reshape(-1, 4),
-        'qry_isegmaps': np.stack(masks).astype(bool) if masks else
-        np.zeros((0, height, width), bool),
+        'qry_isegmaps': {'polygons': polys, 'size': [height, width]} if polygons == 'poly' else
+        np.stack(masks).astype(bool) if masks else np.zeros((0, height, width), bool),
         'spp_imgs': spp,
         'spp_bboxes': spp_boxes,
         'spp_isegmaps': spp_masks,
@@ -103,8 +127,8 @@ def collate(samples: list) -> dict:
             batch[key] = vals[0]
             continue
         if isinstance(vals[0], list):
-            batch[key] = [[v if rle.is_item(v) or colormask.is_color(v) else torch.as_tensor(v) for v in lst]
-                          for lst in vals]                 # (RLE, box + colour: as it is)
+            batch[key] = [[v if rle.is_item(v) or colormask.is_color(v) or polygon.is_poly(v) else torch.as_tensor(v) for v in lst]
+                          for lst in vals]                 # (RLE, box + colour, polygons: as it is)
             continue
         if isinstance(vals[0], torch.Tensor):
             batch[key] = torch.stack(vals)
@@ -112,9 +136,10 @@ def collate(samples: list) -> dict:
             batch[key] = torch.as_tensor(np.stack([np.asarray(v) for v in vals]))
     for key in _LIST_KEYS:                       # ... then the ragged keys as lists of tensors, in the reference's order
         if key in samples[0]:
-            batch[key] = [s[key] if key == 'qry_isegmaps' and (rle.is_rle(s[key]) or colormask.is_color(s[key])) else
+            batch[key] = [s[key] if key == 'qry_isegmaps' and (rle.is_rle(s[key]) or colormask.is_color(s[key]) or
+                                                               polygon.is_poly(s[key])) else
                           torch.as_tensor(s[key]) for s in samples]
-            # (masks given as COCO RLE or as box + colour stay what they are)
+            # (masks given as COCO RLE, as box + colour or as polygons stay what they are)
     return batch
 
 

@@ -1161,7 +1161,10 @@ def draw_support_augment(rng):
 
 class SyntheticFewShotISEG(Dataset):
     def __init__(self, n_ways=3, k_shots=3, length=64, height=800, width=1333, spp_img_size=256, batch=4,
-                 seed=1234, suffix='SYNTH_val_novel'):
+                 seed=1234, suffix='SYNTH_val_novel', polygons=None):
+        # ``polygons`` (``episodes.make_episode``): None - ellipses, dense masks, as ever; 'dense' / 'poly' - polygonal
+        # instances whose masks travel dense or as COCO polygons
+        self.polygons = polygons
         self.n_ways, self.k_shots = n_ways, k_shots
         self.length, self.batch = length, batch
         self.height, self.width, self.spp_img_size = height, width, spp_img_size
@@ -1176,7 +1179,7 @@ class SyntheticFewShotISEG(Dataset):
 
     def __getitem__(self, idx):
         return episodes.make_episode(int(idx), self.n_ways, self.k_shots, self.height, self.width,
-                                     self.spp_img_size, seed=self.seed)
+                                     self.spp_img_size, seed=self.seed, polygons=self.polygons)
 
     def reshuffle(self):
         self.seed += self.length

@@ -93,6 +93,7 @@ SIGNATURES = {
     'fgn_dense_mask_rle': (_i, [_p, _p, C.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     'fgn_rle_decode_u8': (_i, [_p, C.c_longlong, _p, _p, C.c_longlong, _i, _i, _i, _p]),
     'fgn_color_mask_u8': (_i, [_p, C.c_longlong, C.c_longlong, _i, _p, _i, _p, C.c_longlong, _i, _i, _i, _p]),
+    'fgn_poly_masks_u8': (_i, [_p, C.c_longlong, _i, _i, _i, _p, C.c_longlong, _p, C.c_longlong, _i, _i, _p]),
     'fgn_mask_bits_u64': (_i, [_p, _p, _p, _i, _i, _i, _p]),
     'fgn_mask_overlap_i32': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
     'fgn_mask_overlap_src_i32': (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),

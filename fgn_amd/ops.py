@@ -1955,6 +1955,113 @@ def color_mask_rows(src_slot: torch.Tensor, msk_slot: torch.Tensor, items: list)
     return msk_slot
 
 
+POLY_REC_INTS = 8            # csrc/poly.hip: mask {h, w, wy, wx, wh, ww, part0, n_parts}, part {edge0, n_edges, points,
+#                              ends0, cap, h, w, 0}, edge {xs, ys, steps, major | flip << 1, s lo, s hi, first, 0}
+
+
+def _poly_launch(entries: list, n_out: int, out: torch.Tensor, stride: int, max_wh: int, max_ww: int) -> int:
+    """ONE upload - [mask records | part records | edge records], int32, 8 per record - and ONE call of
+    ``fgn_poly_masks_u8`` (two launches) into ``out`` (output i at byte i * stride), on the current stream.  ``entries``
+    = (output index, (h, w), (wy, wx, wh, ww), the instance's parts) each; an output without an entry keeps an all-zero
+    record, whose empty window writes nothing.  -> the bytes uploaded."""
+    from . import polygon
+    recs = np.zeros((n_out, POLY_REC_INTS), np.int32)
+    parts, edges, n_edges, ends0 = [], [], 0, 0
+    for i, (h, w), window, inst in entries:
+        recs[i] = (h, w) + tuple(window) + (len(parts), len(inst))
+        for xy in inst:
+            e, points, cap = polygon.edge_records(xy)
+            if cap > polygon.CROSSING_CAP or points > polygon.POINT_CAP:
+                raise _lib.FgnHipError(f'poly_masks: a part of {points} points / up to {cap} crossings exceeds what the '
+                                       f'device takes; such an instance goes the host route')
+            parts.append((n_edges, len(e), points, ends0, cap, h, w, 0))
+            edges.append(e)
+            n_edges += len(e)
+            ends0 += cap
+    tables = [recs.reshape(-1), np.asarray(parts, np.int32).reshape(-1)] + [e.reshape(-1) for e in edges]
+    blob = torch.from_numpy(np.concatenate(tables).astype(np.int32, copy=False)).to(out.device, non_blocking=True)
+    scratch = torch.empty(max(ends0, 1), device=out.device, dtype=torch.int32)
+    _lib.check(_lib.load().fgn_poly_masks_u8(_ptr(blob), int(blob.numel()), int(n_out), len(parts), int(n_edges),
+                                             _ptr(scratch), int(scratch.numel()), _ptr(out), int(stride), int(max_wh),
+                                             int(max_ww), _stream()), 'fgn_poly_masks_u8')
+    return int(blob.numel()) * 4
+
+
+def poly_masks(pm, window=None, out: Optional[torch.Tensor] = None, device=None,
+               routes: Optional[list] = None) -> torch.Tensor:
+    """The n masks of a ``polygon.PolyMasks`` (what ``polygon.as_polys`` makes of COCO polygons) -> dense uint8 0/1
+    [n,h,w] on the device, or [n,wh,ww] for one ``window`` = (wy, wx, wh, ww) of every mask: ``polygon.dense`` bit for
+    bit, i.e. the bytes a dense upload would have put there (maskUtils.frPyObjects + merge + decode, moved behind the
+    bus).  One upload of the records, two launches (crossings, fill); only vertices cross the bus.  The route is decided
+    on the host before anything is queued (``PolyMasks.on_host``): an instance with a part over the device's capacity
+    travels as ``polygon.to_rle`` through ``rle_decode_masks`` instead.  ``routes``: a list that receives 'device' or
+    'host' per instance.  ``out``: a contiguous uint8 tensor of that shape to write; else a fresh one on ``device``
+    (default: the current GPU).  An entry without masks launches nothing."""
+    from . import rle
+    n = int(pm.shape[0])
+    wy, wx, wh, ww = _rle_window(pm, window)
+    if out is None:
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        out = torch.empty((n, wh, ww), device=dev, dtype=torch.uint8)
+    else:
+        _chk(out, 'out', torch.uint8)
+        if tuple(out.shape) != (n, wh, ww):
+            raise _lib.FgnHipError(f'poly_masks: out is {tuple(out.shape)}, expected {(n, wh, ww)}')
+    host = pm.on_host()
+    if routes is not None:
+        routes.extend('host' if v else 'device' for v in host)
+    if n == 0:
+        return out
+    hw = (int(pm.shape[1]), int(pm.shape[2]))
+    entries = [(i, hw, (wy, wx, wh, ww), pm.parts(i)) for i in range(n) if not host[i]]
+    if entries:
+        _poly_launch(entries, n, out, wh * ww, wh, ww)
+    idx = np.flatnonzero(host)
+    if idx.size:
+        runs = rle.as_masks(pm.rle_items(idx), hw, 'poly_masks')
+        if idx.size == n:
+            rle_decode_masks(runs, window, out=out)
+        else:
+            out[torch.from_numpy(idx).to(out.device)] = rle_decode_masks(runs, window, device=out.device)
+    return out
+
+
+def poly_mask_rows(slot: torch.Tensor, items: list, routes: Optional[list] = None) -> torch.Tensor:
+    """``poly_masks`` into rows of an existing slot (the support path: ``spp_msk``, the static slot of a captured graph
+    included): ``slot`` uint8 [rows, capacity], contiguous; ``items`` = (row, PolyMasks of ONE mask, window) each: the
+    window's wh * ww bytes go to the front of that row - the layout ``rle_decode_rows`` writes -, what lies behind them
+    and every other row stays as it is.  One upload, two launches for all items of the device route; those of the host
+    route go through ``rle_decode_rows``; none, no launch.  ``routes`` as for ``poly_masks``, per item."""
+    from . import rle
+    _chk(slot, 'slot', torch.uint8)
+    if slot.dim() != 2:
+        raise _lib.FgnHipError('poly_mask_rows: slot must be [rows, capacity]')
+    rows, cap = slot.shape
+    if not items:
+        return slot
+    entries, on_host, seen, max_wh, max_ww = [], [], set(), 0, 0
+    for row, m, window in items:
+        if not 0 <= int(row) < rows or int(m.shape[0]) != 1 or int(row) in seen:
+            raise _lib.FgnHipError(f'poly_mask_rows: row {row} of {rows}: one mask per item, one item per row')
+        seen.add(int(row))
+        wy, wx, wh, ww = _rle_window(m, window)
+        if wh * ww > cap:
+            raise _lib.FgnHipError(f'poly_mask_rows: a window of {wh * ww} bytes exceeds the slot capacity {cap}')
+        hw = (int(m.shape[1]), int(m.shape[2]))
+        host = bool(m.on_host()[0])
+        if routes is not None:
+            routes.append('host' if host else 'device')
+        if host:
+            on_host.append((int(row), rle.as_masks(m.rle_items([0]), hw, 'poly_mask_rows'), (wy, wx, wh, ww)))
+        else:
+            entries.append((int(row), hw, (wy, wx, wh, ww), m.parts(0)))
+            max_wh, max_ww = max(max_wh, wh), max(max_ww, ww)
+    if entries:
+        _poly_launch(entries, rows, slot, cap, max_wh, max_ww)
+    rle_decode_rows(slot, on_host)
+    return slot
+
+
 def mask_bits(masks: torch.Tensor):
     """Bit planes of dense binary masks [G,H,W] (bool / uint8, non-zero = set), the ground-truth operand of
     ``mask_overlap``: returns (bits int64 [H, ceil(W/64), G] - bit b of word xw of a row = pixel 64 xw + b - ,

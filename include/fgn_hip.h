@@ -571,6 +571,42 @@ int fgn_color_mask_u8(const unsigned char* src, long long src_stride_bytes, long
                       const int32_t* recs, int n, unsigned char* out, long long out_stride_bytes, int n_out, int max_h,
                       int max_w, void* stream);
 
+/* COCO polygons as an INPUT, rasterised on the device (fgn_amd/polygon.py states the rule: pycocotools' rleFrPoly and
+ * merge, which the reference runs once at dataset build, coco_ds.py:246-263).  n masks, or windows of them, from ONE
+ * blob in TWO launches; output i is exactly the bytes a dense upload of that window would hold.
+ *   blob int32, read ON THE DEVICE, three tables of 8 ints per record, back to back:
+ *        masks [n]       {h, w, wy, wx, wh, ww, part0, n_parts}: the mask size, the window of it to produce (rows
+ *                        [wy, wy + wh), columns [wx, wx + ww)) and its parts [part0, part0 + n_parts), ORed
+ *        parts [n_parts] {edge0, n_edges, points, ends0, cap, h, w, 0}: its edges [edge0, edge0 + n_edges), the length
+ *                        of its path, its slice scratch[ends0, ends0 + cap) with cap a power of two within 1..8192 that
+ *                        is at least the number of positions the part toggles, and the size of its mask
+ *        edges [n_edges] {xs, ys, steps, major | flip << 1, s lo, s hi, first, 0}: on the 5x grid, the start after the
+ *                        flip, max(dx, dy), whether x is the major axis, whether the edge is walked from its far end,
+ *                        the slope as the two halves of a double, and the index of its first point in its part's path
+ *        blob_ints >= 8 * (n + n_parts + n_edges) ints can be read.
+ *   scratch uint32 [scratch_len]: every part's sorted positions, padded with 0xFFFFFFFF to cap; written by the first
+ *        launch, read by the second; its contents before the call do not matter
+ *   out  output i is [wh][ww] bytes, each 0 or 1, row-major, at out + i * out_stride_bytes; no alignment is assumed, and
+ *        the bytes behind the window in its row of the slot are not written
+ * Point d of an edge is t = flip ? steps - d : d, (major + t, (int)(minor + s * t + .5)) - a product rounded, then two
+ * sums rounded, never an fma.  Where u changes between neighbours of the path, m = u[j] < u[j-1] ? u[j] : u[j] - 1 toggles
+ * position cx * h + cy, cx = (m - 2) / 5, cy = clamp(floor((min(v[j], v[j-1]) + 2) / 5), 0, h), iff m >= 2, m % 5 == 2
+ * and cx <= w - 1.  Pixel (y, x) of a part is set where an odd number of its positions are <= x * h + y.
+ * The kernels are safe for ANY contents of the blob: every index they form lies inside the blob's tables, a part's
+ * slice or a mask's window; edge contents give garbage bits at worst.  A part is out of range when its edges leave
+ * [0, n_edges), points is outside 1..2^20, cap is no power of two within 1..8192, its slice leaves the scratch or a
+ * size is outside 1..16384: it writes nothing and no mask reads it (nor one whose size differs from the mask's).  A mask
+ * is out of range when a size is outside 1..16384, the window is empty or leaves the mask, wh > max_wh or ww > max_ww,
+ * wh * ww > out_stride_bytes, n_parts < 1 or its parts leave [0, n_parts): its window is written as zeros where
+ * wh >= 1, ww >= 1 and wh * ww <= out_stride_bytes, and not at all otherwise.
+ * Negative counts, lengths or stride, max_wh / max_ww above 16384, scratch_len >= 2^31, a blob shorter than its three
+ * tables, or n * ceil(max_ww / 256) >= 2^24 (the grid) is FGN_ERR_SHAPE; n == 0 or an empty maximum window FGN_OK with
+ * no launch (pointers are not looked at); a null blob or out, or a null scratch with n_parts > 0, FGN_ERR_ARG.  No
+ * allocation, no synchronisation, no environment variable. */
+int fgn_poly_masks_u8(const int32_t* blob, long long blob_ints, int n, int n_parts, int n_edges, uint32_t* scratch,
+                      long long scratch_len, unsigned char* out, long long out_stride_bytes, int max_wh, int max_ww,
+                      void* stream);
+
 /* Matching on the device: the exact pixel counts the evaluator needs from the masks, so that no RLE is decoded on the
  * host.  Step 1, bit planes of the ground-truth masks: masks [n][H][W] bytes (non-zero = set) -> bits, one 64-bit word
  * per 64 consecutive x of a row (bit b of word xw = pixel x = 64 xw + b; bits of x >= W are zero), laid out
