@@ -17,6 +17,7 @@ import numpy as np
 from . import cluttered_chars as cc
 
 MAX_DIM = 16384          # ops.RESIZE_MAX_DIM (this module stays free of torch)
+REC_BYTES = 64           # 4 * ops.CM_REC_INTS: the record that crosses the bus per mask
 DEFAULT_SHIFT = 75       # create_img_from_chars.py:136: get_char_mask_by_color(..., shift=75)
 _KEYS = ({'bboxes', 'colors'}, {'bboxes', 'colors', 'shift'})
 
@@ -42,6 +43,15 @@ class ColorMasks:
         """(lo, hi) int32 [n,3]: the inclusive colour window, ``max(c - shift, 0)`` .. ``min(c + shift, 255)``."""
         c = self.colors.astype(np.int32)
         return np.maximum(c - self.shift, 0), np.minimum(c + self.shift, 255)
+
+    def in_window(self, wy: int, wx: int, wh: int, ww: int, what: str = 'masks', reader: str = 'the crop'):
+        """This ONE mask moved into the frame of the window (wy, wx, wh, ww) of its image, which ``reader`` reads; the
+        window must hold the whole box - and with it every pixel the mask is made from."""
+        y0, x0, y1, x1 = (int(v) for v in self.boxes[0])
+        if not (wy <= y0 and y1 <= wy + wh and wx <= x0 and x1 <= wx + ww):
+            raise ValueError(f'{what}: the box {[y0, x0, y1, x1]} of the colour item leaves the window '
+                             f'{[wy, wx, wy + wh, wx + ww]} that {reader} reads: give the instance\'s own box')
+        return ColorMasks(self.boxes - np.array([wy, wx] * 2, np.int32), self.colors, (wh, ww), self.shift)
 
     def dense(self, img=None) -> np.ndarray:
         """Host masks: bool [n,h,w] by ``cluttered_chars.char_mask_by_color`` on ``img`` (uint8 [h,w,3]; default: the

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import config as _config
-from . import colormask, ops, polygon, rle
+from . import maskforms, ops, rle
 from .weights import backbone_state_from_pretrained, init_state_dict
 
 
@@ -431,38 +431,31 @@ def _host(v) -> np.ndarray:
 
 
 def _gt_entries(qry_isegmaps, sizes, imgs=None):
-    """``qry_isegmaps`` normalised once at the front (host only, nothing is queued): an entry given as COCO RLE
-    (``rle.as_masks``: a list of dicts or ``[size, counts]`` pairs, an ``RleMasks``, the empty list) becomes a checked
-    ``RleMasks`` at ``sizes[i]`` = (h, w) - a size that disagrees is a ValueError -, a dense entry stays as it is.
-    An entry given as box + colour (``colormask.as_color_masks``: a ``ColorMasks`` or a dict of ``bboxes`` and
-    ``colors``) becomes a checked ``ColorMasks`` at ``sizes[i]``, bound to ``imgs[i]`` - the image's bytes [h,w,3] as
-    they were handed over, which is what its mask is made from; ``imgs`` is None where the images are not bytes (float
-    input), and a colour entry is refused then.  An entry given as COCO polygons (``polygon.as_polys``: a ``PolyMasks``
-    or a dict ``{'polygons': [...][, 'size']}``) becomes a checked ``PolyMasks`` at ``sizes[i]``; a bare nested list is
-    never polygons - it reads as a dense mask, and one that is no [n,h,w] array of numbers is refused here.  Without an
-    RLE, colour or polygon entry the argument itself comes back."""
+    """``qry_isegmaps`` normalised once at the front (host only, nothing is queued): an entry in a compact form
+    (``maskforms``: COCO RLE - the empty list included -, box + colour, COCO polygons) becomes its checked carrier at
+    ``sizes[i]`` = (h, w) - a size that disagrees is a ValueError -, a dense entry stays as it is.  A colour carrier is
+    bound to ``imgs[i]`` - the image's bytes [h,w,3] as they were handed over, which is what its mask is made from;
+    ``imgs`` is None where the images are not bytes (float input), and a colour entry is refused then.  A bare nested
+    list is never polygons - it reads as a dense mask, and one that is no [n,h,w] array of numbers is refused here.
+    Without a compact entry the argument itself comes back."""
     if qry_isegmaps is None or not isinstance(qry_isegmaps, (list, tuple)):
         return qry_isegmaps
+    forms = [maskforms.form_of(g) for g in qry_isegmaps]
     for i, g in enumerate(qry_isegmaps):
-        if isinstance(g, (list, tuple)) and not rle.is_rle(g):
+        if isinstance(g, (list, tuple)) and forms[i] is None:
             _dense_lists(g, f'qry_isegmaps[{i}]', sizes[i] if sizes is not None and i < len(sizes) else None)
-    if not any(rle.is_rle(g) or colormask.is_color(g) or polygon.is_poly(g) for g in qry_isegmaps):
+    if all(f is None for f in forms):
         return qry_isegmaps
     if sizes is not None and len(sizes) != len(qry_isegmaps):
         raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {len(sizes)} images')
     out = []
-    for i, g in enumerate(qry_isegmaps):
-        if colormask.is_color(g):
-            if imgs is None:
-                raise ValueError(f'qry_isegmaps[{i}]: a box + colour entry is made into a mask from the image\'s bytes on '
-                                 f'the device: give qry_img as uint8 pixels (set_input_norm, with or without '
-                                 f'qry_resize_to), not as a normalised float tensor')
-            g = colormask.as_color_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]', img=imgs[i])
-        elif polygon.is_poly(g):
-            g = polygon.as_polys(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]')
-        elif rle.is_rle(g):
-            g = rle.as_masks(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]')
-        out.append(g)
+    for i, (g, form) in enumerate(zip(qry_isegmaps, forms)):
+        if form is maskforms.COLOR and imgs is None:
+            raise ValueError(f'qry_isegmaps[{i}]: a box + colour entry is made into a mask from the image\'s bytes on '
+                             f'the device: give qry_img as uint8 pixels (set_input_norm, with or without '
+                             f'qry_resize_to), not as a normalised float tensor')
+        out.append(g if form is None else form.check(g, None if sizes is None else sizes[i], f'qry_isegmaps[{i}]',
+                                                     imgs[i] if form is maskforms.COLOR else None))
     return out
 
 
@@ -482,7 +475,7 @@ def _dense_lists(g, what: str, hw=None) -> None:
 
 
 def _has_color(entries) -> bool:
-    return isinstance(entries, (list, tuple)) and any(isinstance(g, colormask.ColorMasks) for g in entries)
+    return isinstance(entries, (list, tuple)) and any(maskforms.form_of(g) is maskforms.COLOR for g in entries)
 
 
 def _dense_supports_only(spp_isegmaps) -> None:
@@ -490,13 +483,14 @@ def _dense_supports_only(spp_isegmaps) -> None:
     padded there, and no dataset holds such masks as runs - nor is there a source image to derive a box + colour mask
     from."""
     flat = spp_isegmaps if isinstance(spp_isegmaps, (list, tuple)) else [spp_isegmaps]
-    if any(polygon.is_poly(m) or (isinstance(m, (list, tuple)) and any(polygon.is_poly(v) for v in m)) for m in flat):
+    found = {maskforms.form_of_one(v) for m in flat for v in ([m, *m] if isinstance(m, (list, tuple)) else [m])}
+    if maskforms.POLY in found:
         raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; polygon masks '
                          'are taken in their source images\' frame, with spp_crop_to')
-    if any(colormask.is_color(m) or (isinstance(m, (list, tuple)) and any(colormask.is_color(v) for v in m)) for m in flat):
+    if maskforms.COLOR in found:
         raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; box + colour '
                          'masks are made from the instances\' source images, with spp_crop_to')
-    if isinstance(spp_isegmaps, (list, tuple, dict, rle.RleMasks)):
+    if isinstance(spp_isegmaps, (list, tuple, dict, maskforms.RLE.carrier)):
         raise ValueError('spp_isegmaps: without spp_crop_to the supports are the dense [B,N*K,S,S] tensor; RLE masks '
                          'are taken at source size, with spp_crop_to')
 
@@ -1127,12 +1121,7 @@ class FGN(torch.nn.Module):
             if len(qry_isegmaps) != B:
                 raise ValueError(f'qry_isegmaps has {len(qry_isegmaps)} entries for {B} images')
             for i, (g, hw) in enumerate(zip(qry_isegmaps, sizes)):
-                if colormask.is_color(g):                  # (a ``ColorMasks`` of ``_gt_entries`` passes by its shape)
-                    g = colormask.as_color_masks(g, hw, f'qry_isegmaps[{i}]')
-                elif polygon.is_poly(g):                   # (a ``PolyMasks`` of ``_gt_entries`` passes by its shape)
-                    g = polygon.as_polys(g, hw, f'qry_isegmaps[{i}]')
-                elif rle.is_rle(g):                        # (an ``RleMasks`` of ``_gt_entries`` passes by its shape)
-                    g = rle.as_masks(g, hw, f'qry_isegmaps[{i}]')
+                g = maskforms.checked(g, hw, f'qry_isegmaps[{i}]')     # (a carrier of ``_gt_entries`` passes by its shape)
                 if len(g.shape) != 3 or (int(g.shape[1]), int(g.shape[2])) != hw:
                     raise ValueError(f'qry_isegmaps: with qry_resize_to the masks are at source size {hw}, got '
                                      f'{list(g.shape)}')
@@ -1185,8 +1174,7 @@ class FGN(torch.nn.Module):
     def _gt_front(self, qry_isegmaps, qry_img, img_shape, qry_resize_to):
         """``_gt_entries`` with the sizes and images of this call."""
         if qry_isegmaps is None or not isinstance(qry_isegmaps, (list, tuple)) or \
-                not any(rle.is_rle(g) or colormask.is_color(g) or polygon.is_poly(g) or isinstance(g, (list, tuple))
-                        for g in qry_isegmaps):
+                not any(isinstance(g, (list, tuple)) or maskforms.form_of(g) is not None for g in qry_isegmaps):
             return qry_isegmaps
         return _gt_entries(qry_isegmaps, self._gt_sizes(qry_img, img_shape, qry_resize_to),
                            self._gt_images(qry_img, qry_resize_to))
@@ -1197,11 +1185,11 @@ class FGN(torch.nn.Module):
         [n_b,h_b,w_b] on the device from ``slot`` - uint8 [B, bytes], image b as [h_b,w_b,3] at the front of row b, AS
         UPLOADED - in ONE launch on the current stream, which is the stream that carried those bytes up (DESIGN
         4.4.11); every other entry stays as it is.  Without a colour entry nothing is called."""
-        items = [(b, g) for b, g in enumerate(entries or ()) if isinstance(g, colormask.ColorMasks)]
-        if not items:
+        colour = [maskforms.form_of(g) is maskforms.COLOR for g in entries or ()]
+        if not any(colour):
             return entries
-        made = iter(ops.color_masks(slot, items))
-        return [next(made) if isinstance(g, colormask.ColorMasks) else g for g in entries]
+        made = iter(ops.color_masks(slot, [(b, g) for b, g in enumerate(entries) if colour[b]]))
+        return [next(made) if c else g for g, c in zip(entries, colour)]
 
     @staticmethod
     def _augment_plans(qry_augment, qry_bboxes, rs: dict) -> tuple:
@@ -1440,12 +1428,10 @@ class FGN(torch.nn.Module):
         (``fewshot_ds.support_geometry``), and every window fits the slot.  -> B, n = B*N*K, S, the records int32 [n,16],
         the boxes in the S x S supports float32 (``support_from_instance``'s, computed here on the host) [B,N*K,4], the
         image and mask windows as flat byte tensors, the largest of each and the slot sizes in bytes per instance.  A mask
-        may be ONE COCO RLE item (``rle.as_masks``: dict or ``[size, counts]`` pair) at its image's size: the geometry is
-        the same, its entry of ``mflats`` is empty - no mask byte is uploaded - and ``mrle`` lists (row, ``RleMasks``,
-        window) for ``_upload_supports``; ``window_bytes`` counts the bytes of its run ends instead.  Or ONE box + colour
-        item (``colormask.as_color_masks``) in its image's frame: likewise no mask byte, ``mcol`` lists (row, the item
-        moved into the window's frame) - the window holds the item's whole box, which is checked here - and
-        ``window_bytes`` counts its record."""
+        may be ONE mask in a compact form (``maskforms.checked_one``) in its image's frame: the geometry is the same, its
+        entry of ``mflats`` is empty - no mask byte is uploaded -, ``mrle`` / ``mpoly`` list (row, carrier, window) and
+        ``mcol`` lists (row, the colour item moved into the window's frame, which must hold its whole box) for
+        ``_upload_supports``, and ``window_bytes`` counts what crosses the bus instead (``Form.nbytes``)."""
         from . import fewshot_ds as fd
         if isinstance(spp_crop_to, bool) or not isinstance(spp_crop_to, (int, np.integer)) or \
                 not 1 <= int(spp_crop_to) <= ops.RESIZE_MAX_DIM:
@@ -1456,7 +1442,7 @@ class FGN(torch.nn.Module):
             raise ValueError('spp_crop_to needs the normalisation table: call set_input_norm first')
         NK = self.n_ways * self.k_shots
         nested = lambda v: isinstance(v, (list, tuple)) and len(v) > 0 and isinstance(v[0], (list, tuple)) and \
-            not rle.is_item(v[0])                          # (a ``[size, counts]`` pair is one mask, not a support set)
+            not maskforms.is_pair(v[0])                    # (a ``[size, counts]`` pair is one mask, not a support set)
         if not isinstance(spp_imgs, (list, tuple)) or not isinstance(spp_isegmaps, (list, tuple)):
             raise ValueError('spp_imgs / spp_isegmaps: with spp_crop_to, lists of N*K source images [h,w,3] and masks '
                              '[h,w] (or B such lists)')
@@ -1471,27 +1457,15 @@ class FGN(torch.nn.Module):
             raise ValueError(f'spp_bboxes: with spp_crop_to, [..,{NK},4] YXYX in the source frame for {B} support '
                              f'set(s), got {list(bb.shape)}')
         bb = bb.reshape(B * NK, 4)
-        recs, boxes, wins, mrle, mcol, mpoly = [], [], [], [], [], []
+        recs, boxes, wins, compact = [], [], [], {f: [] for f in maskforms.FORMS}
         for i, (im, mk) in enumerate((im, mk) for g in groups for im, mk in zip(*g)):
             im = _host(im)
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
                 raise ValueError(f'spp_imgs: with spp_crop_to every image is channels-last uint8 pixels [h,w,3], got '
                                  f'{im.dtype} {list(im.shape)}')
-            runs = col = poly = None
-            if polygon.is_poly(mk):                                 # ONE mask as COCO polygons, in its image's frame
-                poly = polygon.as_polys(mk, im.shape[:2], f'spp_isegmaps[{i}]', single=True)
-                if len(poly) != 1:
-                    raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(poly)}')
-                mk = np.zeros((0, 0), np.uint8)
-            elif colormask.is_color(mk):                              # ONE mask as box + colour, in its image's frame
-                col = colormask.as_color_masks(mk, im.shape[:2], f'spp_isegmaps[{i}]')
-                if len(col) != 1:
-                    raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(col)}')
-                mk = np.zeros((0, 0), np.uint8)
-            elif rle.is_item(mk) or isinstance(mk, rle.RleMasks):   # ONE mask as COCO RLE, at its image's size
-                runs = rle.as_masks(mk if isinstance(mk, rle.RleMasks) else [mk], im.shape[:2], f'spp_isegmaps[{i}]')
-                if len(runs) != 1:
-                    raise ValueError(f'spp_isegmaps[{i}]: one mask per support instance, got {len(runs)}')
+            form = maskforms.form_of_one(mk)
+            if form is not None:        # ONE mask in a compact form, in its image's frame: no mask byte is uploaded
+                one = maskforms.checked_one(mk, im.shape[:2], f'spp_isegmaps[{i}]')
                 mk = np.zeros((0, 0), np.uint8)
             else:
                 mk = _host(mk)
@@ -1500,23 +1474,13 @@ class FGN(torch.nn.Module):
                                      f'{list(im.shape[:2])}, got {list(mk.shape)}')
             rec, box = fd.support_geometry(im.shape[0], im.shape[1], bb[i], S, spp_fill_ratio, crop_square)
             recs.append(rec); boxes.append(box); wins.append(fd.support_window(im, mk, rec))
-            if runs is not None:        # no mask byte is uploaded: the window is decoded into its row (_upload_supports)
+            if form is not None:        # its window is decoded, rasterised or made into row i (_upload_supports)
                 g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
-                mrle.append((i, runs, (g['wy'], g['wx'], g['wh'], g['ww'])))
-            if poly is not None:        # no mask byte is uploaded: the window is rasterised into its row (_upload_supports)
-                g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
-                mpoly.append((i, poly, (g['wy'], g['wx'], g['wh'], g['ww'])))
-            if col is not None:         # no mask byte is uploaded: the mask is made from the image window in row i
-                g = dict(zip(fd.SPP_REC_FIELDS, (int(v) for v in rec)))
-                y0, x0, y1, x1 = (int(v) for v in col.boxes[0])
-                # (``support_geometry``: the crop reads the rows and columns of the instance's box unreflected, so the
-                # window holds the whole box - and with it every pixel the mask is made from)
-                if not (g['wy'] <= y0 and y1 <= g['wy'] + g['wh'] and g['wx'] <= x0 and x1 <= g['wx'] + g['ww']):
-                    raise ValueError(f'spp_isegmaps[{i}]: the box {[y0, x0, y1, x1]} of the colour item leaves the window '
-                                     f'{[g["wy"], g["wx"], g["wy"] + g["wh"], g["wx"] + g["ww"]]} that the crop of '
-                                     f'spp_bboxes[{i}] reads: give the instance\'s own box')
-                mcol.append((i, colormask.ColorMasks(col.boxes - np.array([g['wy'], g['wx']] * 2, np.int32), col.colors,
-                                                     (g['wh'], g['ww']), col.shift)))
+                win = (g['wy'], g['wx'], g['wh'], g['ww'])
+                # (colour: ``support_geometry``'s crop reads the rows and columns of the instance's box unreflected, so
+                # the window holds the whole box; the item travels in the window's frame, beside the image window)
+                compact[form].append((i, one.in_window(*win, f'spp_isegmaps[{i}]', f'the crop of spp_bboxes[{i}]'))
+                                     if form is maskforms.COLOR else (i, one, win))
         need = max(w[0].size for w in wins)
         mneed = need // 3                                  # (wh * ww of the largest window, dense or not)
         capacity, mcapacity = need, mneed
@@ -1530,9 +1494,10 @@ class FGN(torch.nn.Module):
                     boxes=torch.from_numpy(np.stack(boxes).reshape(B, NK, 4)),
                     flats=[torch.from_numpy(w.reshape(-1)) for w, _ in wins],
                     mflats=[torch.from_numpy(m.reshape(-1)) for _, m in wins], need=need, mneed=mneed,
-                    capacity=capacity, mcapacity=mcapacity, mrle=mrle, mcol=mcol, mpoly=mpoly,
-                    window_bytes=int(sum(w.size + m.size for w, m in wins) + sum(r.ends.nbytes for _, r, _ in mrle) +
-                                     4 * ops.CM_REC_INTS * len(mcol) + sum(p.xy.nbytes for _, p, _ in mpoly)))
+                    capacity=capacity, mcapacity=mcapacity, mrle=compact[maskforms.RLE], mcol=compact[maskforms.COLOR],
+                    mpoly=compact[maskforms.POLY],
+                    window_bytes=int(sum(w.size + m.size for w, m in wins) +
+                                     sum(f.nbytes(item[1]) for f, items in compact.items() for item in items)))
 
     @staticmethod
     def _slot_rows(flats: list, width: int, capacity: int, dev, slot: Optional[torch.Tensor]) -> torch.Tensor:
@@ -1913,13 +1878,13 @@ class FGN(torch.nn.Module):
         """Ground-truth masks of one image (array or tensor) on the device as contiguous bool / uint8 [n,h,w].  Masks
         given as COCO RLE (``_gt_entries``) are decoded there (``ops.rle_decode_masks``): the same bytes, uint8 0/1, and
         only their runs cross the bus."""
-        if rle.is_rle(g):
-            return ops.rle_decode_masks(rle.as_masks(g, what='qry_isegmaps'), device=dev)
-        if polygon.is_poly(g):                 # COCO polygons: rasterised there, only the vertices cross the bus
-            return ops.poly_masks(polygon.as_polys(g, None, 'qry_isegmaps'), device=dev)
-        if colormask.is_color(g):              # (made beside the upload of its image: ``_color_on_device``)
+        form = maskforms.form_of(g)
+        if form is maskforms.COLOR:            # (made beside the upload of its image: ``_color_on_device``)
             raise ValueError('qry_isegmaps: a box + colour entry is made into a mask from its image\'s bytes, where those '
                              'are uploaded; it cannot be moved to the device on its own')
+        if form is not None:                   # polygons are rasterised there: only vertices, or runs, cross the bus
+            decode = ops.poly_masks if form is maskforms.POLY else ops.rle_decode_masks
+            return decode(form.check(g, None, 'qry_isegmaps', None), device=dev)
         g = g if isinstance(g, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(g))
         g = g.to(dev, non_blocking=True)
         g = g if g.dtype in (torch.bool, torch.uint8) else (g != 0)
@@ -1959,13 +1924,12 @@ class FGN(torch.nn.Module):
         source, spp_source = form.source, form.spp_source
         gts = None
         if gt_masks is not None:
-            gts = [g if isinstance(g, (torch.Tensor, colormask.ColorMasks)) or rle.is_rle(g) or polygon.is_poly(g) else
+            gts = [g if isinstance(g, torch.Tensor) or maskforms.form_of(g) is not None else
                    torch.from_numpy(np.ascontiguousarray(g)) for g in gt_masks]
         colour = _has_color(gts)
         on_host = [t for t in list(tensors.values()) + (gts or []) + (source['flats'] if source else []) +
                    (spp_source['flats'] + spp_source['mflats'] if spp_source else [])
-                   if t is not None and (rle.is_rle(t) or isinstance(t, colormask.ColorMasks) or polygon.is_poly(t) or
-                                         not t.is_cuda)]
+                   if t is not None and (maskforms.form_of(t) is not None or not t.is_cuda)]
         # (runs, boxes, colours and vertices are host data)
         if not on_host and gts is None and source is None:
             return tensors, None, None
@@ -2523,12 +2487,7 @@ class FGN(torch.nn.Module):
             raise ValueError('results_at_source: these detections were not made with detect_device(results_at_source=True)')
 
         def host_mask(m):
-            if colormask.is_color(m):           # box + colour: derived on the host from the image it is bound to, here only
-                m = colormask.as_color_masks(m, None, 'qry_isegmaps').dense()
-            elif polygon.is_poly(m):            # COCO polygons: rasterised on the host, here only
-                m = polygon.as_polys(m, None, 'qry_isegmaps').dense()
-            elif rle.is_rle(m):                 # masks given as COCO RLE: decoded on the host, here only
-                m = rle.as_masks(m, what='qry_isegmaps').dense()
+            m = maskforms.dense(m, 'qry_isegmaps')      # a compact form: decoded, rasterised or derived on the host here only
             m = np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m)
             if results_at_source:               # as given
                 return m

@@ -13,7 +13,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import colormask, polygon, rle
+from . import maskforms, polygon
 
 
 def _ellipse_mask(h, w, y0, x0, y1, x1):
@@ -127,7 +127,7 @@ def collate(samples: list) -> dict:
             batch[key] = vals[0]
             continue
         if isinstance(vals[0], list):
-            batch[key] = [[v if rle.is_item(v) or colormask.is_color(v) or polygon.is_poly(v) else torch.as_tensor(v) for v in lst]
+            batch[key] = [[torch.as_tensor(v) if maskforms.form_of_one(v) is None else v for v in lst]
                           for lst in vals]                 # (RLE, box + colour, polygons: as it is)
             continue
         if isinstance(vals[0], torch.Tensor):
@@ -136,8 +136,7 @@ def collate(samples: list) -> dict:
             batch[key] = torch.as_tensor(np.stack([np.asarray(v) for v in vals]))
     for key in _LIST_KEYS:                       # ... then the ragged keys as lists of tensors, in the reference's order
         if key in samples[0]:
-            batch[key] = [s[key] if key == 'qry_isegmaps' and (rle.is_rle(s[key]) or colormask.is_color(s[key]) or
-                                                               polygon.is_poly(s[key])) else
+            batch[key] = [s[key] if key == 'qry_isegmaps' and maskforms.form_of(s[key]) is not None else
                           torch.as_tensor(s[key]) for s in samples]
             # (masks given as COCO RLE, as box + colour or as polygons stay what they are)
     return batch

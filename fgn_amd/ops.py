@@ -1797,6 +1797,42 @@ def _rle_decode(parts: list, recs: np.ndarray, out: torch.Tensor, stride: int, m
                'fgn_rle_decode_u8')
 
 
+def _masks_front(m, window, out: Optional[torch.Tensor], device, fn: str) -> tuple:
+    """The front ``rle_decode_masks`` and ``poly_masks`` share: the window of every mask checked, ``out`` allocated on
+    ``device`` (default: the current GPU) or verified.  -> (n, (wy, wx, wh, ww), out)."""
+    n = int(m.shape[0])
+    window = _rle_window(m, window)
+    wh, ww = window[2:]
+    if out is None:
+        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        out = torch.empty((n, wh, ww), device=dev, dtype=torch.uint8)
+    else:
+        _chk(out, 'out', torch.uint8)
+        if tuple(out.shape) != (n, wh, ww):
+            raise _lib.FgnHipError(f'{fn}: out is {tuple(out.shape)}, expected {(n, wh, ww)}')
+    return n, window, out
+
+
+def _row_items(slot: torch.Tensor, items: list, fn: str) -> list:
+    """The front ``rle_decode_rows`` and ``poly_mask_rows`` share: ``slot`` is uint8 [rows, capacity], contiguous, and
+    every item (row, carrier of ONE mask, window) names a row of its own whose window fits the capacity.  -> the items
+    as (row, carrier, (wy, wx, wh, ww)), the window checked."""
+    _chk(slot, 'slot', torch.uint8)
+    if slot.dim() != 2:
+        raise _lib.FgnHipError(f'{fn}: slot must be [rows, capacity]')
+    rows, cap = slot.shape
+    seen, checked = set(), []
+    for row, m, window in items:
+        if not 0 <= int(row) < rows or int(m.shape[0]) != 1 or int(row) in seen:
+            raise _lib.FgnHipError(f'{fn}: row {row} of {rows}: one mask per item, one item per row')
+        seen.add(int(row))
+        window = _rle_window(m, window)
+        if window[2] * window[3] > cap:
+            raise _lib.FgnHipError(f'{fn}: a window of {window[2] * window[3]} bytes exceeds the slot capacity {cap}')
+        checked.append((int(row), m, window))
+    return checked
+
+
 def rle_decode_masks(m, window=None, out: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
     """The n masks of an ``rle.RleMasks`` (what ``rle.as_masks`` makes of COCO RLE items) -> dense uint8 0/1 [n,h,w] on
     the device, or [n,wh,ww] for one ``window`` = (wy, wx, wh, ww) of every mask: ``rle.decode`` bit for bit, i.e. the
@@ -1804,15 +1840,7 @@ def rle_decode_masks(m, window=None, out: Optional[torch.Tensor] = None, device=
     bus).  One upload of the run ends and records, one launch; only the runs cross the bus.  ``out``: a contiguous uint8
     tensor of that shape to write; else a fresh one on ``device`` (default: the current GPU).  An entry without masks
     launches nothing."""
-    n = int(m.shape[0])
-    wy, wx, wh, ww = _rle_window(m, window)
-    if out is None:
-        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        out = torch.empty((n, wh, ww), device=dev, dtype=torch.uint8)
-    else:
-        _chk(out, 'out', torch.uint8)
-        if tuple(out.shape) != (n, wh, ww):
-            raise _lib.FgnHipError(f'rle_decode_masks: out is {tuple(out.shape)}, expected {(n, wh, ww)}')
+    n, (wy, wx, wh, ww), out = _masks_front(m, window, out, device, 'rle_decode_masks')
     if n == 0:
         return out
     first = np.asarray(m.first, np.int64)
@@ -1829,25 +1857,17 @@ def rle_decode_rows(slot: torch.Tensor, items: list) -> torch.Tensor:
     graph included): ``slot`` uint8 [rows, capacity], contiguous; ``items`` = (row, RleMasks of ONE mask, window) each:
     the window's wh * ww bytes go to the front of that row, what lies behind them and every other row stays as it is.
     One upload, one launch for all items; none, no launch."""
-    _chk(slot, 'slot', torch.uint8)
-    if slot.dim() != 2:
-        raise _lib.FgnHipError('rle_decode_rows: slot must be [rows, capacity]')
-    rows, cap = slot.shape
+    items = _row_items(slot, items, 'rle_decode_rows')
     if not items:
         return slot
+    rows, cap = slot.shape
     recs = np.zeros((rows, RLE_REC_INTS), np.int32)          # (an all-zero record has an empty window: nothing is written)
-    parts, run0, max_wh, max_ww = [], 0, 0, 0
+    parts, run0 = [], 0
     for row, m, window in items:
-        if not 0 <= int(row) < rows or int(m.shape[0]) != 1 or recs[int(row), 4]:
-            raise _lib.FgnHipError(f'rle_decode_rows: row {row} of {rows}: one mask per item, one item per row')
-        wy, wx, wh, ww = _rle_window(m, window)
-        if wh * ww > cap:
-            raise _lib.FgnHipError(f'rle_decode_rows: a window of {wh * ww} bytes exceeds the slot capacity {cap}')
-        recs[int(row)] = (m.shape[1], m.shape[2], wy, wx, wh, ww, run0, m.ends.size)
+        recs[row] = (m.shape[1], m.shape[2]) + window + (run0, m.ends.size)
         parts.append(m.ends)
         run0 += int(m.ends.size)
-        max_wh, max_ww = max(max_wh, wh), max(max_ww, ww)
-    _rle_decode(parts, recs, slot, cap, max_wh, max_ww)
+    _rle_decode(parts, recs, slot, cap, max(w[2] for _, _, w in items), max(w[3] for _, _, w in items))
     return slot
 
 
@@ -1998,15 +2018,7 @@ def poly_masks(pm, window=None, out: Optional[torch.Tensor] = None, device=None,
     'host' per instance.  ``out``: a contiguous uint8 tensor of that shape to write; else a fresh one on ``device``
     (default: the current GPU).  An entry without masks launches nothing."""
     from . import rle
-    n = int(pm.shape[0])
-    wy, wx, wh, ww = _rle_window(pm, window)
-    if out is None:
-        dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        out = torch.empty((n, wh, ww), device=dev, dtype=torch.uint8)
-    else:
-        _chk(out, 'out', torch.uint8)
-        if tuple(out.shape) != (n, wh, ww):
-            raise _lib.FgnHipError(f'poly_masks: out is {tuple(out.shape)}, expected {(n, wh, ww)}')
+    n, (wy, wx, wh, ww), out = _masks_front(pm, window, out, device, 'poly_masks')
     host = pm.on_host()
     if routes is not None:
         routes.extend('host' if v else 'device' for v in host)
@@ -2033,29 +2045,21 @@ def poly_mask_rows(slot: torch.Tensor, items: list, routes: Optional[list] = Non
     and every other row stays as it is.  One upload, two launches for all items of the device route; those of the host
     route go through ``rle_decode_rows``; none, no launch.  ``routes`` as for ``poly_masks``, per item."""
     from . import rle
-    _chk(slot, 'slot', torch.uint8)
-    if slot.dim() != 2:
-        raise _lib.FgnHipError('poly_mask_rows: slot must be [rows, capacity]')
-    rows, cap = slot.shape
+    items = _row_items(slot, items, 'poly_mask_rows')
     if not items:
         return slot
-    entries, on_host, seen, max_wh, max_ww = [], [], set(), 0, 0
+    rows, cap = slot.shape
+    entries, on_host, max_wh, max_ww = [], [], 0, 0
     for row, m, window in items:
-        if not 0 <= int(row) < rows or int(m.shape[0]) != 1 or int(row) in seen:
-            raise _lib.FgnHipError(f'poly_mask_rows: row {row} of {rows}: one mask per item, one item per row')
-        seen.add(int(row))
-        wy, wx, wh, ww = _rle_window(m, window)
-        if wh * ww > cap:
-            raise _lib.FgnHipError(f'poly_mask_rows: a window of {wh * ww} bytes exceeds the slot capacity {cap}')
         hw = (int(m.shape[1]), int(m.shape[2]))
         host = bool(m.on_host()[0])
         if routes is not None:
             routes.append('host' if host else 'device')
         if host:
-            on_host.append((int(row), rle.as_masks(m.rle_items([0]), hw, 'poly_mask_rows'), (wy, wx, wh, ww)))
+            on_host.append((row, rle.as_masks(m.rle_items([0]), hw, 'poly_mask_rows'), window))
         else:
-            entries.append((int(row), hw, (wy, wx, wh, ww), m.parts(0)))
-            max_wh, max_ww = max(max_wh, wh), max(max_ww, ww)
+            entries.append((row, hw, window, m.parts(0)))
+            max_wh, max_ww = max(max_wh, window[2]), max(max_ww, window[3])
     if entries:
         _poly_launch(entries, rows, slot, cap, max_wh, max_ww)
     rle_decode_rows(slot, on_host)
