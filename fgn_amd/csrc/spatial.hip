@@ -3,6 +3,7 @@
 // All tensors are NHWC fp32; every lane moves 16 B and a wave covers contiguous
 // channels, so global accesses are fully coalesced.
 #include "common.h"
+#include "roi_geom.h"
 
 // ----------------------------------------------------------------------------------
 // NCHW [B,3,H,W] -> NHWC4 [B,H,W,4] (4th channel zero) so the 7x7 stem conv can stage
@@ -1178,30 +1179,8 @@ extern "C" int fgn_maxpool3x3s2_nhwc_f32(const float* x, float* y, int n_img, in
 // bilinear_interpolate: outside [-1,size] -> 0, coordinates clamped at 0, the last
 // row/column snaps.
 // ----------------------------------------------------------------------------------
-struct AxisSample {
-    int lo, hi;
-    float l, h;
-    bool valid;
-};
-
-__device__ __forceinline__ AxisSample axis_sample(float c, int size) {
-    AxisSample s;
-    s.valid = !(c < -1.0f || c > (float)size);
-    if (c <= 0.f) c = 0.f;
-    int lo = (int)c;
-    int hi;
-    if (lo >= size - 1) {
-        hi = lo = size - 1;
-        c = (float)lo;
-    } else {
-        hi = lo + 1;
-    }
-    s.lo = lo; s.hi = hi;
-    s.l = c - (float)lo;
-    s.h = 1.f - s.l;
-    return s;
-}
-
+// The geometry (box transform, grid, sample coordinates, axis_sample) is stated once, in roi_geom.h, for these
+// kernels and for the adjoint in train_bwd.hip.
 __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict__ fmap,
                                                         const float* __restrict__ rois,
                                                         float* __restrict__ out,
@@ -1222,21 +1201,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
     const int ph = pb / P, pw = pb - ph * P;
 
     const float* roi = rois + (size_t)r * 5;
-    const int b = (int)roi[0];
-    const float off = aligned ? 0.5f : 0.f;
-    const float x1 = roi[1] * spatial_scale - off;
-    const float y1 = roi[2] * spatial_scale - off;
-    const float x2 = roi[3] * spatial_scale - off;
-    const float y2 = roi[4] * spatial_scale - off;
-    float rw = x2 - x1, rh = y2 - y1;
-    if (!aligned) {
-        rw = fmaxf(rw, 1.f);
-        rh = fmaxf(rh, 1.f);
-    }
-    const float bin_h = rh / (float)P, bin_w = rw / (float)P;
-    const int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / (float)P);
-    const int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / (float)P);
-    const float count = (float)max(gh * gw, 1);
+    FGN_ROI_GEOMETRY(roi)
     const float* base1 = fmap + (size_t)b * H * W * C;
     const float* base2 = fmap2 ? fmap2 + (size_t)b * H * W * C2 : nullptr;
     const int c_all = C + (fmap2 ? C2 : 0);
@@ -1255,25 +1220,17 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
     if (threadIdx.x < 2) {
         const bool is_y = threadIdx.x == 0;
         const int g = is_y ? gh : gw, size = is_y ? H : W;
-        const float start = (is_y ? y1 + (float)ph * bin_h : x1 + (float)pw * bin_w), step = is_y ? bin_h : bin_w;
+        const float start = (is_y ? FGN_BIN_START(y1, ph, bin_h) : FGN_BIN_START(x1, pw, bin_w)), step = is_y ? bin_h : bin_w;
         float* w = is_y ? wy_sh : wx_sh;
         // (an empty sampling grid - a box of no extent - has no pixels: the bin is 0, as in the per-sample form)
-        // (the samples run upwards from the first, or downwards where an aligned box has a negative extent and the grid
-        // is fixed: the span lies between the two end samples either way)
-        int first = 0, last = -1;
-        if (g > 0) {
-            const AxisSample s0 = axis_sample(start + 0.5f * step / (float)g, size);
-            const AxisSample s1 = axis_sample(start + ((float)(g - 1) + 0.5f) * step / (float)g, size);
-            first = min(s0.lo, s1.lo);
-            last = max(s0.hi, s1.hi);
-        }
+        FGN_AXIS_SPAN(start, step, g, size)
         const int n = last - first + 1;
         span_sh[is_y ? 0 : 2] = first;
         span_sh[is_y ? 1 : 3] = n;
         if (n <= MAXS) {
             for (int i = 0; i < n; ++i) w[i] = 0.f;
             for (int i = 0; i < g; ++i) {
-                const AxisSample sp = axis_sample(start + ((float)i + 0.5f) * step / (float)g, size);
+                const AxisSample sp = axis_sample(FGN_SAMPLE_COORD(start, i, step, g), size);
                 if (sp.valid) {
                     w[sp.lo - first] += sp.h;
                     w[sp.hi - first] += sp.l;
@@ -1306,10 +1263,10 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
             }
         } else {
             for (int iy = 0; iy < gh; ++iy) {
-                const float y = y1 + (float)ph * bin_h + ((float)iy + 0.5f) * bin_h / (float)gh;
+                const float y = FGN_SAMPLE_COORD(FGN_BIN_START(y1, ph, bin_h), iy, bin_h, gh);
                 const AxisSample sy = axis_sample(y, H);
                 for (int ix = 0; ix < gw; ++ix) {
-                    const float x = x1 + (float)pw * bin_w + ((float)ix + 0.5f) * bin_w / (float)gw;
+                    const float x = FGN_SAMPLE_COORD(FGN_BIN_START(x1, pw, bin_w), ix, bin_w, gw);
                     const AxisSample sx = axis_sample(x, W);
                     if (!(sy.valid && sx.valid)) continue;
                     const float w1 = sy.h * sx.h, w2 = sy.h * sx.l, w3 = sy.l * sx.h, w4 = sy.l * sx.l;
@@ -1350,27 +1307,13 @@ __global__ __launch_bounds__(256) void roi_align_mask_kernel(const uint8_t* __re
     const int pb = i - r * P * P;
     const int ph = pb / P, pw = pb - ph * P;
     const float* roi = rois + (size_t)r * 5;
-    const int b = (int)roi[0];
-    const float off = aligned ? 0.5f : 0.f;
-    const float x1 = roi[1] * spatial_scale - off;
-    const float y1 = roi[2] * spatial_scale - off;
-    const float x2 = roi[3] * spatial_scale - off;
-    const float y2 = roi[4] * spatial_scale - off;
-    float rw = x2 - x1, rh = y2 - y1;
-    if (!aligned) {
-        rw = fmaxf(rw, 1.f);
-        rh = fmaxf(rh, 1.f);
-    }
-    const float bin_h = rh / (float)P, bin_w = rw / (float)P;
-    const int gh = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rh / (float)P);
-    const int gw = sampling_ratio > 0 ? sampling_ratio : (int)ceilf(rw / (float)P);
-    const float count = (float)max(gh * gw, 1);
+    FGN_ROI_GEOMETRY(roi)
     const uint8_t* base = mask + (size_t)b * H * W;
     float acc = 0.f;
     for (int s = lane; s < gh * gw; s += 64) {
         const int iy = s / gw, ix = s - iy * gw;
-        const float y = y1 + (float)ph * bin_h + ((float)iy + 0.5f) * bin_h / (float)gh;
-        const float x = x1 + (float)pw * bin_w + ((float)ix + 0.5f) * bin_w / (float)gw;
+        const float y = FGN_SAMPLE_COORD(FGN_BIN_START(y1, ph, bin_h), iy, bin_h, gh);
+        const float x = FGN_SAMPLE_COORD(FGN_BIN_START(x1, pw, bin_w), ix, bin_w, gw);
         const AxisSample sy = axis_sample(y, H);
         const AxisSample sx = axis_sample(x, W);
         if (!(sy.valid && sx.valid)) continue;

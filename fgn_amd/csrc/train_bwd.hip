@@ -791,3 +791,213 @@ extern "C" int fgn_adagrad_step_f32(float* param, const float* grad, float* stat
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Feature gradients: what reaches the two C4 feature tensors (the interface of a backbone's own backward pass).
+// Neither kernel uses an atomic: every output element is owned by one thread, which adds its terms in a fixed order.
+// ---------------------------------------------------------------------------------------------------------
+#include "roi_geom.h"
+
+// RoIAlign backward, gather form: the adjoint of roi_align_kernel (spatial.hip).  A workgroup owns a RAB_TY x RAB_TX
+// tile of pixels of one image times RAB_CQ channel quads; a thread owns one pixel and one channel quad.  The
+// workgroup walks ALL RoIs in index order, skips those of other images, those with an empty sampling grid and those
+// whose pixel span (the forward's first / last, taken over the first and the last bin) misses the tile - a test its
+// threads make for blockDim.x RoIs at a time, one each; for a RoI that stays, its threads build the per-axis weights of every bin at the tile's rows and columns in LDS - the sum, in
+// sample order, of the bilinear weights the bin's valid samples give that row / column: the forward's wy_sh / wx_sh -
+// and every thread adds  (wy * wx / count) * dy[r, ph, pw, c]  over the bins in (ph, pw) order.  Summation order per
+// output element: (RoI index, bin row, bin column); terms of zero weight are skipped.
+constexpr int RAB_TY = 4, RAB_TX = 4, RAB_CQ = 16, RAB_MAXP = 32;
+
+// [first, last] of bin p of an axis (FGN_AXIS_SPAN, the forward's own statements)
+__device__ __forceinline__ void rab_bin_span(float box_start, int p, float step, int g, int size, int& f, int& l) {
+#pragma clang fp contract(off)
+    const float start = FGN_BIN_START(box_start, p, step);
+    FGN_AXIS_SPAN(start, step, g, size)
+    f = first; l = last;
+}
+
+__global__ __launch_bounds__(RAB_TY * RAB_TX * RAB_CQ) void roi_align_backward_kernel(
+    const float* __restrict__ dy, const float* __restrict__ rois, float* __restrict__ dx, int n_rois, int H, int W, int C,
+    int P, float spatial_scale, int sampling_ratio, int aligned, int accumulate, int tiles_x) {
+#pragma clang fp contract(off)
+    const int img = blockIdx.z;
+    const int ty0 = (blockIdx.x / tiles_x) * RAB_TY, tx0 = (blockIdx.x % tiles_x) * RAB_TX;
+    const int cq = threadIdx.x % RAB_CQ, pix = threadIdx.x / RAB_CQ;
+    const int ly = pix / RAB_TX, lx = pix % RAB_TX;
+    const int py = ty0 + ly, px = tx0 + lx;
+    const int c = (blockIdx.y * RAB_CQ + cq) * 4;
+    const bool active = py < H && px < W && c < C;
+    __shared__ float wy_sh[RAB_MAXP][RAB_TY], wx_sh[RAB_MAXP][RAB_TX];
+    __shared__ int hit_sh[RAB_TY * RAB_TX * RAB_CQ];
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r0 = 0; r0 < n_rois; r0 += blockDim.x) {
+        // the reject, one RoI per thread for a chunk of blockDim.x RoIs; the chunk's survivors are then walked in index order
+        __syncthreads();                                       // the previous chunk's flags and weights have been read
+        {
+            const int r = r0 + threadIdx.x;
+            int hit = 0;
+            if (r < n_rois) {
+                const float* roi = rois + (size_t)r * 5;
+                FGN_ROI_GEOMETRY(roi)
+                (void)count;
+                if (b == img && gh > 0 && gw > 0) {
+                    int f0, l0, f1, l1;
+                    rab_bin_span(y1, 0, bin_h, gh, H, f0, l0);
+                    rab_bin_span(y1, P - 1, bin_h, gh, H, f1, l1);
+                    hit = !(max(l0, l1) < ty0 || min(f0, f1) >= ty0 + RAB_TY);
+                    rab_bin_span(x1, 0, bin_w, gw, W, f0, l0);
+                    rab_bin_span(x1, P - 1, bin_w, gw, W, f1, l1);
+                    hit = hit && !(max(l0, l1) < tx0 || min(f0, f1) >= tx0 + RAB_TX);
+                }
+            }
+            hit_sh[threadIdx.x] = hit;
+        }
+        __syncthreads();
+        const int r_end = min(r0 + (int)blockDim.x, n_rois);
+        for (int r = r0; r < r_end; ++r) {
+            // (uniform over the workgroup: the barriers further down are reached by all or by none)
+            if (!hit_sh[r - r0]) continue;
+            const float* roi = rois + (size_t)r * 5;
+            FGN_ROI_GEOMETRY(roi)
+            (void)b;
+            __syncthreads();                               // the previous RoI's weights have been read
+            for (int e = threadIdx.x; e < P * (RAB_TY + RAB_TX); e += blockDim.x) {
+                const bool is_y = e < P * RAB_TY;
+                const int e2 = is_y ? e : e - P * RAB_TY, T = is_y ? RAB_TY : RAB_TX;
+                const int p = e2 / T, k = e2 - p * T;
+                const int g = is_y ? gh : gw, size = is_y ? H : W;
+                const int q = (is_y ? ty0 : tx0) + k;          // the row / column of the map
+                const float step = is_y ? bin_h : bin_w;
+                const float start = is_y ? FGN_BIN_START(y1, p, bin_h) : FGN_BIN_START(x1, p, bin_w);
+                FGN_AXIS_SPAN(start, step, g, size)
+                float w = 0.f;
+                if (q >= first && q <= last) {
+                    for (int i = 0; i < g; ++i) {
+                        const AxisSample sp = axis_sample(FGN_SAMPLE_COORD(start, i, step, g), size);
+                        if (sp.valid) {
+                            if (sp.lo == q) w += sp.h;
+                            if (sp.hi == q) w += sp.l;
+                        }
+                    }
+                }
+                (is_y ? wy_sh[p] : wx_sh[p])[k] = w;
+            }
+            __syncthreads();
+            if (!active) continue;                             // (no barrier follows inside this iteration)
+            const float* dyr = dy + (size_t)r * P * P * C + c;
+            for (int ph = 0; ph < P; ++ph) {
+                const float wy = wy_sh[ph][ly];
+                if (wy == 0.f) continue;
+                for (int pw = 0; pw < P; ++pw) {
+                    const float wx = wx_sh[pw][lx];
+                    if (wx == 0.f) continue;
+                    const float wq = wy * wx / count;
+                    const float4 g4 = *reinterpret_cast<const float4*>(dyr + (size_t)(ph * P + pw) * C);
+                    acc.x += wq * g4.x; acc.y += wq * g4.y; acc.z += wq * g4.z; acc.w += wq * g4.w;
+                }
+            }
+        }
+    }
+    if (!active) return;
+    float4* o = reinterpret_cast<float4*>(dx + (((size_t)img * H + py) * W + px) * C + c);
+    if (accumulate) {
+        const float4 old = *o;
+        acc.x = old.x + acc.x; acc.y = old.y + acc.y; acc.z = old.z + acc.z; acc.w = old.w + acc.w;
+    }
+    *o = acc;
+}
+
+extern "C" int fgn_roi_align_backward_nhwc_f32(const float* dy, const float* rois, float* dx, int n_rois, int n_img,
+                                               int H, int W, int C, int out_size, float spatial_scale,
+                                               int sampling_ratio, int aligned, int accumulate, hipStream_t stream) {
+    if (!dx || n_rois < 0 || (n_rois > 0 && (!dy || !rois))) return FGN_ERR_ARG;
+    if (C <= 0 || C % 4 || out_size <= 0 || out_size > RAB_MAXP || n_img < 0 || n_img > 65535 || H < 0 || W < 0)
+        return FGN_ERR_SHAPE;
+    if (n_img == 0 || H == 0 || W == 0) return FGN_OK;
+    if (n_rois == 0 && accumulate) return FGN_OK;
+    const int tiles_x = cdiv(W, RAB_TX), tiles_y = cdiv(H, RAB_TY);
+    hipLaunchKernelGGL(roi_align_backward_kernel, dim3(tiles_x * tiles_y, cdiv(C, 4 * RAB_CQ), n_img),
+                       dim3(RAB_TY * RAB_TX * RAB_CQ), 0, stream, dy, rois, dx, n_rois, H, W, C, out_size, spatial_scale,
+                       sampling_ratio, aligned, accumulate, tiles_x);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}
+
+// AG-RPN guidance backward.  The guided input of rpn_conv is G[bN+n, y, x, c] = qry_fmap[b, y, x, c] * vec[bN+n, c]; its
+// gradient dG = conv3x3_dgrad(dpre) is non-zero only in the 3x3 neighbourhoods of the few hundred sampled rows, and
+// arrives as the tap tensor T [rows, 9, C] (row r, tap ky*3+kx: the gradient row r sends to the pixel at
+// (y + ky - 1, x + kx - 1)) with a host-built index in CSR form: pix [touched] (flat pixel b*h*w + y*w + x, ascending),
+// seg [touched*N + 1] (the entries of (touched pixel t, pass n) are ent[seg[t*N+n] .. seg[t*N+n+1])), ent [nnz]
+// (row*9 + tap, ascending per segment), img_seg [B + 1] (the touched pixels of image b are t in img_seg[b] ..
+// img_seg[b+1]).  One workgroup per touched pixel, lanes over channel quads:
+//   dG_n[c] = sum of its taps in list order;  d_qry[b,y,x,c] (+)= sum_n vec[bN+n,c] * dG_n[c] (n ascending);
+//   slab[t,n,c] = qry_fmap[b,y,x,c] * dG_n[c];
+// then d_vec[bN+n,c] = sum over the touched pixels of image b of slab[t,n,c], t ascending, one thread per element.
+__global__ __launch_bounds__(256) void guidance_backward_kernel(const float* __restrict__ T, const int32_t* __restrict__ pix,
+                                                                const int32_t* __restrict__ seg,
+                                                                const int32_t* __restrict__ ent,
+                                                                const float* __restrict__ qry, const float* __restrict__ vec,
+                                                                float* __restrict__ d_qry, float* __restrict__ slab, int N,
+                                                                int hw, int C, int accumulate) {
+    const int t = blockIdx.x;
+    const int p = pix[t];
+    const int b = p / hw;
+    for (int c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
+        const float4 q = *reinterpret_cast<const float4*>(qry + (size_t)p * C + c);
+        float4 dq = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int n = 0; n < N; ++n) {
+            float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+            const int e1 = seg[t * N + n + 1];
+            for (int e = seg[t * N + n]; e < e1; ++e) {
+                const float4 v = *reinterpret_cast<const float4*>(T + (size_t)ent[e] * C + c);
+                g.x += v.x; g.y += v.y; g.z += v.z; g.w += v.w;
+            }
+            const float4 s = *reinterpret_cast<const float4*>(vec + (size_t)(b * N + n) * C + c);
+            dq.x += s.x * g.x; dq.y += s.y * g.y; dq.z += s.z * g.z; dq.w += s.w * g.w;
+            *reinterpret_cast<float4*>(slab + ((size_t)t * N + n) * C + c) =
+                make_float4(q.x * g.x, q.y * g.y, q.z * g.z, q.w * g.w);
+        }
+        float4* o = reinterpret_cast<float4*>(d_qry + (size_t)p * C + c);
+        if (accumulate) {
+            const float4 old = *o;
+            dq.x = old.x + dq.x; dq.y = old.y + dq.y; dq.z = old.z + dq.z; dq.w = old.w + dq.w;
+        }
+        *o = dq;
+    }
+}
+
+__global__ __launch_bounds__(64) void guidance_vec_kernel(const float* __restrict__ slab, const int32_t* __restrict__ img_seg,
+                                                          float* __restrict__ d_vec, int N, int C) {
+    const int bn = blockIdx.x, b = bn / N, n = bn - b * N;
+    const int c = (blockIdx.y * 64 + threadIdx.x) * 4;
+    if (c >= C) return;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int t1 = img_seg[b + 1];
+    for (int t = img_seg[b]; t < t1; ++t) {
+        const float4 v = *reinterpret_cast<const float4*>(slab + ((size_t)t * N + n) * C + c);
+        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+    *reinterpret_cast<float4*>(d_vec + (size_t)bn * C + c) = a;
+}
+
+extern "C" int fgn_guidance_backward_f32(const float* T, const int32_t* pix, const int32_t* seg, const int32_t* ent,
+                                         const int32_t* img_seg, const float* qry_fmap, const float* vec, float* d_qry,
+                                         float* slab, float* d_vec, int n_touched, int B, int N, int hw, int C,
+                                         int accumulate, hipStream_t stream) {
+    if (!img_seg || !qry_fmap || !vec || !d_qry || !d_vec || n_touched < 0) return FGN_ERR_ARG;
+    if (n_touched > 0 && (!T || !pix || !seg || !ent || !slab)) return FGN_ERR_ARG;
+    if (C <= 0 || C % 4 || B <= 0 || N <= 0 || hw <= 0) return FGN_ERR_SHAPE;
+    if (!accumulate) {
+        const hipError_t e = hipMemsetAsync(d_qry, 0, (size_t)B * hw * C * sizeof(float), stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (n_touched > 0) {
+        const int threads = C >= 1024 ? 256 : (C >= 512 ? 128 : 64);
+        hipLaunchKernelGGL(guidance_backward_kernel, dim3(n_touched), dim3(threads), 0, stream, T, pix, seg, ent, qry_fmap,
+                           vec, d_qry, slab, N, hw, C, accumulate);
+        FGN_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(guidance_vec_kernel, dim3(B * N, cdiv(C, 256)), dim3(64), 0, stream, slab, img_seg, d_vec, N, C);
+    FGN_LAUNCH_CHECK();
+    return FGN_OK;
+}

@@ -127,6 +127,8 @@ SIGNATURES = {
     'fgn_optim_multi_f32': (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _f, _f, _f, _f, C.c_double, C.c_double, _i, _p, _f, _p]),
     'fgn_grad_sqnorm_multi_f32': (_i, [_p, _p, _i, _f, _f, _p, C.c_longlong, _p, _p]),
     'fgn_grad_accumulate_multi_f32': (_i, [_p, _p, _p, _i, _f, _i, _p]),
+    'fgn_roi_align_backward_nhwc_f32': (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _i, _i, _i, _p]),
+    'fgn_guidance_backward_f32': (_i, [_p] * 10 + [_i] * 6 + [_p]),
 }
 
 ABI_VERSION = 33

@@ -2490,6 +2490,111 @@ def gemm_small(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False) -> torch
     return out
 
 
+def roi_align_backward(dy: torch.Tensor, rois: torch.Tensor, fmap_shape, spatial_scale: float, sampling_ratio: int,
+                       aligned: bool, out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """The adjoint of ``roi_align`` (no post_shift, no ReLU): dy [R,P,P,C], rois [R,5] -> dx ``fmap_shape`` = [B,H,W,C].
+    ``out`` with ``accumulate``: added onto; otherwise overwritten (R = 0: zeros).  Gather form without atomics: the
+    terms of an element are added in (RoI index, bin row, bin column) order, so two runs give the same bytes."""
+    _chk(dy, 'dy')
+    _chk(rois, 'rois')
+    b, h, w, c = (int(v) for v in fmap_shape)
+    if rois.dim() != 2 or rois.shape[1] != 5:
+        raise _lib.FgnHipError('roi_align_backward: rois must be [R,5]')
+    r = rois.shape[0]
+    if dy.dim() != 4 or dy.shape[0] != r or dy.shape[1] != dy.shape[2] or dy.shape[3] != c:
+        raise _lib.FgnHipError('roi_align_backward: dy must be [R,P,P,C] for rois [R,5] and a [B,H,W,C] map')
+    if out is None:
+        out = torch.empty((b, h, w, c), device=dy.device, dtype=torch.float32)
+        accumulate = False
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != (b, h, w, c):
+            raise _lib.FgnHipError('roi_align_backward: bad out shape')
+    rc = _lib.load().fgn_roi_align_backward_nhwc_f32(_ptr(dy), _ptr(rois), _ptr(out), r, b, h, w, c, int(dy.shape[1]),
+                                                     float(spatial_scale), int(sampling_ratio), int(aligned),
+                                                     int(accumulate), _stream())
+    _lib.check(rc, 'fgn_roi_align_backward_nhwc_f32')
+    return out
+
+
+def guidance_index(g, y, x, batch: int, n_ways: int, h: int, w: int) -> dict:
+    """The host-side index of ``guidance_backward``.  Active row r of the gradient in front of rpn_conv's ReLU sits at
+    pixel (y[r], x[r]) of guided pass g[r] = b * n_ways + n; its tap ky*3+kx reaches the pixel (y + ky - 1, x + kx - 1)
+    of image b (taps that fall outside the map are dropped).  -> dict of int32 arrays in CSR form: ``pix`` [touched]
+    flat pixels b*h*w + y*w + x, ascending; ``seg`` [touched*n_ways + 1]: the entries of (touched pixel t, pass n) are
+    ``ent[seg[t*n_ways+n] : seg[t*n_ways+n+1]]``; ``ent`` [nnz] = r*9 + tap, ascending within a segment; ``img_seg``
+    [batch + 1]: the touched pixels of image b are ``pix[img_seg[b] : img_seg[b+1]]``."""
+    g, y, x = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (g, y, x))
+    if not (g.size == y.size == x.size):
+        raise ValueError('guidance_index: g, y and x must have one entry per active row')
+    if g.size and (g.min() < 0 or g.max() >= batch * n_ways or y.min() < 0 or y.max() >= h or x.min() < 0 or x.max() >= w):
+        raise ValueError('guidance_index: a row lies outside the [batch*n_ways, h, w] map')
+    tap = np.arange(9, dtype=np.int64)[None, :]
+    ty, tx = y[:, None] + tap // 3 - 1, x[:, None] + tap % 3 - 1
+    ok = (ty >= 0) & (ty < h) & (tx >= 0) & (tx < w)
+    pixel = ((g[:, None] // n_ways) * h + ty) * w + tx
+    key = pixel * n_ways + g[:, None] % n_ways                    # (pixel, pass)
+    entry = np.arange(g.size, dtype=np.int64)[:, None] * 9 + tap
+    key, entry = key[ok], entry[ok]
+    order = np.lexsort((entry, key))
+    key, entry = key[order], entry[order]
+    pix = np.unique(key // n_ways)
+    t = np.searchsorted(pix, key // n_ways)
+    counts = np.bincount(t * n_ways + key % n_ways, minlength=pix.size * n_ways)
+    seg = np.concatenate([[0], np.cumsum(counts)])
+    img_seg = np.searchsorted(pix, np.arange(batch + 1, dtype=np.int64) * h * w)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    return dict(pix=i32(pix), seg=i32(seg), ent=i32(entry), img_seg=i32(img_seg))
+
+
+def guidance_backward(taps: torch.Tensor, index: dict, qry_fmap: torch.Tensor, vec: torch.Tensor,
+                      out: Optional[torch.Tensor] = None, accumulate: bool = False, upload=None):
+    """Backward of the AG-RPN guidance ``qry_fmap[b] * vec[b*N+n]`` from the sparse gradient of rpn_conv's input:
+    taps [rows,9,C] (tap ky*3+kx of active row r), ``index`` = ``guidance_index`` (host arrays; checked here against
+    the operand shapes, then uploaded in one copy - ``upload``: host int32 array -> device tensor, default a plain
+    copy), qry_fmap [B,h,w,C], vec [B*N,C] -> (d_qry [B,h,w,C], d_vec [B*N,C]).  ``out`` with ``accumulate``: d_qry is
+    added onto it at the touched pixels and left as it was elsewhere; otherwise zero at untouched pixels."""
+    _chk(taps, 'taps')
+    _chk(qry_fmap, 'qry_fmap')
+    _chk(vec, 'vec')
+    b, h, w, c = qry_fmap.shape
+    if vec.dim() != 2 or vec.shape[1] != c or vec.shape[0] % b:
+        raise _lib.FgnHipError('guidance_backward: vec must be [B*N,C]')
+    n = vec.shape[0] // b
+    rows = taps.shape[0]
+    if taps.dim() != 3 or taps.shape[1] != 9 or taps.shape[2] != c:
+        raise _lib.FgnHipError('guidance_backward: taps must be [rows,9,C]')
+    pix, seg, ent, img_seg = (np.ascontiguousarray(index[k], dtype=np.int32) for k in ('pix', 'seg', 'ent', 'img_seg'))
+    nt = pix.size
+    bad = seg.size != nt * n + 1 or img_seg.size != b + 1 or seg[0] != 0 or seg[-1] != ent.size \
+        or (np.diff(seg) < 0).any() or (np.diff(img_seg) < 0).any() or img_seg[0] != 0 or img_seg[-1] != nt
+    if not bad and nt:
+        bad = pix.min() < 0 or pix.max() >= b * h * w or (np.diff(pix) <= 0).any() \
+            or (pix // (h * w) != np.repeat(np.arange(b), np.diff(img_seg))).any()
+    if not bad and ent.size:
+        bad = ent.min() < 0 or ent.max() >= rows * 9
+    if bad:
+        raise _lib.FgnHipError('guidance_backward: the index does not fit the operands')
+    packed = np.concatenate([pix, seg, ent, img_seg])
+    dev_idx = torch.from_numpy(packed).to(taps.device, non_blocking=True) if upload is None else upload(packed)
+    _chk(dev_idx, 'index', torch.int32)
+    o1, o2, o3 = nt, nt + seg.size, nt + seg.size + ent.size
+    if out is None:
+        out = torch.empty_like(qry_fmap)
+        accumulate = False
+    else:
+        _chk(out, 'out')
+        if out.shape != qry_fmap.shape:
+            raise _lib.FgnHipError('guidance_backward: bad out shape')
+    slab = torch.empty((max(nt, 1), n, c), device=taps.device, dtype=torch.float32)
+    d_vec = torch.empty_like(vec)
+    rc = _lib.load().fgn_guidance_backward_f32(_ptr(taps), _ptr(dev_idx[:o1]), _ptr(dev_idx[o1:o2]), _ptr(dev_idx[o2:o3]),
+                                               _ptr(dev_idx[o3:]), _ptr(qry_fmap), _ptr(vec), _ptr(out), _ptr(slab),
+                                               _ptr(d_vec), nt, b, n, h * w, c, int(accumulate), _stream())
+    _lib.check(rc, 'fgn_guidance_backward_f32')
+    return out, d_vec
+
+
 def adagrad_multi(params, grads, states, lrs, weight_decay: float, eps: float = 1e-10, table: Optional[dict] = None) -> None:
     """``adagrad_step`` for a list of tensors in one launch (each with its own learning rate).  ``table``: a dict the
     caller keeps between steps - the checked parameter / state pointer arrays are built once per (tensors, lrs) and only

@@ -21,6 +21,9 @@ trainable heads, the Adagrad update and the re-pack of the kernel layouts itself
     and accumulation: ``csrc/optim.hip``; data gradients: the forward
     convolution kernel with transposed (1x1) / flipped (3x3) weights; the 6-row fc products and the 75-channel
     AG-RPN head (shapes the MFMA kernels do not take) on ``fgn_gemm_small_f32`` - no rocBLAS call in the step
+  * on request (``Trainer.forward_backward(feature_grads=True)``): the gradient of the summed losses at the two C4
+    feature tensors - RoIAlign backward and the sparse backward of the AG-RPN guidance, ``csrc/train_bwd.hip``, no
+    atomics - and ``features=`` to put externally computed features in
 """
 from __future__ import annotations
 
@@ -255,9 +258,37 @@ def _zero(dev):
     return torch.zeros((), device=dev, dtype=torch.float32)
 
 
+def c4_size(backbone_cfg: dict, H: int, W: int) -> tuple:
+    """(h, w) of the C4 map of an H x W image: the stem's stride-2 convolution, the 3x3 / 2 max-pool and every stride-2
+    stage halve a side to (n - 1) // 2 + 1 (3x3 / pad 1 convolutions and the ceil-mode average pool of avg_down alike)."""
+    n = 2 + sum(1 for s_ in backbone_cfg['strides'] if s_ == 2)
+    for _ in range(n):
+        H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return H, W
+
+
+def _checked_feature(model, t, name: str, n: int, img_hw, dev) -> torch.Tensor:
+    """One tensor of ``features=``: fp32, contiguous, on ``dev``, [n, h, w, C] for images of ``img_hw``."""
+    want = (n,) + c4_size(model.cfg['backbone'], int(img_hw[0]), int(img_hw[1])) + (model.cfg['rpn_head']['in_channels'],)
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f'{name} must be a tensor, got {type(t).__name__}')
+    if t.device != dev:
+        raise ValueError(f'{name} must be on {dev} (the trainer\'s device), got {t.device}')
+    if t.dtype != torch.float32:
+        raise ValueError(f'{name} must be float32, got {t.dtype}')
+    if tuple(t.shape) != want:
+        raise ValueError(f'{name} must be {list(want)} (the layout of FGN.extract_feat), got {list(t.shape)}')
+    if not t.is_contiguous():
+        raise ValueError(f'{name} must be contiguous (a NCHW map: permute(0, 2, 3, 1).contiguous())')
+    return t.detach()
+
+
 def forward_train(model, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bboxes_ignore=None, proposals=None,
                   spp_imgs=None, spp_bboxes=None, spp_isegmaps=None, img_shape=None, perm_fn=torch.randperm,
-                  bn_momentum: float = 0.1, **kwargs) -> dict:
+                  bn_momentum: float = 0.1, features=None, **kwargs) -> dict:
+    """``features`` = (qry_fmap [B,h,w,C], spp_fmaps [B*N*K,s,s,C]), fp32 and contiguous on the current device, in the
+    layout of ``FGN.extract_feat``: the two backbone passes are skipped and the given tensors stand in (read, never
+    written) - the way a feature extractor of the caller's own trains under the heads (``Trainer.feature_grads``)."""
     if not torch.cuda.is_available():
         raise ops._lib.FgnHipError('FGN.forward_train needs a GPU: the HIP path has no CPU fallback')
     if qry_bboxes_ignore is not None and any(b is not None for b in qry_bboxes_ignore):
@@ -289,8 +320,17 @@ def forward_train(model, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bbo
         raise ValueError('all images of a batch must share img_shape (the dataset batches by size)')
 
     # ---- backbone passes (frozen) and the AG-RPN on the N guided maps of every image
-    sc = model._support_front(spp_imgs, spp_bboxes, spp_isegmaps, B, dev, main)
-    qry_fmap = model.extract_feat(qry)
+    if features is None:
+        sc = model._support_front(spp_imgs, spp_bboxes, spp_isegmaps, B, dev, main)
+        qry_fmap = model.extract_feat(qry)
+    else:
+        if not isinstance(features, (tuple, list)) or len(features) != 2:
+            raise ValueError('features must be the pair (qry_fmap, spp_fmaps)')
+        qry_fmap = _checked_feature(model, features[0], 'features[0] (qry_fmap)', B, model._image_dims(qry_img, 'qry_img')[1:], dev)
+        sc = model._support_front(spp_imgs, spp_bboxes, spp_isegmaps, B, dev, main, defer_backbone=True)
+        spp = sc.pop('spp')
+        spp_hw = model._image_dims(spp, 'spp_imgs')[1:] if isinstance(spp, torch.Tensor) else tuple(spp.shape[1:3])
+        model._support_vectors(sc, _checked_feature(model, features[1], 'features[1] (spp_fmaps)', B * N * K, spp_hw, dev))
     fh, fw, C = qry_fmap.shape[1:]
     wg = P['rpn_conv_wg']
     if wg is not None and ops.winograd_fits(B * N, fh, fw, C, wg.cout, wg.m):
@@ -477,7 +517,8 @@ def forward_train(model, qry_img, qry_bboxes, qry_cat_ids, qry_isegmaps, qry_bbo
                            bbox_pred=bbox_pred, labels=labels, lw=lw, avg=avg, pos_rows=pos_rows, n_rois=n_rois,
                            pos_pred=pos_pred, pos_tgt=pos_tgt,
                            img_counts=[s['n_pos'] + s['n_neg'] for s in samples])
-        tape['spp'] = dict(blocks=spp_tape, masks7=sc['masks7'], cat_mean=sc['cat_mean'], B=B)
+        tape['spp'] = dict(blocks=spp_tape, masks7=sc['masks7'], cat_mean=sc['cat_mean'], B=B, spp_xyxy=sc['spp_xyxy'],
+                           spp_shape=tuple(sc['spp_fmaps'].shape))
 
     # ---- mask branch (fgn_roi_head.py:498-527, 384-417): shared RoI extractor -> the positives' bbox_feats
     n_pos = int(pos_rows_h.size)
@@ -602,22 +643,60 @@ def _block_backward(blk: _SharedBlockTrain, W: dict, t: dict, dout: torch.Tensor
     return g_id + _dgrad_1x1(d1, w1).view_as(t['x'])
 
 
-def _shared_backward(model, W, blocks_tape, dout, grads):
+def _shared_backward(model, W, blocks_tape, dout, grads, need_input_grad: bool = False):
+    """-> the gradient at the head's input when ``need_input_grad`` (feature gradients), else None."""
     eps = model.cfg['backbone']['bn_eps']
     blks = model._PT['shared']
     for bi in range(len(blks) - 1, -1, -1):
-        dout = _block_backward(blks[bi], W, blocks_tape[bi], dout, eps, bi > 0, grads)
+        dout = _block_backward(blks[bi], W, blocks_tape[bi], dout, eps, bi > 0 or need_input_grad, grads)
+    return dout
 
 
-def backward(model, W: dict, tape: dict) -> dict:
+def backward(model, W: dict, tape: dict, feature_grads: Optional[dict] = None) -> dict:
     """Gradients of the summed losses (mmdet ``_parse_losses``: every key containing 'loss') with respect to the
     trainable parameters ``W`` (torch-layout master weights on the device), from the tape of ``forward_train``.
-    The backbone is frozen (fgn.py:67-73), so nothing flows below RoIAlign / the AG-RPN input."""
+    The backbone is frozen (fgn.py:67-73), so nothing flows below RoIAlign / the AG-RPN input - unless
+    ``feature_grads`` is a dict: it then receives the gradient of the same sum at the two C4 feature tensors,
+    ``qry_fmap`` [B,h,w,C] and ``spp_fmaps`` [B*N*K,s,s,C], which is what a backbone's own backward pass
+    would start from.  The parameter gradients are the same bits either way."""
     grads: dict = {}
-    if tape['roi'] is not None:
-        _backward_roi_stage(model, W, tape, grads)
-    _backward_rpn_stage(model, W, tape, grads)
+    want = feature_grads is not None
+    below = _backward_roi_stage(model, W, tape, grads, want) if tape['roi'] is not None else None
+    d_qry, d_vec = _backward_rpn_stage(model, W, tape, grads, want)
+    if want:
+        _feature_grads(model, tape, below, d_qry, d_vec, feature_grads)
     return grads
+
+
+def _feature_grads(model, tape: dict, below, d_qry: torch.Tensor, d_vec: torch.Tensor, out: dict) -> None:
+    """The two results from their parts.  ``d_qry``: the AG-RPN part of d qry_fmap (``ops.guidance_backward``); the RoI
+    batch's input gradient is added onto it by the RoIAlign backward (aligned, the head's sampling ratio).  ``d_vec``
+    [B*N,C] reaches the supports through vec = mean over (K, s, s): d_vec / (K s s) at every pixel of the class's K
+    supports is the initial content of d spp_fmaps, and the RoIAlign backward of the pooled support features
+    (torchvision's flavour, RoI i on image i) adds onto it.  ``below`` = (d_xr, d_spool) or None (no RoI sampled: the
+    RoI-stage parts are zero).  With ``model.debug_trace`` a dict, the four parts are recorded there."""
+    rh = model.cfg['roi_head']
+    K = model.k_shots
+    scale = 1.0 / rh['featmap_stride']
+    spp_shape = tape['spp']['spp_shape']
+    n_spp, s1, s2, C = spp_shape
+    d_spp = (d_vec / float(K * s1 * s2)).repeat_interleave(K, dim=0)[:, None, None, :].expand(spp_shape).contiguous()
+    trace = model.debug_trace if isinstance(model.debug_trace, dict) else None
+    if trace is not None:
+        trace['d_qry_fmap_rpn'], trace['d_spp_fmaps_vec'] = d_qry.clone(), d_spp.clone()
+        trace['d_qry_fmap_roi'], trace['d_spp_fmaps_roi'] = torch.zeros_like(d_qry), torch.zeros_like(d_spp)
+    if below is not None:
+        d_xr, d_spool = below
+        rois = tape['roi']['rois']
+        bidx = torch.arange(n_spp, device=d_spp.device, dtype=torch.float32)[:, None]
+        spp_rois = torch.cat([bidx, tape['spp']['spp_xyxy']], 1).contiguous()        # as FGN._support_pool builds them
+        if trace is not None:
+            ops.roi_align_backward(d_xr, rois, d_qry.shape, scale, rh['roi_sampling_ratio'], True,
+                                   out=trace['d_qry_fmap_roi'])
+            ops.roi_align_backward(d_spool, spp_rois, spp_shape, scale, -1, False, out=trace['d_spp_fmaps_roi'])
+        ops.roi_align_backward(d_xr, rois, d_qry.shape, scale, rh['roi_sampling_ratio'], True, out=d_qry, accumulate=True)
+        ops.roi_align_backward(d_spool, spp_rois, spp_shape, scale, -1, False, out=d_spp, accumulate=True)
+    out['qry_fmap'], out['spp_fmaps'] = d_qry, d_spp
 
 
 def _backward_mask_head(model, W: dict, tape: dict, grads: dict):
@@ -669,7 +748,9 @@ def _backward_mask_head(model, W: dict, tape: dict, grads: dict):
     return d_feats, d_cat_mean_mp
 
 
-def _backward_roi_stage(model, W: dict, tape: dict, grads: dict) -> None:
+def _backward_roi_stage(model, W: dict, tape: dict, grads: dict, need_input_grad: bool = False):
+    """-> None, or with ``need_input_grad`` (d_xr [n_rois,7,7,C], d_spool [B*N*K,7,7,C]): the gradients at the pooled
+    query and support features, the inputs of the shared head."""
     cfg = model.cfg
     N, K = model.n_ways, model.k_shots
     P = model._P
@@ -732,17 +813,19 @@ def _backward_roi_stage(model, W: dict, tape: dict, grads: dict) -> None:
     d_cat_mean = _dgrad_1x1(dS, ws.contiguous()).view_as(cat_mean)          # [B*N, 7, 7, C]
 
     # ---- shared head, RoI batch then support batch (count_spp, fgn_roi_head.py:419-449) ------------------
-    _shared_backward(model, W, tr_['blocks'], d_feats, grads)
+    d_xr = _shared_backward(model, W, tr_['blocks'], d_feats, grads, need_input_grad)
     # cat_mean = mean_k sfeat; cat_mean_mp = mean_{k,p} sfeat * masks7
     ps = cat_mean.shape[1]
     d_sfeat = (d_cat_mean / K).repeat_interleave(K, dim=0)
     if d_cat_mean_mp is not None:
         m7 = tape['spp']['masks7'].view(-1, ps, ps, 1)
         d_sfeat = d_sfeat + d_cat_mean_mp.repeat_interleave(K, dim=0)[:, None, None, :] * m7 / float(K * ps * ps)
-    _shared_backward(model, W, tape['spp']['blocks'], d_sfeat.contiguous(), grads)
+    d_spool = _shared_backward(model, W, tape['spp']['blocks'], d_sfeat.contiguous(), grads, need_input_grad)
+    return (d_xr.contiguous(), d_spool.contiguous()) if need_input_grad else None
 
 
-def _backward_rpn_stage(model, W: dict, tape: dict, grads: dict) -> None:
+def _backward_rpn_stage(model, W: dict, tape: dict, grads: dict, need_input_grad: bool = False):
+    """-> (None, None), or with ``need_input_grad`` the AG-RPN parts (d qry_fmap [B,h,w,C], d vec [B*N,C])."""
     N = model.n_ways
     dev = tape['rpn']['head'].device
     # ---- AG-RPN head (fgn_ag_rpn_head.py:48 -> RPNHead.forward_single; losses my_anchor_head.py:402-451) ----
@@ -785,6 +868,16 @@ def _backward_rpn_stage(model, W: dict, tape: dict, grads: dict) -> None:
     patches = (torch.stack(taps, 1) * vec[gi][:, None, :]).reshape(rows.numel(), 9 * Cin)
     grads['rpn_head.rpn_conv.weight'] = _mm_tn(dpre, patches).view(Cf, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
     grads['rpn_head.rpn_conv.bias'] = ops.colsum(dpre)
+    if not need_input_grad:
+        return None, None
+    # The gradient of the guided input, dG = conv3x3_dgrad(dpre), is non-zero only in the 3x3 neighbourhoods of the
+    # active rows: their nine taps T = dpre x W[Cf, (ky, kx, cin)] (one small product instead of the dense data-gradient
+    # convolution over the whole map), an index of who sends what where built on the host, one gather kernel.
+    w9 = W['rpn_head.rpn_conv.weight'].permute(0, 2, 3, 1).reshape(Cf, 9 * Cin).contiguous()
+    T = _dgrad_1x1(dpre, w9).view(-1, 9, Cin) if rows.numel() else torch.zeros((0, 9, Cin), device=dev)
+    rows_h = rows.cpu().numpy()
+    index = ops.guidance_index(rows_h // hw, (rows_h % hw) // fw, rows_h % fw, G // N, N, fh, fw)
+    return ops.guidance_backward(T.contiguous(), index, qf, vec, upload=lambda a: _staging(model).h2d(a, dev))
 
 
 TRAINABLE_PREFIXES = ('rpn_head.', 'roi_head.')
@@ -1130,6 +1223,7 @@ class Trainer:
         self.buffers ={k: v.to(dev).float().contiguous().clone() for k, v in sd.items()
                         if k.startswith('roi_head.shared_head') and 'running_' in k}
         self.grads: dict = {}
+        self.feature_grads: dict = {}        # forward_backward(feature_grads=True): d loss / d (qry_fmap, spp_fmaps)
         self.n_steps = 0
         # num_batches_tracked of the shared head's BatchNorms = the loaded counter + the train-mode passes made since
         # (one over the support RoIs per step, one over the sampled RoIs when the step sampled any)
@@ -1175,17 +1269,31 @@ class Trainer:
             self.model._pack(self.device)
         self.refresh()
 
-    def forward_backward(self, batch: dict, perm_fn=torch.randperm) -> dict:
+    def forward_backward(self, batch: dict, perm_fn=torch.randperm, features=None, feature_grads: bool = False) -> dict:
+        """Losses and ``self.grads`` of one batch.  ``features`` = (qry_fmap [B,h,w,C], spp_fmaps [B*N*K,s,s,C]) in the
+        layout of ``FGN.extract_feat`` (fp32, contiguous, on the trainer's device; read, never written): the two backbone
+        passes are skipped and these stand in; the batch stays whole (boxes, masks, ``img_shape`` and the image tensors'
+        sizes are still read); a mismatch raises a ValueError naming the argument.  ``feature_grads``: also the gradient of
+        the summed losses - the sum the parameter gradients are taken of - at those two tensors, in
+        ``self.feature_grads`` = {'qry_fmap', 'spp_fmaps'} (of this call alone: not divided by ``cumulative_iters``, not
+        all-reduced; {} when not asked).  A caller's extractor trains with
+        ``qry_fmap_with_graph.backward(trainer.feature_grads['qry_fmap'])``.  ``self.grads`` are the same bits with and
+        without it, and without it a step makes the launches it always made."""
         m = self.model
         m._tape = {}
+        fg = {} if feature_grads else None
+        self.feature_grads = {}
         try:
             with ops.gemm_math('f32'):      # the transposed-weight layers packed inside backward() live for one call
                 # (the detector's front: source-size queries, supports cut from their sources, augmentation)
-                losses = forward_train(m, perm_fn=perm_fn, bn_momentum=self.bn_momentum, **m._train_front(**batch))
+                losses = forward_train(m, perm_fn=perm_fn, bn_momentum=self.bn_momentum, features=features,
+                                       **m._train_front(**batch))
                 self._bn_calls += 1 + (m._tape.get('roi') is not None)
-                g = backward(m, self.W, m._tape)
+                g = backward(m, self.W, m._tape, fg)
         finally:
             m._tape = None
+        if fg is not None:
+            self.feature_grads = fg
         # a gradient for EVERY trainable tensor, zeros where this batch produced none (no positive RoI -> the mask
         # head, no sampled RoI -> the whole RoI stage).  The reference gets zero - not None - gradients there
         # (loss_mask = mask_pred.sum() * 0 on an empty selection), so Adagrad still applies its weight decay; and the
@@ -1193,12 +1301,12 @@ class Trainer:
         self.grads = {k: g[k] if k in g else torch.zeros_like(w) for k, w in self.W.items()}
         return losses
 
-    def step(self, batch: dict, perm_fn=torch.randperm) -> dict:
+    def step(self, batch: dict, perm_fn=torch.randperm, features=None, feature_grads: bool = False) -> dict:
         """One optimisation step on this rank's batch.  Under an initialised ``torch.distributed`` group (one process
         per GPU, backend "nccl" = RCCL) the gradients are averaged over the ranks first - one all-reduce of one flat
         bucket - so every rank applies the same update (data-parallel training; BatchNorm statistics stay per rank,
-        like torch DDP without SyncBN)."""
-        losses = self.forward_backward(batch, perm_fn)
+        like torch DDP without SyncBN).  ``features`` / ``feature_grads``: as for ``forward_backward``."""
+        losses = self.forward_backward(batch, perm_fn, features=features, feature_grads=feature_grads)
         if self.cumulative_iters == 1:
             losses.update(self.apply_gradients())
             return losses

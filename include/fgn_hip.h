@@ -777,6 +777,30 @@ int fgn_grad_sqnorm_multi_f32(const float* const* grads, const long long* n, int
 int fgn_grad_accumulate_multi_f32(float* const* accs, const float* const* grads, const long long* n, int count, float a,
                                   int first, void* stream);
 
+/* ---- feature gradients: the gradient of the summed losses at the two C4 feature tensors ---------------------- */
+
+/* Adjoint of fgn_roi_align_nhwc_f32 (both flavours; no post_shift, no ReLU): dy [R,P,P,C], rois [R,5] -> dx
+ * [n_img,H,W,C]; accumulate = 0 overwrites dx (R = 0: zero fill), 1 adds onto it.  Same box transform, sampling grid,
+ * sample coordinates and validity as the forward kernel (csrc/roi_geom.h).  Gather form, no atomics: every dx element
+ * is owned by one thread, which adds its terms in (RoI index, bin row, bin column) order - the same bits on every
+ * run.  RoIs of other images (batch index != the image), with an empty sampling grid or wholly outside the map
+ * contribute nothing.  C % 4 == 0, 0 < out_size <= 32, n_img <= 65535, else FGN_ERR_SHAPE. */
+int fgn_roi_align_backward_nhwc_f32(const float* dy, const float* rois, float* dx, int n_rois, int n_img, int H, int W,
+                                    int C, int out_size, float spatial_scale, int sampling_ratio, int aligned,
+                                    int accumulate, void* stream);
+
+/* Backward of the AG-RPN guidance G[bN+n,y,x,c] = qry_fmap[b,y,x,c] * vec[bN+n,c] from the sparse gradient of rpn_conv's
+ * input: T [rows,9,C] = the nine taps each active (pass, pixel) row sends to its 3x3 neighbourhood, and a CSR index
+ * built on the host: pix [n_touched] flat pixels b*hw + y*w + x in ascending order, seg [n_touched*N + 1] the entry range
+ * of every (touched pixel, pass), ent [nnz] = row*9 + tap, img_seg [B + 1] the touched-pixel range of every image.
+ * d_qry [B,hw,C] (accumulate = 0: zero-filled first, untouched pixels stay zero; 1: added onto) receives
+ * sum_n vec[bN+n,c] dG_n[c], dG_n = the taps of pass n in list order; slab [n_touched,N,C] (scratch) = qry_fmap dG_n;
+ * d_vec [B*N,C] = the sum of slab over the image's touched pixels in ascending order.  No atomics.  The index is
+ * trusted (the caller validates it on the host).  C % 4 == 0. */
+int fgn_guidance_backward_f32(const float* T, const int32_t* pix, const int32_t* seg, const int32_t* ent,
+                              const int32_t* img_seg, const float* qry_fmap, const float* vec, float* d_qry, float* slab,
+                              float* d_vec, int n_touched, int B, int N, int hw, int C, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
