@@ -1538,7 +1538,7 @@ static int h2_pick(long long M, int Cout, int K, int grp_rows, int grp_valid, in
     return (bm_x3 == 128 && !grp_rows) ? 64 : bm_x3;
 }
 
-template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1>
+template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1, bool DUAL = false>
 static int launch_h2_cfg(ConvParams& p, const H2Im2col& q2, int M_max, hipStream_t stream) {
     constexpr int BM = 32 * RB * WMW, BN = 64 * WNW;
     const int m_tiles = cdiv(M_max, BM);
@@ -1546,13 +1546,19 @@ static int launch_h2_cfg(ConvParams& p, const H2Im2col& q2, int M_max, hipStream
     set_band(p, BM, m_tiles, (long long)BN * p.K * 4);
     const int tiles = m_tiles * p.n_tiles_n;
     static unsigned long long ok = 0ull;
-    hipError_t attr = fgn_allow_full_lds(reinterpret_cast<const void*>(conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL, KG>), &ok);
+    const void* fn;
+    if constexpr (DUAL) fn = reinterpret_cast<const void*>(conv_pw_h2_kernel_dual<WMW, WNW, RB, NST, KG>);
+    else fn = reinterpret_cast<const void*>(conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL, KG>);
+    hipError_t attr = fgn_allow_full_lds(fn, &ok);
     if (attr != hipSuccess) return (int)attr;
     const size_t lds = (size_t)KG * NST * (BM * 128 + 2 * BN * 64);            // a ring per K-group
     const int per_cu = std::min(3, (int)(160 * 1024 / lds));         // resident workgroups per CU (LDS-bound)
     const int grid = std::min(256 * per_cu, (tiles + 7) / 8 * 8);
     p.stamp = fgn_next_stamp_record();
-    FGN_LAUNCH_TIMED((conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL, KG>), dim3(grid), dim3(64 * WMW * WNW * KG), lds, stream, p, q2, tiles);
+    if constexpr (DUAL)
+        FGN_LAUNCH_TIMED((conv_pw_h2_kernel_dual<WMW, WNW, RB, NST, KG>), dim3(grid), dim3(64 * WMW * WNW * KG), lds, stream, p, q2, tiles);
+    else
+        FGN_LAUNCH_TIMED((conv_pw_h2_kernel<WMW, WNW, RB, NST, IM2COL, KG>), dim3(grid), dim3(64 * WMW * WNW * KG), lds, stream, p, q2, tiles);
     FGN_LAUNCH_CHECK();
     return FGN_OK;
 }
@@ -1597,6 +1603,13 @@ static int launch_h2(const ConvParams& p0, int M_max, int n_groups, int bm, hipS
     const int cfg = h2_pick(M_max, p.Cout, p.K, p.grp_rows, p.grp_valid, bm == H2_BM_KG2 ? 64 : bm);
     if (cfg == 0) return FGN_ERR_SHAPE;
     const int kgroups = bm == H2_BM_KG2 ? 2 : (bm == 0 ? fgn_h2_k_groups(M_max, p.Cout, p.K, p.grp_rows, p.grp_valid) : 1);
+    if (p.x2) {        // two operands: the dual instances (never with the implicit-GEMM loader)
+        if (im) return FGN_ERR_SHAPE;
+        if (kgroups == 2) return launch_h2_cfg<2, 2, 1, 2, false, 2, true>(p, none, M_max, stream);
+        if (cfg == 264) return launch_h2_cfg<4, 1, 1, 2, false, 1, true>(p, none, M_max, stream);
+        return cfg == 128 ? launch_h2_cfg<2, 2, 2, 2, false, 1, true>(p, none, M_max, stream)
+                          : launch_h2_cfg<2, 2, 1, 2, false, 1, true>(p, none, M_max, stream);
+    }
     if (kgroups == 2)
         return im ? launch_h2_cfg<2, 2, 1, 2, true, 2>(p, *im, M_max, stream) : launch_h2_cfg<2, 2, 1, 2, false, 2>(p, none, M_max, stream);
     if (im) {
@@ -1771,6 +1784,15 @@ extern "C" int fgn_conv1x1_dual_h2_nhwc_f32(const float* x, const float* x2, con
     const int rc = describe_dual(p, MATH_H2, x, x2, x2_rows, x2_total_rows, w_h2, y, shift, rows, Cin1, Cin2, Cout, cout_pad, relu);
     if (rc != FGN_DESCRIBED) return rc;
     return launch_h2(p, rows, 1, 0, stream);
+}
+// the same with the tile code forced (bm as for fgn_gemm_h2_f32; tests, tools)
+extern "C" int fgn_conv1x1_dual_h2_bm_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
+                                               const void* w_h2, float* y, const float* shift, int rows, int Cin1, int Cin2,
+                                               int Cout, int cout_pad, int relu, int bm, hipStream_t stream) {
+    ConvParams p;
+    const int rc = describe_dual(p, MATH_H2, x, x2, x2_rows, x2_total_rows, w_h2, y, shift, rows, Cin1, Cin2, Cout, cout_pad, relu);
+    if (rc != FGN_DESCRIBED) return rc;
+    return launch_h2(p, rows, 1, bm, stream);
 }
 
 // y[rows, Cout] = relu?(x[rows, K] * W^T + shift + residual) with W given as its plane image (ops.pack_x3 / ops.pack_h2);

@@ -150,8 +150,18 @@ struct H2Im2col {
 #endif
 struct H2Yes { static constexpr bool value = true; };
 struct H2No { static constexpr bool value = false; };
-template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1>
-__global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_h2_kernel(const ConvParams p, const H2Im2col q2, const int total_tiles) {
+// The body of both kernels below.  Two operands: the K-tiles from p.kt1 on come from a second one (p.x2, p.x2_rows: conv3 +
+// shortcut of a stage's first block as one K loop, three launches of an episode).  DUAL says at compile time whether
+// there is one: H2_ONE - the instance holds no second descriptor, no second set of row offsets and no select of descriptor
+// and offsets per K-tile (that select cost the one-operand launches 1.4 %: DESIGN 8, item 1) -, H2_TWO, or H2_EITHER: the
+// look at p.x2 at run time that every instance had before.  Only the one-operand two-K-group instance without the
+// implicit-GEMM loader keeps H2_EITHER: as H2_ONE each of the five 6504 x 1024 -> 256 launches of an episode measured 2 us
+// (8 %) slower in isolation, in both runs (profiles/launch_fixed_cost_ab.json, DESIGN appendix A row 63) - the instance
+// that lost to the branch-free cursor too (OLD_CURSOR below).
+constexpr int H2_ONE = 0, H2_TWO = 1, H2_EITHER = 2;
+template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG, int DUAL>
+__device__ __forceinline__ void conv_pw_h2_body(const ConvParams p, const H2Im2col q2, const int total_tiles) {
+    static_assert(!(DUAL != H2_ONE && IM2COL), "the implicit-GEMM loader reads one operand");
     // NW / NTHR_G: waves / threads of ONE K-group (the roles wm, wn and the DMA rows are those of the wave inside its group)
     constexpr int BM = 32 * RB * WMW, BN = 64 * WNW, NW = WMW * WNW, NTHR_G = 64 * NW, NTHR = NTHR_G * KG;
     static_assert(KG == 1 || KG == 2, "one or two K-groups");
@@ -202,8 +212,8 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     const int src_c4 = col4 ^ ((row0 >> 1) & 7);
     const i32x4 x_rs = make_rsrc(p.x, p.x_bytes);
     const i32x4 w_rs = make_rsrc(p.w3, p.w3_bytes);
-    const bool dual = !IM2COL && p.x2 != nullptr;
-    const i32x4 x2_rs = make_rsrc(dual ? p.x2 : p.x, dual ? p.x2_bytes : p.x_bytes);
+    [[maybe_unused]] const bool dual = DUAL == H2_EITHER ? p.x2 != nullptr : DUAL == H2_TWO;
+    [[maybe_unused]] const i32x4 x2_rs = DUAL != H2_ONE ? make_rsrc(dual ? p.x2 : p.x, dual ? p.x2_bytes : p.x_bytes) : x_rs;
     const int KT = p.K / BK / KG;                // K-steps: the K-tiles of one group; >= 2, K / BK a multiple of KG (launcher)
     const unsigned kt_bytes = (unsigned)(2 * p.npad3 * 64);          // one K-tile of the image, both planes, all rows
     const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)reinterpret_cast<size_t>(smem_h2) + kg * (NST * STAGE));   // the group's ring
@@ -240,8 +250,10 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     };
 
     // IM2COL: a[i] = byte offset of filter tap (0, 0) of the row's receptive field (may lie before the tensor: wraps),
-    // a2[i] = bit (ky KW + kx) set when the tap is inside the image (and the row < M) | bit 31 when the row is of tensor 1
-    struct Offs { unsigned a[A_LD], a2[A_LD], b[B_LD]; };
+    // a2[i] = bit (ky KW + kx) set when the tap is inside the image (and the row < M) | bit 31 when the row is of tensor 1;
+    // two operands: a2[i] = the row's byte offset in the second one; H2_ONE outside IM2COL: no a2
+    constexpr int A2_LD = (IM2COL || DUAL != H2_ONE) ? A_LD : 1;
+    struct Offs { unsigned a[A_LD], a2[A2_LD], b[B_LD]; };
     unsigned b_lds[B_LD];
 #pragma unroll
     for (int i = 0; i < B_LD; ++i) {
@@ -250,6 +262,7 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     }
     auto offsets = [&](int m0, int n0) -> Offs {
         Offs o;
+        o.a2[0] = 0u;
         // rows past M, and the rows of a group past its valid ones (the unwritten tail of a Winograd V), are fetched out of
         // bounds - zeros: a wave's rows share one scale, so whatever lies in memory there must not reach the fragment
         const int g_end = p.grp_rows ? (m0 / p.grp_rows) * p.grp_rows + grp_valid : M;
@@ -282,8 +295,10 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
             }
             const bool in = m < M && m < g_end;
             o.a[i] = in ? (unsigned)((m * p.Cin + src_c4 * 4) * 4) : OOB;
-            o.a2[i] = OOB;
-            if (dual && in) o.a2[i] = (unsigned)(((p.x2_rows ? p.x2_rows[m] : m) * p.cin2 + src_c4 * 4) * 4);
+            if constexpr (DUAL != H2_ONE) {
+                o.a2[i] = OOB;
+                if (dual && in) o.a2[i] = (unsigned)(((p.x2_rows ? p.x2_rows[m] : m) * p.cin2 + src_c4 * 4) * 4);
+            }
         }
         unsigned g0 = 0;
         if (p.grp_rows) g0 = (unsigned)(m0 / p.grp_rows) * (unsigned)(KT * KG) * kt_bytes;
@@ -300,7 +315,7 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     // and no branch per K-tile.  IM2COL: the K-tiles of a filter row are contiguous in an NHWC row (Cin * 4 = 128 bytes
     // x the slices of a tap), so the tap offset grows by 128 per K-tile and by the rest of the image row at a row's end.
     const unsigned ko_step = (unsigned)(KG * BK * 4), kb_step = (unsigned)KG * kt_bytes;
-    const unsigned ko1 = dual ? (unsigned)(p.kt1 * BK * 4) : 0xffffffffu;      // the second operand's first K-tile, in bytes of a row (one operand: never reached)
+    [[maybe_unused]] const unsigned ko1 = (DUAL != H2_ONE && dual) ? (unsigned)(p.kt1 * BK * 4) : 0xffffffffu;      // the second operand's first K-tile, in bytes of a row (one operand: never reached)
     unsigned c_ko = 0u, c_kb = 0u;                   // the K-tile's bytes in an activation row / in the weight image
     int c_tap = 0, c_cs = 0, c_kx = 0;               // IM2COL: filter tap, channel slice of it, column of the tap
     unsigned c_off0 = 0u, c_off1 = 0u;               //         the tap's byte offset in tensor 0 / 1
@@ -351,13 +366,16 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
             const bool ok = (o.a2[i] >> c_tap) & 1u;
             const unsigned voff = ok ? o.a[i] + ((o.a2[i] >> 31) ? c_off1 : c_off0) : OOB;     // out-of-image taps: zeros
             lds_dma16_s(x_rs, dst, voff, 0u);
-        } else {
+        } else if constexpr (DUAL != H2_ONE) {
             // the K-tiles from p.kt1 on come from the second operand: a select of descriptor and offsets, not a branch
             const bool second = c_ko >= ko1;
             i32x4 rs;
             rs[0] = second ? x2_rs[0] : x_rs[0]; rs[1] = second ? x2_rs[1] : x_rs[1];
             rs[2] = second ? x2_rs[2] : x_rs[2]; rs[3] = x_rs[3];
-            lds_dma16_s(rs, dst, second ? o.a2[i] : o.a[i], second ? c_ko - ko1 : c_ko);
+            // (the K offset is selected next to the row offset, in a vector register: back into a scalar one by hand)
+            lds_dma16_s(rs, dst, second ? o.a2[i] : o.a[i], __builtin_amdgcn_readfirstlane(second ? c_ko - ko1 : c_ko));
+        } else {
+            lds_dma16_s(x_rs, dst, o.a[i], c_ko);
         }
     };
 
@@ -368,10 +386,12 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
         const unsigned st = lds_base + wr;
         const unsigned sa = st + wave_row_bytes;
         const unsigned ko = (unsigned)(kt * BK * 4);
-        if (dual && kt >= p.kt1) {
+        bool second = false;
+        if constexpr (DUAL != H2_ONE) second = dual && kt >= p.kt1;
+        if (second) {
             const unsigned ko2 = (unsigned)((kt - p.kt1) * BK * 4);
 #pragma unroll
-            for (int i = 0; i < A_LD; ++i) lds_dma16_s(x2_rs, sa + i * ROWS_PER_PASS * 128, o.a2[i], ko2);
+            for (int i = 0; i < A_LD; ++i) lds_dma16_s(x2_rs, sa + i * ROWS_PER_PASS * 128, o.a2[DUAL != H2_ONE ? i : 0], ko2);
         } else {
 #pragma unroll
             for (int i = 0; i < A_LD; ++i) lds_dma16_s(x_rs, sa + i * ROWS_PER_PASS * 128, o.a[i], ko);
@@ -803,4 +823,15 @@ __global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_
     }
 #endif
     leave();
+}
+
+// The one-operand instance: every launch but conv3 + shortcut.
+template <int WMW, int WNW, int RB, int NST, bool IM2COL, int KG = 1>
+__global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_h2_kernel(const ConvParams p, const H2Im2col q2, const int total_tiles) {
+    conv_pw_h2_body<WMW, WNW, RB, NST, IM2COL, KG, (KG == 2 && !IM2COL) ? H2_EITHER : H2_ONE>(p, q2, total_tiles);
+}
+// The two-operand instance (launches with p.x2; never the implicit-GEMM loader).
+template <int WMW, int WNW, int RB, int NST, int KG = 1>
+__global__ __launch_bounds__(64 * WMW * WNW * KG, KG == 1 ? 2 : 1) void conv_pw_h2_kernel_dual(const ConvParams p, const H2Im2col q2, const int total_tiles) {
+    conv_pw_h2_body<WMW, WNW, RB, NST, false, KG, H2_TWO>(p, q2, total_tiles);
 }

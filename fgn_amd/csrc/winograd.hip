@@ -384,6 +384,202 @@ __global__ __launch_bounds__(256) void wg4_output_kernel(const float* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The narrow instances: the same values through a short prologue.  Most layers of an episode start under one wave per
+// SIMD, so nothing hides the instructions in front of the first load, and in the kernels above (the wide instances) they
+// are many: two 64-bit and three 32-bit divisions per thread, 36 64-bit multiplies for the position addresses, 36 loads
+// each under its own bounds branch, and the device count on the way to all of it.  Here
+//   - a thread is one (tile, channel vector) of the grid, no loop; every offset is an unsigned 32-bit BYTE offset from a
+//     wave-uniform base (the launcher shows that every tensor of the launch ends below 2 GiB, wg4_narrow_fits),
+//   - the three divisions (channel vectors, tiles per row, tile rows per image) are a multiply-high each by a constant
+//     of the launcher (WgDiv), whatever the channel count,
+//   - the two tensors of a WgSeg launch own whole workgroups: which tensor a thread works on is a scalar,
+//   - the patch loads go to the clamped coordinate and are issued without a condition, the zero fill is a select behind
+//     them; position addresses advance by one add each,
+//   - the device count is requested first and compared last: every tile below the capacity n_img loads (x, in_scale and
+//     Mo are allocated at capacity), only the stores wait for the count.
+// The arithmetic of a (tile, channel vector) - vmul_rn, wg4_bt / wg4_at, the order of the passes, shift, ReLU - is the
+// code of the wide instances: the results are the same bytes (tests/test_hip_wg_index.py).
+// ------------------------------------------------------------------------------------------------
+// n / d for 0 <= n < 2^31 as (n * mul) >> (32 + shift); mul == 0 stands for d == 1.  With L = ceil(log2 d) and
+// mul = ceil(2^(31 + L) / d) the quotient is exact: mul * d - 2^(31 + L) < d <= 2^L (Granlund & Montgomery 1994, thm 4.2).
+struct WgDiv {
+    uint32_t mul, shift;
+};
+static WgDiv wg_div(uint32_t d) {
+    WgDiv r = {0u, 0u};
+    if (d > 1) {
+        const int L = 32 - __builtin_clz(d - 1);
+        r.mul = (uint32_t)(((1ull << (31 + L)) + d - 1) / d);
+        r.shift = (uint32_t)(L - 1);
+    }
+    return r;
+}
+__device__ __forceinline__ uint32_t wg_quot(uint32_t n, WgDiv d) { return d.mul ? __umulhi(n, d.mul) >> d.shift : n; }
+
+struct WgMap {            // one tensor of a narrow launch
+    const float* p;       // x of the input transform / y of the output transform
+    int H, W;
+    int n_img;            // capacity (logical images)
+    uint32_t ty, tx;
+    WgDiv dty, dtx;
+    uint32_t elems;       // tiles * channel vectors
+};
+struct WgNarrow {
+    WgMap m[2];
+    uint32_t blocks0;     // workgroups of tensor 0 (all of them when there is no second tensor)
+    uint32_t tiles0;      // tiles of tensor 0 = first tile of tensor 1 in V / Mo
+    uint32_t CV;          // channel vectors per pixel
+    WgDiv dcv, ddiv;      // by CV, by a_img_div
+    uint32_t gs;          // bytes between two positions of V / Mo
+};
+
+template <typename T>
+__device__ __forceinline__ T wg_ld(const void* base, uint32_t off) {
+    return *reinterpret_cast<const T*>(static_cast<const char*>(base) + off);
+}
+template <typename T>
+__device__ __forceinline__ void wg_st(void* base, uint32_t off, T v) {
+    *reinterpret_cast<T*>(static_cast<char*>(base) + off) = v;
+}
+
+// The device count as a VECTOR load, first in the queue of the patch loads.  As a scalar load it shares the counter of
+// the kernel-argument loads, which return out of order: the first late argument would make every wave wait for the
+// count in front of its first patch load.  Vector loads return in order, so a wait for any patch covers the count.
+__device__ __forceinline__ int wg_count_early(const int32_t* n_img_dev) {
+    if (!n_img_dev) return 0x7fffffff;
+    const int32_t* p = n_img_dev;
+    asm volatile("" : "+v"(p));                        // keep the address in vector registers
+    return *p;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void wg4_input_narrow_kernel(const WgNarrow P, const float* __restrict__ in_scale,
+                                                               float* __restrict__ Vo, const int32_t* __restrict__ n_img_dev) {
+    typedef vf<V> T;
+    const int dev_count = wg_count_early(n_img_dev);                   // requested now, needed at the stores
+    const bool second = blockIdx.x >= P.blocks0;                       // scalar
+    const float* __restrict__ x = second ? P.m[1].p : P.m[0].p;
+    const int H = second ? P.m[1].H : P.m[0].H, W = second ? P.m[1].W : P.m[0].W;
+    const uint32_t ty = second ? P.m[1].ty : P.m[0].ty, tx = second ? P.m[1].tx : P.m[0].tx;
+    const WgDiv dty = second ? P.m[1].dty : P.m[0].dty, dtx = second ? P.m[1].dtx : P.m[0].dtx;
+    const uint32_t elems = second ? P.m[1].elems : P.m[0].elems;
+    const int n_cap = second ? P.m[1].n_img : P.m[0].n_img;
+    const uint32_t i = (blockIdx.x - (second ? P.blocks0 : 0u)) * 256u + threadIdx.x;
+    if (i >= elems) return;
+    const uint32_t tl = wg_quot(i, P.dcv), c = i - tl * P.CV;
+    const uint32_t r = wg_quot(tl, dtx), xx = tl - r * tx;
+    const uint32_t img = wg_quot(r, dty), yy = r - img * ty;
+    const uint32_t t = tl + (second ? P.tiles0 : 0u);
+    const uint32_t px = (uint32_t)sizeof(T) * P.CV;                    // bytes of a pixel
+    const int iy0 = 4 * (int)yy - 1, ix0 = 4 * (int)xx - 1;
+    uint32_t ro[6], co[6];
+    bool rok[6], cok[6];
+    const uint32_t row0 = wg_quot(img, P.ddiv) * (uint32_t)H;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        const int iy = iy0 + a, ix = ix0 + a;
+        rok[a] = (unsigned)iy < (unsigned)H;
+        cok[a] = (unsigned)ix < (unsigned)W;
+        ro[a] = (row0 + (uint32_t)min(max(iy, 0), H - 1)) * (uint32_t)W * px;
+        co[a] = (uint32_t)min(max(ix, 0), W - 1) * px + c * (uint32_t)sizeof(T);
+    }
+    T tt[6][6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b < 6; ++b) tt[a][b] = wg_ld<T>(x, ro[a] + co[b]);
+    T s;
+    if (in_scale) s = wg_ld<T>(in_scale, (img * P.CV + c) * (uint32_t)sizeof(T));
+    else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) s[k] = 1.f;
+    }
+#pragma unroll
+    for (int b = 0; b < 6; ++b) {                     // tt[.][b] = B^T (d * s)[.][b], in place
+        T d[6], rr[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) d[a] = vmul_rn<V>((rok[a] && cok[b]) ? tt[a][b] : vzero<V>(), s);
+        wg4_bt<V>(d, rr);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) tt[a][b] = rr[a];
+    }
+    if ((int)img >= min(n_cap, dev_count)) return;
+    uint32_t o = (t * P.CV + c) * (uint32_t)sizeof(T);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        T rr[6];
+        wg4_bt<V>(tt[a], rr);                          // (B^T d) B, row a
+#pragma unroll
+        for (int b = 0; b < 6; ++b) {
+            wg_st<T>(Vo, o, rr[b]);
+            o += P.gs;
+        }
+    }
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void wg4_output_narrow_kernel(const WgNarrow P, const float* __restrict__ Mo,
+                                                                const float* __restrict__ shift,
+                                                                const int32_t* __restrict__ n_img_dev, int relu) {
+    typedef vf<V> T;
+    const int dev_count = wg_count_early(n_img_dev);
+    const bool second = blockIdx.x >= P.blocks0;                       // scalar
+    float* __restrict__ y = const_cast<float*>(second ? P.m[1].p : P.m[0].p);
+    const int H = second ? P.m[1].H : P.m[0].H, W = second ? P.m[1].W : P.m[0].W;
+    const uint32_t ty = second ? P.m[1].ty : P.m[0].ty, tx = second ? P.m[1].tx : P.m[0].tx;
+    const WgDiv dty = second ? P.m[1].dty : P.m[0].dty, dtx = second ? P.m[1].dtx : P.m[0].dtx;
+    const uint32_t elems = second ? P.m[1].elems : P.m[0].elems;
+    const int n_cap = second ? P.m[1].n_img : P.m[0].n_img;
+    const uint32_t i = (blockIdx.x - (second ? P.blocks0 : 0u)) * 256u + threadIdx.x;
+    if (i >= elems) return;
+    const uint32_t tl = wg_quot(i, P.dcv), c = i - tl * P.CV;
+    const uint32_t t = tl + (second ? P.tiles0 : 0u);
+    T mm[6][6];                                        // all 36 loads in flight at once
+    {
+        uint32_t o = (t * P.CV + c) * (uint32_t)sizeof(T);
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = 0; b < 6; ++b) {
+                mm[a][b] = wg_ld<T>(Mo, o);
+                o += P.gs;
+            }
+    }
+    const T sh = shift ? wg_ld<T>(shift, c * (uint32_t)sizeof(T)) : vzero<V>();
+    const uint32_t r = wg_quot(tl, dtx), xx = tl - r * tx;
+    const uint32_t img = wg_quot(r, dty), yy = r - img * ty;
+    T st[4][6];                                        // st[i][b] = (A^T m)[i][b]
+#pragma unroll
+    for (int b = 0; b < 6; ++b) {
+        T m[6], rr[4];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) m[a] = mm[a][b];
+        wg4_at<V>(m, rr);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) st[k][b] = rr[k];
+    }
+    if ((int)img >= min(n_cap, dev_count)) return;
+    const uint32_t px = (uint32_t)sizeof(T) * P.CV;
+    const uint32_t oy0 = 4u * yy, ox0 = 4u * xx;
+    uint32_t orow = ((img * (uint32_t)H + oy0) * (uint32_t)W + ox0) * px + c * (uint32_t)sizeof(T);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        T rr[4];
+        wg4_at<V>(st[a], rr);
+        if ((int)(oy0 + a) < H) {
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                if ((int)(ox0 + b) >= W) continue;
+                T v = rr[b] + sh;
+                if (relu) v = vrelu<V>(v);
+                wg_st<T>(y, orow + b * px, v);
+            }
+        }
+        orow += (uint32_t)W * px;
+    }
+}
+
 // Channel vector width of a thread for `elems` = tiles * channels (tile, channel) pairs, and whether the input transform
 // issues its 36 loads up front.  Measured on MI355X at the cfg3 layer shapes (tools/wg4_ab.py, r03): loads up front wins
 // at every size and width (AG-RPN map 55 -> 36 us at 16-byte vectors, shared_head on 300 RoIs 36 -> 20, layer1 31 -> 14:
@@ -392,6 +588,20 @@ __global__ __launch_bounds__(256) void wg4_output_kernel(const float* __restrict
 // floor of a launch whose every thread does one load and one store round trip - on the rest); 16-byte vectors are kept
 // for launches with several million elements (batched AG-RPN maps).  (The A/B was driven by environment variables, removed
 // since: the library reads none.)
+// With the narrow instances (tools/wg4_ab.py, the vector width forced through fgn_winograd4_*_ix_f32; us per launch at
+// 4 / 8 / 16 bytes, two runs, both within 0.5 us of each other; wide instance at 8 bytes in brackets):
+//             input transform               output transform
+//   AG-RPN    31.0 / 33.9 / 35.2  (34.5)    25.6 / 25.4 / 26.3  (32.3)
+//   300 RoIs  22.2 / 21.3 / 20.0  (21.8)    19.8 / 18.7 / 18.2  (23.0)
+//   100 RoIs   9.8 /  8.8 /  8.7   (9.5)     7.4 /  7.5 /  6.5   (9.9)
+//   mask 0    14.2 / 16.0 / 13.4  (16.6)     4.4 /  4.3 /  4.8   (6.8)
+//   mask 1     6.2 /  5.9 /  7.1   (6.9)     4.5 /  4.4 /  4.8   (6.8)
+//   layer3     4.7 /  5.1 /  6.3   (6.9)     4.4 /  4.5 /  4.7   (6.8)
+//   layer2     6.5 /  7.9 /  7.7   (9.5)     4.6 /  6.1 /  5.5   (8.3)
+//   layer1    11.2 / 12.0 / 13.0  (13.4)     9.9 / 10.4 / 10.9  (13.2)
+// 4 bytes now wins the input transform of the backbone layers and the AG-RPN map by 0.4-2.9 us and loses the shared head's
+// by 1 us; the winners are not ordered by size, so no threshold on `elems` separates them: the rule stays (8 bytes is
+// best or within 1.5 us of the best everywhere but the AG-RPN and mask-0 inputs: 2.9, 2.6).  (profiles/launch_fixed_cost_wg4_widths.txt)
 static int wg4_vec(long long elems) { return elems >= (4ll << 20) ? 4 : 2; }
 static bool wg4_eager(long long) { return true; }
 // vec * 10 + eager of the input transform / vec * 10 of the output transform for a layer (lets a profiler name the
@@ -401,14 +611,68 @@ extern "C" int fgn_winograd4_variant(int tiles_total, int C, int is_output) {
     return v * 10 + ((!is_output && wg4_eager((long long)tiles_total * (C / v))) ? 1 : 0);
 }
 
+// Whether the narrow instances can address a launch: every tensor it touches ends below 2 GiB, so a 32-bit byte offset
+// reaches each element (the element count is then below 2^31 as well).  From the sizes alone: nothing is allocated.
+static bool wg4_narrow_fits(long long imgs0, int H0, int W0, long long imgs1, int H1, int W1, long long n_scale, int C,
+                            int t_pad) {
+    const long long lim = 0x7fffffffll, cb = 4ll * C;
+    return imgs0 * H0 * W0 * cb <= lim && imgs1 * H1 * W1 * cb <= lim && n_scale * cb <= lim && 36ll * t_pad * cb <= lim;
+}
+static void wg4_map(WgMap& m, const float* p, int n_img, int H, int W, int cv) {
+    m.p = p; m.H = H; m.W = W; m.n_img = n_img;
+    m.ty = (uint32_t)(H + 3) / 4; m.tx = (uint32_t)(W + 3) / 4;
+    m.dty = wg_div(m.ty); m.dtx = wg_div(m.tx);
+    m.elems = p ? (uint32_t)n_img * m.ty * m.tx * (uint32_t)cv : 0u;
+}
+static WgNarrow wg4_narrow(const float* p0, int n_img0, int a_img_div, int H0, int W0, const float* p1, int n_img1, int H1,
+                           int W1, int C, int vec, int t_pad, int* grid) {
+    WgNarrow P;
+    const int cv = C / vec;
+    wg4_map(P.m[0], p0, n_img0, H0, W0, cv);
+    wg4_map(P.m[1], p1, n_img1, H1, W1, cv);
+    P.blocks0 = (P.m[0].elems + 255u) / 256u;
+    P.tiles0 = (uint32_t)n_img0 * P.m[0].ty * P.m[0].tx;
+    P.CV = (uint32_t)cv;
+    P.dcv = wg_div(P.CV);
+    P.ddiv = wg_div((uint32_t)a_img_div);
+    P.gs = (uint32_t)t_pad * (uint32_t)C * 4u;
+    *grid = (int)(P.blocks0 + (P.m[1].elems + 255u) / 256u);
+    return P;
+}
+// THE rule of the launchers below and of fgn_winograd4_index_bits: whether a launch of these sizes runs on the narrow
+// instances.  n_img1 = 0: one tensor; input transform: x holds ceil(n_img / a_img_div) images and, with_scale, an
+// in_scale of n_img rows is read; output transform: y holds n_img images (a_img_div 1, no scale).  The narrow input
+// instances issue their loads up front: a launch that wg4_eager sends to the column-by-column form stays wide.
+static bool wg4_takes_narrow(bool is_output, int n_img, int a_img_div, int H, int W, int n_img1, int H1, int W1, int C,
+                             int t_pad, bool with_scale, int vec_force) {
+    if (a_img_div < 1 || C < 4) return false;
+    const long long tiles_all = (long long)n_img * ((H + 3) / 4) * ((W + 3) / 4) + (long long)n_img1 * ((H1 + 3) / 4) * ((W1 + 3) / 4);
+    const int vec = vec_force ? vec_force : wg4_vec(tiles_all * C);
+    if (!is_output && !wg4_eager(tiles_all * (C / vec))) return false;
+    const long long imgs0 = is_output ? n_img : (n_img + a_img_div - 1) / a_img_div;
+    return wg4_narrow_fits(imgs0, H, W, n_img1, H1, W1, (!is_output && with_scale) ? n_img : 0, C, t_pad);
+}
+// The index width a launch of these sizes takes: 32 (narrow instances: wg4_input_narrow_kernel / wg4_output_narrow_kernel)
+// or 64 (wide: wg4_input_kernel / wg4_output_kernel).  Arguments as for fgn_winograd4_input_ix_f32 / _output_ix_f32.
+extern "C" int fgn_winograd4_index_bits(int n_img, int a_img_div, int H, int W, int n_img1, int H1, int W1, int C, int t_pad,
+                                        int with_scale, int is_output) {
+    return wg4_takes_narrow(is_output != 0, n_img, a_img_div, H, W, n_img1, H1, W1, C, t_pad, with_scale != 0, 0) ? 32 : 64;
+}
+
 #define WG4_IN_LAUNCH(VV, EE)                                                                                          \
     FGN_LAUNCH_TIMED((wg4_input_kernel<VV, EE>), dim3(grid), dim3(256), 0, stream, x, in_scale, V, n_img_dev, n_img,  \
                      a_img_div, H, W, C / VV, ty, tx, t_pad, total, seg)
+#define WG4_IN_NARROW(VV)                                                                                              \
+    FGN_LAUNCH_TIMED((wg4_input_narrow_kernel<VV>), dim3(ngrid), dim3(256), 0, stream, P, in_scale, V, n_img_dev)
 
+// index_bits: 0 = by the sizes, 32 / 64 = that instance (32 on sizes it cannot address: FGN_ERR_SHAPE);
+// vec_force: 0 = wg4_vec's width, 1 / 2 / 4 = that many channels per thread (tools/wg4_ab.py)
 static int wg4_input_launch(const float* x, const float* in_scale, float* V, const int32_t* n_img_dev, int n_img,
                             int a_img_div, int H, int W, int C, int t_pad, const float* x1, int n_img1, int H1, int W1,
-                            hipStream_t stream) {
+                            int index_bits, int vec_force, hipStream_t stream) {
     if (!x || !V) return FGN_ERR_ARG;
+    if (index_bits != 0 && index_bits != 32 && index_bits != 64) return FGN_ERR_ARG;
+    if (vec_force != 0 && vec_force != 1 && vec_force != 2 && vec_force != 4) return FGN_ERR_ARG;
     if (n_img <= 0) return FGN_OK;
     const int ty = (H + 3) / 4, tx = (W + 3) / 4;
     WgSeg seg;
@@ -417,10 +681,23 @@ static int wg4_input_launch(const float* x, const float* in_scale, float* V, con
     const long long tiles_all = (long long)seg.tiles0 + (x1 ? (long long)n_img1 * seg.ty * seg.tx : 0);
     if (C % 4 != 0 || a_img_div < 1 || H < 1 || W < 1 || tiles_all > t_pad) return FGN_ERR_SHAPE;
     if (x1 && (in_scale || n_img_dev || a_img_div != 1 || n_img1 < 1 || H1 < 1 || W1 < 1)) return FGN_ERR_SHAPE;
-    const int vec = wg4_vec(tiles_all * C);
+    const int vec = vec_force ? vec_force : wg4_vec(tiles_all * C);
     const long long total = tiles_all * (C / vec);
-    const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 32);
     const bool eager = wg4_eager(total);
+    const bool fits = wg4_takes_narrow(false, n_img, a_img_div, H, W, x1 ? n_img1 : 0, H1, W1, C, t_pad, in_scale != nullptr, vec_force);
+    if (index_bits == 32 && !fits) return FGN_ERR_SHAPE;
+    if (fits && index_bits != 64) {
+        int ngrid = 0;
+        const WgNarrow P = wg4_narrow(x, n_img, a_img_div, H, W, x1, n_img1, H1, W1, C, vec, t_pad, &ngrid);
+        switch (vec) {
+            case 1: WG4_IN_NARROW(1); break;
+            case 2: WG4_IN_NARROW(2); break;
+            default: WG4_IN_NARROW(4); break;
+        }
+        FGN_LAUNCH_CHECK();
+        return FGN_OK;
+    }
+    const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 32);
     switch (vec * 10 + (eager ? 1 : 0)) {
         case 11: WG4_IN_LAUNCH(1, true); break;
         case 10: WG4_IN_LAUNCH(1, false); break;
@@ -435,32 +712,57 @@ static int wg4_input_launch(const float* x, const float* in_scale, float* V, con
 
 extern "C" int fgn_winograd4_input_f32(const float* x, const float* in_scale, float* V, const int32_t* n_img_dev,
                                        int n_img, int a_img_div, int H, int W, int C, int t_pad, hipStream_t stream) {
-    return wg4_input_launch(x, in_scale, V, n_img_dev, n_img, a_img_div, H, W, C, t_pad, nullptr, 0, 1, 1, stream);
+    return wg4_input_launch(x, in_scale, V, n_img_dev, n_img, a_img_div, H, W, C, t_pad, nullptr, 0, 1, 1, 0, 0, stream);
 }
 // two tensors (e.g. the query map and the support maps of a backbone layer) into consecutive tile ranges of one V
 extern "C" int fgn_winograd4_input2_f32(const float* x0, int n_img0, int H0, int W0, const float* x1, int n_img1, int H1,
                                         int W1, float* V, int C, int t_pad, hipStream_t stream) {
     if (!x1) return FGN_ERR_ARG;
-    return wg4_input_launch(x0, nullptr, V, nullptr, n_img0, 1, H0, W0, C, t_pad, x1, n_img1, H1, W1, stream);
+    return wg4_input_launch(x0, nullptr, V, nullptr, n_img0, 1, H0, W0, C, t_pad, x1, n_img1, H1, W1, 0, 0, stream);
+}
+// both forms with the index width and the vector width forced (tests, tools): x1 == nullptr is the one-tensor form
+extern "C" int fgn_winograd4_input_ix_f32(const float* x, const float* in_scale, float* V, const int32_t* n_img_dev,
+                                          int n_img, int a_img_div, int H, int W, int C, int t_pad, const float* x1,
+                                          int n_img1, int H1, int W1, int index_bits, int vec, hipStream_t stream) {
+    return wg4_input_launch(x, in_scale, V, n_img_dev, n_img, a_img_div, H, W, C, t_pad, x1, x1 ? n_img1 : 0, x1 ? H1 : 1,
+                            x1 ? W1 : 1, index_bits, vec, stream);
 }
 
 #define WG4_OUT_LAUNCH(VV)                                                                                             \
     FGN_LAUNCH_TIMED((wg4_output_kernel<VV>), dim3(grid), dim3(256), 0, stream, Mo, y, shift, n_img_dev, n_img, H, W, \
                      C / VV, ty, tx, t_pad, relu, total, seg)
+#define WG4_OUT_NARROW(VV)                                                                                             \
+    FGN_LAUNCH_TIMED((wg4_output_narrow_kernel<VV>), dim3(ngrid), dim3(256), 0, stream, P, Mo, shift, n_img_dev, relu)
 
 static int wg4_output_launch(const float* Mo, float* y, const float* shift, const int32_t* n_img_dev, int n_img, int H,
-                             int W, int C, int t_pad, int relu, float* y1, int n_img1, int H1, int W1, hipStream_t stream) {
+                             int W, int C, int t_pad, int relu, float* y1, int n_img1, int H1, int W1, int index_bits,
+                             int vec_force, hipStream_t stream) {
     if (!Mo || !y) return FGN_ERR_ARG;
+    if (index_bits != 0 && index_bits != 32 && index_bits != 64) return FGN_ERR_ARG;
+    if (vec_force != 0 && vec_force != 1 && vec_force != 2 && vec_force != 4) return FGN_ERR_ARG;
     if (n_img <= 0) return FGN_OK;
     const int ty = (H + 3) / 4, tx = (W + 3) / 4;
     WgSeg seg;
     seg.x = y1; seg.n_img = n_img1; seg.H = H1; seg.W = W1; seg.ty = (H1 + 3) / 4; seg.tx = (W1 + 3) / 4;
     seg.tiles0 = n_img * ty * tx;
     const long long tiles_all = (long long)seg.tiles0 + (y1 ? (long long)n_img1 * seg.ty * seg.tx : 0);
-    if (C % 4 != 0 || tiles_all > t_pad) return FGN_ERR_SHAPE;
+    if (C % 4 != 0 || H < 1 || W < 1 || tiles_all > t_pad) return FGN_ERR_SHAPE;
     if (y1 && (n_img_dev || n_img1 < 1 || H1 < 1 || W1 < 1)) return FGN_ERR_SHAPE;
-    const int vec = wg4_vec(tiles_all * C);
+    const int vec = vec_force ? vec_force : wg4_vec(tiles_all * C);
     const long long total = tiles_all * (C / vec);
+    const bool fits = wg4_takes_narrow(true, n_img, 1, H, W, y1 ? n_img1 : 0, H1, W1, C, t_pad, false, vec_force);
+    if (index_bits == 32 && !fits) return FGN_ERR_SHAPE;
+    if (fits && index_bits != 64) {
+        int ngrid = 0;
+        const WgNarrow P = wg4_narrow(y, n_img, 1, H, W, y1, n_img1, H1, W1, C, vec, t_pad, &ngrid);
+        switch (vec) {
+            case 1: WG4_OUT_NARROW(1); break;
+            case 2: WG4_OUT_NARROW(2); break;
+            default: WG4_OUT_NARROW(4); break;
+        }
+        FGN_LAUNCH_CHECK();
+        return FGN_OK;
+    }
     const int grid = (int)std::min<long long>((total + 255) / 256, 256 * 32);
     switch (vec) {
         case 1: WG4_OUT_LAUNCH(1); break;
@@ -473,13 +775,20 @@ static int wg4_output_launch(const float* Mo, float* y, const float* shift, cons
 
 extern "C" int fgn_winograd4_output_f32(const float* Mo, float* y, const float* shift, const int32_t* n_img_dev,
                                         int n_img, int H, int W, int C, int t_pad, int relu, hipStream_t stream) {
-    return wg4_output_launch(Mo, y, shift, n_img_dev, n_img, H, W, C, t_pad, relu, nullptr, 0, 1, 1, stream);
+    return wg4_output_launch(Mo, y, shift, n_img_dev, n_img, H, W, C, t_pad, relu, nullptr, 0, 1, 1, 0, 0, stream);
 }
 extern "C" int fgn_winograd4_output2_f32(const float* Mo, const float* shift, float* y0, int n_img0, int H0, int W0,
                                          float* y1, int n_img1, int H1, int W1, int C, int t_pad, int relu,
                                          hipStream_t stream) {
     if (!y1) return FGN_ERR_ARG;
-    return wg4_output_launch(Mo, y0, shift, nullptr, n_img0, H0, W0, C, t_pad, relu, y1, n_img1, H1, W1, stream);
+    return wg4_output_launch(Mo, y0, shift, nullptr, n_img0, H0, W0, C, t_pad, relu, y1, n_img1, H1, W1, 0, 0, stream);
+}
+// both forms with the index width and the vector width forced (tests, tools): y1 == nullptr is the one-tensor form
+extern "C" int fgn_winograd4_output_ix_f32(const float* Mo, float* y, const float* shift, const int32_t* n_img_dev,
+                                           int n_img, int H, int W, int C, int t_pad, int relu, float* y1, int n_img1,
+                                           int H1, int W1, int index_bits, int vec, hipStream_t stream) {
+    return wg4_output_launch(Mo, y, shift, n_img_dev, n_img, H, W, C, t_pad, relu, y1, y1 ? n_img1 : 0, y1 ? H1 : 1,
+                             y1 ? W1 : 1, index_bits, vec, stream);
 }
 
 // ----------------------------------------------------------------------------------------------

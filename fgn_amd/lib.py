@@ -33,6 +33,9 @@ SIGNATURES = {
     'fgn_winograd4_output_f32': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_winograd_output_f32': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_winograd4_variant': (_i, [_i, _i, _i]),
+    'fgn_winograd4_index_bits': (_i, [_i] * 11),
+    'fgn_winograd4_input_ix_f32': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p]),
+    'fgn_winograd4_output_ix_f32': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _i, _i, _i, _i, _p]),
     'fgn_winograd_pack_weights_f32': (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     'fgn_winograd4_input2_f32': (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _p]),
     'fgn_winograd4_output2_f32': (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
@@ -80,6 +83,7 @@ SIGNATURES = {
     'fgn_gemm_h2_f32': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_conv1x1_h2_nhwc_f32': (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_conv1x1_dual_h2_nhwc_f32': (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    'fgn_conv1x1_dual_h2_bm_nhwc_f32': (_i, [_p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_winograd_gemm_h2_f32': (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_gemm_x3_f32': (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     'fgn_conv2d_pair_nhwc_f32': (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p] + [_i] * 8 + [_p]),

@@ -43,6 +43,10 @@ X3_KERNELS = {64: 'conv_pw_x3_kernel<2, 1, 6, 2, true>', 128: 'conv_pw_x3_kernel
 H2_KERNELS = {64: 'conv_pw_h2_kernel<2, 2, 1, 2, %s, 1>', 128: 'conv_pw_h2_kernel<2, 2, 2, 2, %s, 1>',
               264: 'conv_pw_h2_kernel<4, 1, 1, 2, %s, 1>', 1064: 'conv_pw_h2_kernel<2, 2, 1, 2, %s, 2>'}
 H2_BM_KG2 = 1064
+# the instances of the launches with a second operand (conv1x1_dual), by the same tile codes; template arguments: waves
+# along M, waves along N, 32-row blocks per wave, LDS stages, K-groups
+H2_DUAL_KERNELS = {64: 'conv_pw_h2_kernel_dual<2, 2, 1, 2, 1>', 128: 'conv_pw_h2_kernel_dual<2, 2, 2, 2, 1>',
+                   264: 'conv_pw_h2_kernel_dual<4, 1, 1, 2, 1>', 1064: 'conv_pw_h2_kernel_dual<2, 2, 1, 2, 2>'}
 
 
 def x3_kernel(rows: int, cout: int, k: int, grp_rows: int = 0, grp_valid: int = 0) -> str:
@@ -57,6 +61,17 @@ def h2_kernel(rows: int, cout: int, k: int, grp_rows: int = 0, grp_valid: int = 
     if tile == 64 and L.fgn_h2_k_groups(rows, cout, k, grp_rows, grp_valid) == 2:
         tile = H2_BM_KG2
     return H2_KERNELS.get(tile, 'conv_pw_h2_kernel<?, %s>') % ('true' if im2col else 'false')
+
+
+def h2_dual_kernel(rows: int, cout: int, k: int, bm: int = 0) -> str:
+    """The conv_pw_h2_kernel_dual instance a two-operand launch of this shape runs on (``bm``: a forced tile code)."""
+    L = _lib.load()
+    tile = bm
+    if tile == 0:
+        tile = L.fgn_h2_row_tile(rows, cout, k, 0, 0)
+        if tile == 64 and L.fgn_h2_k_groups(rows, cout, k, 0, 0) == 2:
+            tile = H2_BM_KG2
+    return H2_DUAL_KERNELS.get(tile, 'conv_pw_h2_kernel_dual<?>')
 
 
 class gemm_math:
@@ -618,9 +633,10 @@ def strided_rows(shapes, stride: int, device) -> torch.Tensor:
 
 
 def conv1x1_dual(x1: torch.Tensor, x2: torch.Tensor, layer: DualConvLayer, out: Optional[torch.Tensor] = None,
-                 x2_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 x2_rows: Optional[torch.Tensor] = None, bm: int = 0) -> torch.Tensor:
     """x1 [..., Cin1] -> relu?(x1 W1^T + x2' W2^T + shift) [..., Cout], x2' = x2 over the same leading dims (rows), or -
-    with ``x2_rows`` (int32 [rows], ``strided_rows``) - row x2_rows[m] of x2 [..., Cin2] for output row m."""
+    with ``x2_rows`` (int32 [rows], ``strided_rows``) - row x2_rows[m] of x2 [..., Cin2] for output row m.
+    bm != 0 (tests, tools): conv_pw_h2_kernel_dual with that tile code forced (``gemm_h2``)."""
     _chk(x1, 'x1')
     _chk(x2, 'x2')
     rows = x1.numel() // layer.cin1
@@ -646,14 +662,24 @@ def conv1x1_dual(x1: torch.Tensor, x2: torch.Tensor, layer: DualConvLayer, out: 
     route = 'f32'
     if max(x1.numel(), x2.numel()) * 4 < 0x7fffff00:
         route = _gemm_route(L, layer.w3, layer.wh, rows, layer.cout, k)
-    w = {'h2': layer.wh, 'x3': layer.w3, 'f32': layer.w}[route]
-    rc = getattr(L, 'fgn_conv1x1_dual_%snhwc_f32' % _ROUTE_INFIX[route])(
-        _ptr(x1), _ptr(x2), _ptr(x2_rows), x2_total, w.data_ptr(), _ptr(out), _ptr(layer.shift), rows, layer.cin1, layer.cin2,
-        layer.cout, layer.cout_pad, int(layer.relu), _stream())
+    if bm != 0:
+        if layer.wh is None or max(x1.numel(), x2.numel()) * 4 >= 0x7fffff00:
+            raise _lib.FgnHipError('conv1x1_dual: a forced tile code needs a layer packed for conv_pw_h2_kernel')
+        route = 'h2'
+        rc = L.fgn_conv1x1_dual_h2_bm_nhwc_f32(_ptr(x1), _ptr(x2), _ptr(x2_rows), x2_total, layer.wh.data_ptr(), _ptr(out),
+                                               _ptr(layer.shift), rows, layer.cin1, layer.cin2, layer.cout, layer.cout_pad,
+                                               int(layer.relu), bm, _stream())
+    else:
+        w = {'h2': layer.wh, 'x3': layer.w3, 'f32': layer.w}[route]
+        rc = getattr(L, 'fgn_conv1x1_dual_%snhwc_f32' % _ROUTE_INFIX[route])(
+            _ptr(x1), _ptr(x2), _ptr(x2_rows), x2_total, w.data_ptr(), _ptr(out), _ptr(layer.shift), rows, layer.cin1, layer.cin2,
+            layer.cout, layer.cout_pad, int(layer.relu), _stream())
     _lib.check(rc, 'fgn_conv1x1_dual_nhwc_f32')
     if prof is not None:
         flop = 2.0 * rows * layer.cout * k
-        prof.append(dict(kind='conv', kernel=_gemm_kernel(route, 'conv_pw_persist_kernel', rows, layer.cout, k),
+        kernel = h2_dual_kernel(rows, layer.cout, k, bm) if route == 'h2' else \
+            _gemm_kernel(route, 'conv_pw_persist_kernel', rows, layer.cout, k)
+        prof.append(dict(kind='conv', kernel=kernel,
                          math=route, e0=e0, e1=e1, flop_direct=flop, flop_issued=flop,
                          n_img=1, n_img_dev=None, gemm=(1, rows, layer.cout, k), residual=False,
                          shape=(1, rows, 1, k, layer.cout, 1, 1)))
@@ -876,15 +902,20 @@ def _winograd_gemm(L, layer: WinogradLayer, V, Mo, n_img_dev, n_img: int, tiles:
 
 
 def _winograd_records(prof, ev, L, layer: WinogradLayer, route: str, t_pad: int, valid: int, tiles: int, pixels: int,
-                      **common) -> None:
+                      bits=(64, 64), **common) -> None:
     """The three PROFILE records of a Winograd convolution (ev: the event pairs of input transform, GEMM, output transform).
-    ``valid`` tiles are computed per group; a record's FLOPs are per image of ``tiles`` tiles and ``pixels`` pixels."""
+    ``valid`` tiles are computed per group; a record's FLOPs are per image of ``tiles`` tiles and ``pixels`` pixels.
+    ``bits``: the index width (``winograd4_index_bits``) of the input / output transform launch: 32 = the narrow instance."""
     G, cin, cout = layer.groups, layer.cin, layer.cout
     kin, kout = 'wg_input_kernel', 'wg_output_kernel'
     if layer.m == 4:     # the template instances of the F(4x4) transforms (csrc/winograd.hip): <vector width, eager>
         vi, vo = L.fgn_winograd4_variant(valid, cin, 0), L.fgn_winograd4_variant(valid, cout, 1)
         kin = 'wg4_input_kernel<%d, %s>' % (vi // 10, 'true' if vi % 10 else 'false')
         kout = 'wg4_output_kernel<%d>' % (vo // 10)
+        if bits[0] == 32:
+            kin = 'wg4_input_narrow_kernel<%d>' % (vi // 10)
+        if bits[1] == 32:
+            kout = 'wg4_output_narrow_kernel<%d>' % (vo // 10)
     prof.append(dict(kind='wg_in', kernel=kin, e0=ev[0][0], e1=ev[0][1], flop_direct=0.0, flop_issued=0.0, **common))
     # direct-convolution FLOPs of the layer (what the reference's formulation executes) are booked on the GEMM record; the
     # MFMA work issued is (m+2)^2 products per m x m output tile instead of 9 m^2.  The GEMM: point-wise over [G * t_pad] rows
@@ -941,9 +972,49 @@ def conv3x3_winograd(x: torch.Tensor, layer: WinogradLayer, in_scale: Optional[t
     _lib.check(f_out(_ptr(Mo), _ptr(y), _ptr(layer.shift), _ptr(n_img_dev), n_img, H, W, layer.cout, t_pad,
                      int(layer.relu), st), 'fgn_winograd_output_f32')
     if ev is not None:
-        _winograd_records(prof, ev, L, layer, route, t_pad, n_img * tiles, tiles, H * W, n_img=n_img, n_img_dev=n_img_dev,
+        bits = (64, 64) if layer.m != 4 else (
+            winograd4_index_bits(n_img, H, W, cin, t_pad, a_img_div=a_img_div, with_scale=in_scale is not None),
+            winograd4_index_bits(n_img, H, W, layer.cout, t_pad, output=True))
+        _winograd_records(prof, ev, L, layer, route, t_pad, n_img * tiles, tiles, H * W, bits=bits, n_img=n_img, n_img_dev=n_img_dev,
                           shape=(n_img, H, W, cin, layer.cout, 3, 1))
     return y
+
+
+def winograd4_index_bits(n_img: int, H: int, W: int, C: int, t_pad: int, a_img_div: int = 1, second=None,
+                         with_scale: bool = False, output: bool = False) -> int:
+    """32 / 64: the index width the F(4x4) input (``output``: output) transform takes at these sizes (``second`` = (n, H, W)
+    of a second tensor): the launchers' own rule.  Computed from the sizes; nothing is allocated."""
+    n1, h1, w1 = second if second is not None else (0, 1, 1)
+    return _lib.load().fgn_winograd4_index_bits(n_img, a_img_div, H, W, n1, h1, w1, C, t_pad, int(with_scale), int(output))
+
+
+def winograd4_input(x: torch.Tensor, V: torch.Tensor, in_scale: Optional[torch.Tensor] = None, a_img_div: int = 1,
+                    n_img_dev: Optional[torch.Tensor] = None, x1: Optional[torch.Tensor] = None, index_bits: int = 0,
+                    vec: int = 0) -> None:
+    """The F(4x4) input transform alone (tests, tools): x [n_in,H,W,C] (and ``x1`` behind it) -> V [36,t_pad,C] in place,
+    with the kernel instance forced: index_bits 32 (narrow) / 64 (wide) / 0 (by the sizes); vec 1 / 2 / 4 channels per
+    thread / 0 (the library's rule)."""
+    _chk(x, 'x')
+    _chk(V, 'V')
+    n_in, H, W, C = x.shape
+    n1, h1, w1 = (0, 1, 1) if x1 is None else tuple(x1.shape[:3])
+    rc = _lib.load().fgn_winograd4_input_ix_f32(_ptr(x), _ptr(in_scale), _ptr(V), _ptr(n_img_dev), n_in * a_img_div, a_img_div,
+                                                H, W, C, V.shape[1], _ptr(x1), n1, h1, w1, index_bits, vec, _stream())
+    _lib.check(rc, 'fgn_winograd4_input_ix_f32')
+
+
+def winograd4_output(Mo: torch.Tensor, y: torch.Tensor, shift: Optional[torch.Tensor] = None, relu: bool = False,
+                     n_img_dev: Optional[torch.Tensor] = None, y1: Optional[torch.Tensor] = None, index_bits: int = 0,
+                     vec: int = 0) -> None:
+    """The F(4x4) output transform alone (tests, tools): Mo [36,t_pad,C] -> y [n,H,W,C] (and ``y1``) in place, with the
+    kernel instance forced as for ``winograd4_input``."""
+    _chk(Mo, 'Mo')
+    _chk(y, 'y')
+    n, H, W, C = y.shape
+    n1, h1, w1 = (0, 1, 1) if y1 is None else tuple(y1.shape[:3])
+    rc = _lib.load().fgn_winograd4_output_ix_f32(_ptr(Mo), _ptr(y), _ptr(shift), _ptr(n_img_dev), n, H, W, C, Mo.shape[1],
+                                                 int(relu), _ptr(y1), n1, h1, w1, index_bits, vec, _stream())
+    _lib.check(rc, 'fgn_winograd4_output_ix_f32')
 
 
 def conv3x3_winograd_multi(xs, layer: WinogradLayer, outs) -> None:
@@ -1003,7 +1074,9 @@ def conv3x3_winograd_multi(xs, layer: WinogradLayer, outs) -> None:
             off += n_t
     if prof is not None:
         pixels = sum(x.shape[0] * x.shape[1] * x.shape[2] for x in xs)
-        _winograd_records(prof, ev, L, layer, route, t_pad, total, total, pixels, n_img=1, n_img_dev=None,
+        bits = (winograd4_index_bits(n0, h0, w0, cin, t_pad, second=(n1, h1, w1)),
+                winograd4_index_bits(n0, h0, w0, cout, t_pad, second=(n1, h1, w1), output=True))
+        _winograd_records(prof, ev, L, layer, route, t_pad, total, total, pixels, bits=bits, n_img=1, n_img_dev=None,
                           shape=(len(xs), pixels, 1, cin, cout, 3, 1))
 
 

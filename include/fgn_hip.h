@@ -180,6 +180,14 @@ int fgn_conv1x1_h2_nhwc_f32(const float* x, const void* w_h2, float* y, const fl
 int fgn_conv1x1_dual_h2_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
                                  const void* w_h2, float* y, const float* shift, int rows, int Cin1, int Cin2, int Cout,
                                  int cout_pad, int relu, void* stream);
+/* the same with the tile code forced (bm as for fgn_gemm_h2_f32; tests, tools).  Launches with a second operand run on
+ * conv_pw_h2_kernel_dual<waves along M, waves along N, row blocks, stages, K-groups>, every other launch on
+ * conv_pw_h2_kernel<..., implicit-GEMM loader, K-groups>, which holds no second descriptor and no operand select - with one
+ * exception: conv_pw_h2_kernel<2, 2, 1, 2, false, 2> (two K-groups, no implicit-GEMM loader) keeps the look at x2 at run
+ * time (as a one-operand instance it measured slower), though launch_h2 never hands it a second operand. */
+int fgn_conv1x1_dual_h2_bm_nhwc_f32(const float* x, const float* x2, const int32_t* x2_rows, int x2_total_rows,
+                                    const void* w_h2, float* y, const float* shift, int rows, int Cin1, int Cin2, int Cout,
+                                    int cout_pad, int relu, int bm, void* stream);
 /* rows written, device count, untouched rows: as stated at fgn_winograd_gemm_f32, with the row tile of fgn_h2_row_tile(
  * n_groups * t_pad, Cout, Cin, t_pad, n_img * tiles_per_img) (64 / 128, 264 = 128 rows; rows of V past the valid ones reach neither a
  * wave's scale nor a valid row); where that is 0 the call returns FGN_ERR_SHAPE and writes nothing */
@@ -233,6 +241,28 @@ int fgn_winograd4_input2_f32(const float* x0, int n_img0, int H0, int W0, const 
                              float* V, int C, int t_pad, void* stream);
 int fgn_winograd4_output2_f32(const float* Mo, const float* shift, float* y0, int n_img0, int H0, int W0, float* y1,
                               int n_img1, int H1, int W1, int C, int t_pad, int relu, void* stream);
+/* Index width of the F(4x4) transforms.  The transforms above choose between two instances of each kernel from the sizes
+ * alone: the NARROW one (32-bit byte offsets, a short prologue) when every tensor of the launch - x / y of both tensors,
+ * in_scale, V / Mo [36][t_pad][C] - ends below 2 GiB, else the WIDE one (64-bit indices).  Both give the same bytes.
+ * fgn_winograd4_index_bits -> 32 / 64, the choice for these sizes (n_img1 = 0: one tensor; with_scale: in_scale is read;
+ * is_output: the output transform, else the input transform) - the launchers' own rule, one function;
+ * nothing is allocated or launched.  32: the device kernels are wg4_input_narrow_kernel<V> / wg4_output_narrow_kernel<V>,
+ * 64: wg4_input_kernel<V, eager> / wg4_output_kernel<V> (V, eager: fgn_winograd4_variant).
+ * WHAT A DEVICE COUNT BELOW n_img LEAVES READABLE: the narrow instances load the patches of EVERY tile below the capacity
+ * n_img and compare against *n_img_dev only before the stores, so with any of the F(4x4) entry points x must be readable
+ * for all ceil(n_img / a_img_div) images, in_scale for all n_img rows and Mo for all n_img * tiles rows of each position,
+ * whatever the count is (their values past the count reach no output); V and y past the count are not touched.  The _ix entries (tests, tools) run either form of the transform - x1 / y1 == NULL:
+ * one tensor, else the two-tensor form - with index_bits 0 (by the sizes), 32 or 64 forced; 32 on sizes the narrow
+ * instance cannot address is FGN_ERR_SHAPE.  vec: 0 = the channel vector width of fgn_winograd4_variant, 1 / 2 / 4 = that
+ * many floats per thread (tools/wg4_ab.py measures the rule with it). */
+int fgn_winograd4_index_bits(int n_img, int a_img_div, int H, int W, int n_img1, int H1, int W1, int C, int t_pad,
+                             int with_scale, int is_output);
+int fgn_winograd4_input_ix_f32(const float* x, const float* in_scale, float* V, const int32_t* n_img_dev, int n_img,
+                               int a_img_div, int H, int W, int C, int t_pad, const float* x1, int n_img1, int H1, int W1,
+                               int index_bits, int vec, void* stream);
+int fgn_winograd4_output_ix_f32(const float* Mo, float* y, const float* shift, const int32_t* n_img_dev, int n_img, int H,
+                                int W, int C, int t_pad, int relu, float* y1, int n_img1, int H1, int W1, int index_bits,
+                                int vec, void* stream);
 /* Which instance of the F(4x4) transform kernels a layer with `tiles_total` tiles and C channels launches: the
  * channel vector width of a thread (1, 2 or 4 floats) * 10 + 1 when the input transform issues all 36 loads up front.
  * Informational (lets a profiler name the kernel of a launch); the transforms choose it themselves. */
